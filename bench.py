@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- optimised frame-pairs/sec at 640x192, 4 GN iterations (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--windows-per-gpu B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--windows-per-gpu B] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts itself: the parent process, which never touches
@@ -433,6 +433,9 @@ def main():
                          "host launch per call instead of nine, same kernels, bit-identical results); 0: plain launches; auto: untimed blocks of "
                          "both before the timed region, the faster mode is timed (a slow host favours replay, a fast one plain launches)")
     ap.add_argument("--dump-poses", default="", help="rank 0 writes the gathered refined poses [world, pairs, 6] to this .npy file (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes what the timed steps computed to DIR/poses.npy (float32, "
+                    "[world, ring calls, pairs, 6]): the refined poses of every window of the ring, in ring order, as the blocks of the timed "
+                    "mode left them (the last step's among them); the inputs are seeded, so equal arguments give equal inputs")
     ap.add_argument("--modes-budget", type=float, default=12.0, help="seconds given to the `modes` block (BASELINE configs 4 / 5, the KITTI window, the "
                     "reference-loss dense mode: windows/s and roofline fraction each); 0 = skip")
     ap.add_argument("--shim-sample", type=float, default=4.0, help="seconds given to the `shim` block (DepthOptimizer.optimize_window end to end); 0 = skip")
@@ -442,10 +445,9 @@ def main():
         raise SystemExit(self_launch(args.gpus))
 
     import numpy as np
-    # this application owns its process: it sets the two HIP runtime variables the launch structure likes BEFORE HIP initialises (the package
-    # itself no longer touches the environment on import: tightly_coupled_sfm_amd/_lib.py)
+    # this application owns its process: it sets the HIP runtime variable the launch structure likes BEFORE HIP initialises (the package
+    # itself no longer touches the environment on import: tightly_coupled_sfm_amd/_lib.py); the hardware queue count is left to the machine
     os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch
     import torch.distributed as dist
 
@@ -596,6 +598,7 @@ def main():
     host_enqueue_us = float(np.median(enqueue_s)) / args.steps * 1e6
     for l in range(lanes):                   # a deferred device-side error of any lane surfaces here
         eng.lane_synchronize(l)
+    timed_out = torch.stack([w["out"] for w in ring])        # (--dump-outputs) what the timed blocks left in every window's output
     # the round-3 protocol beside it: the same blocks re-running ONE window per lane (inputs, packs and records all cache resident)
     hot = None
     if R > lanes:
@@ -645,6 +648,7 @@ def main():
                      "mode": "graph replay" if use_replay else "plain launches (9 per call)"}
         if c_el < elapsed:          # the merged sequences are the faster way of running these steps: they are the headline
             elapsed, blocks = c_el, c_blocks
+            timed_out = torch.stack([w["out"] for w in ring])
             host_enqueue_us = merged["host_enqueue_us_per_step"]
             merged["timed"] = True
         else:
@@ -674,6 +678,17 @@ def main():
     assert torch.isfinite(final_all).all()
     if args.dump_poses and rank == 0:
         np.save(args.dump_poses, final_all.cpu().numpy())
+    if args.dump_outputs:
+        if distributed:
+            parts = [torch.empty_like(timed_out.to(coll_dev)) for _ in range(world)]
+            dist.all_gather(parts, timed_out.to(coll_dev))
+            dump_all = torch.stack(parts)
+        else:
+            dump_all = timed_out[None]
+        assert dump_all.numel() * 4 <= 64 << 20, f"--dump-outputs: {tuple(dump_all.shape)} poses exceed 64 MB"
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "poses.npy"), dump_all.cpu().numpy().astype(np.float32))
 
     # instrumented pass on EVERY rank: in-kernel brackets + HIP events around every kernel launch, same steps (ring rotation, one call
     # in flight: the kernel has the chip -- what a roofline compares against)

@@ -149,6 +149,32 @@ def test_bench_strong_scaling_option():
     assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) < 0.01 * d["value"]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the refined poses of every ring window as the timed blocks left them, equal to what one plain call on the
+    same seeded window computes, bit for bit"""
+    import numpy as np
+    import torch
+    out_dir = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2", "--cpu-sample", "0",
+                        "--sat-windows", "0", "--modes-budget", "0", "--shim-sample", "0", "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    assert d["steps"] == 10 and d["ms_per_step"] > 0
+    got = np.load(out_dir / "poses.npy")
+    R = d["config"]["ring_calls"]
+    assert got.dtype == np.float32 and got.shape == (1, R, 2, 6) and np.isfinite(got).all()
+    from tightly_coupled_sfm_amd import synth
+    from tightly_coupled_sfm_amd.engine import Engine, default_opts
+    e = Engine(192, 640, 2)
+    for j in (0, R - 1):           # the bench's ring entry j: seed 7919 j, pair form (fwd, inv) -> window form (fwd pairs, inv pairs)
+        b = synth.make_batch(2, 192, 640, seed0=7919 * j, both_directions=True)
+        t = {k: torch.as_tensor(v).cuda().contiguous() for k, v in b.items()}
+        pose, _, _ = e.refine(t["tgt"], t["src"], t["depth_t"], t["depth_s"], t["K"], t["pose_init"], default_opts(n_iters=4))
+        pose = pose.cpu().numpy()
+        assert np.array_equal(np.concatenate([pose[0::2], pose[1::2]]), got[0, j]), j
+
+
 def test_bench_world_size_one_over_rccl():
     """the RCCL code path of bench.py on hardware: one rank, backend nccl (= RCCL) -- init_process_group, the all_reduce of the
     block count / block times, the final all_gather of the poses and the barriers all run on the card (the 8-GPU run itself is

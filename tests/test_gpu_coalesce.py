@@ -265,7 +265,7 @@ def test_lanes_are_probed_and_safe_when_the_handle_comes_first():
     code = r'''
 import json, os, sys, time
 sys.path.insert(0, %r)
-os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1"); os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 import torch
 from tightly_coupled_sfm_amd.engine import Engine, default_opts
 from tightly_coupled_sfm_amd import synth

