@@ -248,7 +248,7 @@ int tcsfm_refine_dense(tcsfm_handle h, const tcsfm_opts *o, int N, const float *
 /* Window form of tcsfm_refine_dense (the `optimize_depth_pred` mode of optimize_window with its default options,
  * optimizer.py:194-198 + 47-69): B targets x S sources given once as in tcsfm_refine_window; depth_out [2*S*B,1,H,W] in the
  * stacked pair order.
- *   JOINT (o->dense_joint, the default, S = 2 or 3): the reference optimises ONE disparity per frame that every term of the loss
+ *   JOINT (o->dense_joint, the default, S = 2 or 3; S >= 4 in this mode runs the per-pair copies below): the reference optimises ONE disparity per frame that every term of the loss
  *     sees (optimizer.py:235-247).  The S forward pairs of target b share one inverse-depth map; unknowns per target = S poses +
  *     the map; cost = the forward term of the reference's loss (min over the sources under o->argmin, or every valid source
  *     without it, :71-73) with every pixel weighted by the depth-consistency map of the source it counts for, + the depth prior.
@@ -263,7 +263,8 @@ int tcsfm_refine_dense(tcsfm_handle h, const tcsfm_opts *o, int N, const float *
  *     count, lambda, iterate].  The inverse pairs refine their pose and the depth of THEIR target (source frame (s,b)) as before.
  *   PER-PAIR COPIES (o->dense_joint = 0, or S = 1 where the two coincide): every directed pair refines ITS OWN copy of its
  *     target's depth; with o->argmin the forward pairs use the min over the sources at the current poses and depth copies.
- *   REFERENCE LOSS (o->window_rule = TCSFM_WINDOW_REFERENCE; S = 1 .. 3, Gauss-Newton; round 4): the scalar that is minimised is
+ *   REFERENCE LOSS (o->window_rule = TCSFM_WINDOW_REFERENCE; S = 1 .. 4 -- the five-frame window t-2 .. t+2 included --, Gauss-Newton;
+ *     round 4; S >= 5 returns TCSFM_E_ARG): the scalar that is minimised is
  *     the reference's compute_optimization_loss as optimize_depth_pred sees it (optimizer.py:47-90):
  *       c_f / K_f sum M_s W_x diff_s  (forward term: K_f summed over the call's B targets; W_x = the weight map of SOURCE 0 on every
  *                                      selected pixel under o->argmin, c_f = 1; without argmin W_x = W_s, c_f = 0.25, no auto-mask)
@@ -293,7 +294,7 @@ int tcsfm_refine_dense_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S,
 
 /* ONE linearisation of tcsfm_refine_dense_window's REFERENCE-LOSS mode at `pose` and `depth_t` (nothing is updated): the loss and its
  * exact gradients, for pinning against the reference's loss and autograd (golden G13) -- the dense counterpart of
- * tcsfm_linearize_window.  Outputs (HOST pointers, float64): scal_out [8] = loss, forward group (forward term + its depth
+ * tcsfm_linearize_window.  S = 1 .. 4 (S >= 5: TCSFM_E_ARG).  Outputs (HOST pointers, float64): scal_out [8] = loss, forward group (forward term + its depth
  * consistency + prior), inverse photometric term, inverse depth-consistency term, K_f, K_i, a_f = c_f / K_f, the l_pose_consist term
  * (o->w_pose_consist; part of the loss and of g_pose_out, golden G13 `full_pc`);
  * g_pose_out [2*S*B][6] = d loss / d (left SE(3) perturbation of every directed pair's warp transform) in the stacked pair order;
@@ -311,7 +312,7 @@ int tcsfm_linearize_dense_window(tcsfm_handle h, const tcsfm_opts *o, int B, int
  * map is the back-projected depth of its inverse pair (local: photometric term through the SSIM window, the pair's own weight, its depth-
  * consistency term) and the depth its forward pair SAMPLES (stn.py:271: through that pair's depth-consistency term and the weight map it
  * provides -- source 0's multiplies every selected pixel under o->argmin, optimizer.py:69): both parts, the second as the adjoint of the
- * bilinear sample.  Equals reference autograd (golden G13 `full_grad_depth_s`; oracle: dref_source_depth_gradient).  With this every leaf
+ * bilinear sample.  S = 1 .. 4 as there.  Equals reference autograd (golden G13 `full_grad_depth_s`; oracle: dref_source_depth_gradient).  With this every leaf
  * of the reference's loss has its exact gradient on the device; making the source maps unknowns of the Gauss-Newton step is not done. */
 int tcsfm_linearize_dense_window_sources(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
                                          const float *depth_t, const float *depth_s, const float *K, const float *pose, const float *depth0,
@@ -435,7 +436,7 @@ int tcsfm_coalesce_counts(tcsfm_handle h, int *batches, int *calls);
 /* The dense counterpart (arguments of tcsfm_refine_dense_window, device pointers, no statistics): queued per-pair Gauss-Newton dense calls
  * with ONE source per target (S = 1, TCSFM_WINDOW_PAIR) of the same shape and options are merged like the pose calls -- every call's
  * refined poses and depth maps go to its own outputs, bit-identical to the call on its own.  Round 5: calls under TCSFM_WINDOW_REFERENCE (the
- * reference's own loss, optimizer.py:47-90; S <= 3, Gauss-Newton, fixed source maps, per-pixel or quarter-resolution unknown) are merged as
+ * reference's own loss, optimizer.py:47-90; S <= 4, Gauss-Newton, fixed source maps, per-pixel or quarter-resolution unknown) are merged as
  * well: that loss couples the windows of ONE call through its batch normalisers, so inside the merged sequence every call is a normaliser
  * group of its own (mask counts, per-map weights) and its results are the bits of the call run alone.  Any other dense call (the joint mode
  * for S > 1 under TCSFM_WINDOW_PAIR, LM, free_source_depths) flushes what is waiting and runs at once.  Pose calls and dense calls are never

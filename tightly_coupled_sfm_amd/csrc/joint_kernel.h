@@ -24,7 +24,8 @@
 
 namespace tc {
 
-constexpr int JMAXS = 3;                       // sources per target the joint kernels are instantiated for (2 .. JMAXS)
+constexpr int JMAXS = 4;                       // sources per target the joint kernels are instantiated for (1 .. JMAXS) under the reference's loss
+constexpr int JMAXS_OWN = 3;                   // ... and in the library's own joint mode (opts.dense_joint with window rule PAIR: 2 .. 3)
 template <int NS> struct JointLayout {
     static constexpr int NP = 6 * NS;
     static constexpr int NHJ = NP * (NP + 1) / 2;
@@ -682,7 +683,8 @@ __global__ __launch_bounds__(NT, (JointShape<NS, NT, true, false>::OCC)) void k_
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct JointState {                 // per target (fp64): LM bookkeeping + the accepted reduced system [S | -gS] (NP x (NP+1))
+struct JointState {                 // per target (fp64): LM bookkeeping + the accepted reduced system [S | -gS] (NP x (NP+1)):
+                                    // 24 x 25 doubles at S = JMAXS = 4, 4824 bytes per target in all
     double lambda, cost_cur;
     int have_cur, pad;
     double M[6 * JMAXS * (6 * JMAXS + 1)];
@@ -731,9 +733,10 @@ __device__ __forceinline__ void solve_joint_body(const JointSolveParams &P, cons
     constexpr int NP = JL::NP, NC = NP + 1;
     // thread = (accumulator, record subset).  S = 1 (32 accumulators): 32 subsets, so a target's 300-480 tile records are ONE batch of at most 16 loads per thread
     // (third session of round 5: with 128 accumulator slots only a quarter of the threads loaded, in two dependent batches: 5.5 of the launch's 9.3 us)
-    constexpr int APAD = JL::NACC <= 32 ? 32 : (JL::NACC <= 128 ? 128 : 256), PARTS = JSOLVE_NT / APAD;
+    // (S = 4: 335 accumulators -> 512 columns, two record subsets; S <= 3 keep their widths and so their summation order)
+    constexpr int APAD = JL::NACC <= 32 ? 32 : (JL::NACC <= 128 ? 128 : (JL::NACC <= 256 ? 256 : 512)), PARTS = JSOLVE_NT / APAD;
     constexpr int NBATCH = PARTS >= 32 ? 16 : 32;        // loads in flight per thread and batch
-    static_assert(JL::NACC <= 256 && NP * NC <= JSOLVE_NT, "k_solve_joint: one thread per accumulator column and per matrix entry");
+    static_assert(JL::NACC <= 512 && NP * NC <= JSOLVE_NT, "k_solve_joint: one thread per accumulator column and per matrix entry");
     __shared__ double tot[JL::NACC];
     __shared__ double part[JSOLVE_NT];
     __shared__ double M[NP * NC];

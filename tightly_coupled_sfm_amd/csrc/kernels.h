@@ -1244,7 +1244,7 @@ __global__ __launch_bounds__(NT, 4) void k_linearize(LinParams P) {
     // error among the sources before / after s (torch.min keeps the FIRST minimum), the union of their validity and the
     // smallest auto-mask threshold.  Same arithmetic as the maps pass + selection it replaces (the dense modes keep the maps pass: ext_selected).
     float sel_before = 3.0e38f, sel_after = 3.0e38f, sel_valid = 0.f, sel_ae = 3.0e38f;
-    float sel_d1 = 3.0e38f, sel_d2 = 3.0e38f;      // FRONT: the errors of sources 1 and 2 on their own (the row of pair (0, b) decides for every source)
+    float sel_d1 = 3.0e38f, sel_d2 = 3.0e38f, sel_d3 = 3.0e38f;      // FRONT: the errors of sources 1, 2 and 3 on their own (the row of pair (0, b) decides for every source)
     float sel_w0 = 1.f;      // REFERENCE rule: depth-consistency weight of SOURCE 0 at this pixel (pairs of the other sources)
     const bool sel_pair = SEL && n < P.sel_B * P.sel_S;
     const int s_own = (SEL && sel_pair) ? n / P.sel_B : 0;
@@ -1350,7 +1350,7 @@ __global__ __launch_bounds__(NT, 4) void k_linearize(LinParams P) {
                 const float d_o = e01.x + e01.y + (TS ? ssim_l1_value_ts<float>(yx2c.y, yx2c.x, cs2, S2.y, S2.x, SS2.y, SS2.x, Sxy2, P.ws, P.wl)
                                                       : ssim_l1_value<float>(yx2c.y, yx2c.x, S2.y, S2.x, SS2.y, SS2.x, Sxy2, P.ws, P.wl));
                 if (so < s_own) sel_before = fminf(sel_before, d_o); else sel_after = fminf(sel_after, d_o);
-                if (FRONT) { if (so == 1) sel_d1 = d_o; else sel_d2 = d_o; }
+                if (FRONT) { if (so == 1) sel_d1 = d_o; else if (so == 2) sel_d2 = d_o; else sel_d3 = d_o; }
                 sel_valid = fmaxf(sel_valid, q2.z);
                 sel_ae = fminf(sel_ae, q2.w);
                 if (P.rule && so == 0) sel_w0 = lds_read1(ctr + 1).x;
@@ -1599,10 +1599,15 @@ __global__ __launch_bounds__(NT, 4) void k_linearize(LinParams P) {
                 front_m = inimg && sel_keep;                  // exactly one source keeps the pixel
                 if (inimg) {
                     const size_t o = (size_t)(y00 + ly - 1) * W + (x00 + lx - 1);
-                    const bool m1 = sel_keep && sel_d1 < diff && sel_d1 <= sel_d2, m2 = sel_keep && sel_d2 < diff && sel_d2 < sel_d1;
+                    // (first minimum, as torch.min: a later source wins only against STRICTLY larger errors of the earlier ones; with
+                    // fewer than four sources the comparisons with the unused sel_d3 = 3e38 hold for every real error)
+                    const bool m1 = sel_keep && sel_d1 < diff && sel_d1 <= sel_d2 && sel_d1 <= sel_d3,
+                               m2 = sel_keep && sel_d2 < diff && sel_d2 < sel_d1 && sel_d2 <= sel_d3,
+                               m3 = sel_keep && sel_d3 < diff && sel_d3 < sel_d1 && sel_d3 < sel_d2;
                     P.sel_out[(size_t)n * hw + o] = m ? 1.f : 0.f;
                     P.sel_out[(size_t)(P.sel_B + n) * hw + o] = m1 ? 1.f : 0.f;
                     if (P.sel_S > 2) P.sel_out[(size_t)(2 * P.sel_B + n) * hw + o] = m2 ? 1.f : 0.f;
+                    if (P.sel_S > 3) P.sel_out[(size_t)(3 * P.sel_B + n) * hw + o] = m3 ? 1.f : 0.f;
                 }
             }
             continue;

@@ -564,26 +564,43 @@ SolveParams solve_params(tcsfm_ctx *h, const tcsfm_opts *o, int np, int shared) 
 
 namespace {
 // Scratch of the joint dense kernels, allocated ONCE on first use (a captured call graph -- tcsfm_set_graph_replay -- bakes these pointers
-// in, so they are never freed or re-sized while the handle lives).  The per-PIXEL records (jrec, jrec_acc) and the workgroup records are
-// sized in floats for the largest layout any call can need: S sources -> max_pairs / (2 S) targets x JREC(S) floats, largest at S = JMAXS
-// (20 floats x max_pairs / 4 targets; S = 1 under the reference's loss needs 8 x max_pairs / 2).  The per-TARGET arrays (state, step,
-// accepted depth) are sized for the most targets any call can have: (max_pairs + 1) / 2, reached at S = 1 (they were sized
-// for S >= 2 and the S = 1 reference-loss mode indexed past them).
+// in, so they are never freed or re-sized while the handle lives).  The per-PIXEL records (jrec, jrec_acc, the quarter-resolution cell records)
+// and the per-target record arrays (workgroup records, split partial sums) are sized for the largest layout any call can need: a call of S
+// sources has at most max_pairs / (2 S) targets of JREC(S) floats per pixel and NACC(S) per record, so the capacity is the maximum over
+// S = 1 .. JMAXS of (targets at S) x JREC(S) -- 8 x max_pairs / 2 at S = 1 and S = 2, 28 x max_pairs / 8 at S = 4 -- not JREC(JMAXS) x the most
+// targets (the per-pixel records of a handle are smaller than the S <= 3 layouts had them: 20 x max_pairs / 4).  The workgroup records also
+// hold, behind the forward groups', the free-source mode's S B inverse groups of one source.  The per-TARGET arrays (state, step, accepted
+// depth) are sized for the most targets any call can have: (max_pairs + 1) / 2, reached at S = 1 (they were sized for S >= 2 and
+// the S = 1 reference-loss mode indexed past them).
 constexpr int kJointSplitMax = 8;
+static_assert(JMAXS == 4, "joint_max_over_S lists the layouts S = 1 .. 4");
+constexpr size_t joint_jrec(int S) { return S == 1 ? JointLayout<1>::JREC : S == 2 ? JointLayout<2>::JREC : S == 3 ? JointLayout<3>::JREC : JointLayout<4>::JREC; }
+constexpr size_t joint_nacc(int S) { return S == 1 ? JointLayout<1>::NACC : S == 2 ? JointLayout<2>::NACC : S == 3 ? JointLayout<3>::NACC : JointLayout<4>::NACC; }
+// what 0: floats per pixel of jrec / jrec_acc / qres_rec; 1: accumulator rows of one half of jpart (and the forward groups' share of a
+// jblockrec row); 2: one jblockrec row = forward groups + the free-source mode's inverse groups
+constexpr size_t joint_max_over_S(size_t n, int what) {
+    size_t m = 0;
+    for (int S = 1; S <= JMAXS; S++) {
+        const size_t t = S == 1 ? (n + 1) / 2 : n / (2 * S);          // targets of a call with S sources (2 B S <= max_pairs)
+        const size_t v = t * (what == 0 ? joint_jrec(S) : what == 1 ? joint_nacc(S) : joint_nacc(S) + S * joint_nacc(1));
+        m = v > m ? v : m;
+    }
+    return m;
+}
+inline size_t joint_rec_floats(size_t n) { return joint_max_over_S(n, 0); }
+inline size_t joint_acc_floats(size_t n) { return joint_max_over_S(n, 1); }
+inline size_t joint_blockrec_floats(size_t n) { return joint_max_over_S(n, 2); }
 int joint_scratch(tcsfm_ctx *h) {
     if (h->jrec) return TCSFM_OK;
-    using JM = JointLayout<JMAXS>;
     const size_t hw = (size_t)h->H * h->W, n = h->max_pairs;
-    const size_t nb = (n + 3) / 4, nt = (n + 1) / 2;
-    static_assert(JointLayout<1>::JREC * 2 <= JM::JREC && JointLayout<2>::JREC <= JM::JREC, "pixel records: max_pairs / 4 targets of the S = JMAXS layout hold every case");
-    static_assert(JointLayout<1>::NACC * 2 <= JM::NACC && JointLayout<2>::NACC <= JM::NACC, "workgroup records: likewise");
-    HIPCHK(h, hipMalloc((void **)&h->jrec, nb * hw * JM::JREC * sizeof(float)));
-    HIPCHK(h, hipMalloc((void **)&h->jrec_acc, nb * hw * JM::JREC * sizeof(float)));
+    const size_t nt = (n + 1) / 2, nrec = joint_rec_floats(n), nacc = joint_acc_floats(n), nblkrec = joint_blockrec_floats(n);
+    HIPCHK(h, hipMalloc((void **)&h->jrec, hw * nrec * sizeof(float)));
+    HIPCHK(h, hipMalloc((void **)&h->jrec_acc, hw * nrec * sizeof(float)));
     HIPCHK(h, hipMalloc((void **)&h->jdepth_acc, nt * hw * sizeof(float)));
-    HIPCHK(h, hipMalloc((void **)&h->jblockrec, nb * 2 * h->nblk_alloc * JM::NACC * sizeof(float)));      // (tile records + the quarter-resolution mode's cell-group records)
+    HIPCHK(h, hipMalloc((void **)&h->jblockrec, 2 * h->nblk_alloc * nblkrec * sizeof(float)));      // (tile records + the quarter-resolution mode's cell-group records)
     HIPCHK(h, hipMalloc((void **)&h->jstate, nt * sizeof(JointState)));
     HIPCHK(h, hipMalloc((void **)&h->jdelta, nt * 6 * JMAXS * sizeof(double)));
-    HIPCHK(h, hipMalloc((void **)&h->jpart, 2 * nt * kJointSplitMax * JM::NACC * sizeof(double)));      // (forward groups, then the free-source mode's inverse groups)
+    HIPCHK(h, hipMalloc((void **)&h->jpart, 2 * kJointSplitMax * nacc * sizeof(double)));      // (forward groups, then the free-source mode's inverse groups)
     HIPCHK(h, hipMalloc((void **)&h->jtick, 2 * nt * sizeof(int)));
     HIPCHK(h, hipMemset(h->jtick, 0, 2 * nt * sizeof(int)));
     h->jrec_S = JMAXS;
@@ -593,10 +610,9 @@ int joint_scratch(tcsfm_ctx *h) {
 template <int NS>
 bool joint_scratch_fits(const tcsfm_ctx *h, int B, int recs_per_target) {
     using JL = JointLayout<NS>;
-    using JM = JointLayout<JMAXS>;
-    const size_t n = h->max_pairs, nb = (n + 3) / 4, nt = (n + 1) / 2;
-    return (size_t)B <= nt && (size_t)B * JL::JREC <= nb * JM::JREC &&
-           (size_t)B * recs_per_target * JL::NACC <= nb * 2 * (size_t)h->nblk_alloc * JM::NACC;
+    const size_t n = h->max_pairs, nt = (n + 1) / 2;
+    return (size_t)B <= nt && (size_t)B * JL::JREC <= joint_rec_floats(n) && (size_t)B * JL::NACC <= joint_acc_floats(n) &&
+           (size_t)B * recs_per_target * JL::NACC <= 2 * (size_t)h->nblk_alloc * joint_blockrec_floats(n);
 }
 
 // tile height of k_dense_joint's own grid (32 x 8 tiles of 256 threads by default; 16: the round-4 grid shared with the pair-form kernels)
@@ -793,7 +809,6 @@ int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, 
                   const float *d_K, const float *d_pose_in, float *d_pose_out, float *d_depth_out, float *d_stats, const WinOff *wo, const DrefExport *ex,
                   const CoalTab *ct = nullptr, float *const *ct_pose = nullptr, float *const *ct_depth = nullptr) {
     using JL = JointLayout<NS>;
-    using JM = JointLayout<JMAXS>;
     constexpr int S = NS;
     // B: targets of the launch sequence.  Coalesced calls (ct): ncall queued calls of cB targets each run as ONE sequence over B = ncall cB
     // targets; the loss couples the windows of ONE call (batch normalisers, means over the call's maps): every call is a normaliser group of
@@ -831,7 +846,7 @@ int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, 
     if (qres && !h->qres_rho) {
         const size_t nb = (n + 1) / 2;
         HIPCHK(h, hipMalloc((void **)&h->qres_rho, 2 * nb * nq * sizeof(float)));       // (two buffers: k_qres_step_up ping-pongs)
-        HIPCHK(h, hipMalloc((void **)&h->qres_rec, nb * nq * JM::JREC * sizeof(float)));
+        HIPCHK(h, hipMalloc((void **)&h->qres_rec, nq * joint_rec_floats(n) * sizeof(float)));
     }
     if (qres && nblk + nqblk > 2 * h->nblk_alloc) return fail(h, TCSFM_E_ARG, "internal: quarter-resolution records exceed the scratch");
     if (!joint_scratch_fits<NS>(h, B, nblk + nqblk)) return fail(h, TCSFM_E_ARG, "internal: the joint dense scratch does not hold this many targets");
@@ -852,7 +867,7 @@ int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, 
     }
     // (the inverse groups' workgroup records follow the forward groups' in jblockrec: both joint launches of a linearisation run before the solve)
     const size_t jrec2_off = (size_t)B * (nblk + nqblk) * JL::NACC;
-    if (free_src && jrec2_off + (size_t)SB * (nblk + nqblk) * JointLayout<1>::NACC > ((n + 3) / 4) * 2 * (size_t)h->nblk_alloc * JM::NACC)
+    if (free_src && jrec2_off + (size_t)SB * (nblk + nqblk) * JointLayout<1>::NACC > 2 * (size_t)h->nblk_alloc * joint_blockrec_floats(n))
         return fail(h, TCSFM_E_ARG, "internal: the inverse groups' records exceed the scratch");
     tcsfm_opts oo = *o;
     oo.refine = TCSFM_REFINE_POSE;
@@ -1145,7 +1160,7 @@ int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, 
     {
         const size_t nt = (n + 1) / 2;
         Sj.nsplit = split_env > 0 ? std::min(split_env, kJointSplitMax) : split_of(Sj.nblk, NS); Sj.jpart = h->jpart; Sj.jtick = h->jtick;
-        Sj2.nsplit = split_env > 0 ? std::min(split_env, kJointSplitMax) : split_of(Sj2.nblk, 1); Sj2.jpart = h->jpart + nt * kJointSplitMax * JM::NACC; Sj2.jtick = h->jtick + nt;
+        Sj2.nsplit = split_env > 0 ? std::min(split_env, kJointSplitMax) : split_of(Sj2.nblk, 1); Sj2.jpart = h->jpart + kJointSplitMax * joint_acc_floats(n); Sj2.jtick = h->jtick + nt;
     }
     if (pc) {     // c = weight / (6 S B) of the CALL (merged calls never carry the term); forward pairs at [0, SB), inverse pairs at [SB, 2 SB) of a buffer
         const double c = (double)o->w_pose_consist / (6.0 * SB);
@@ -1936,7 +1951,7 @@ static int dense_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int
     const bool ref_mode = win_B && o->window_rule == TCSFM_WINDOW_REFERENCE;      // the reference's own loss (dense_ref_kernel.h)
     if (o->w_dc > 0.f && !ref_mode) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: w_dc must be 0 (use prior_depth), except under window_rule = TCSFM_WINDOW_REFERENCE");
     if (ref_mode && (win_S > JMAXS || o->solver != TCSFM_SOLVER_GN || !(o->prior_init >= 0.f)))
-        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window: window_rule REFERENCE needs S <= 3, the Gauss-Newton solver and prior_init >= 0");
+        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window: window_rule REFERENCE needs S <= 4, the Gauss-Newton solver and prior_init >= 0");
     if (!(o->w_pose_consist >= 0.f) || (o->w_pose_consist > 0.f && (!ref_mode || o->param != TCSFM_PARAM_SE3)))
         return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: w_pose_consist needs the window form under window_rule = TCSFM_WINDOW_REFERENCE and the SE(3) chart");
     if (o->free_source_depths != 0 && !ref_mode)
@@ -1986,7 +2001,8 @@ static int dense_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int
     if (ref_mode) {
         rc = win_S == 1 ? dense_ref_run<1>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth)
            : win_S == 2 ? dense_ref_run<2>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth)
-                        : dense_ref_run<3>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth);
+           : win_S == 3 ? dense_ref_run<3>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth)
+                        : dense_ref_run<4>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth);
         if (rc) return rc;
         if ((rc = copy_back(h, o, pose_out, d_pose_out, (size_t)N * 6))) return rc;
         if ((rc = copy_back(h, o, depth_out, d_depth_out, N * hw))) return rc;
@@ -1994,7 +2010,8 @@ static int dense_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int
         if (o->host_ptrs) HIPCHK(h, hipStreamSynchronize(h->stream));
         return TCSFM_OK;
     }
-    if (win_B && o->dense_joint && win_S >= 2 && win_S <= JMAXS) {   // one depth map per target, 6S x 6S reduced system (joint_kernel.h)
+    // (the library's own joint mode stays at S <= JMAXS_OWN = 3: wider windows there keep the per-pair depth copies below)
+    if (win_B && o->dense_joint && win_S >= 2 && win_S <= JMAXS_OWN) {   // one depth map per target, 6S x 6S reduced system (joint_kernel.h)
         rc = win_S == 2 ? dense_joint_run<2>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo)
                         : dense_joint_run<3>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo);
         if (rc) return rc;
@@ -2300,7 +2317,7 @@ static int linearize_dense_window_impl(tcsfm_handle h, const tcsfm_opts *o, int 
                                        double *scal_out, double *g_pose_out, float *g_rho_out, float *g_rho_src_out) {
     if (int rc_q = drain_queued(h)) return rc_q;
     if (!h) return TCSFM_E_ARG;
-    if (B < 1 || S < 1 || S > JMAXS || (long long)2 * B * S > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_linearize_dense_window: need 1 <= S <= 3 and 2*B*S <= max_pairs");
+    if (B < 1 || S < 1 || S > JMAXS || (long long)2 * B * S > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_linearize_dense_window: need 1 <= S <= 4 and 2*B*S <= max_pairs");
     const int N = 2 * B * S;
     int rc = check_common(h, o, N);
     if (rc) return rc;
@@ -2327,7 +2344,8 @@ static int linearize_dense_window_impl(tcsfm_handle h, const tcsfm_opts *o, int 
     DrefExport ex{scal_out, g_pose_out, d_g, d_d0, d_gs};
     rc = S == 1 ? dense_ref_run<1>(h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex)
        : S == 2 ? dense_ref_run<2>(h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex)
-                : dense_ref_run<3>(h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex);
+       : S == 3 ? dense_ref_run<3>(h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex)
+                : dense_ref_run<4>(h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex);
     if (rc) return rc;
     if ((rc = copy_back(h, o, g_rho_out, d_g, (size_t)B * hw))) return rc;
     if (g_rho_src_out && (rc = copy_back(h, o, g_rho_src_out, d_gs, (size_t)S * B * hw))) return rc;

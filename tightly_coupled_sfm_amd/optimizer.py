@@ -17,7 +17,8 @@ The reference's `optimize_depth_pred` switch (Adam on the disparity maps themsel
 refine='pose+depth' unless `refine` is given: pose + per-pixel inverse depth of the target by Gauss-Newton with a Schur complement,
 by default ON THE REFERENCE'S OWN LOSS (optimizer.py:47-90: forward term with source 0's weight map, 0.25 x inverse term, depth
 consistency, l_depth_init SSIM prior; `diff_img_argmin`, `automasking`, `l_depth_consist(+_weight)`, `l_depth_init(+_weight)` honoured;
-include/tcsfm.h "REFERENCE LOSS"); options['window_rule'] = 'pair' or solver 'lm' select the library's own joint / per-pair dense modes.
+include/tcsfm.h "REFERENCE LOSS"; up to four source images per target, so the five-frame window t-2 .. t+2 too); options['window_rule'] = 'pair'
+or solver 'lm' select the library's own joint / per-pair dense modes.
 Its weight-tuning switches (optimize_depth_encoder, ...) need autograd through the networks, which is out of scope:
 they are ignored with a warning, or refused when options['strict_legacy'] is set.
 """
@@ -127,7 +128,7 @@ class DepthOptimizer:
 
     def _dense_reference(self):
         """pose + depth by default minimises the reference's own loss (window rule REFERENCE, Gauss-Newton; the kernels are instantiated for
-        S <= 3 sources per target: optimize_window checks the ACTUAL number of source images before it calls the engine);
+        S <= 4 sources per target: optimize_window checks the ACTUAL number of source images before it calls the engine);
         options['window_rule'] = 'pair' or solver 'lm' select the library's own dense modes"""
         o = self.options
         return o.get("window_rule", "reference") != "pair" and o.get("solver", "gn") != "lm"
@@ -238,8 +239,8 @@ class DepthOptimizer:
         S = len(source_img_list)
         split = S * B
         dense = self._refine_mode() == "pose+depth"
-        if dense and self._dense_reference() and S > 3:      # (the real S, before anything is launched: options['num_source_imgs'] may not match the batch)
-            raise ValueError("pose + depth on the reference's loss handles up to 3 source images per target (options['window_rule'] = 'pair' lifts it)")
+        if dense and self._dense_reference() and S > 4:      # (the real S, before anything is launched: options['num_source_imgs'] may not match the batch)
+            raise ValueError("pose + depth on the reference's loss handles up to 4 source images per target (options['window_rule'] = 'pair' lifts it)")
         eng = self._eng(H, W, 2 * split)
         cfg = self.config
 
