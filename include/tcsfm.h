@@ -138,7 +138,10 @@ enum { TCSFM_STAT_COST = 0, TCSFM_STAT_COST_PHOTO = 1, TCSFM_STAT_NMASK = 2, TCS
 /* ---- lifetime ------------------------------------------------------------------------------- */
 
 /* Allocates all device scratch for up to max_pairs directed pairs of H x W images on `device`.
- * Nothing in the reference corresponds to this: PyTorch owns memory there (optimizer.py:15-27). */
+ * Nothing in the reference corresponds to this: PyTorch owns memory there (optimizer.py:15-27).
+ * Frame sizes: 4 <= H, W <= 16384, and every mode takes every such size, ragged against any tile grid -- the joint and
+ * reference-loss dense modes included; the one further restriction is the quarter-resolution unknown's (o->depth_param =
+ * TCSFM_DEPTH_QUARTER: H and W multiples of 4, otherwise the call returns TCSFM_E_ARG). */
 int tcsfm_create(tcsfm_handle *out, int device, int H, int W, int max_pairs);
 void tcsfm_destroy(tcsfm_handle h);
 const char *tcsfm_last_error(tcsfm_handle h); /* h may be NULL: last create() error */

@@ -21,6 +21,7 @@ problems.  Instead of loosening the tolerance in such cases, every iterate-level
       must be a near-tie of the two costs.
 """
 import numpy as np
+import torch
 
 POSE_TOL = 1e-4          # BASELINE.json: pose translations / rotations within 1e-4 relative
 COST_TOL = 2e-5          # cost at every linearisation, relative
@@ -114,16 +115,33 @@ def check_flips_every_linearisation(orc, nit, pixels, tag=None, max_frac=5e-5):
     return int(fn.sum())
 
 
+def traced_and_production(e, n_lin, n_pairs, call):
+    """PRODUCTION == RECORDING: `call()` -- one Engine.refine* call -> tuple of output tensors (poses, depth maps or log-scales,
+    stats; None where absent) -- runs once with the decision trace on (the TRACE = true instantiations of the kernels, whose decisions
+    the oracle replays) and once with it off (the TRACE = false ones users and bench.py run: compiled separately, registers allocated
+    differently).  Every output must be the same bits, so that every oracle comparison of the traced run vouches for the production
+    kernels.  -> (traced outputs, bits, decide)"""
+    e.trace_begin(n_lin, n_pairs)
+    traced = call()
+    bits, dec = e.trace_end()
+    prod = call()
+    assert len(traced) == len(prod)
+    for i, (a, p) in enumerate(zip(traced, prod)):
+        assert (a is None) == (p is None), i
+        if a is not None:
+            assert torch.equal(a, p), ("production kernels differ from the recording ones: output", i,
+                                       int((a != p).sum()), float((a.double() - p.double()).abs().max()))
+    return traced, bits, dec
+
+
 def replay_pairs(e, orc, b, o, oopts, tdev, log_scale=None, pose_key="pose_init", first_masks=True):
     """N directed pairs through Engine.refine with the decision trace on, then the oracle replay per pair.
     b: synth batch (numpy); o: engine opts; oopts: oracle opts; tdev: numpy -> cuda tensor.  -> dict of results"""
     N = b["tgt"].shape[0]
     nl, nit = n_lin(o), int(o.n_iters)
     refine = int(o.refine)
-    e.trace_begin(nl, N)
     args = (tdev(b["tgt"]), tdev(b["src"]), tdev(b["depth_t"]), tdev(b["depth_s"]), tdev(b["K"]), tdev(b[pose_key]))
-    pose, ls, st = e.refine(*args, o, log_scale=tdev(log_scale) if refine else None, stats=True)
-    bits, dec = e.trace_end()
+    (pose, ls, st), bits, dec = traced_and_production(e, nl, N, lambda: e.refine(*args, o, log_scale=tdev(log_scale) if refine else None, stats=True))
     pose, st = pose.cpu().numpy().astype(np.float64), st.cpu().numpy()
     ls = ls.cpu().numpy() if refine else None
     out = dict(pose=pose, stats=st, bits=bits, decide=dec, log_scale=ls, ref_pose=[], ref_stats=[], mask_flips=0, lm_flips=0)
@@ -170,19 +188,18 @@ def replay_window(e, orc, w, o, oopts, tdev, argmin=True, dense=False, log_scale
     refine = int(o.refine)
     args = tuple(tdev(w[k]) for k in ("target", "sources", "depth_t", "depth_s", "K", "first"))
     oargs = (w["target"], w["sources"], w["depth_t"][:, 0], w["depth_s"][:, :, 0], w["K"], w["first"])
-    e.trace_begin(nl, N)
     depth = ls = None
     if dense:
         import ctypes as _C
         o2 = type(o)(); _C.memmove(_C.byref(o2), _C.byref(o), _C.sizeof(o2)); o = o2
         o.dense_joint = 1 if joint else 0            # joint: one depth map per target shared by its S forward pairs (tcsfm.h)
         o.window_rule = 0
-        pose, depth, st = e.refine_dense_window(*args, o, stats=True, argmin=argmin)
+        (pose, depth, st), bits, dec = traced_and_production(e, nl, N, lambda: e.refine_dense_window(*args, o, stats=True, argmin=argmin))
         depth = depth.cpu().numpy()[:, 0]
     else:
-        pose, ls, st = e.refine_window(*args, o, stats=True, argmin=argmin, log_scale=tdev(log_scale) if refine else None)
+        (pose, ls, st), bits, dec = traced_and_production(
+            e, nl, N, lambda: e.refine_window(*args, o, stats=True, argmin=argmin, log_scale=tdev(log_scale) if refine else None))
         ls = ls.cpu().numpy() if refine else None
-    bits, dec = e.trace_end()
     pose, st = pose.cpu().numpy().astype(np.float64), st.cpu().numpy()
     orc.flip_stats_reset()
     if dense and joint:
@@ -253,9 +270,8 @@ def replay_dense_pairs(e, orc, b, d0, o, oopts, tdev, pose_key="pose_init", pose
     N = b["tgt"].shape[0]
     nl, nit = n_lin(o), int(o.n_iters)
     p0 = b[pose_key] if poses is None else poses
-    e.trace_begin(nl, N)
-    pose, depth, st = e.refine_dense(tdev(b["tgt"]), tdev(b["src"]), tdev(d0), tdev(b["depth_s"]), tdev(b["K"]), tdev(p0), o, stats=True)
-    bits, dec = e.trace_end()
+    (pose, depth, st), bits, dec = traced_and_production(
+        e, nl, N, lambda: e.refine_dense(tdev(b["tgt"]), tdev(b["src"]), tdev(d0), tdev(b["depth_s"]), tdev(b["K"]), tdev(p0), o, stats=True))
     pose, depth, st = pose.cpu().numpy().astype(np.float64), depth.cpu().numpy()[:, 0], st.cpu().numpy()
     rows = nit + (1 if int(o.solver) == 1 and nit > 0 else 0)
     out = dict(pose=pose, depth=depth, stats=st, bits=bits, decide=dec, ref_pose=[], ref_depth=[], ref_stats=[], mask_flips=0, lm_flips=0)

@@ -10,7 +10,7 @@ import torch
 
 from conftest import load_golden
 from oracle.oracle import Oracle, default_opts as oracle_opts
-from parity_util import check_dense_ref_flips
+from parity_util import check_dense_ref_flips, traced_and_production
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +24,7 @@ def _dev(a):
     return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).cuda()
 
 
-@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160"])
+@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160", "winloss28x48"])
 def test_linearize_dense_window_vs_reference_autograd_G13(name, orc):
     from tightly_coupled_sfm_amd.engine import Engine, default_opts
     g = load_golden(name)
@@ -65,7 +65,7 @@ def test_linearize_dense_window_vs_reference_autograd_G13(name, orc):
         assert np.abs(L["g_rho"][:, 0].cpu().numpy() - Lo["g_rho"]).max() < 2e-4 * np.abs(Lo["g_rho"]).max()
 
 
-@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160"])
+@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160", "winloss28x48"])
 def test_gradient_wrt_the_source_depth_maps_vs_reference_autograd_G13(name, orc):
     """tcsfm_linearize_dense_window_sources: the gradient of the reference's loss w.r.t. the SOURCE depth maps -- leaves of the reference's
     optimize_depth_pred (optimizer.py:194-198) that the refinement holds fixed -- equals reference autograd (golden G13 `full_grad_depth_s`),
@@ -120,9 +120,7 @@ def test_dense_reference_iterates_follow_the_oracle(H, W, S, mind, maxd, orc):
     o = default_opts(n_iters=n_it, w_dc=0.15, prior_init=0.1, min_depth=mind, max_depth=maxd, window_rule=_lib.WINDOW_REFERENCE, lambda_depth=1.0)
     t = {k: _dev(v) for k, v in w.items()}
     dt4, ds5 = t["depth_t"][:, None].contiguous(), t["depth_s"][:, :, None].contiguous()
-    e.trace_begin(n_it, N)
-    pose, depth, st = e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=True)
-    bits, _ = e.trace_end()
+    (pose, depth, st), bits, _ = traced_and_production(e, n_it, N, lambda: e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=True))
     pose = pose.cpu().numpy().astype(np.float64); depth = depth.cpu().numpy().astype(np.float64)
     f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)          # the oracle starts from the SAME float32 inputs
     oo = oracle_opts(n_iters=n_it, w_dc=0.15)
@@ -158,9 +156,7 @@ def test_dense_reference_minibatches_on_an_exactly_sized_handle(B, S, H, W, quar
                      depth_param=_lib.DEPTH_QUARTER if quarter else _lib.DEPTH_FULL)
     t = {k: _dev(v) for k, v in w.items()}
     dt4, ds5 = t["depth_t"][:, None].contiguous(), t["depth_s"][:, :, None].contiguous()
-    e.trace_begin(n_it, N)
-    pose, depth, _ = e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=True)
-    bits, _ = e.trace_end()
+    (pose, depth, _), bits, _ = traced_and_production(e, n_it, N, lambda: e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=True))
     pose = pose.cpu().numpy().astype(np.float64); depth = depth.cpu().numpy().astype(np.float64)
     f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
     orc.flip_stats_reset()
@@ -200,9 +196,7 @@ def test_free_source_depth_maps_follow_the_oracle(B, H, W, S, mind, maxd, argmin
                      free_source_depths=1)
     t = {k: _dev(v) for k, v in w.items()}
     dt4, ds5 = t["depth_t"][:, None].contiguous(), t["depth_s"][:, :, None].contiguous()
-    e.trace_begin(n_it, N)
-    pose, depth, st = e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=argmin)
-    bits, _ = e.trace_end()
+    (pose, depth, st), bits, _ = traced_and_production(e, n_it, N, lambda: e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=argmin))
     pose = pose.cpu().numpy().astype(np.float64); depth = depth.cpu().numpy().astype(np.float64)
     f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
     oo = oracle_opts(n_iters=n_it, w_dc=0.15)
@@ -235,7 +229,7 @@ def test_free_source_depth_maps_follow_the_oracle(B, H, W, S, mind, maxd, argmin
     e.close()
 
 
-@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160"])
+@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160", "winloss28x48"])
 def test_quarter_resolution_gradient_vs_reference_autograd_G13(name, orc):
     """the reference's PARAMETRISATION (optimizer.py:194-198, 235-239): at the x4-upsampled quarter-resolution maps the engine's loss and
     pose gradients are the reference's, and its depth gradient carried through the transposed upsampling equals reference autograd w.r.t.
@@ -278,9 +272,7 @@ def test_quarter_resolution_iterates_follow_the_oracle(H, W, S, mind, maxd, orc)
                      depth_param=_lib.DEPTH_QUARTER)
     t = {k: _dev(v) for k, v in w.items()}
     dt4, ds5 = t["depth_t"][:, None].contiguous(), t["depth_s"][:, :, None].contiguous()
-    e.trace_begin(n_it, N)
-    pose, depth, st = e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=True)
-    bits, _ = e.trace_end()
+    (pose, depth, st), bits, _ = traced_and_production(e, n_it, N, lambda: e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=True))
     pose = pose.cpu().numpy().astype(np.float64); depth = depth.cpu().numpy().astype(np.float64)
     f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
     oo = oracle_opts(n_iters=n_it, w_dc=0.15)
@@ -324,9 +316,7 @@ def test_the_reference_leaf_set_quarter_resolution_target_and_sources(B, S, H, W
                      depth_param=_lib.DEPTH_QUARTER, free_source_depths=1)
     t = {k: _dev(v) for k, v in w.items()}
     dt4, ds5 = t["depth_t"][:, None].contiguous(), t["depth_s"][:, :, None].contiguous()
-    e.trace_begin(n_it, N)
-    pose, depth, st = e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=True)
-    bits, _ = e.trace_end()
+    (pose, depth, st), bits, _ = traced_and_production(e, n_it, N, lambda: e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=True))
     pose = pose.cpu().numpy().astype(np.float64); depth = depth.cpu().numpy().astype(np.float64)
     f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
     oo = oracle_opts(n_iters=n_it, w_dc=0.15)
@@ -364,9 +354,7 @@ def test_quarter_resolution_batches_and_source_counts(B, S, H, W, orc):
                      depth_param=_lib.DEPTH_QUARTER)
     t = {k: _dev(v) for k, v in w.items()}
     dt4, ds5 = t["depth_t"][:, None].contiguous(), t["depth_s"][:, :, None].contiguous()
-    e.trace_begin(n_it, N)
-    pose, depth, _ = e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=True)
-    bits, _ = e.trace_end()
+    (pose, depth, _), bits, _ = traced_and_production(e, n_it, N, lambda: e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], o, stats=True, argmin=True))
     pose = pose.cpu().numpy().astype(np.float64); depth = depth.cpu().numpy().astype(np.float64)
     f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
     orc.flip_stats_reset()
@@ -398,9 +386,7 @@ def test_dense_reference_with_smoothness_term_follows_the_oracle(quarter, orc):
               depth_param=_lib.DEPTH_QUARTER if quarter else _lib.DEPTH_FULL)
     t = {k: _dev(v) for k, v in w.items()}
     dt4, ds5 = t["depth_t"][:, None].contiguous(), t["depth_s"][:, :, None].contiguous()
-    e.trace_begin(n_it, N)
-    pose, depth, _ = e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], default_opts(w_smooth=2.0, **kw), stats=True, argmin=True)
-    bits, _ = e.trace_end()
+    (pose, depth, _), bits, _ = traced_and_production(e, n_it, N, lambda: e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], default_opts(w_smooth=2.0, **kw), stats=True, argmin=True))
     pose = pose.cpu().numpy().astype(np.float64); depth = depth.cpu().numpy().astype(np.float64)
     f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
     orc.flip_stats_reset()
@@ -470,9 +456,7 @@ def test_dense_reference_with_pose_consistency_term_follows_the_oracle(mode, orc
               depth_param=_lib.DEPTH_QUARTER if mode == "quarter" else _lib.DEPTH_FULL, free_source_depths=1 if mode == "free" else 0)
     t = {k: _dev(v) for k, v in w.items()}
     dt4, ds5 = t["depth_t"][:, None].contiguous(), t["depth_s"][:, :, None].contiguous()
-    e.trace_begin(n_it, N)
-    pose, depth, _ = e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], default_opts(w_pose_consist=wpc, **kw), stats=True, argmin=True)
-    bits, _ = e.trace_end()
+    (pose, depth, _), bits, _ = traced_and_production(e, n_it, N, lambda: e.refine_dense_window(t["tgt"], t["srcs"], dt4, ds5, t["K"], t["pose"], default_opts(w_pose_consist=wpc, **kw), stats=True, argmin=True))
     pose = pose.cpu().numpy().astype(np.float64); depth = depth.cpu().numpy().astype(np.float64)
     f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
     orc.flip_stats_reset()

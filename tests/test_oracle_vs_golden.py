@@ -284,7 +284,7 @@ G13_VARIANTS = (("fwd", dict(w_dc=0.0), True, "fwd"), ("fwd_inv", dict(w_dc=0.0)
                 ("full_pc", dict(w_dc=0.15, w_pose_consist=0.1), True, "all"))
 
 
-@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160"])
+@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160", "winloss28x48"])
 def test_window_reference_rule_vs_reference_loss_G13(name, oracle64):
     """The REFERENCE window rule (tcsfm_opts.window_rule = 1): the scalar the window refinement minimises IS the reference's
     compute_optimization_loss (optimizer.py:47-86; batch-summed normalisers, source 0's weight map on every forward pixel,
@@ -351,7 +351,7 @@ def test_window_reference_rule_refines_and_reduces(oracle64):
     assert abs(st[:, 0, 0].sum() - before) < 1e-12
 
 
-@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160"])
+@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160", "winloss28x48"])
 def test_joint_dense_gradients_vs_reference_autograd_G13(name, oracle64):
     """joint dense mode (ONE inverse-depth map per target frame, shared by its S forward pairs -- optimizer.py:194-198,235-247):
     the gradient of the forward term of the reference's loss w.r.t. the SHARED target depth and w.r.t. the S poses equals reference
@@ -567,7 +567,7 @@ def test_pose_vec2mat_a3(oracle64):
     assert _maxabs(stn.pose_vec2mat(torch.tensor(g["pose_vec"])).numpy(), g["pose_mat"]) < 1e-14
 
 
-@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160"])
+@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160", "winloss28x48"])
 def test_dense_reference_loss_and_gradients_vs_reference_autograd_G13(name, oracle64):
     """round 4: the dense mode's restatement of the reference's COMPLETE loss (optimizer.py:47-90: forward term with source 0's
     weight map, 0.25 x inverse term, depth consistency of both directions, l_depth_init = SSIM between the target's current and
@@ -659,7 +659,7 @@ def test_dense_reference_refinement_with_free_source_maps(oracle64):
     assert np.isfinite(p2).all() and np.abs(ds2 / a[3] - 1).max() > 1e-3
 
 
-@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160"])
+@pytest.mark.parametrize("name", ["winloss24x40", "winloss48x160", "winloss28x48"])
 def test_quarter_resolution_parametrisation_vs_reference_G13(name, oracle64):
     """round 4: the reference's own parametrisation of optimize_depth_pred (optimizer.py:194-198, 235-239) -- the leaf is the QUARTER-
     resolution sigmoid disparity, upsampled x4 (bilinear) every epoch.  (a) the oracle's down / up-sampling weights are torch's (the

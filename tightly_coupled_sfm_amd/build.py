@@ -14,7 +14,9 @@ OUT = os.path.join(HERE, "libtcsfm_hip.so")
 # across statements depending on how many uses a product has -- which made the decision-recording instantiations of the kernels
 # (TRACE=true: same arithmetic, a few extra stores) round differently from the production ones by an ulp here and there).  With
 # "on" every instantiation of a template performs bit-identical arithmetic, so the parity tests that run the recording build
-# vouch for the production build; tests assert the two agree bit for bit.
+# vouch for the production build.  tests/parity_util.py traced_and_production asserts the two agree bit for bit wherever the oracle
+# replays a trace: in replay_pairs / replay_window / replay_dense_pairs (pose, dense and joint dense modes) and at every replay of
+# tests/test_gpu_dense_reference.py and tests/test_gpu_dense_shapes.py (the reference-loss modes); test_gpu_four_sources.py for S = 4.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=on", "-fPIC", "-shared"]
 
 

@@ -105,7 +105,8 @@ struct tcsfm_ctx {
     double *lin_out = nullptr;   // device [max_pairs][7*7+7+4]
     float *pose_dev = nullptr, *ls_dev = nullptr, *K_dev = nullptr, *stats_dev = nullptr;
     int tiles_x = 0, tiles_y = 0, nblk = 0, ngrp = 0, ngrp_pad = 0, stats_cap_iters = 0;
-    int nblk_alloc = 0, ngrp_alloc = 0;   // scratch capacity (covers the 32x8 tiling of the dense kernel too)
+    int nblk_alloc = 0, ngrp_alloc = 0;   // scratch capacity of the pose path and of the pair-form dense kernels (16 x 16 tiles or coarser)
+    int jrec_alloc = 0;                    // workgroup records per target jblockrec holds: joint_records_per_target (the joint kernels' own grid)
     float *dense_rec = nullptr, *depth0 = nullptr;   // dense mode scratch, allocated on first use
     float *dense_rec2 = nullptr, *depth_alt = nullptr;   // ... second record / depth buffers of the fused back-substitution (ping-pong)
     float *dense_rec_acc = nullptr, *depth_acc = nullptr;   // dense LM: accepted per-pixel records / depth maps
@@ -587,6 +588,17 @@ constexpr size_t joint_max_over_S(size_t n, int what) {
     }
     return m;
 }
+// tile height of k_dense_joint's own grid (32 x 8 tiles of 256 threads by default; 16: the round-4 grid shared with the pair-form kernels)
+#ifndef TC_JOINT_TILE_H
+#define TC_JOINT_TILE_H 8
+#endif
+constexpr int kJointTileW = 32, kJointTileH = TC_JOINT_TILE_H;      // k_dense_joint / k_dense_joint2's tiles (both joint modes launch on them)
+inline int joint_tiles(const tcsfm_ctx *h) { return ((h->W + kJointTileW - 1) / kJointTileW) * ((h->H + kJointTileH - 1) / kJointTileH); }
+// k_qres_*'s cell groups: their records follow the joint kernel's tiles' in a target's row of jblockrec
+inline int qres_groups(const tcsfm_ctx *h) { return ((h->H / 4) * (h->W / 4) + QRES_CELLS_PER_WG - 1) / QRES_CELLS_PER_WG; }
+// workgroup records of one target, the most any call can write: the joint tiles, then the quarter-resolution unknown's cell groups.  (Not the
+// pose path's 16 x 16 tile count: that is the smaller one whenever ceil(W / 16) is odd and ceil(H / 8) even -- 16 x 48, 28 x 48, 192 x 624.)
+inline int joint_records_per_target(const tcsfm_ctx *h) { return joint_tiles(h) + qres_groups(h); }
 inline size_t joint_rec_floats(size_t n) { return joint_max_over_S(n, 0); }
 inline size_t joint_acc_floats(size_t n) { return joint_max_over_S(n, 1); }
 inline size_t joint_blockrec_floats(size_t n) { return joint_max_over_S(n, 2); }
@@ -597,7 +609,8 @@ int joint_scratch(tcsfm_ctx *h) {
     HIPCHK(h, hipMalloc((void **)&h->jrec, hw * nrec * sizeof(float)));
     HIPCHK(h, hipMalloc((void **)&h->jrec_acc, hw * nrec * sizeof(float)));
     HIPCHK(h, hipMalloc((void **)&h->jdepth_acc, nt * hw * sizeof(float)));
-    HIPCHK(h, hipMalloc((void **)&h->jblockrec, 2 * h->nblk_alloc * nblkrec * sizeof(float)));      // (tile records + the quarter-resolution mode's cell-group records)
+    h->jrec_alloc = joint_records_per_target(h);
+    HIPCHK(h, hipMalloc((void **)&h->jblockrec, (size_t)h->jrec_alloc * nblkrec * sizeof(float)));      // (tile records + the quarter-resolution mode's cell-group records)
     HIPCHK(h, hipMalloc((void **)&h->jstate, nt * sizeof(JointState)));
     HIPCHK(h, hipMalloc((void **)&h->jdelta, nt * 6 * JMAXS * sizeof(double)));
     HIPCHK(h, hipMalloc((void **)&h->jpart, 2 * kJointSplitMax * nacc * sizeof(double)));      // (forward groups, then the free-source mode's inverse groups)
@@ -612,13 +625,8 @@ bool joint_scratch_fits(const tcsfm_ctx *h, int B, int recs_per_target) {
     using JL = JointLayout<NS>;
     const size_t n = h->max_pairs, nt = (n + 1) / 2;
     return (size_t)B <= nt && (size_t)B * JL::JREC <= joint_rec_floats(n) && (size_t)B * JL::NACC <= joint_acc_floats(n) &&
-           (size_t)B * recs_per_target * JL::NACC <= 2 * (size_t)h->nblk_alloc * joint_blockrec_floats(n);
+           recs_per_target <= h->jrec_alloc && (size_t)B * recs_per_target * JL::NACC <= (size_t)h->jrec_alloc * joint_blockrec_floats(n);
 }
-
-// tile height of k_dense_joint's own grid (32 x 8 tiles of 256 threads by default; 16: the round-4 grid shared with the pair-form kernels)
-#ifndef TC_JOINT_TILE_H
-#define TC_JOINT_TILE_H 8
-#endif
 
 // JOINT dense mode of a window (include/tcsfm.h, tcsfm_refine_dense_window): the S forward pairs of every target share one depth map
 // and are solved together (k_dense_joint / k_solve_joint / k_dense_joint_update); the inverse pairs run the pair-form dense kernels on
@@ -637,8 +645,8 @@ int dense_joint_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt
     const int tiles_x = (h->W + DTW - 1) / DTW, tiles_y = (h->H + DTH - 1) / DTH, nblk = tiles_x * tiles_y;
     // the joint kernel runs on its own tile grid, as under the reference's loss (third session of round 5): 256-thread workgroups, for S = 2 the
     // LEAN form of the kernel (161 VGPRs: three workgroups per CU instead of one 512-thread workgroup at 212-232)
-    constexpr int JTW = 32, JTH = TC_JOINT_TILE_H, JNT = JTW * JTH;
-    const int jtiles_x = (h->W + JTW - 1) / JTW, jtiles_y = (h->H + JTH - 1) / JTH, jnblk = jtiles_x * jtiles_y;
+    constexpr int JTW = kJointTileW, JTH = kJointTileH, JNT = JTW * JTH;
+    const int jtiles_x = (h->W + JTW - 1) / JTW, jtiles_y = (h->H + JTH - 1) / JTH, jnblk = jtiles_x * jtiles_y;      // = joint_tiles(h)
     if (n_sel && !h->sel_maps) HIPCHK(h, hipMalloc((void **)&h->sel_maps, (size_t)2 * h->max_pairs * hw * sizeof(float)));
     if (!h->dense_rec) {
         HIPCHK(h, hipMalloc((void **)&h->dense_rec, n * hw * 8 * sizeof(float)));
@@ -652,7 +660,7 @@ int dense_joint_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt
     }
     if ((rc = joint_scratch(h))) return rc;
     if (lm && !h->lm_accept) HIPCHK(h, hipMalloc((void **)&h->lm_accept, n * sizeof(int)));
-    if ((size_t)nblk > (size_t)h->nblk_alloc || (size_t)jnblk > (size_t)h->nblk_alloc) return fail(h, TCSFM_E_ARG, "internal: dense tile grid exceeds scratch");
+    if ((size_t)nblk > (size_t)h->nblk_alloc) return fail(h, TCSFM_E_ARG, "internal: dense tile grid exceeds scratch");
     if (!joint_scratch_fits<NS>(h, B, jnblk)) return fail(h, TCSFM_E_ARG, "internal: the joint dense scratch does not hold this many targets");
     tcsfm_opts oo = *o;
     oo.refine = TCSFM_REFINE_POSE;
@@ -821,11 +829,10 @@ int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, 
     // The joint kernel's own tile grid (round 5): 32 x 8 tiles of 256 threads by default.  At 256 VGPRs the kernel holds 8 waves per CU either
     // way; as TWO independent 4-wave workgroups their barriers and load phases no longer coincide (one workgroup's gathers run under the
     // other's arithmetic), which a single 8-wave workgroup cannot do -- at the price of a larger halo share (TC_JOINT_TILE_H=16: the round-4 grid).
-    constexpr int DTW = 32, DTH = TC_JOINT_TILE_H, DNT = DTW * DTH;
+    constexpr int DTW = kJointTileW, DTH = kJointTileH, DNT = DTW * DTH;
     const int jtiles_x = (h->W + DTW - 1) / DTW, jtiles_y = (h->H + DTH - 1) / DTH;
-    const int nblk = jtiles_x * jtiles_y;              // workgroup records per target of the joint kernel
+    const int nblk = jtiles_x * jtiles_y;              // workgroup records per target of the joint kernel (= joint_tiles(h))
     const int nblk_lin = h->nblk;                      // ... and of k_linearize (the inverse pairs' systems, the FRONT launch)
-    if (nblk > h->nblk_alloc) return fail(h, TCSFM_E_ARG, "internal: the joint kernel's tile grid exceeds the scratch");
     const bool sel = o->argmin && S > 1, dc = o->w_dc > 0.f;
     if (!h->sel_maps) HIPCHK(h, hipMalloc((void **)&h->sel_maps, (size_t)2 * h->max_pairs * hw * sizeof(float)));
     if (!h->dense_rec) {
@@ -842,13 +849,12 @@ int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, 
     }
     // the reference's parametrisation (optimizer.py:194-198, 235-239): quarter-resolution unknown, x4 bilinear upsampling (dense_ref_kernel.h)
     const bool qres = !ex && o->depth_param == TCSFM_DEPTH_QUARTER;
-    const int nq = (h->H / 4) * (h->W / 4), nqblk = qres ? (nq + QRES_CELLS_PER_WG - 1) / QRES_CELLS_PER_WG : 0;
+    const int nq = (h->H / 4) * (h->W / 4), nqblk = qres ? qres_groups(h) : 0;
     if (qres && !h->qres_rho) {
         const size_t nb = (n + 1) / 2;
         HIPCHK(h, hipMalloc((void **)&h->qres_rho, 2 * nb * nq * sizeof(float)));       // (two buffers: k_qres_step_up ping-pongs)
         HIPCHK(h, hipMalloc((void **)&h->qres_rec, nq * joint_rec_floats(n) * sizeof(float)));
     }
-    if (qres && nblk + nqblk > 2 * h->nblk_alloc) return fail(h, TCSFM_E_ARG, "internal: quarter-resolution records exceed the scratch");
     if (!joint_scratch_fits<NS>(h, B, nblk + nqblk)) return fail(h, TCSFM_E_ARG, "internal: the joint dense scratch does not hold this many targets");
     // opts.free_source_depths: the inverse pairs as S B groups of one source (the joint kernel / solve / update on views offset by S B pairs)
     const bool free_src = !ex && o->free_source_depths != 0;
@@ -867,7 +873,7 @@ int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, 
     }
     // (the inverse groups' workgroup records follow the forward groups' in jblockrec: both joint launches of a linearisation run before the solve)
     const size_t jrec2_off = (size_t)B * (nblk + nqblk) * JL::NACC;
-    if (free_src && jrec2_off + (size_t)SB * (nblk + nqblk) * JointLayout<1>::NACC > 2 * (size_t)h->nblk_alloc * joint_blockrec_floats(n))
+    if (free_src && jrec2_off + (size_t)SB * (nblk + nqblk) * JointLayout<1>::NACC > (size_t)h->jrec_alloc * joint_blockrec_floats(n))
         return fail(h, TCSFM_E_ARG, "internal: the inverse groups' records exceed the scratch");
     tcsfm_opts oo = *o;
     oo.refine = TCSFM_REFINE_POSE;
@@ -1267,7 +1273,8 @@ int tcsfm_create(tcsfm_handle *out, int device, int H, int W, int max_pairs) {
     h->device = device; h->H = H; h->W = W; h->max_pairs = max_pairs;
     h->tiles_x = (W + TILE_W - 1) / TILE_W; h->tiles_y = (H + TILE_H - 1) / TILE_H; h->nblk = h->tiles_x * h->tiles_y;
     h->ngrp = (h->nblk + RG - 1) / RG;
-    h->nblk_alloc = ((W + 15) / 16) * ((H + 15) / 16);   // the finest tiling any kernel uses (dense mode, 16x16)
+    h->nblk_alloc = ((W + 15) / 16) * ((H + 15) / 16);   // the finest tiling of the pose path and the pair-form dense kernels (16 x 16); the
+                                                          // joint kernels' 32 x 8 tiles size their own scratch (joint_records_per_target)
     if (h->nblk_alloc < h->nblk) h->nblk_alloc = h->nblk;
     h->ngrp_alloc = (h->nblk_alloc + RG - 1) / RG;
     h->ngrp_pad = (h->ngrp_alloc + 63) / 64 * 64;
