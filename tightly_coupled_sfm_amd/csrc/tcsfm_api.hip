@@ -295,47 +295,63 @@ void apply_window_rule(const tcsfm_ctx *h, const tcsfm_opts *o, int win_B, int w
     }
 }
 
-// Stage a host array on the device (slot-indexed scratch that grows on demand) or pass a device pointer through.
-template <typename T>
-int to_dev(tcsfm_ctx *h, const tcsfm_opts *o, int slot, const T *p, size_t count, const T **out) {
-    if (!o->host_ptrs || !p) { *out = p; return TCSFM_OK; }
-    if ((int)h->stage.size() <= slot) h->stage.resize(slot + 1);
-    HostStage &s = h->stage[slot];
-    size_t bytes = count * sizeof(T);
-    if (s.cap < bytes) {
+// The array arguments of one call.  With opts.host_ptrs in() copies a host array to the device and out() hands out a device buffer
+// that finish() copies back to its host pointer; with device pointers both pass the pointer through.  The device buffers are the
+// handle's staging slots (grown on demand), taken in order of registration -- a null argument takes its slot too, so an argument's
+// slot does not depend on which optional arguments a call passes.  The first error sticks in rc: later steps do nothing.  Holds the
+// handle's device for the call and starts with the pending device-side error check.
+struct Staging {
+    tcsfm_ctx *h;
+    const tcsfm_opts *o;
+    DeviceGuard dev_guard;
+    int rc = TCSFM_OK;
+    size_t slot = 0;
+    struct Back { void *host; const void *dev; size_t bytes; };
+    std::vector<Back> back;
+
+    Staging(tcsfm_ctx *h_, const tcsfm_opts *o_) : h(h_), o(o_), dev_guard(h_->device) { rc = pending_error(h); }
+
+    // the next slot's device buffer, at least `bytes` long (null after an error)
+    void *scratch(size_t bytes) {
+        const size_t i = slot++;
+        if (rc) return nullptr;
+        if (h->stage.size() <= i) h->stage.resize(i + 1);
+        if (h->stage[i].cap < bytes) rc = grow(h->stage[i], bytes);
+        return rc ? nullptr : h->stage[i].p;
+    }
+    int grow(HostStage &s, size_t bytes) {
         if (s.p) HIPCHK(h, hipFree(s.p));
         s.p = nullptr; s.cap = 0;
         HIPCHK(h, hipMalloc(&s.p, bytes));
         s.cap = bytes;
+        return TCSFM_OK;
     }
-    HIPCHK(h, hipMemcpyAsync(s.p, p, bytes, hipMemcpyHostToDevice, h->stream));
-    *out = (const T *)s.p;
-    return TCSFM_OK;
-}
-
-// Output counterpart: returns a device buffer to write into; copy_back() moves it to the host pointer.
-template <typename T>
-int out_dev(tcsfm_ctx *h, const tcsfm_opts *o, int slot, T *p, size_t count, T **out) {
-    if (!o->host_ptrs || !p) { *out = p; return TCSFM_OK; }
-    if ((int)h->stage.size() <= slot) h->stage.resize(slot + 1);
-    HostStage &s = h->stage[slot];
-    size_t bytes = count * sizeof(T);
-    if (s.cap < bytes) {
-        if (s.p) HIPCHK(h, hipFree(s.p));
-        s.p = nullptr; s.cap = 0;
-        HIPCHK(h, hipMalloc(&s.p, bytes));
-        s.cap = bytes;
+    int upload(void *dev, const void *host, size_t bytes) {
+        HIPCHK(h, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream));
+        return TCSFM_OK;
     }
-    *out = (T *)s.p;
-    return TCSFM_OK;
-}
-
-template <typename T>
-int copy_back(tcsfm_ctx *h, const tcsfm_opts *o, T *host, const T *dev, size_t count) {
-    if (!o->host_ptrs || !host) return TCSFM_OK;
-    HIPCHK(h, hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    return TCSFM_OK;
-}
+    template <typename T>
+    const T *in(const T *p, size_t count) {
+        if (!o->host_ptrs || !p) { slot++; return p; }
+        void *d = scratch(count * sizeof(T));
+        if (d) rc = upload(d, p, count * sizeof(T));
+        return (const T *)d;
+    }
+    template <typename T>
+    T *out(T *p, size_t count) {
+        if (!o->host_ptrs || !p) { slot++; return p; }
+        void *d = scratch(count * sizeof(T));
+        if (d) back.push_back({p, d, count * sizeof(T)});
+        return (T *)d;
+    }
+    // the outputs' copies back, in registration order, then a synchronisation when `sync` and the call staged host arrays
+    int finish(bool sync = true) {
+        if (rc) return rc;
+        for (const Back &b : back) HIPCHK(h, hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, h->stream));
+        if (o->host_ptrs && sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+        return TCSFM_OK;
+    }
+};
 
 // intrinsics must be pinhole; checked on the host when they are host pointers, otherwise after a small D2H copy
 int check_intrinsics(tcsfm_ctx *h, const tcsfm_opts *o, const float *K_host_or_dev, int n) {
@@ -628,6 +644,29 @@ bool joint_scratch_fits(const tcsfm_ctx *h, int B, int recs_per_target) {
            recs_per_target <= h->jrec_alloc && (size_t)B * recs_per_target * JL::NACC <= (size_t)h->jrec_alloc * joint_blockrec_floats(n);
 }
 
+// Scratch of the dense modes, allocated on first use by whichever mode needs it (dense_body, dense_joint_run, dense_ref_run).  Like the joint
+// scratch above it is never freed or re-sized while the handle lives: captured call graphs bake the pointers in.
+int ensure_dense_rec(tcsfm_ctx *h) {        // per-pixel records, prior centres and steps of the pair-form dense kernels
+    if (h->dense_rec) return TCSFM_OK;
+    const size_t hw = (size_t)h->H * h->W, n = h->max_pairs;
+    HIPCHK(h, hipMalloc((void **)&h->dense_rec, n * hw * 8 * sizeof(float)));
+    HIPCHK(h, hipMalloc((void **)&h->depth0, n * hw * sizeof(float)));
+    HIPCHK(h, hipMalloc((void **)&h->delta, n * 8 * sizeof(double)));
+    return TCSFM_OK;
+}
+int ensure_dense_lm(tcsfm_ctx *h) {         // dense LM: accepted per-pixel records / depth maps, accept flags
+    if (h->dense_rec_acc) return TCSFM_OK;
+    const size_t hw = (size_t)h->H * h->W, n = h->max_pairs;
+    HIPCHK(h, hipMalloc((void **)&h->dense_rec_acc, n * hw * 8 * sizeof(float)));
+    HIPCHK(h, hipMalloc((void **)&h->depth_acc, n * hw * sizeof(float)));
+    HIPCHK(h, hipMalloc((void **)&h->lm_accept, n * sizeof(int)));
+    return TCSFM_OK;
+}
+int ensure_sel_maps(tcsfm_ctx *h) {         // the forward pairs' diff | valid maps
+    if (!h->sel_maps) HIPCHK(h, hipMalloc((void **)&h->sel_maps, (size_t)2 * h->max_pairs * h->H * h->W * sizeof(float)));
+    return TCSFM_OK;
+}
+
 // JOINT dense mode of a window (include/tcsfm.h, tcsfm_refine_dense_window): the S forward pairs of every target share one depth map
 // and are solved together (k_dense_joint / k_solve_joint / k_dense_joint_update); the inverse pairs run the pair-form dense kernels on
 // offset views of the same scratch.  Inputs already on the device.
@@ -647,19 +686,7 @@ int dense_joint_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt
     // LEAN form of the kernel (161 VGPRs: three workgroups per CU instead of one 512-thread workgroup at 212-232)
     constexpr int JTW = kJointTileW, JTH = kJointTileH, JNT = JTW * JTH;
     const int jtiles_x = (h->W + JTW - 1) / JTW, jtiles_y = (h->H + JTH - 1) / JTH, jnblk = jtiles_x * jtiles_y;      // = joint_tiles(h)
-    if (n_sel && !h->sel_maps) HIPCHK(h, hipMalloc((void **)&h->sel_maps, (size_t)2 * h->max_pairs * hw * sizeof(float)));
-    if (!h->dense_rec) {
-        HIPCHK(h, hipMalloc((void **)&h->dense_rec, n * hw * 8 * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->depth0, n * hw * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->delta, n * 8 * sizeof(double)));
-    }
-    if (lm && !h->dense_rec_acc) {
-        HIPCHK(h, hipMalloc((void **)&h->dense_rec_acc, n * hw * 8 * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->depth_acc, n * hw * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->lm_accept, n * sizeof(int)));
-    }
-    if ((rc = joint_scratch(h))) return rc;
-    if (lm && !h->lm_accept) HIPCHK(h, hipMalloc((void **)&h->lm_accept, n * sizeof(int)));
+    if ((n_sel && (rc = ensure_sel_maps(h))) || (rc = ensure_dense_rec(h)) || (lm && (rc = ensure_dense_lm(h))) || (rc = joint_scratch(h))) return rc;
     if ((size_t)nblk > (size_t)h->nblk_alloc) return fail(h, TCSFM_E_ARG, "internal: dense tile grid exceeds scratch");
     if (!joint_scratch_fits<NS>(h, B, jnblk)) return fail(h, TCSFM_E_ARG, "internal: the joint dense scratch does not hold this many targets");
     tcsfm_opts oo = *o;
@@ -834,13 +861,7 @@ int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, 
     const int nblk = jtiles_x * jtiles_y;              // workgroup records per target of the joint kernel (= joint_tiles(h))
     const int nblk_lin = h->nblk;                      // ... and of k_linearize (the inverse pairs' systems, the FRONT launch)
     const bool sel = o->argmin && S > 1, dc = o->w_dc > 0.f;
-    if (!h->sel_maps) HIPCHK(h, hipMalloc((void **)&h->sel_maps, (size_t)2 * h->max_pairs * hw * sizeof(float)));
-    if (!h->dense_rec) {
-        HIPCHK(h, hipMalloc((void **)&h->dense_rec, n * hw * 8 * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->depth0, n * hw * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->delta, n * 8 * sizeof(double)));
-    }
-    if ((rc = joint_scratch(h))) return rc;
+    if ((rc = ensure_sel_maps(h)) || (rc = ensure_dense_rec(h)) || (rc = joint_scratch(h))) return rc;
     if (!h->dref_norms) {
         HIPCHK(h, hipMalloc((void **)&h->dref_norms, 2 * TC_MAX_COAL * sizeof(int)));             // (one (K_f, K_i) pair per normaliser group)
         HIPCHK(h, hipMalloc((void **)&h->dref_ext, ((n + 1) / 2) * hw * 2 * sizeof(long long)));  // (targets <= max_pairs / 2; two sums per pixel)
@@ -1221,6 +1242,8 @@ int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, 
     h->dref_dirty = o->n_iters == 0;      // (every linearisation's sums were consumed and cleared; with no iteration the pack's zeroed counters are all there is)
     return TCSFM_OK;
 }
+// dense_ref_run of a window with S = 1 .. JMAXS sources: dense_ref_runs[S - 1]
+constexpr decltype(&dense_ref_run<1>) dense_ref_runs[JMAXS] = {dense_ref_run<1>, dense_ref_run<2>, dense_ref_run<3>, dense_ref_run<4>};
 
 }  // namespace
 
@@ -1342,7 +1365,7 @@ void tcsfm_destroy(tcsfm_handle h) {
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
     void *ptrs[] = {h->stamp_buf, h->tgtpack, h->srcpack, h->depth_work, h->partials, h->blockrec, h->tickets, h->state, h->pconst, h->lin_out,
                     h->jrec, h->jrec_acc, h->jblockrec, h->jdepth_acc, h->jstate, h->jdelta, h->jpart, h->jtick, h->dref_norms, h->dref_ext, h->dref_export, h->qres_rho, h->qres_rec, h->pose_lin, h->dref_smooth, h->jrec_src, h->jstate_src, h->jdelta_src, h->dref_ext_src, h->qres_rho_src, h->qres_rec_src,
-                    h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept,
+                    h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept, h->dbg_stamps,
                     h->seq_fpack, h->seq_fdepth, h->pair_idx, h->seq_img, h->seq_depth, h->seq_pose_in, h->seq_pose_out, h->seq_ls_out, h->seq_K, h->seq_dense, h->seq_dense_tmp};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -1390,39 +1413,28 @@ int tcsfm_disp_to_depth(tcsfm_handle h, const tcsfm_opts *o, int64_t n, const fl
     if (!h) return TCSFM_E_ARG;
     if (!o || !disp || n < 1) return fail(h, TCSFM_E_ARG, "tcsfm_disp_to_depth: bad argument");
     if (!(o->min_depth > 0 && o->max_depth > o->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
-    const float *d_in; float *d_s, *d_d;
-    int rc;
-    if ((rc = to_dev(h, o, 0, disp, (size_t)n, &d_in))) return rc;
-    if ((rc = out_dev(h, o, 1, scaled, (size_t)n, &d_s))) return rc;
-    if ((rc = out_dev(h, o, 2, depth, (size_t)n, &d_d))) return rc;
+    Staging st(h, o);
+    const float *d_in = st.in(disp, (size_t)n);
+    float *d_s = st.out(scaled, (size_t)n), *d_d = st.out(depth, (size_t)n);
+    if (st.rc) return st.rc;
     hipLaunchKernelGGL(k_disp_to_depth, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, d_in, d_s, d_d, (long long)n,
                        1.f / o->max_depth, 1.f / o->min_depth);
     HIPCHK(h, hipGetLastError());
-    if ((rc = copy_back(h, o, scaled, d_s, (size_t)n))) return rc;
-    if ((rc = copy_back(h, o, depth, d_d, (size_t)n))) return rc;
-    if (o->host_ptrs) HIPCHK(h, hipStreamSynchronize(h->stream));
-    return TCSFM_OK;
+    return st.finish();
 }
 
 int tcsfm_ssim(tcsfm_handle h, const tcsfm_opts *o, int planes, const float *x, const float *y, float *out) {
     if (int rc_q = drain_queued(h)) return rc_q;
     if (!h) return TCSFM_E_ARG;
     if (!o || !x || !y || !out || planes < 1) return fail(h, TCSFM_E_ARG, "tcsfm_ssim: bad argument");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
     size_t hw = (size_t)h->H * h->W, n = hw * planes;
-    const float *d_x, *d_y; float *d_o;
-    int rc;
-    if ((rc = to_dev(h, o, 0, x, n, &d_x))) return rc;
-    if ((rc = to_dev(h, o, 1, y, n, &d_y))) return rc;
-    if ((rc = out_dev(h, o, 2, out, n, &d_o))) return rc;
+    const float *d_x = st.in(x, n), *d_y = st.in(y, n);
+    float *d_o = st.out(out, n);
+    if (st.rc) return st.rc;
     hipLaunchKernelGGL(k_ssim, dim3((unsigned)((hw + 255) / 256), planes), dim3(256), 0, h->stream, d_x, d_y, d_o, h->H, h->W);
     HIPCHK(h, hipGetLastError());
-    if ((rc = copy_back(h, o, out, d_o, n))) return rc;
-    if (o->host_ptrs) HIPCHK(h, hipStreamSynchronize(h->stream));
-    return TCSFM_OK;
+    return st.finish();
 }
 
 int tcsfm_warp(tcsfm_handle h, const tcsfm_opts *o, int N, const float *src, const float *depth_t, const float *depth_s,
@@ -1431,22 +1443,15 @@ int tcsfm_warp(tcsfm_handle h, const tcsfm_opts *o, int N, const float *src, con
     int rc = check_common(h, o, N);
     if (rc) return rc;
     if (!src || !depth_t || !depth_s || !pose || !K) return fail(h, TCSFM_E_ARG, "tcsfm_warp: NULL input");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
+    if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
-    size_t hw = (size_t)h->H * h->W;
-    const float *d_src, *d_dt, *d_ds, *d_pose, *d_K;
-    float *d_rec, *d_valid, *d_pd, *d_cd;
-    if ((rc = to_dev(h, o, 0, src, N * 3 * hw, &d_src))) return rc;
-    if ((rc = to_dev(h, o, 1, depth_t, N * hw, &d_dt))) return rc;
-    if ((rc = to_dev(h, o, 2, depth_s, N * hw, &d_ds))) return rc;
-    if ((rc = to_dev(h, o, 3, pose, (size_t)N * 6, &d_pose))) return rc;
-    if ((rc = to_dev(h, o, 4, K, (size_t)N * 9, &d_K))) return rc;
-    if ((rc = out_dev(h, o, 5, img_rec, N * 3 * hw, &d_rec))) return rc;
-    if ((rc = out_dev(h, o, 6, valid, N * hw, &d_valid))) return rc;
-    if ((rc = out_dev(h, o, 7, proj_depth, N * hw, &d_pd))) return rc;
-    if ((rc = out_dev(h, o, 8, comp_depth, N * hw, &d_cd))) return rc;
     if (o->depth_is_disp) return fail(h, TCSFM_E_ARG, "tcsfm_warp takes depth maps (call tcsfm_disp_to_depth first)");
+    size_t hw = (size_t)h->H * h->W;
+    const float *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
+    const float *d_pose = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
+    float *d_rec = st.out(img_rec, N * 3 * hw), *d_valid = st.out(valid, N * hw), *d_pd = st.out(proj_depth, N * hw), *d_cd = st.out(comp_depth, N * hw);
+    if (st.rc) return st.rc;
     if ((rc = run_init(h, o, N, d_pose, nullptr, d_K, 0))) return rc;
     WarpParams P;
     P.src = d_src; P.depth_t = d_dt; P.depth_s = d_ds; P.pc = h->pconst;
@@ -1454,12 +1459,7 @@ int tcsfm_warp(tcsfm_handle h, const tcsfm_opts *o, int N, const float *src, con
     P.tgt = nullptr; P.posenet_in = nullptr; P.win_B = 0; P.win_S = 0;
     hipLaunchKernelGGL(k_warp, dim3((unsigned)((hw + 255) / 256), N), dim3(256), 0, h->stream, P);
     HIPCHK(h, hipGetLastError());
-    if ((rc = copy_back(h, o, img_rec, d_rec, N * 3 * hw))) return rc;
-    if ((rc = copy_back(h, o, valid, d_valid, N * hw))) return rc;
-    if ((rc = copy_back(h, o, proj_depth, d_pd, N * hw))) return rc;
-    if ((rc = copy_back(h, o, comp_depth, d_cd, N * hw))) return rc;
-    if (o->host_ptrs) HIPCHK(h, hipStreamSynchronize(h->stream));
-    return TCSFM_OK;
+    return st.finish();
 }
 
 int tcsfm_warp_posenet_input(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *src, const float *depth_t,
@@ -1469,20 +1469,14 @@ int tcsfm_warp_posenet_input(tcsfm_handle h, const tcsfm_opts *o, int N, const f
     if (rc) return rc;
     if (!tgt || !src || !depth_t || !depth_s || !pose || !K || !posenet_in) return fail(h, TCSFM_E_ARG, "tcsfm_warp_posenet_input: NULL argument");
     if (o->depth_is_disp) return fail(h, TCSFM_E_ARG, "tcsfm_warp_posenet_input takes depth maps");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
+    if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt, *d_src, *d_dt, *d_ds, *d_pose, *d_K;
-    float *d_out, *d_valid;
-    if ((rc = to_dev(h, o, 0, tgt, N * 3 * hw, &d_tgt))) return rc;
-    if ((rc = to_dev(h, o, 1, src, N * 3 * hw, &d_src))) return rc;
-    if ((rc = to_dev(h, o, 2, depth_t, N * hw, &d_dt))) return rc;
-    if ((rc = to_dev(h, o, 3, depth_s, N * hw, &d_ds))) return rc;
-    if ((rc = to_dev(h, o, 4, pose, (size_t)N * 6, &d_pose))) return rc;
-    if ((rc = to_dev(h, o, 5, K, (size_t)N * 9, &d_K))) return rc;
-    if ((rc = out_dev(h, o, 6, posenet_in, N * 6 * hw, &d_out))) return rc;
-    if ((rc = out_dev(h, o, 7, valid, N * hw, &d_valid))) return rc;
+    const float *d_tgt = st.in(tgt, N * 3 * hw), *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
+    const float *d_pose = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
+    float *d_out = st.out(posenet_in, N * 6 * hw), *d_valid = st.out(valid, N * hw);
+    if (st.rc) return st.rc;
     if ((rc = run_init(h, o, N, d_pose, nullptr, d_K, 0))) return rc;
     WarpParams P;
     P.src = d_src; P.depth_t = d_dt; P.depth_s = d_ds; P.pc = h->pconst;
@@ -1490,10 +1484,7 @@ int tcsfm_warp_posenet_input(tcsfm_handle h, const tcsfm_opts *o, int N, const f
     P.win_B = 0; P.win_S = 0;
     hipLaunchKernelGGL(k_warp, dim3((unsigned)((hw + 255) / 256), N), dim3(256), 0, h->stream, P);
     HIPCHK(h, hipGetLastError());
-    if ((rc = copy_back(h, o, posenet_in, d_out, N * 6 * hw))) return rc;
-    if ((rc = copy_back(h, o, valid, d_valid, N * hw))) return rc;
-    if (o->host_ptrs) HIPCHK(h, hipStreamSynchronize(h->stream));
-    return TCSFM_OK;
+    return st.finish();
 }
 
 int tcsfm_photometric(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *src, const float *depth_t,
@@ -1503,30 +1494,22 @@ int tcsfm_photometric(tcsfm_handle h, const tcsfm_opts *o, int N, const float *t
     int rc = check_common(h, o, N);
     if (rc) return rc;
     if (!tgt || !src || !depth_t || !depth_s || !pose || !K) return fail(h, TCSFM_E_ARG, "tcsfm_photometric: NULL input");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
+    if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt, *d_src, *d_dt, *d_ds, *d_pose, *d_K;
-    if ((rc = to_dev(h, o, 0, tgt, N * 3 * hw, &d_tgt))) return rc;
-    if ((rc = to_dev(h, o, 1, src, N * 3 * hw, &d_src))) return rc;
-    if ((rc = to_dev(h, o, 2, depth_t, N * hw, &d_dt))) return rc;
-    if ((rc = to_dev(h, o, 3, depth_s, N * hw, &d_ds))) return rc;
-    if ((rc = to_dev(h, o, 4, pose, (size_t)N * 6, &d_pose))) return rc;
-    if ((rc = to_dev(h, o, 5, K, (size_t)N * 9, &d_K))) return rc;
+    const float *d_tgt = st.in(tgt, N * 3 * hw), *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
+    const float *d_pose = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
     float *outs[6] = {diff, valid, weight, auto_err, auto_mask, img_rec}, *d_out[6];
-    for (int i = 0; i < 6; i++)
-        if ((rc = out_dev(h, o, 6 + i, outs[i], (i == 5 ? 3 : 1) * N * hw, &d_out[i]))) return rc;
+    for (int i = 0; i < 6; i++) d_out[i] = st.out(outs[i], (i == 5 ? 3 : 1) * N * hw);
+    if (st.rc) return st.rc;
     if ((rc = run_pack(h, o, N, d_tgt, d_src, d_dt, d_ds))) return rc;
     if ((rc = run_init(h, o, N, d_pose, nullptr, d_K, 0))) return rc;
     LinParams P = lin_params(h, o, 6);
     P.o_diff = d_out[0]; P.o_valid = d_out[1]; P.o_weight = d_out[2]; P.o_auto_err = d_out[3]; P.o_auto_mask = d_out[4]; P.o_rec = d_out[5];
     launch_lin(h, P, N, 6, false, MODE_MAPS);
     HIPCHK(h, hipGetLastError());
-    for (int i = 0; i < 6; i++)
-        if ((rc = copy_back(h, o, outs[i], d_out[i], (i == 5 ? 3 : 1) * N * hw))) return rc;
-    if (o->host_ptrs) HIPCHK(h, hipStreamSynchronize(h->stream));
-    return TCSFM_OK;
+    return st.finish();
 }
 
 // shared by tcsfm_linearize and tcsfm_loss_surface: one evaluation at given poses, results to host doubles
@@ -1551,6 +1534,17 @@ static int eval_once(tcsfm_ctx *h, const tcsfm_opts *o, int N, int Nimg, const f
     return TCSFM_OK;
 }
 
+// the per-pair records of a linearisation (k_solve mode 2: H [np][np], g [np], 4 statistics) into the caller's arrays (each optional)
+static void unpack_lin_records(const std::vector<double> &host, int N, int np, double *Hmat, double *g, double *stats) {
+    const int rec = np * np + np + 4;
+    for (int n = 0; n < N; n++) {
+        const double *r = &host[(size_t)n * rec];
+        if (Hmat) memcpy(Hmat + (size_t)n * np * np, r, sizeof(double) * np * np);
+        if (g) memcpy(g + (size_t)n * np, r + np * np, sizeof(double) * np);
+        if (stats) memcpy(stats + (size_t)n * 4, r + np * np + np, sizeof(double) * 4);
+    }
+}
+
 int tcsfm_linearize(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *src, const float *depth_t,
                     const float *depth_s, const float *pose, const float *log_scale, const float *K, double *Hmat, double *g,
                     double *stats) {
@@ -1558,27 +1552,16 @@ int tcsfm_linearize(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt
     int rc = check_common(h, o, N);
     if (rc) return rc;
     if (!tgt || !src || !depth_t || !depth_s || !pose || !K) return fail(h, TCSFM_E_ARG, "tcsfm_linearize: NULL input");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
+    if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt, *d_src, *d_dt, *d_ds, *d_pose, *d_K, *d_ls;
-    if ((rc = to_dev(h, o, 0, tgt, N * 3 * hw, &d_tgt))) return rc;
-    if ((rc = to_dev(h, o, 1, src, N * 3 * hw, &d_src))) return rc;
-    if ((rc = to_dev(h, o, 2, depth_t, N * hw, &d_dt))) return rc;
-    if ((rc = to_dev(h, o, 3, depth_s, N * hw, &d_ds))) return rc;
-    if ((rc = to_dev(h, o, 4, pose, (size_t)N * 6, &d_pose))) return rc;
-    if ((rc = to_dev(h, o, 5, K, (size_t)N * 9, &d_K))) return rc;
-    if ((rc = to_dev(h, o, 6, log_scale, (size_t)N, &d_ls))) return rc;
+    const float *d_tgt = st.in(tgt, N * 3 * hw), *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
+    const float *d_pose = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9), *d_ls = st.in(log_scale, (size_t)N);
+    if (st.rc) return st.rc;
     std::vector<double> host;
     if ((rc = eval_once(h, o, N, N, d_tgt, d_src, d_dt, d_ds, d_pose, d_ls, d_K, MODE_LIN, host))) return rc;
-    int np = np_of(o), rec = np * np + np + 4;
-    for (int n = 0; n < N; n++) {
-        const double *r = &host[(size_t)n * rec];
-        if (Hmat) memcpy(Hmat + (size_t)n * np * np, r, sizeof(double) * np * np);
-        if (g) memcpy(g + (size_t)n * np, r + np * np, sizeof(double) * np);
-        if (stats) memcpy(stats + (size_t)n * 4, r + np * np + np, sizeof(double) * 4);
-    }
+    unpack_lin_records(host, N, np_of(o), Hmat, g, stats);
     return TCSFM_OK;
 }
 
@@ -1592,19 +1575,15 @@ int tcsfm_linearize_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, co
     int rc = check_common(h, o, N);
     if (rc) return rc;
     if (!tgt || !srcs || !depth_t || !depth_s || !pose || !K) return fail(h, TCSFM_E_ARG, "tcsfm_linearize_window: NULL input");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
+    if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, B))) return rc;
     const size_t hw = (size_t)h->H * h->W;
     const int np = np_of(o);
-    const float *d_tgt, *d_src, *d_dt, *d_ds, *d_K, *d_pose, *d_ls;
-    if ((rc = to_dev(h, o, 0, tgt, B * 3 * hw, &d_tgt))) return rc;
-    if ((rc = to_dev(h, o, 1, srcs, (size_t)B * S * 3 * hw, &d_src))) return rc;
-    if ((rc = to_dev(h, o, 2, depth_t, B * hw, &d_dt))) return rc;
-    if ((rc = to_dev(h, o, 3, depth_s, (size_t)B * S * hw, &d_ds))) return rc;
-    if ((rc = to_dev(h, o, 4, K, (size_t)B * 9, &d_K))) return rc;
-    if ((rc = to_dev(h, o, 5, pose, (size_t)N * 6, &d_pose))) return rc;
-    if ((rc = to_dev(h, o, 6, log_scale, (size_t)N, &d_ls))) return rc;
+    const float *d_tgt = st.in(tgt, B * 3 * hw), *d_src = st.in(srcs, (size_t)B * S * 3 * hw), *d_dt = st.in(depth_t, B * hw);
+    const float *d_ds = st.in(depth_s, (size_t)B * S * hw), *d_K = st.in(K, (size_t)B * 9), *d_pose = st.in(pose, (size_t)N * 6);
+    const float *d_ls = st.in(log_scale, (size_t)N);
+    if (st.rc) return st.rc;
     InitParams I = init_params(h, o, N, d_pose, np == 7 ? d_ls : nullptr, d_K, 0);
     I.K_mod = B;
     if ((rc = run_pack(h, o, N, d_tgt, d_src, d_dt, d_ds, &I, B, S))) return rc;
@@ -1616,16 +1595,10 @@ int tcsfm_linearize_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, co
     Sv.mode = 2;
     launch_solve(h, Sv, N, np);
     HIPCHK(h, hipGetLastError());
-    const int rec = np * np + np + 4;
-    std::vector<double> host((size_t)N * rec);
+    std::vector<double> host((size_t)N * (np * np + np + 4));
     HIPCHK(h, hipMemcpyAsync(host.data(), h->lin_out, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int n = 0; n < N; n++) {
-        const double *r = &host[(size_t)n * rec];
-        if (Hmat) memcpy(Hmat + (size_t)n * np * np, r, sizeof(double) * np * np);
-        if (g) memcpy(g + (size_t)n * np, r + np * np, sizeof(double) * np);
-        if (stats) memcpy(stats + (size_t)n * 4, r + np * np + np, sizeof(double) * 4);
-    }
+    unpack_lin_records(host, N, np, Hmat, g, stats);
     return TCSFM_OK;
 }
 
@@ -1635,17 +1608,13 @@ int tcsfm_loss_surface(tcsfm_handle h, const tcsfm_opts *o, const float *tgt, co
     int rc = check_common(h, o, P);
     if (rc) return rc;
     if (!tgt || !src || !depth_t || !depth_s || !poses || !K || !cost_out) return fail(h, TCSFM_E_ARG, "tcsfm_loss_surface: NULL argument");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
+    if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, 1))) return rc;
     size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt, *d_src, *d_dt, *d_ds, *d_pose, *d_K;
-    if ((rc = to_dev(h, o, 0, tgt, 3 * hw, &d_tgt))) return rc;
-    if ((rc = to_dev(h, o, 1, src, 3 * hw, &d_src))) return rc;
-    if ((rc = to_dev(h, o, 2, depth_t, hw, &d_dt))) return rc;
-    if ((rc = to_dev(h, o, 3, depth_s, hw, &d_ds))) return rc;
-    if ((rc = to_dev(h, o, 4, poses, (size_t)P * 6, &d_pose))) return rc;
-    if ((rc = to_dev(h, o, 5, K, (size_t)9, &d_K))) return rc;
+    const float *d_tgt = st.in(tgt, 3 * hw), *d_src = st.in(src, 3 * hw), *d_dt = st.in(depth_t, hw), *d_ds = st.in(depth_s, hw);
+    const float *d_pose = st.in(poses, (size_t)P * 6), *d_K = st.in(K, (size_t)9);
+    if (st.rc) return st.rc;
     std::vector<double> host;
     tcsfm_opts oo = *o;
     oo.refine = TCSFM_REFINE_POSE;
@@ -1669,28 +1638,20 @@ static int refine_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, in
         tgt = ct->tgt[0]; src = ct->src[0]; depth_t = ct->dt[0]; depth_s = ct->ds[0]; K = ct->K[0]; pose_in = ct->pose[0]; pose_out = ct_out[0];
     }
     if (!tgt || !src || !depth_t || !depth_s || !pose_in || !pose_out || !K) return fail(h, TCSFM_E_ARG, "tcsfm_refine: NULL input");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
+    if (st.rc) return st.rc;
     const int nimg_t = ct ? ct->cB : (win_B ? win_B : N), nimg_s = ct ? ct->cB * ct->cS : (win_B ? win_B * win_S : N);   // image sets behind tgt / src
     if (!ct && (rc = check_intrinsics(h, o, K, nimg_t))) return rc;
     const size_t hw = (size_t)h->H * h->W;
     const int np = np_of(o);
-    const float *d_tgt, *d_src, *d_dt, *d_ds, *d_K, *d_pose_in, *d_ls_in;
-    if ((rc = to_dev(h, o, 0, tgt, nimg_t * 3 * hw, &d_tgt))) return rc;
-    if ((rc = to_dev(h, o, 1, src, nimg_s * 3 * hw, &d_src))) return rc;
-    if ((rc = to_dev(h, o, 2, depth_t, nimg_t * hw, &d_dt))) return rc;
-    if ((rc = to_dev(h, o, 3, depth_s, nimg_s * hw, &d_ds))) return rc;
-    if ((rc = to_dev(h, o, 4, K, (size_t)nimg_t * 9, &d_K))) return rc;
-    if ((rc = to_dev(h, o, 5, pose_in, (size_t)N * 6, &d_pose_in))) return rc;
-    if ((rc = to_dev(h, o, 6, log_scale_in, (size_t)N, &d_ls_in))) return rc;
-    float *d_pose_out, *d_ls_out = nullptr, *d_stats = nullptr;
-    if ((rc = out_dev(h, o, 7, pose_out, (size_t)N * 6, &d_pose_out))) return rc;
-    if (np == 7 && log_scale_out && (rc = out_dev(h, o, 8, log_scale_out, (size_t)N, &d_ls_out))) return rc;
+    const float *d_tgt = st.in(tgt, nimg_t * 3 * hw), *d_src = st.in(src, nimg_s * 3 * hw), *d_dt = st.in(depth_t, nimg_t * hw);
+    const float *d_ds = st.in(depth_s, nimg_s * hw), *d_K = st.in(K, (size_t)nimg_t * 9), *d_pose_in = st.in(pose_in, (size_t)N * 6);
+    const float *d_ls_in = st.in(log_scale_in, (size_t)N);
     const size_t nstats = (size_t)N * (o->n_iters + 1) * TCSFM_NSTAT;
-    if (stats_out) {
-        if ((rc = out_dev(h, o, 9, stats_out, nstats, &d_stats))) return rc;
-        HIPCHK(h, hipMemsetAsync(d_stats, 0, nstats * sizeof(float), h->stream));
-    }
+    float *d_pose_out = st.out(pose_out, (size_t)N * 6), *d_ls_out = st.out(np == 7 ? log_scale_out : nullptr, (size_t)N);
+    float *d_stats = st.out(stats_out, nstats);
+    if (st.rc) return st.rc;
+    if (d_stats) HIPCHK(h, hipMemsetAsync(d_stats, 0, nstats * sizeof(float), h->stream));
     // per-pixel min over the sources: the forward pairs also evaluate the other sources' residuals (k_linearize<SEL>)
     const int n_sel = (win_B && win_S > 1 && o->argmin) ? win_B * win_S : 0;
 
@@ -1752,11 +1713,7 @@ static int refine_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, in
         hipLaunchKernelGGL(k_finish, dim3((N + 63) / 64), dim3(64), 0, h->stream, F);
         HIPCHK(h, hipGetLastError());
     }
-    if ((rc = copy_back(h, o, pose_out, d_pose_out, (size_t)N * 6))) return rc;
-    if (d_ls_out && (rc = copy_back(h, o, log_scale_out, d_ls_out, (size_t)N))) return rc;
-    if ((rc = copy_back(h, o, stats_out, d_stats, nstats))) return rc;
-    if (o->host_ptrs == 1) HIPCHK(h, hipStreamSynchronize(h->stream));   // host_ptrs == 2: pinned + asynchronous, the caller synchronises
-    return TCSFM_OK;
+    return st.finish(o->host_ptrs == 1);   // host_ptrs == 2: pinned + asynchronous, the caller synchronises
 }
 
 // Graph replay (tcsfm_set_graph_replay).  A B = 1 refinement is nine short launches: ~42 us of host time against ~40 us of GPU time
@@ -1872,22 +1829,17 @@ int tcsfm_scale_recovery(tcsfm_handle h, const tcsfm_opts *o, int N, const float
     if (rc) return rc;
     if (!depth || !K || !scale_out) return fail(h, TCSFM_E_ARG, "tcsfm_scale_recovery: NULL argument");
     if (h->H < 5 || h->W < 5) return fail(h, TCSFM_E_ARG, "tcsfm_scale_recovery: image too small");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
+    if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     const size_t hw = (size_t)h->H * h->W;
     if (!h->scale_keys) {
         HIPCHK(h, hipMalloc((void **)&h->scale_keys, (size_t)h->max_pairs * hw * sizeof(unsigned)));
         HIPCHK(h, hipMalloc((void **)&h->scale_hist, 260 * sizeof(unsigned)));
     }
-    const float *d_depth, *d_K;
-    float *d_scale, *d_med, *d_h, *d_m;
-    if ((rc = to_dev(h, o, 0, depth, N * hw, &d_depth))) return rc;
-    if ((rc = to_dev(h, o, 1, K, (size_t)N * 9, &d_K))) return rc;
-    if ((rc = out_dev(h, o, 2, scale_out, (size_t)1, &d_scale))) return rc;
-    if ((rc = out_dev(h, o, 3, median_out, (size_t)1, &d_med))) return rc;
-    if ((rc = out_dev(h, o, 4, height_out, N * hw, &d_h))) return rc;
-    if ((rc = out_dev(h, o, 5, mask_out, N * hw, &d_m))) return rc;
+    const float *d_depth = st.in(depth, N * hw), *d_K = st.in(K, (size_t)N * 9);
+    float *d_scale = st.out(scale_out, (size_t)1), *d_med = st.out(median_out, (size_t)1), *d_h = st.out(height_out, N * hw), *d_m = st.out(mask_out, N * hw);
+    if (st.rc) return st.rc;
     HIPCHK(h, hipMemsetAsync(h->scale_hist, 0, 260 * sizeof(unsigned), h->stream));
     GroundParams G;
     G.depth = d_depth; G.K = d_K; G.height = d_h; G.mask = d_m; G.keys = h->scale_keys; G.H = h->H; G.W = h->W; G.err = h->err_dev;
@@ -1902,12 +1854,7 @@ int tcsfm_scale_recovery(tcsfm_handle h, const tcsfm_opts *o, int N, const float
         hipLaunchKernelGGL(k_sel_pick, dim3(1), dim3(64), 0, h->stream, hist, state, shift, real_cam_height, d_scale, d_med);
     }
     HIPCHK(h, hipGetLastError());
-    if ((rc = copy_back(h, o, scale_out, d_scale, (size_t)1))) return rc;
-    if ((rc = copy_back(h, o, median_out, d_med, (size_t)1))) return rc;
-    if ((rc = copy_back(h, o, height_out, d_h, N * hw))) return rc;
-    if ((rc = copy_back(h, o, mask_out, d_m, N * hw))) return rc;
-    if (o->host_ptrs) HIPCHK(h, hipStreamSynchronize(h->stream));
-    return TCSFM_OK;
+    return st.finish();
 }
 
 int tcsfm_smooth_loss(tcsfm_handle h, const tcsfm_opts *o, int N, const float *disp, const float *img, double *loss_out) {
@@ -1916,19 +1863,13 @@ int tcsfm_smooth_loss(tcsfm_handle h, const tcsfm_opts *o, int N, const float *d
     if (rc) return rc;
     if (!disp || !img || !loss_out) return fail(h, TCSFM_E_ARG, "tcsfm_smooth_loss: NULL argument");
     if (h->H < 2 || h->W < 2) return fail(h, TCSFM_E_ARG, "tcsfm_smooth_loss: image too small");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
     const size_t hw = (size_t)h->H * h->W;
     const int nb = (int)((hw + 255) / 256);
-    const float *d_disp, *d_img;
-    if ((rc = to_dev(h, o, 0, disp, N * hw, &d_disp))) return rc;
-    if ((rc = to_dev(h, o, 1, img, N * 3 * hw, &d_img))) return rc;
-    // scratch: N means (double) + N * nb * 2 partial sums, carved from the staging slot 2
-    float *scratch;
-    tcsfm_opts os = *o; os.host_ptrs = 1;
-    const size_t nfl = (size_t)N * 2 + (size_t)N * nb * 2;
-    float dummy;
-    if ((rc = out_dev(h, &os, 2, &dummy, nfl, &scratch))) return rc;
+    const float *d_disp = st.in(disp, N * hw), *d_img = st.in(img, N * 3 * hw);
+    // scratch: N means (double) + N * nb * 2 partial sums, carved from the next staging slot
+    float *scratch = (float *)st.scratch(((size_t)N * 2 + (size_t)N * nb * 2) * sizeof(float));
+    if (st.rc) return st.rc;
     double *mean = reinterpret_cast<double *>(scratch);
     float *partial = scratch + (size_t)N * 2;
     hipLaunchKernelGGL(k_smooth_mean, dim3(N), dim3(1024), 0, h->stream, d_disp, (int)hw, mean);
@@ -1969,8 +1910,8 @@ static int dense_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int
         return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: depth_param QUARTER needs window_rule = TCSFM_WINDOW_REFERENCE (window form) and H, W multiples of 4");
     if (o->param != TCSFM_PARAM_SE3) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: SE(3) chart only");
     if (!(o->min_depth > 0 && o->max_depth > o->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
+    if (st.rc) return st.rc;
     const int nimg_t = ct ? ct->cB : (win_B ? win_B : N), nimg_s = ct ? ct->cB * ct->cS : (win_B ? win_B * win_S : N);   // image sets behind tgt / src
     if (!ct && (rc = check_intrinsics(h, o, K, nimg_t))) return rc;
     const size_t hw = (size_t)h->H * h->W, n = h->max_pairs;
@@ -1978,161 +1919,125 @@ static int dense_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int
     if (ct && !ref_mode && (n_sel || o->solver != TCSFM_SOLVER_GN || o->host_ptrs || o->n_iters < 1 || (o->dense_joint && win_S >= 2)))
         return fail(h, TCSFM_E_ARG, "internal: only per-pair Gauss-Newton dense calls on device pointers are merged");
     if (ct && ref_mode && (o->host_ptrs || o->n_iters < 1 || stats_out)) return fail(h, TCSFM_E_ARG, "internal: merged reference-loss calls take device pointers and no statistics");
-    if (n_sel && !h->sel_maps) HIPCHK(h, hipMalloc((void **)&h->sel_maps, (size_t)2 * h->max_pairs * hw * sizeof(float)));
     const bool lm = o->solver == TCSFM_SOLVER_LM;
-    if (lm && !h->dense_rec_acc) {
-        HIPCHK(h, hipMalloc((void **)&h->dense_rec_acc, n * hw * 8 * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->depth_acc, n * hw * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->lm_accept, n * sizeof(int)));
-    }
-    if (!h->dense_rec) {
-        HIPCHK(h, hipMalloc((void **)&h->dense_rec, n * hw * 8 * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->depth0, n * hw * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->delta, n * 8 * sizeof(double)));
-    }
-    const float *d_tgt, *d_src, *d_dt, *d_ds, *d_K, *d_pose_in;
-    if ((rc = to_dev(h, o, 0, tgt, nimg_t * 3 * hw, &d_tgt))) return rc;
-    if ((rc = to_dev(h, o, 1, src, nimg_s * 3 * hw, &d_src))) return rc;
-    if ((rc = to_dev(h, o, 2, depth_t, nimg_t * hw, &d_dt))) return rc;
-    if ((rc = to_dev(h, o, 3, depth_s, nimg_s * hw, &d_ds))) return rc;
-    if ((rc = to_dev(h, o, 4, K, (size_t)nimg_t * 9, &d_K))) return rc;
-    if ((rc = to_dev(h, o, 5, pose_in, (size_t)N * 6, &d_pose_in))) return rc;
-    float *d_pose_out, *d_depth_out, *d_stats = nullptr;
-    if ((rc = out_dev(h, o, 7, pose_out, (size_t)N * 6, &d_pose_out))) return rc;
-    if ((rc = out_dev(h, o, 8, depth_out, N * hw, &d_depth_out))) return rc;
+    if ((n_sel && (rc = ensure_sel_maps(h))) || (lm && (rc = ensure_dense_lm(h))) || (rc = ensure_dense_rec(h))) return rc;
+    const float *d_tgt = st.in(tgt, nimg_t * 3 * hw), *d_src = st.in(src, nimg_s * 3 * hw), *d_dt = st.in(depth_t, nimg_t * hw);
+    const float *d_ds = st.in(depth_s, nimg_s * hw), *d_K = st.in(K, (size_t)nimg_t * 9), *d_pose_in = st.in(pose_in, (size_t)N * 6);
     const size_t nstats = (size_t)N * (o->n_iters + 1) * TCSFM_NSTAT;
-    if (stats_out) {
-        if ((rc = out_dev(h, o, 9, stats_out, nstats, &d_stats))) return rc;
-        HIPCHK(h, hipMemsetAsync(d_stats, 0, nstats * sizeof(float), h->stream));
-    }
+    float *d_pose_out = st.out(pose_out, (size_t)N * 6), *d_depth_out = st.out(depth_out, N * hw), *d_stats = st.out(stats_out, nstats);
+    if (st.rc) return st.rc;
+    if (d_stats) HIPCHK(h, hipMemsetAsync(d_stats, 0, nstats * sizeof(float), h->stream));
     if (ref_mode) {
-        rc = win_S == 1 ? dense_ref_run<1>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth)
-           : win_S == 2 ? dense_ref_run<2>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth)
-           : win_S == 3 ? dense_ref_run<3>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth)
-                        : dense_ref_run<4>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth);
-        if (rc) return rc;
-        if ((rc = copy_back(h, o, pose_out, d_pose_out, (size_t)N * 6))) return rc;
-        if ((rc = copy_back(h, o, depth_out, d_depth_out, N * hw))) return rc;
-        if ((rc = copy_back(h, o, stats_out, d_stats, nstats))) return rc;
-        if (o->host_ptrs) HIPCHK(h, hipStreamSynchronize(h->stream));
-        return TCSFM_OK;
-    }
-    // (the library's own joint mode stays at S <= JMAXS_OWN = 3: wider windows there keep the per-pair depth copies below)
-    if (win_B && o->dense_joint && win_S >= 2 && win_S <= JMAXS_OWN) {   // one depth map per target, 6S x 6S reduced system (joint_kernel.h)
+        if ((rc = dense_ref_runs[win_S - 1](h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth)))
+            return rc;
+    } else if (win_B && o->dense_joint && win_S >= 2 && win_S <= JMAXS_OWN) {   // one depth map per target, 6S x 6S reduced system (joint_kernel.h)
+        // (the library's own joint mode stays at S <= JMAXS_OWN = 3: wider windows there keep the per-pair depth copies below)
         rc = win_S == 2 ? dense_joint_run<2>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo)
                         : dense_joint_run<3>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo);
         if (rc) return rc;
-        if ((rc = copy_back(h, o, pose_out, d_pose_out, (size_t)N * 6))) return rc;
-        if ((rc = copy_back(h, o, depth_out, d_depth_out, N * hw))) return rc;
-        if ((rc = copy_back(h, o, stats_out, d_stats, nstats))) return rc;
-        if (o->host_ptrs) HIPCHK(h, hipStreamSynchronize(h->stream));
-        return TCSFM_OK;
-    }
-    tcsfm_opts oo = *o;
-    oo.refine = TCSFM_REFINE_POSE;
-    oo.window_rule = TCSFM_WINDOW_PAIR;
-    InitParams I = init_params(h, &oo, N, d_pose_in, nullptr, d_K, 0);
-    I.K_mod = win_B;
-    // Gauss-Newton in the pair form: the back-substitution of iteration k is fused into the linearisation of iteration k+1 (depth
-    // maps and per-pixel records ping-pong between two buffers); LM rolls maps back and the min over sources needs the current map
-    // materialised before the linearisation, so those keep the separate update launch
-    const bool fuse = !lm && !n_sel && o->n_iters > 0;
-    if (fuse && !h->dense_rec2) {
-        HIPCHK(h, hipMalloc((void **)&h->dense_rec2, n * hw * 8 * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->depth_alt, n * hw * sizeof(float)));
-    }
-    // every pair gets its OWN copy of its target's depth; the pack also leaves the prior centre depth0
-    if ((rc = run_pack(h, &oo, N, d_tgt, d_src, d_dt, d_ds, &I, win_B, win_S, h->depth0, wo, ct))) return rc;
-    // the dense kernel's own tile grid (32x16 tiles of 512 threads, as k_linearize; 16x16 / 256 threads measured slower except
-    // for 320x240 at B=1: 10.9 vs 11.8 us per launch there, 234 vs 200 us with the chip full) and reduction-group count
-    constexpr int DTW = 32, DTH = 16, DNT = 512;
-    LinParams P = lin_params(h, &oo, 6);
-    P.tiles_x = (h->W + DTW - 1) / DTW; P.tiles_y = (h->H + DTH - 1) / DTH;
-    const int nblk = P.tiles_x * P.tiles_y;
-    P.ngrp = (nblk + RG - 1) / RG;
-    if ((size_t)nblk > (size_t)h->nblk_alloc || P.ngrp > h->ngrp_alloc) return fail(h, TCSFM_E_ARG, "internal: dense tile grid exceeds scratch");
-    SolveParams S = solve_params(h, &oo, 6, 0);
-    P.direct = nblk <= 512;
-    S.partials = P.direct ? h->blockrec : h->partials; S.ngrp = P.direct ? nblk : P.ngrp;
-    S.stats = d_stats; S.delta_out = h->delta;
-    if (ct) {
-        S.c_ncall = ct->ncall; S.c_B = ct->cB; S.c_S = ct->cS;
-        for (int i = 0; i < ct->ncall; i++) S.c_pose_out[i] = ct_pose[i];
-    }
-    DenseParams Dn;
-    Dn.dense_rec = h->dense_rec; Dn.depth0 = h->depth0; Dn.lambda_depth = o->lambda_depth; Dn.w_prior = o->prior_depth;
-    Dn.prev_rec = nullptr; Dn.prev_delta = h->delta; Dn.depth_next = nullptr;
-    Dn.rho_lo = 1.f / o->max_depth; Dn.rho_hi = 1.f / o->min_depth;
-    DenseUpdateParams U;
-    memset(&U, 0, sizeof(U));
-    U.dense_rec = h->dense_rec; U.delta = h->delta; U.depth = h->depth_work; U.depth_out = h->depth_work; U.hw = (int)hw;
-    U.rho_lo = Dn.rho_lo; U.rho_hi = Dn.rho_hi;
-    float *Dbuf[2] = {h->depth_work, h->depth_alt}, *Rbuf[2] = {h->dense_rec, h->dense_rec2};
-    // min over the sources (window form): selection masks of the forward pairs from their residual maps at the current poses
-    // AND current depth copies, rebuilt before every linearisation (same two launches as in the pose mode)
-    float *sel_diff = h->sel_maps, *sel_valid = h->sel_maps ? h->sel_maps + (size_t)h->max_pairs * hw : nullptr;
-    if (n_sel) { P.ext_diff = sel_diff; P.ext_valid = sel_valid; P.n_ext = n_sel; P.ext_B = win_B; P.ext_S = win_S; }
-    auto select_pass = [&]() {
-        LinParams M = lin_params(h, &oo, 6);
-        M.o_diff = sel_diff; M.o_valid = sel_valid;
-        launch_lin(h, M, n_sel, 6, false, MODE_MAPS, 2);          // (the selection itself: ext_selected, inside the dense kernel)
-    };
-    auto linearize = [&]() {
-        if (n_sel) select_pass();
-        take_stamp(h, P, (size_t)nblk * N);
-        ProfScope prof(h, 0);
-        if (P.trace != nullptr) hipLaunchKernelGGL((k_dense_linearize<DTW, DTH, DNT, true>), dim3(nblk, N), dim3(DNT), 0, h->stream, P, Dn);
-        else hipLaunchKernelGGL((k_dense_linearize<DTW, DTH, DNT>), dim3(nblk, N), dim3(DNT), 0, h->stream, P, Dn);
-    };
-    DenseLmParams Ul;
-    Ul.rec_try = h->dense_rec; Ul.rec_acc = h->dense_rec_acc; Ul.depth_acc = h->depth_acc; Ul.depth = h->depth_work; Ul.delta = h->delta;
-    Ul.accept = h->lm_accept; Ul.hw = (int)hw; Ul.rho_lo = U.rho_lo; Ul.rho_hi = U.rho_hi;
-    S.accept_out = lm ? h->lm_accept : nullptr;
-    const dim3 px_grid((unsigned)((hw + 255) / 256), N);
-    if ((rc = trace_check(h, o, N))) return rc;
-    for (int it = 0; it < o->n_iters; it++) {
-        trace_at(h, it, N, P, S);
-        if (fuse) {   // reads depth_{it-1} + the records / step of iteration it-1, leaves depth_it and the records of iteration it
-            P.depth_t = Dbuf[it & 1]; Dn.depth_next = Dbuf[(it + 1) & 1];
-            Dn.dense_rec = Rbuf[it & 1]; Dn.prev_rec = it > 0 ? Rbuf[(it - 1) & 1] : nullptr;
+    } else {
+        tcsfm_opts oo = *o;
+        oo.refine = TCSFM_REFINE_POSE;
+        oo.window_rule = TCSFM_WINDOW_PAIR;
+        InitParams I = init_params(h, &oo, N, d_pose_in, nullptr, d_K, 0);
+        I.K_mod = win_B;
+        // Gauss-Newton in the pair form: the back-substitution of iteration k is fused into the linearisation of iteration k+1 (depth
+        // maps and per-pixel records ping-pong between two buffers); LM rolls maps back and the min over sources needs the current map
+        // materialised before the linearisation, so those keep the separate update launch
+        const bool fuse = !lm && !n_sel && o->n_iters > 0;
+        if (fuse && !h->dense_rec2) {
+            HIPCHK(h, hipMalloc((void **)&h->dense_rec2, n * hw * 8 * sizeof(float)));
+            HIPCHK(h, hipMalloc((void **)&h->depth_alt, n * hw * sizeof(float)));
         }
-        linearize();
-        S.it = it; S.mode = 0;
-        const bool last = !lm && it == o->n_iters - 1;
-        S.pose_out = last ? d_pose_out : nullptr; S.log_scale_out = nullptr;
-        launch_solve(h, S, N, 6);
-        if (lm) hipLaunchKernelGGL(k_dense_update_lm, px_grid, dim3(256), 0, h->stream, Ul);
-        else if (!fuse) hipLaunchKernelGGL(k_dense_update, px_grid, dim3(256), 0, h->stream, U);
-    }
-    if (fuse) {   // the last back-substitution writes the caller's depth map directly
-        const int nit = o->n_iters;
-        U.dense_rec = Rbuf[(nit - 1) & 1]; U.depth = Dbuf[nit & 1]; U.depth_out = d_depth_out;
+        // every pair gets its OWN copy of its target's depth; the pack also leaves the prior centre depth0
+        if ((rc = run_pack(h, &oo, N, d_tgt, d_src, d_dt, d_ds, &I, win_B, win_S, h->depth0, wo, ct))) return rc;
+        // the dense kernel's own tile grid (32x16 tiles of 512 threads, as k_linearize; 16x16 / 256 threads measured slower except
+        // for 320x240 at B=1: 10.9 vs 11.8 us per launch there, 234 vs 200 us with the chip full) and reduction-group count
+        constexpr int DTW = 32, DTH = 16, DNT = 512;
+        LinParams P = lin_params(h, &oo, 6);
+        P.tiles_x = (h->W + DTW - 1) / DTW; P.tiles_y = (h->H + DTH - 1) / DTH;
+        const int nblk = P.tiles_x * P.tiles_y;
+        P.ngrp = (nblk + RG - 1) / RG;
+        if ((size_t)nblk > (size_t)h->nblk_alloc || P.ngrp > h->ngrp_alloc) return fail(h, TCSFM_E_ARG, "internal: dense tile grid exceeds scratch");
+        SolveParams S = solve_params(h, &oo, 6, 0);
+        P.direct = nblk <= 512;
+        S.partials = P.direct ? h->blockrec : h->partials; S.ngrp = P.direct ? nblk : P.ngrp;
+        S.stats = d_stats; S.delta_out = h->delta;
         if (ct) {
-            U.c_ncall = ct->ncall; U.c_B = ct->cB; U.c_S = ct->cS;
-            for (int i = 0; i < ct->ncall; i++) U.c_depth_out[i] = ct_depth[i];
+            S.c_ncall = ct->ncall; S.c_B = ct->cB; S.c_S = ct->cS;
+            for (int i = 0; i < ct->ncall; i++) S.c_pose_out[i] = ct_pose[i];
         }
-        hipLaunchKernelGGL(k_dense_update, px_grid, dim3(256), 0, h->stream, U);
+        DenseParams Dn;
+        Dn.dense_rec = h->dense_rec; Dn.depth0 = h->depth0; Dn.lambda_depth = o->lambda_depth; Dn.w_prior = o->prior_depth;
+        Dn.prev_rec = nullptr; Dn.prev_delta = h->delta; Dn.depth_next = nullptr;
+        Dn.rho_lo = 1.f / o->max_depth; Dn.rho_hi = 1.f / o->min_depth;
+        DenseUpdateParams U;
+        memset(&U, 0, sizeof(U));
+        U.dense_rec = h->dense_rec; U.delta = h->delta; U.depth = h->depth_work; U.depth_out = h->depth_work; U.hw = (int)hw;
+        U.rho_lo = Dn.rho_lo; U.rho_hi = Dn.rho_hi;
+        float *Dbuf[2] = {h->depth_work, h->depth_alt}, *Rbuf[2] = {h->dense_rec, h->dense_rec2};
+        // min over the sources (window form): selection masks of the forward pairs from their residual maps at the current poses
+        // AND current depth copies, rebuilt before every linearisation (same two launches as in the pose mode)
+        float *sel_diff = h->sel_maps, *sel_valid = h->sel_maps ? h->sel_maps + (size_t)h->max_pairs * hw : nullptr;
+        if (n_sel) { P.ext_diff = sel_diff; P.ext_valid = sel_valid; P.n_ext = n_sel; P.ext_B = win_B; P.ext_S = win_S; }
+        auto select_pass = [&]() {
+            LinParams M = lin_params(h, &oo, 6);
+            M.o_diff = sel_diff; M.o_valid = sel_valid;
+            launch_lin(h, M, n_sel, 6, false, MODE_MAPS, 2);          // (the selection itself: ext_selected, inside the dense kernel)
+        };
+        auto linearize = [&]() {
+            if (n_sel) select_pass();
+            take_stamp(h, P, (size_t)nblk * N);
+            ProfScope prof(h, 0);
+            if (P.trace != nullptr) hipLaunchKernelGGL((k_dense_linearize<DTW, DTH, DNT, true>), dim3(nblk, N), dim3(DNT), 0, h->stream, P, Dn);
+            else hipLaunchKernelGGL((k_dense_linearize<DTW, DTH, DNT>), dim3(nblk, N), dim3(DNT), 0, h->stream, P, Dn);
+        };
+        DenseLmParams Ul;
+        Ul.rec_try = h->dense_rec; Ul.rec_acc = h->dense_rec_acc; Ul.depth_acc = h->depth_acc; Ul.depth = h->depth_work; Ul.delta = h->delta;
+        Ul.accept = h->lm_accept; Ul.hw = (int)hw; Ul.rho_lo = U.rho_lo; Ul.rho_hi = U.rho_hi;
+        S.accept_out = lm ? h->lm_accept : nullptr;
+        const dim3 px_grid((unsigned)((hw + 255) / 256), N);
+        if ((rc = trace_check(h, o, N))) return rc;
+        for (int it = 0; it < o->n_iters; it++) {
+            trace_at(h, it, N, P, S);
+            if (fuse) {   // reads depth_{it-1} + the records / step of iteration it-1, leaves depth_it and the records of iteration it
+                P.depth_t = Dbuf[it & 1]; Dn.depth_next = Dbuf[(it + 1) & 1];
+                Dn.dense_rec = Rbuf[it & 1]; Dn.prev_rec = it > 0 ? Rbuf[(it - 1) & 1] : nullptr;
+            }
+            linearize();
+            S.it = it; S.mode = 0;
+            const bool last = !lm && it == o->n_iters - 1;
+            S.pose_out = last ? d_pose_out : nullptr; S.log_scale_out = nullptr;
+            launch_solve(h, S, N, 6);
+            if (lm) hipLaunchKernelGGL(k_dense_update_lm, px_grid, dim3(256), 0, h->stream, Ul);
+            else if (!fuse) hipLaunchKernelGGL(k_dense_update, px_grid, dim3(256), 0, h->stream, U);
+        }
+        if (fuse) {   // the last back-substitution writes the caller's depth map directly
+            const int nit = o->n_iters;
+            U.dense_rec = Rbuf[(nit - 1) & 1]; U.depth = Dbuf[nit & 1]; U.depth_out = d_depth_out;
+            if (ct) {
+                U.c_ncall = ct->ncall; U.c_B = ct->cB; U.c_S = ct->cS;
+                for (int i = 0; i < ct->ncall; i++) U.c_depth_out[i] = ct_depth[i];
+            }
+            hipLaunchKernelGGL(k_dense_update, px_grid, dim3(256), 0, h->stream, U);
+        }
+        if (lm && o->n_iters > 0) {   // evaluate the last trial once more; keep it only if it lowered the cost (pose and depth map)
+            trace_at(h, o->n_iters, N, P, S);
+            linearize();
+            S.it = o->n_iters; S.mode = 1;
+            S.pose_out = d_pose_out; S.log_scale_out = nullptr;
+            launch_solve(h, S, N, 6);
+            hipLaunchKernelGGL(k_dense_final_lm, px_grid, dim3(256), 0, h->stream, (const int *)h->lm_accept, (const float *)h->depth_acc, h->depth_work, (int)hw);
+        }
+        HIPCHK(h, hipGetLastError());
+        if (o->n_iters == 0) {
+            FinishParams F;
+            F.st = h->state; F.pose_out = d_pose_out; F.log_scale_out = nullptr; F.N = N;
+            hipLaunchKernelGGL(k_finish, dim3((N + 63) / 64), dim3(64), 0, h->stream, F);
+        }
+        if (!fuse) HIPCHK(h, hipMemcpyAsync(d_depth_out, h->depth_work, N * hw * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     }
-    if (lm && o->n_iters > 0) {   // evaluate the last trial once more; keep it only if it lowered the cost (pose and depth map)
-        trace_at(h, o->n_iters, N, P, S);
-        linearize();
-        S.it = o->n_iters; S.mode = 1;
-        S.pose_out = d_pose_out; S.log_scale_out = nullptr;
-        launch_solve(h, S, N, 6);
-        hipLaunchKernelGGL(k_dense_final_lm, px_grid, dim3(256), 0, h->stream, (const int *)h->lm_accept, (const float *)h->depth_acc, h->depth_work, (int)hw);
-    }
-    HIPCHK(h, hipGetLastError());
-    if (o->n_iters == 0) {
-        FinishParams F;
-        F.st = h->state; F.pose_out = d_pose_out; F.log_scale_out = nullptr; F.N = N;
-        hipLaunchKernelGGL(k_finish, dim3((N + 63) / 64), dim3(64), 0, h->stream, F);
-    }
-    if (!fuse) HIPCHK(h, hipMemcpyAsync(d_depth_out, h->depth_work, N * hw * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    if ((rc = copy_back(h, o, pose_out, d_pose_out, (size_t)N * 6))) return rc;
-    if ((rc = copy_back(h, o, depth_out, d_depth_out, N * hw))) return rc;
-    if ((rc = copy_back(h, o, stats_out, d_stats, nstats))) return rc;
-    if (o->host_ptrs) HIPCHK(h, hipStreamSynchronize(h->stream));
-    return TCSFM_OK;
+    return st.finish();
 }
 
 static int dense_impl(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int win_S, const float *tgt, const float *src,
@@ -2330,34 +2235,20 @@ static int linearize_dense_window_impl(tcsfm_handle h, const tcsfm_opts *o, int 
     if (rc) return rc;
     if (!tgt || !srcs || !depth_t || !depth_s || !K || !pose || !scal_out || !g_pose_out || !g_rho_out) return fail(h, TCSFM_E_ARG, "tcsfm_linearize_dense_window: NULL argument");
     if (!(o->min_depth > 0 && o->max_depth > o->min_depth) || !(o->prior_init >= 0.f)) return fail(h, TCSFM_E_ARG, "min_depth / max_depth / prior_init invalid");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
+    Staging st(h, o);
+    if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, B))) return rc;
     const size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt, *d_src, *d_dt, *d_ds, *d_K, *d_pose;
-    if ((rc = to_dev(h, o, 0, tgt, (size_t)B * 3 * hw, &d_tgt))) return rc;
-    if ((rc = to_dev(h, o, 1, srcs, (size_t)S * B * 3 * hw, &d_src))) return rc;
-    if ((rc = to_dev(h, o, 2, depth_t, (size_t)B * hw, &d_dt))) return rc;
-    if ((rc = to_dev(h, o, 3, depth_s, (size_t)S * B * hw, &d_ds))) return rc;
-    if ((rc = to_dev(h, o, 4, K, (size_t)B * 9, &d_K))) return rc;
-    if ((rc = to_dev(h, o, 5, pose, (size_t)N * 6, &d_pose))) return rc;
-    const float *d_d0 = nullptr;
-    if (depth0 && (rc = to_dev(h, o, 6, depth0, (size_t)B * hw, &d_d0))) return rc;
-    float *d_g, *d_gs = nullptr;
-    if ((rc = out_dev(h, o, 7, g_rho_out, (size_t)B * hw, &d_g))) return rc;
-    if (g_rho_src_out && (rc = out_dev(h, o, 8, g_rho_src_out, (size_t)S * B * hw, &d_gs))) return rc;
+    const float *d_tgt = st.in(tgt, (size_t)B * 3 * hw), *d_src = st.in(srcs, (size_t)S * B * 3 * hw), *d_dt = st.in(depth_t, (size_t)B * hw);
+    const float *d_ds = st.in(depth_s, (size_t)S * B * hw), *d_K = st.in(K, (size_t)B * 9), *d_pose = st.in(pose, (size_t)N * 6);
+    const float *d_d0 = st.in(depth0, (size_t)B * hw);
+    float *d_g = st.out(g_rho_out, (size_t)B * hw), *d_gs = st.out(g_rho_src_out, (size_t)S * B * hw);
+    if (st.rc) return st.rc;
     tcsfm_opts oo = *o;
     oo.n_iters = 1; oo.solver = TCSFM_SOLVER_GN;
     DrefExport ex{scal_out, g_pose_out, d_g, d_d0, d_gs};
-    rc = S == 1 ? dense_ref_run<1>(h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex)
-       : S == 2 ? dense_ref_run<2>(h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex)
-       : S == 3 ? dense_ref_run<3>(h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex)
-                : dense_ref_run<4>(h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex);
-    if (rc) return rc;
-    if ((rc = copy_back(h, o, g_rho_out, d_g, (size_t)B * hw))) return rc;
-    if (g_rho_src_out && (rc = copy_back(h, o, g_rho_src_out, d_gs, (size_t)S * B * hw))) return rc;
-    if (o->host_ptrs) HIPCHK(h, hipStreamSynchronize(h->stream));
-    return TCSFM_OK;
+    if ((rc = dense_ref_runs[S - 1](h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex, nullptr, nullptr, nullptr))) return rc;
+    return st.finish();
 }
 
 int tcsfm_linearize_dense_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
