@@ -312,6 +312,9 @@ def test_edge_cases():
     pa, _, _ = e.refine(*d, _t(b["pose_init"]), default_opts())
     pb, _, _ = e.refine(d[0], d[1], sd_t, sd_s, d[4], _t(b["pose_init"]), default_opts(depth_is_disp=1, min_depth=0.06, max_depth=2.67))
     assert _maxabs(pa.cpu().numpy(), pb.cpu().numpy()) < 5e-5
+    # ... and are the bits of the depths the library's own disp_to_depth makes of them (k_pack and k_disp_to_depth: one expression)
+    pc, _, _ = e.refine(d[0], d[1], e.disp_to_depth(sd_t, 0.06, 2.67)[1], e.disp_to_depth(sd_s, 0.06, 2.67)[1], d[4], _t(b["pose_init"]), default_opts())
+    assert torch.equal(pb, pc)
 
 
 def _perturbed_depth(b):
