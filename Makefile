@@ -10,8 +10,8 @@ test-gpu: build   ## HIP path vs oracle / golden vectors (needs an MI355X)
 	$(PY) -m pytest tests -q -m gpu
 test-asan: build ## AddressSanitizer + UBSan over the C oracle, the host SE(3) routines and examples/c_caller.c -> profiles/r05_asan.txt
 	bash scripts/run_asan.sh
-bench: build      ## one JSON line: frame-pairs/s + roofline + cpu_baseline
-	$(PY) bench.py
+bench: build      ## one JSON line: frame-pairs/s + roofline + cpu_baseline + the other modes (bench.py --full)
+	$(PY) bench.py --full
 golden:           ## regenerate tests/golden/*.npz by running the reference (needs /root/reference; build container only)
 	$(PY) tests/golden/make_golden.py
 clean:

@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- optimised frame-pairs/sec at 640x192, 4 GN iterations (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--windows-per-gpu B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--windows-per-gpu B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run stops once the headline is known: it builds the inputs, picks the lanes' launch mode on untimed probe blocks, times
+(each after its W warm-up steps) the K-step blocks of the lanes, of `hot_cache`, of `launch_mode.other_mode` and of the merged
+sequences -- every timed leg up to the headline's last block, in the order the headline has always been measured in -- writes
+--dump-outputs and prints the JSON line.  The legs after it (`single_stream`, `roofline`, `roofline_saturated`, `cpu_baseline`,
+`modes`, `shim`, `check`, `final_gather_us`) are measured only with --full and are null without it.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts itself: the parent process, which never touches
 the GPU, launches torch.distributed.run with N ranks of this file (one per GPU, rendezvous on 127.0.0.1) and exits with its code.
@@ -35,7 +41,7 @@ Multi-GPU: windows are independent least-squares problems -> every rank refines 
 the data path); one RCCL all_gather of the refined poses AFTER the timed region is the "final gather" of the north star, timed
 separately (`final_gather_us`).
 
-The JSON line also carries
+The JSON line also carries (roofline and cpu_baseline with --full only)
   launch_mode   the lanes' calls of the timed region were enqueued either as plain launches (nine per call) or as one captured HIP graph
                 per call (tcsfm_set_graph_replay; same kernels, same bits): untimed probe blocks of both modes decide (--graph-replay
                 auto), `other_mode` repeats the blocks in the mode that lost, `host_enqueue_us_per_step` is the host's share of a step.
@@ -418,8 +424,11 @@ def main():
     ap.add_argument("--windows-per-gpu", type=int, default=0, help="windows (B) per rank and step; default 1 on one GPU (config 2), 8 on several (config 3)")
     ap.add_argument("--total-windows", type=int, default=0, help="STRONG scaling instead of the default weak scaling: this many windows per step in "
                     "the whole job (BASELINE config 3: 64), split evenly over the ranks (SURVEY 8e: report both)")
-    ap.add_argument("--sat-windows", type=int, default=32, help="windows per call of the chip-filling roofline leg (0 = skip)")
-    ap.add_argument("--cpu-sample", type=float, default=20.0, help="seconds of wall time given to the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure what comes after the headline (one call in flight, the rooflines, "
+                    "the CPU baseline, the other modes, the shim, the accuracy check, the final gather); a plain run stops once the "
+                    "headline is known")
+    ap.add_argument("--sat-windows", type=int, default=32, help="windows per call of the chip-filling roofline leg (--full; 0 = skip)")
+    ap.add_argument("--cpu-sample", type=float, default=20.0, help="seconds of wall time given to the CPU baseline (--full; 0 = skip)")
     ap.add_argument("--lanes", type=int, default=4, help="refine calls kept in flight (lanes of the handle, include/tcsfm.h); 1 = strictly one after the other")
     ap.add_argument("--ring-mb", type=float, default=320.0, help="the steps rotate over distinct calls whose inputs add up to at least this many MB "
                     "(> the 256 MiB Infinity Cache: a step's images come from HBM); 0 = every step re-runs ONE call (the round-3 protocol)")
@@ -437,8 +446,9 @@ def main():
                     "[world, ring calls, pairs, 6]): the refined poses of every window of the ring, in ring order, as the blocks of the timed "
                     "mode left them (the last step's among them); the inputs are seeded, so equal arguments give equal inputs")
     ap.add_argument("--modes-budget", type=float, default=12.0, help="seconds given to the `modes` block (BASELINE configs 4 / 5, the KITTI window, the "
-                    "reference-loss dense mode: windows/s and roofline fraction each); 0 = skip")
-    ap.add_argument("--shim-sample", type=float, default=4.0, help="seconds given to the `shim` block (DepthOptimizer.optimize_window end to end); 0 = skip")
+                    "reference-loss dense mode: windows/s and roofline fraction each; --full); 0 = skip")
+    ap.add_argument("--shim-sample", type=float, default=4.0, help="seconds given to the `shim` block (DepthOptimizer.optimize_window end to end; "
+                    "--full); 0 = skip")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:     # started the way the driver starts it: launch the ranks, touch no GPU here
@@ -489,10 +499,12 @@ def main():
     R = max(R, lanes)                                                                                         # always runs on the same lane
     opts = default_opts(n_iters=ITERS)
 
-    def make_call(j):
+    def make_host(j):       # ring entry j's seeded inputs on the host (numpy, no shared state: entries can be rendered side by side)
+        return synth.make_batch(npairs, H, W, seed0=100 * rank + 7919 * j, both_directions=True)
+
+    def make_call(b, j):
         # the window form of a batch (the library forms the fwd / inv pairs itself, bit-identical to the pair form): targets [B], the
         # S=1 source of each, initial poses in the stacked order [forward pairs | inverse pairs]
-        b = synth.make_batch(npairs, H, W, seed0=100 * rank + 7919 * j, both_directions=True)
         dev = {k: torch.as_tensor(v).cuda().contiguous() for k, v in b.items()}
         win = dict(tgt=dev["tgt"][0::2].contiguous(), srcs=dev["src"][0::2].contiguous()[None], depth_t=dev["depth_t"][0::2].contiguous(),
                    depth_s=dev["depth_s"][0::2].contiguous()[None], K=dev["K"][0::2].contiguous(),
@@ -500,8 +512,15 @@ def main():
         win["out"] = torch.empty_like(win["pose"])
         return (dev if j == 0 else None), win
 
-    dev, win0 = make_call(0)
-    ring = [win0] + [make_call(j)[1] for j in range(1, R)]
+    # rendering the ring on the host is most of a plain run's setup: the entries are rendered on a pool of threads (numpy releases the
+    # GIL in its array loops) and uploaded here in ring order, as they come -- the same inputs, in the same device allocations
+    from concurrent.futures import ThreadPoolExecutor
+    threads = max(1, min(16, len(os.sched_getaffinity(0))) // int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
+    with ThreadPoolExecutor(threads) as pool:
+        calls = [make_call(b, j) for j, b in enumerate(pool.map(make_host, range(R)))]
+    dev, win0 = calls[0]
+    ring = [c[1] for c in calls]
+    del calls
     for w in ring[1:]:       # ONE camera: every call passes the same intrinsics tensor, as the windows of a sequence do (the library
         assert torch.equal(w["K"], win0["K"])                # validates a device intrinsics pointer, with a blocking copy, the first
         w["K"] = win0["K"]                                   # time it sees it -- 84 different pointers would thrash its 4-entry cache)
@@ -599,6 +618,8 @@ def main():
     for l in range(lanes):                   # a deferred device-side error of any lane surfaces here
         eng.lane_synchronize(l)
     timed_out = torch.stack([w["out"] for w in ring])        # (--dump-outputs) what the timed blocks left in every window's output
+    # (a plain run keeps the two legs below: the merged blocks after them are timed on a chip that has run them, and without them the
+    # median merged block is ~4 % slower at K = 20 while the fastest is not -- the chip has not settled yet)
     # the round-3 protocol beside it: the same blocks re-running ONE window per lane (inputs, packs and records all cache resident)
     hot = None
     if R > lanes:
@@ -655,14 +676,16 @@ def main():
             merged["timed"] = False
     # one call in flight: the host is not what binds (74 us of GPU time against 42 us of launches per call) and a graph launch adds
     # ~4 us of GPU time to the call -- the latency figure uses plain launches
-    single = timed(1) if lanes > 1 else (elapsed, blocks)       # the same steps strictly one after the other
+    single = None
+    if args.full:
+        single = timed(1) if lanes > 1 else (elapsed, blocks)   # the same steps strictly one after the other
     eng.lane_synchronize(0)
     pose_io = ring[0]["out"]
 
     # final gather of the refined poses (RCCL over xGMI), outside the timed region; timed on its own (second call: no setup cost)
     final = pose_io.clone()
     gather_us = None
-    if distributed:
+    if distributed and (args.full or args.dump_poses):
         send = final.to(coll_dev)
         for k in range(2):
             gathered = [torch.empty_like(send) for _ in range(world)]
@@ -690,133 +713,134 @@ def main():
             os.makedirs(args.dump_outputs, exist_ok=True)
             np.save(os.path.join(args.dump_outputs, "poses.npy"), dump_all.cpu().numpy().astype(np.float32))
 
-    # instrumented pass on EVERY rank: in-kernel brackets + HIP events around every kernel launch, same steps (ring rotation, one call
-    # in flight: the kernel has the chip -- what a roofline compares against)
-    n_prof = min(max(args.steps, 300), 500)                 # enough launches for a stable average, whatever K the driver asked for
-    # (in five chunks, each with its own totals: the average is over ALL launches as before; the per-chunk averages show the spread -- with ONE
-    # call in flight the chip is lightly loaded and its shader clock moves between the 2.4 GHz and 1.4 GHz power states, which a VALU-bound
-    # kernel's duration follows: 8.4-8.5 us per launch in the high state, 9.4-9.6 us when the governor has stepped down; an untimed 0.3 s
-    # warm-up of the same load was tried and does not pin the state -- the light load itself is what lets the clock fall:
-    # profiles/r04_bench_repeats.jsonl, scripts/diag/clock_sampler.sh)
-    n_chunks = 5
-    chunk_us, prof = [], {}
-    for ci in range(n_chunks):
-        eng.profile_begin()
-        for k in range(ci * n_prof // n_chunks, (ci + 1) * n_prof // n_chunks):
-            step_k(k, 1)
-        pc = eng.profile_end()
-        chunk_us.append(round(pc["linearize_kernel"][0] / max(pc["linearize_kernel"][1], 1) * 1e3, 3))
-        for key, (ms_, n_) in pc.items():
-            a_, b_ = prof.get(key, (0.0, 0))
-            prof[key] = (a_ + ms_, b_ + n_)
-    alg_bytes = 32 * H * W * npairs                          # 32 B/pixel/pair/iteration x pixels x pairs/launch
-    k_ms, k_n = prof["linearize_kernel"]
-    e_ms, e_n = prof["linearize"]
-    avg_s = k_ms / max(k_n, 1) * 1e-3
-    ev_s = e_ms / max(e_n, 1) * 1e-3
-    mine = {"rank": rank, "avg_launch_us": round(avg_s * 1e6, 3), "achieved": round(alg_bytes / avg_s / 1e9, 2),
-            "frac": round(alg_bytes / avg_s / 1e9 / HBM_PEAK_GBPS, 5)}
-    # the same launches while `lanes` calls are in flight, as in the timed region: each k_linearize then shares the chip with the
-    # other lane's k_solve / k_pack / k_linearize, so ITS duration is longer although the chip as a whole gets more done
-    inflight = None
-    if lanes > 1:
-        eng.profile_begin()
-        for k in range(n_prof):
-            step_k(k, lanes)
-        for l in range(lanes):
-            eng.lane_synchronize(l)
-        prof2 = eng.profile_end()
-        k2_ms, k2_n = prof2["linearize_kernel"]
-        a2 = k2_ms / max(k2_n, 1) * 1e-3
-        inflight = {"steps_in_flight": lanes, "avg_launch_us": round(a2 * 1e6, 3), "achieved": round(alg_bytes / a2 / 1e9, 2),
-                    "frac": round(alg_bytes / a2 / 1e9 / HBM_PEAK_GBPS, 5), "launches": int(k2_n),
-                    "avg_launch_us_hip_events": round(prof2["linearize"][0] / max(prof2["linearize"][1], 1) * 1e3, 3)}
-    # ... and the launches of the TIMED mode when that is the merged sequences: one k_linearize launch then covers the directed pairs of
-    # `coal` queued calls (tcsfm_refine_window_queued); bracketed in-kernel like the others (profiling does not stop the merging)
-    timed_mode = None
-    if merged and merged["timed"]:
-        eng.set_coalesce(coal)
-        eng.set_coalesce_lanes(max(1, min(args.coalesce_lanes, lanes)))
-        queued[0] = True
-        eng.profile_begin()
-        for k in range(coal * 30):
-            step_k(k, lanes)
-        eng.flush()
-        for l in range(lanes):
-            eng.lane_synchronize(l)
-        prm = eng.profile_end()
-        queued[0] = False
-        eng.set_coalesce_lanes(1)
-        eng.set_coalesce(0)
-        km_ms, km_n = prm["linearize_kernel"]
-        am = km_ms / max(km_n, 1) * 1e-3
-        alg_m = alg_bytes * coal
-        timed_mode = {"mode": f"{coal} queued B={B} calls per launch sequence, sequences alternating over {max(1, min(args.coalesce_lanes, lanes))} streams",
-                      "pairs_per_launch": npairs * coal, "avg_launch_us": round(am * 1e6, 3), "launches": int(km_n), "algorithmic_bytes_per_launch": alg_m,
-                      "achieved": round(alg_m / am / 1e9, 2), "frac": round(alg_m / am / 1e9 / HBM_PEAK_GBPS, 5), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                      "frac_source": "this run: in-kernel s_memrealtime bracket of the merged k_linearize launches, as they run in the timed region "
-                                     "(two sequences in flight on two streams: a launch shares the chip with the other sequence's kernels)"}
-        bm_ms, bm_n = prm.get("linearize_busy", (0.0, 0))
-        if bm_ms > 0 and bm_n == km_n:
-            # the launches of the two streams overlap: the chip's rate on the kernel = all their bytes / the time at least one of them ran
-            timed_mode["chip_level"] = {"busy_us": round(bm_ms * 1e3, 1), "launch_us_summed": round(km_ms * 1e3, 1), "overlap": round(km_ms / bm_ms, 3),
-                                        "achieved": round(alg_m * km_n / (bm_ms * 1e-3) / 1e9, 2), "frac": round(alg_m * km_n / (bm_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5),
-                                        "what": "algorithmic bytes of ALL merged k_linearize launches of the pass / the time during which at least one of them was "
-                                                "running (union of the in-kernel [start, end] brackets over both streams): what the chip sustains on the kernel in the timed mode"}
-    per_rank = [mine]
-    if distributed:
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine)
     roof = None
-    if rank == 0:
-        rp = rocprof_avg_us() if B == 1 else None
-        meta = profiles_meta()
-        # Headline: THIS run's in-kernel bracket.  The committed rocprofv3 average of the same kernel stands beside it and must agree
-        # (it includes ~1.2 us of dispatch and completion): frac_consistent.
-        committed = None
-        if rp and "lanes_1" in rp:
-            c_us = rp["lanes_1"]["us"]
-            committed = {"avg_launch_us": c_us, "achieved": round(alg_bytes / (c_us * 1e-6) / 1e9, 2),
-                         "frac": round(alg_bytes / (c_us * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5), "file": rp["lanes_1"]["file"],
-                         "what": "rocprofv3 --kernel-trace --stats AverageNs of the committed run of `python bench.py --lanes 1`",
-                         "dispatch_offset_us": DISPATCH_OFFSET_US}
-        traffic = load_pmc() if B == 1 else None
-        call_traffic = load_pmc("hbm_bytes_per_call") if B == 1 else None
-        vb = valu_bound(avg_s, npairs)
-        roof = {"bound": "hbm", "bound_actual": "valu", "achieved": mine["achieved"], "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": mine["frac"],
-                "frac_source": "this run: in-kernel s_memrealtime bracket of every k_linearize launch (earliest workgroup start -> latest workgroup "
-                               "end), one call in flight, steps rotating over the ring",
-                "avg_launch_us": mine["avg_launch_us"], "avg_launch_us_hip_events": round(ev_s * 1e6, 3),
-                "avg_launch_us_chunks": chunk_us,
-                "valu_frac_of_bound": None if vb is None else vb["frac_of_bound"],
-                "traffic": traffic, "traffic_over_algorithmic": None if traffic is None else round(traffic / alg_bytes, 3),
-                "traffic_note": "below 1 since round 5: the algorithmic figure (32 B / pixel / directed pair: a target texel + the source taps) counts the two "
-                                "image packs of a window once per directed pair, and the window forms now pack every image ONCE -- a pair reads its target "
-                                "from its partner's source pack (LinParams::tshare), so the two pairs of a window fetch the same lines",
-                "kernel": "k_linearize", "launches": int(k_n), "algorithmic_bytes_per_launch": alg_bytes,
-                "rocprof_committed": committed,
-                "frac_consistent": None if committed is None else bool(consistent(mine["avg_launch_us"], committed["avg_launch_us"])),
-                "profiles_match_source": None if meta is None else meta["matches"], "profiles_meta": meta,
-                "rocprof_avg_us": rp,
-                "rocprof_note": "profiles/<tag>_kernel_stats.csv: rocprofv3 --kernel-trace --stats of this very command (its average covers the "
-                                "launches of the timed blocks with `steps_in_flight` calls in flight, of the single-stream blocks and of both instrumented passes); "
-                                "profiles/<tag>_lanes1_kernel_stats.csv: the same command with --lanes 1 (every launch has the chip); "
-                                "profiles/<tag>_sat_kernel_stats.csv: scripts/sat_workload.py (32 windows per call)",
-                "other_kernels_avg_us_hip_events": {k: round(v[0] / max(v[1], 1) * 1e3, 3) for k, v in prof.items() if k in ("solve", "pack")},
-                "valu_bound": vb,
-                "whole_call": {"algorithmic_bytes": ITERS * alg_bytes, "traffic_bytes": call_traffic,
-                               "traffic_over_algorithmic": None if call_traffic is None else round(call_traffic / (ITERS * alg_bytes), 3),
-                               "what": "all launches of one call (pack + 4 x (linearise + solve)) against 4 x the algorithmic bytes of a linearisation"},
-                "measured_with": "ONE call in flight (the kernel has the chip: what a roofline compares against); `in_flight` repeats the live bracket with the "
-                                 "lanes' calls in flight, `timed_mode` brackets the launches of the mode `value` was timed in",
-                "in_flight": inflight, "timed_mode": timed_mode}
+    if args.full:
+        # instrumented pass on EVERY rank: in-kernel brackets + HIP events around every kernel launch, same steps (ring rotation, one call
+        # in flight: the kernel has the chip -- what a roofline compares against)
+        n_prof = min(max(args.steps, 300), 500)                 # enough launches for a stable average, whatever K the driver asked for
+        # (in five chunks, each with its own totals: the average is over ALL launches as before; the per-chunk averages show the spread -- with ONE
+        # call in flight the chip is lightly loaded and its shader clock moves between the 2.4 GHz and 1.4 GHz power states, which a VALU-bound
+        # kernel's duration follows: 8.4-8.5 us per launch in the high state, 9.4-9.6 us when the governor has stepped down; an untimed 0.3 s
+        # warm-up of the same load was tried and does not pin the state -- the light load itself is what lets the clock fall:
+        # profiles/r04_bench_repeats.jsonl, scripts/diag/clock_sampler.sh)
+        n_chunks = 5
+        chunk_us, prof = [], {}
+        for ci in range(n_chunks):
+            eng.profile_begin()
+            for k in range(ci * n_prof // n_chunks, (ci + 1) * n_prof // n_chunks):
+                step_k(k, 1)
+            pc = eng.profile_end()
+            chunk_us.append(round(pc["linearize_kernel"][0] / max(pc["linearize_kernel"][1], 1) * 1e3, 3))
+            for key, (ms_, n_) in pc.items():
+                a_, b_ = prof.get(key, (0.0, 0))
+                prof[key] = (a_ + ms_, b_ + n_)
+        alg_bytes = 32 * H * W * npairs                          # 32 B/pixel/pair/iteration x pixels x pairs/launch
+        k_ms, k_n = prof["linearize_kernel"]
+        e_ms, e_n = prof["linearize"]
+        avg_s = k_ms / max(k_n, 1) * 1e-3
+        ev_s = e_ms / max(e_n, 1) * 1e-3
+        mine = {"rank": rank, "avg_launch_us": round(avg_s * 1e6, 3), "achieved": round(alg_bytes / avg_s / 1e9, 2),
+                "frac": round(alg_bytes / avg_s / 1e9 / HBM_PEAK_GBPS, 5)}
+        # the same launches while `lanes` calls are in flight, as in the timed region: each k_linearize then shares the chip with the
+        # other lane's k_solve / k_pack / k_linearize, so ITS duration is longer although the chip as a whole gets more done
+        inflight = None
+        if lanes > 1:
+            eng.profile_begin()
+            for k in range(n_prof):
+                step_k(k, lanes)
+            for l in range(lanes):
+                eng.lane_synchronize(l)
+            prof2 = eng.profile_end()
+            k2_ms, k2_n = prof2["linearize_kernel"]
+            a2 = k2_ms / max(k2_n, 1) * 1e-3
+            inflight = {"steps_in_flight": lanes, "avg_launch_us": round(a2 * 1e6, 3), "achieved": round(alg_bytes / a2 / 1e9, 2),
+                        "frac": round(alg_bytes / a2 / 1e9 / HBM_PEAK_GBPS, 5), "launches": int(k2_n),
+                        "avg_launch_us_hip_events": round(prof2["linearize"][0] / max(prof2["linearize"][1], 1) * 1e3, 3)}
+        # ... and the launches of the TIMED mode when that is the merged sequences: one k_linearize launch then covers the directed pairs of
+        # `coal` queued calls (tcsfm_refine_window_queued); bracketed in-kernel like the others (profiling does not stop the merging)
+        timed_mode = None
+        if merged and merged["timed"]:
+            eng.set_coalesce(coal)
+            eng.set_coalesce_lanes(max(1, min(args.coalesce_lanes, lanes)))
+            queued[0] = True
+            eng.profile_begin()
+            for k in range(coal * 30):
+                step_k(k, lanes)
+            eng.flush()
+            for l in range(lanes):
+                eng.lane_synchronize(l)
+            prm = eng.profile_end()
+            queued[0] = False
+            eng.set_coalesce_lanes(1)
+            eng.set_coalesce(0)
+            km_ms, km_n = prm["linearize_kernel"]
+            am = km_ms / max(km_n, 1) * 1e-3
+            alg_m = alg_bytes * coal
+            timed_mode = {"mode": f"{coal} queued B={B} calls per launch sequence, sequences alternating over {max(1, min(args.coalesce_lanes, lanes))} streams",
+                          "pairs_per_launch": npairs * coal, "avg_launch_us": round(am * 1e6, 3), "launches": int(km_n), "algorithmic_bytes_per_launch": alg_m,
+                          "achieved": round(alg_m / am / 1e9, 2), "frac": round(alg_m / am / 1e9 / HBM_PEAK_GBPS, 5), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                          "frac_source": "this run: in-kernel s_memrealtime bracket of the merged k_linearize launches, as they run in the timed region "
+                                         "(two sequences in flight on two streams: a launch shares the chip with the other sequence's kernels)"}
+            bm_ms, bm_n = prm.get("linearize_busy", (0.0, 0))
+            if bm_ms > 0 and bm_n == km_n:
+                # the launches of the two streams overlap: the chip's rate on the kernel = all their bytes / the time at least one of them ran
+                timed_mode["chip_level"] = {"busy_us": round(bm_ms * 1e3, 1), "launch_us_summed": round(km_ms * 1e3, 1), "overlap": round(km_ms / bm_ms, 3),
+                                            "achieved": round(alg_m * km_n / (bm_ms * 1e-3) / 1e9, 2), "frac": round(alg_m * km_n / (bm_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5),
+                                            "what": "algorithmic bytes of ALL merged k_linearize launches of the pass / the time during which at least one of them was "
+                                                    "running (union of the in-kernel [start, end] brackets over both streams): what the chip sustains on the kernel in the timed mode"}
+        per_rank = [mine]
         if distributed:
-            roof["per_rank"] = per_rank
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine)
+        if rank == 0:
+            rp = rocprof_avg_us() if B == 1 else None
+            meta = profiles_meta()
+            # Headline: THIS run's in-kernel bracket.  The committed rocprofv3 average of the same kernel stands beside it and must agree
+            # (it includes ~1.2 us of dispatch and completion): frac_consistent.
+            committed = None
+            if rp and "lanes_1" in rp:
+                c_us = rp["lanes_1"]["us"]
+                committed = {"avg_launch_us": c_us, "achieved": round(alg_bytes / (c_us * 1e-6) / 1e9, 2),
+                             "frac": round(alg_bytes / (c_us * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5), "file": rp["lanes_1"]["file"],
+                             "what": "rocprofv3 --kernel-trace --stats AverageNs of the committed run of `python bench.py --lanes 1`",
+                             "dispatch_offset_us": DISPATCH_OFFSET_US}
+            traffic = load_pmc() if B == 1 else None
+            call_traffic = load_pmc("hbm_bytes_per_call") if B == 1 else None
+            vb = valu_bound(avg_s, npairs)
+            roof = {"bound": "hbm", "bound_actual": "valu", "achieved": mine["achieved"], "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": mine["frac"],
+                    "frac_source": "this run: in-kernel s_memrealtime bracket of every k_linearize launch (earliest workgroup start -> latest workgroup "
+                                   "end), one call in flight, steps rotating over the ring",
+                    "avg_launch_us": mine["avg_launch_us"], "avg_launch_us_hip_events": round(ev_s * 1e6, 3),
+                    "avg_launch_us_chunks": chunk_us,
+                    "valu_frac_of_bound": None if vb is None else vb["frac_of_bound"],
+                    "traffic": traffic, "traffic_over_algorithmic": None if traffic is None else round(traffic / alg_bytes, 3),
+                    "traffic_note": "below 1 since round 5: the algorithmic figure (32 B / pixel / directed pair: a target texel + the source taps) counts the two "
+                                    "image packs of a window once per directed pair, and the window forms now pack every image ONCE -- a pair reads its target "
+                                    "from its partner's source pack (LinParams::tshare), so the two pairs of a window fetch the same lines",
+                    "kernel": "k_linearize", "launches": int(k_n), "algorithmic_bytes_per_launch": alg_bytes,
+                    "rocprof_committed": committed,
+                    "frac_consistent": None if committed is None else bool(consistent(mine["avg_launch_us"], committed["avg_launch_us"])),
+                    "profiles_match_source": None if meta is None else meta["matches"], "profiles_meta": meta,
+                    "rocprof_avg_us": rp,
+                    "rocprof_note": "profiles/<tag>_kernel_stats.csv: rocprofv3 --kernel-trace --stats of this very command (its average covers the "
+                                    "launches of the timed blocks with `steps_in_flight` calls in flight, of the single-stream blocks and of both instrumented passes); "
+                                    "profiles/<tag>_lanes1_kernel_stats.csv: the same command with --lanes 1 (every launch has the chip); "
+                                    "profiles/<tag>_sat_kernel_stats.csv: scripts/sat_workload.py (32 windows per call)",
+                    "other_kernels_avg_us_hip_events": {k: round(v[0] / max(v[1], 1) * 1e3, 3) for k, v in prof.items() if k in ("solve", "pack")},
+                    "valu_bound": vb,
+                    "whole_call": {"algorithmic_bytes": ITERS * alg_bytes, "traffic_bytes": call_traffic,
+                                   "traffic_over_algorithmic": None if call_traffic is None else round(call_traffic / (ITERS * alg_bytes), 3),
+                                   "what": "all launches of one call (pack + 4 x (linearise + solve)) against 4 x the algorithmic bytes of a linearisation"},
+                    "measured_with": "ONE call in flight (the kernel has the chip: what a roofline compares against); `in_flight` repeats the live bracket with the "
+                                     "lanes' calls in flight, `timed_mode` brackets the launches of the mode `value` was timed in",
+                    "in_flight": inflight, "timed_mode": timed_mode}
+            if distributed:
+                roof["per_rank"] = per_rank
 
     # the same kernel with the chip full (32 windows = 64 directed pairs per call): the B=1 figure above is bounded by
     # launch latency and a grid of only 480 workgroups, this one by the kernel itself (report both)
     roof_sat = None
-    if rank == 0 and world == 1 and args.sat_windows > 0:
+    if args.full and rank == 0 and world == 1 and args.sat_windows > 0:
         rep = args.sat_windows
         two = {k: dev[k][:2] for k in ("tgt", "src", "depth_t", "depth_s", "K", "pose_init")}
         big = {k: two[k].repeat((rep,) + (1,) * (two[k].dim() - 1)).contiguous() for k in two}
@@ -853,34 +877,40 @@ def main():
 
     if rank == 0:
         windows_per_block = args.steps * B * world
-        # sanity figures from one extra, untimed call: the cost the 4 linearisations saw, and how far the refined poses are from
-        # the scene's true poses
-        _, _, st = eng.refine(dev["tgt"], dev["src"], dev["depth_t"], dev["depth_s"], dev["K"], dev["pose_init"], opts, stats=True)
-        eng.synchronize()           # (the handle runs on its own stream: its outputs are read by torch only after this)
-        cost_traj = [round(float(x), 6) for x in st[:, :ITERS, 0].mean(0).cpu()]
-        err_t = float((final[:, :3] - gt_w[:, :3]).norm(dim=1).mean() / gt_w[:, :3].norm(dim=1).mean())
-        err_0 = float((ring[0]["pose"][:, :3] - gt_w[:, :3]).norm(dim=1).mean() / gt_w[:, :3].norm(dim=1).mean())
-        # The timed windows are rendered with a plain pinhole camera, while the reference's sampler (stn.py:198-231,266) is offset by up to half a
-        # pixel of flow from it: the minimiser of the reference's residual on them is NOT the scene truth (hence ~4 % above).  The same scene
-        # rendered THROUGH the reference's sampling model (synth.make_pair(sampler_consistent=True): only the sampled role can be made
-        # consistent, so forward pairs only) has the truth as its minimiser: one untimed call each with this run's 4 Gauss-Newton iterations
-        # and with 16 Levenberg-Marquardt iterations
-        tb = synth.make_batch(2, H, W, seed0=4242, sampler_consistent=True)
-        td = {k: torch.as_tensor(v).cuda().contiguous() for k, v in tb.items()}
-        def _truth(o_):
-            p_ = eng.refine(td["tgt"], td["src"], td["depth_t"], td["depth_s"], td["K"], td["pose_init"], o_)[0]
-            eng.synchronize()
-            g_ = td["pose_gt"]
-            return {"translation_rel": round(float((p_[:, :3] - g_[:, :3]).norm(dim=1).mean() / g_[:, :3].norm(dim=1).mean()), 5),
-                    "rotation_deg": round(float(torch.rad2deg((p_[:, 3:] - g_[:, 3:]).norm(dim=1)).mean()), 4)}
-        from tightly_coupled_sfm_amd import _lib as _L
-        g0_ = td["pose_gt"]; i0_ = td["pose_init"]
-        truth = {"what": "two forward pairs of the same kind of scene rendered through the reference's own sampling model (the residual's minimiser is "
-                         "the scene truth there), perturbed as the timed windows are; untimed",
-                 "initial": {"translation_rel": round(float((i0_[:, :3] - g0_[:, :3]).norm(dim=1).mean() / g0_[:, :3].norm(dim=1).mean()), 5),
-                             "rotation_deg": round(float(torch.rad2deg((i0_[:, 3:] - g0_[:, 3:]).norm(dim=1)).mean()), 4)},
-                 "gn_4_iterations": _truth(default_opts(n_iters=ITERS)),
-                 "lm_16_iterations": _truth(default_opts(n_iters=16, solver=_L.SOLVER_LM))}
+        check = None
+        if args.full:
+            # sanity figures from one extra, untimed call: the cost the 4 linearisations saw, and how far the refined poses are from
+            # the scene's true poses
+            _, _, st = eng.refine(dev["tgt"], dev["src"], dev["depth_t"], dev["depth_s"], dev["K"], dev["pose_init"], opts, stats=True)
+            eng.synchronize()           # (the handle runs on its own stream: its outputs are read by torch only after this)
+            cost_traj = [round(float(x), 6) for x in st[:, :ITERS, 0].mean(0).cpu()]
+            err_t = float((final[:, :3] - gt_w[:, :3]).norm(dim=1).mean() / gt_w[:, :3].norm(dim=1).mean())
+            err_0 = float((ring[0]["pose"][:, :3] - gt_w[:, :3]).norm(dim=1).mean() / gt_w[:, :3].norm(dim=1).mean())
+            # The timed windows are rendered with a plain pinhole camera, while the reference's sampler (stn.py:198-231,266) is offset by up to half a
+            # pixel of flow from it: the minimiser of the reference's residual on them is NOT the scene truth (hence ~4 % above).  The same scene
+            # rendered THROUGH the reference's sampling model (synth.make_pair(sampler_consistent=True): only the sampled role can be made
+            # consistent, so forward pairs only) has the truth as its minimiser: one untimed call each with this run's 4 Gauss-Newton iterations
+            # and with 16 Levenberg-Marquardt iterations
+            tb = synth.make_batch(2, H, W, seed0=4242, sampler_consistent=True)
+            td = {k: torch.as_tensor(v).cuda().contiguous() for k, v in tb.items()}
+            def _truth(o_):
+                p_ = eng.refine(td["tgt"], td["src"], td["depth_t"], td["depth_s"], td["K"], td["pose_init"], o_)[0]
+                eng.synchronize()
+                g_ = td["pose_gt"]
+                return {"translation_rel": round(float((p_[:, :3] - g_[:, :3]).norm(dim=1).mean() / g_[:, :3].norm(dim=1).mean()), 5),
+                        "rotation_deg": round(float(torch.rad2deg((p_[:, 3:] - g_[:, 3:]).norm(dim=1)).mean()), 4)}
+            from tightly_coupled_sfm_amd import _lib as _L
+            g0_ = td["pose_gt"]; i0_ = td["pose_init"]
+            truth = {"what": "two forward pairs of the same kind of scene rendered through the reference's own sampling model (the residual's minimiser is "
+                             "the scene truth there), perturbed as the timed windows are; untimed",
+                     "initial": {"translation_rel": round(float((i0_[:, :3] - g0_[:, :3]).norm(dim=1).mean() / g0_[:, :3].norm(dim=1).mean()), 5),
+                                 "rotation_deg": round(float(torch.rad2deg((i0_[:, 3:] - g0_[:, 3:]).norm(dim=1)).mean()), 4)},
+                     "gn_4_iterations": _truth(default_opts(n_iters=ITERS)),
+                     "lm_16_iterations": _truth(default_opts(n_iters=16, solver=_L.SOLVER_LM))}
+            check = {"mean_cost_at_each_linearisation": cost_traj,
+                     "rel_translation_distance_to_scene_truth": {"initial": round(err_0, 5), "refined": round(err_t, 5),
+                                                                  "note": "pinhole-rendered windows: the reference's sampler is offset from the renderer, see truth_sampler_consistent"},
+                     "truth_sampler_consistent": truth}
         cfg_name = ("KITTI-like 640x192, batch=1 frame-pair (fwd+inv directed pairs), 4 GN iters, 6-DoF pose" if B == 1 else
                     f"KITTI-like 640x192, {B * world} frame-pairs sharded over {world} GPU(s) ({B} windows = {npairs} directed pairs per GPU and step), 4 GN iters, 6-DoF pose")
         # how the timed steps were EXECUTED is part of the workload's name (every step is one B-window call; the calls are independent windows)
@@ -897,7 +927,7 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 5),
             "higher_is_better": True, "scaling": "strong" if args.total_windows else "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": cfg_name, "timed_as": timed_as, "lane_probe": eng.lane_probe() if lanes > 1 else None, "windows_per_gpu": B, "sources": SOURCES, "directed_pairs_per_step": npairs,
                        "global_batch_frame_pairs": B * world, "gn_iters": ITERS, "solver": "gn", "param": "se3",
                        "steps_in_flight": (coal if (merged and merged["timed"]) else lanes), "lanes": lanes, "ring_calls": R, "ring_input_MB": round(R * call_bytes / 1e6, 1),
@@ -907,10 +937,11 @@ def main():
             "ms_per_step_blocks": {"min": round(blocks[0] / args.steps * 1e3, 5), "median": round(elapsed / args.steps * 1e3, 5),
                                    "max": round(blocks[-1] / args.steps * 1e3, 5)},
             "hot_cache": hot,
-            "single_stream": {"value": round(windows_per_block / single[0], 2), "ms_per_step": round(single[0] / args.steps * 1e3, 5),
-                              "what": "the same K-step blocks with ONE call in flight (steps_in_flight = 1), plain launches: the per-call latency figure; "
-                                      "the headline keeps `steps_in_flight` independent calls in flight on the handle's lanes, which fills "
-                                      "the idle time between the short kernels of a B=1 call"},
+            "single_stream": None if single is None else {
+                "value": round(windows_per_block / single[0], 2), "ms_per_step": round(single[0] / args.steps * 1e3, 5),
+                "what": "the same K-step blocks with ONE call in flight (steps_in_flight = 1), plain launches: the per-call latency figure; "
+                        "the headline keeps `steps_in_flight` independent calls in flight on the handle's lanes, which fills "
+                        "the idle time between the short kernels of a B=1 call"},
             "host_enqueue_us_per_step": round(host_enqueue_us, 2),
             "launch_mode": {"timed": ("merged sequences: the steps are queued calls, the library runs them %d at a time as one launch sequence "
                                       "(tcsfm_refine_window_queued); bit-identical poses" % coal) if (merged and merged["timed"]) else
@@ -922,13 +953,10 @@ def main():
             "final_gather_us": None if gather_us is None else round(gather_us, 1),
             "roofline": roof,
             "roofline_saturated": roof_sat,
-            "cpu_baseline": cpu_baseline(args.cpu_sample) if (args.cpu_sample > 0 and world == 1) else None,
-            "modes": modes_block(args.modes_budget) if (args.modes_budget > 0 and world == 1) else None,
-            "shim": shim_block(args.shim_sample) if (args.shim_sample > 0 and world == 1) else None,
-            "check": {"mean_cost_at_each_linearisation": cost_traj,
-                      "rel_translation_distance_to_scene_truth": {"initial": round(err_0, 5), "refined": round(err_t, 5),
-                                                                   "note": "pinhole-rendered windows: the reference's sampler is offset from the renderer, see truth_sampler_consistent"},
-                      "truth_sampler_consistent": truth},
+            "cpu_baseline": cpu_baseline(args.cpu_sample) if (args.full and args.cpu_sample > 0 and world == 1) else None,
+            "modes": modes_block(args.modes_budget) if (args.full and args.modes_budget > 0 and world == 1) else None,
+            "shim": shim_block(args.shim_sample) if (args.full and args.shim_sample > 0 and world == 1) else None,
+            "check": check,
         }
         print(json.dumps(out), flush=True)
     if distributed:

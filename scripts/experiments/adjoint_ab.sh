@@ -7,12 +7,12 @@ mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 for rep in 1 2; do
 for a in 0 1; do
-  TCSFM_ADJOINT=$a python $ROOT/bench.py --steps 20 --warmup 5 --cpu-sample 0 > $OUT/bench_adj${a}_rep${rep}.json 2> $OUT/bench_adj${a}_rep${rep}.err
+  TCSFM_ADJOINT=$a python $ROOT/bench.py --full --steps 20 --warmup 5 --cpu-sample 0 > $OUT/bench_adj${a}_rep${rep}.json 2> $OUT/bench_adj${a}_rep${rep}.err
 done
 done
 for a in 0 1; do
   export TCSFM_ADJOINT=$a
-  rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU --output-format csv -d $OUT/pmc_adj$a -- python3 $ROOT/bench.py --lanes 1 --graph-replay 0 --steps 20 --warmup 5 --cpu-sample 0 --sat-windows 0 --ring-mb 0 > $OUT/pmc_adj$a.log 2>&1
+  rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU --output-format csv -d $OUT/pmc_adj$a -- python3 $ROOT/bench.py --full --lanes 1 --graph-replay 0 --steps 20 --warmup 5 --cpu-sample 0 --sat-windows 0 --ring-mb 0 > $OUT/pmc_adj$a.log 2>&1
 done
 python3 - <<PY
 import json, glob, csv, collections

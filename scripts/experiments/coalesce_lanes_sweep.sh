@@ -7,7 +7,7 @@ mkdir -p $OUT
 for K in 20 200; do
 for cfg in "10 1" "10 2" "10 3" "10 4" "5 2" "5 4" "16 2" "20 2"; do
   set -- $cfg
-  python $ROOT/bench.py --steps $K --warmup 5 --cpu-sample 0 --sat-windows 0 --coalesce $1 --coalesce-lanes $2 > $OUT/b_${K}_$1_$2.json 2> $OUT/b_${K}_$1_$2.err
+  python $ROOT/bench.py --full --steps $K --warmup 5 --cpu-sample 0 --sat-windows 0 --coalesce $1 --coalesce-lanes $2 > $OUT/b_${K}_$1_$2.json 2> $OUT/b_${K}_$1_$2.err
   python3 - <<PY
 import json
 d = json.loads(open("$OUT/b_${K}_$1_$2.json").read().strip().splitlines()[-1])

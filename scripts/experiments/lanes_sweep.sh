@@ -5,7 +5,7 @@ OUT=$ROOT/gpurun_out/lanes_sweep
 mkdir -p $OUT
 for L in 3 4 5 6 8; do
   for K in 20 1000; do
-    python $ROOT/bench.py --lanes $L --steps $K --warmup 50 --cpu-sample 0 --sat-windows 0 --ring-mb 120 > $OUT/l${L}_k${K}.json 2> $OUT/l${L}_k${K}.err
+    python $ROOT/bench.py --full --lanes $L --steps $K --warmup 50 --cpu-sample 0 --sat-windows 0 --ring-mb 120 > $OUT/l${L}_k${K}.json 2> $OUT/l${L}_k${K}.err
     python3 -c "
 import json
 d = json.loads(open('$OUT/l${L}_k${K}.json').read().strip().splitlines()[-1])

@@ -10,7 +10,7 @@ cp tightly_coupled_sfm_amd/libtcsfm_hip.so /tmp/lib_keep1.so
 for r in $(seq 1 ${1:-3}); do
   for v in 64 32 16; do
     cp tightly_coupled_sfm_amd/variants/pk$v.so tightly_coupled_sfm_amd/libtcsfm_hip.so
-    python bench.py --steps 20 --warmup 5 --cpu-sample 0 --sat-windows 0 --modes-budget 0 --shim-sample 0 2>/dev/null | python -c "
+    python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --sat-windows 0 --modes-budget 0 --shim-sample 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d['roofline']
 print('pack tile $v x', 256//$v, 'pack_us', r['other_kernels_avg_us_hip_events']['pack'], 'value', d['value'], 'single', d['single_stream']['value'], 'merged', d['launch_mode']['merged']['value'])"

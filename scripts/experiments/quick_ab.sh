@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/quick_ab
 mkdir -p $OUT
 for rep in 1 2; do
-  python $ROOT/bench.py --steps 20 --warmup 5 --cpu-sample 0 > $OUT/bench_rep${rep}.json 2> $OUT/bench_rep${rep}.err
+  python $ROOT/bench.py --full --steps 20 --warmup 5 --cpu-sample 0 > $OUT/bench_rep${rep}.json 2> $OUT/bench_rep${rep}.err
   python3 - <<PY
 import json
 d = json.loads(open("$OUT/bench_rep${rep}.json").read().strip().splitlines()[-1])

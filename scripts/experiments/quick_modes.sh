@@ -5,7 +5,7 @@ cd /tmp; export TMPDIR=/tmp
 for MODE in "$@"; do
   OUT=$ROOT/gpurun_out/quick_$MODE
   rm -rf $OUT; mkdir -p $OUT
-  if [ "$MODE" = "bench1" ]; then CMD="$ROOT/bench.py --lanes 1 --steps 300 --warmup 50 --cpu-sample 0 --sat-windows 0";
+  if [ "$MODE" = "bench1" ]; then CMD="$ROOT/bench.py --full --lanes 1 --steps 300 --warmup 50 --cpu-sample 0 --sat-windows 0";
   elif [ "$MODE" = "sat" ]; then CMD="$ROOT/scripts/sat_workload.py";
   elif [ "$MODE" = "seqS2" ]; then CMD="$ROOT/scripts/seq_profile.py 2 1 8";
   elif [ "$MODE" = "seqS1" ]; then CMD="$ROOT/scripts/seq_profile.py 1 1 8";

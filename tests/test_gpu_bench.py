@@ -20,7 +20,7 @@ def _line(out):
 
 
 def test_bench_single_process():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "10", "--cpu-sample", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "60", "--warmup", "10", "--cpu-sample", "1",
                         "--sat-windows", "4", "--modes-budget", "3", "--shim-sample", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -116,7 +116,7 @@ def test_bench_two_ranks_one_card(tmp_path):
     # started the way the driver starts it: `python bench.py --gpus 2` -- the parent launches the ranks itself
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--ring-mb", "100",
-                        "--dump-poses", dump], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--dump-poses", dump, "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)                                                                       # rank 0 prints, once
     assert d["n_gpus"] == 2 and d["cpu_baseline"] is None and d["value"] > 100
@@ -147,6 +147,10 @@ def test_bench_strong_scaling_option():
     d = _line(r.stdout)
     assert d["scaling"] == "strong" and d["config"]["windows_per_gpu"] == 4 and d["config"]["directed_pairs_per_step"] == 8
     assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) < 0.01 * d["value"]
+    # a plain run (no --full) stops once the headline is known: the timed legs up to it ran, nothing after it
+    assert d["full"] is False and d["launch_mode"]["merged"]["value"] > 0 and d["launch_mode"]["lanes"]["value"] > 0
+    assert d["hot_cache"]["value"] > 0 and d["launch_mode"]["other_mode"]["value"] > 0
+    assert all(d[k] is None for k in ("single_stream", "roofline", "roofline_saturated", "cpu_baseline", "modes", "shim", "check", "final_gather_us"))
 
 
 def test_bench_dump_outputs(tmp_path):
@@ -182,7 +186,7 @@ def test_bench_world_size_one_over_rccl():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                TCSFM_BENCH_FORCE_DIST="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-sample", "0",
-                        "--sat-windows", "0"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                        "--sat-windows", "0", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
     assert d["n_gpus"] == 1 and d["value"] > 100 and d["final_gather_us"] is not None and d["final_gather_us"] > 0
