@@ -358,6 +358,36 @@ int tcsfm_posenet_forward(tcsfm_posenet *pn, int N, const float *imgs, float *po
 int tcsfm_solve_pose_iteratively(tcsfm_handle h, tcsfm_posenet *pn, int num_iter, int B, int S, const float *tgt, const float *srcs,
                                  const float *depth_t, const float *depth_s, const float *K, float *poses_out, float *stacked_out);
 
+/* ---- depth network --------------------------------------------------------------------------------
+ * The reference's depth network (models/depth_w_access.py with num_scales = 1, the default of run_mono_training.py): a ResNet18
+ * encoder on (x - 0.45) / 0.22 (conv1 7x7/2 + BN + ReLU -> skip 0, maxpool 3x3/2, layer1..layer4 of BasicBlocks -> skips 1..4;
+ * BatchNorm with its running statistics) and a U-Net decoder (for i = 0..4: ELU(conv3x3_reflect(nearest_up2(x))) (+ skip 3-i for
+ * i < 4), ELU(conv3x3_reflect(.)); then feature_convs.0 32 -> 8 ELU and predict_disps.0 8 -> 1 sigmoid).  Hand-written gfx950
+ * kernels in exact fp32 (matrix instructions), BatchNorm folded into the weights at load time, padding / up-sampling /
+ * normalisation / mirroring applied while the operands are gathered.  The work split of every layer depends on the handle's
+ * H x W only: an image's outputs are bit-identical whatever N and whichever other images share the call.
+ *   tcsfm_depthnet_create   activations for up to max_images images of the handle's H x W; refuses (TCSFM_E_ARG) an H or W that is
+ *                           not a multiple of 32 (the reference's skip additions fail there too)
+ *   tcsfm_depthnet_load     n HOST tensors of the reference module's state_dict: names[i], data host_ptrs[i] (float32, contiguous),
+ *                           shape shapes[4 i .. 4 i + 3] (unused trailing dimensions 0).  Needs encoder.encoder.{conv1, bn1,
+ *                           layer*.*.{conv1,bn1,conv2,bn2}, layer{2,3,4}.0.downsample.{0,1}}.*, depth_upconvs.{i}.1.conv.*,
+ *                           iconvs.{i}.0.conv.*, feature_convs.0.0.conv.*, predict_disps.0.0.conv.*; other names (fc.*,
+ *                           num_batches_tracked) are ignored.  A missing or mis-shaped tensor, and a num_scales > 1 model
+ *                           (feature_convs.1.* present, or predict_disps.0 not 8 input channels), is refused; the error names the key.
+ *   tcsfm_depthnet_encode   imgs [N,3,H,W] planar (device); flip != 0 mirrors every image horizontally first (bit-identical to the
+ *                           mirrored input).  skips_out[k] (device, caller-owned) receive the encoder features NHWC:
+ *                           skip k = [N, H >> (k+1), W >> (k+1), C_k], C = 64, 64, 128, 256, 512
+ *   tcsfm_depthnet_decode   skips_in[5] in that layout (device) -> disp_out [N,1,H,W] (device)
+ *   tcsfm_depthnet_forward  encode + decode with the instance's own skip buffers
+ * All calls are asynchronous on the handle's stream, except load, which waits for the stream before it replaces the weights. */
+typedef struct tcsfm_depthnet tcsfm_depthnet;
+int tcsfm_depthnet_create(tcsfm_handle h, int max_images, tcsfm_depthnet **out);
+void tcsfm_depthnet_destroy(tcsfm_depthnet *dn);
+int tcsfm_depthnet_load(tcsfm_depthnet *dn, int n, const char *const names[], const float *const host_ptrs[], const int64_t *shapes);
+int tcsfm_depthnet_encode(tcsfm_depthnet *dn, int N, const float *imgs, int flip, float *const skips_out[5]);
+int tcsfm_depthnet_decode(tcsfm_depthnet *dn, int N, const float *const skips_in[5], float *disp_out);
+int tcsfm_depthnet_forward(tcsfm_depthnet *dn, int N, const float *imgs, int flip, float *disp_out);
+
 /* ---- lanes: several refinements in flight (streaming a sequence) ----------------------------------
  * The reference's driver refines one window after another (run_sequential_optimization.py:186-247: DataLoader batch -> H2D ->
  * optimize_window); consecutive windows do not depend on each other.  A B=1 refinement leaves the GPU idle between its short

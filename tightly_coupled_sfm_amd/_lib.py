@@ -134,6 +134,12 @@ _SIGNATURES = {
     "tcsfm_posenet_load": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "tcsfm_posenet_forward": (C.c_int, [_P, C.c_int, _P, _P]),
     "tcsfm_solve_pose_iteratively": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int] + [_P] * 7),
+    "tcsfm_depthnet_create": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
+    "tcsfm_depthnet_destroy": (None, [_P]),
+    "tcsfm_depthnet_load": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "tcsfm_depthnet_encode": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "tcsfm_depthnet_decode": (C.c_int, [_P, C.c_int, _P, _P]),
+    "tcsfm_depthnet_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     "tcsfm_set_lanes": (C.c_int, [_P, C.c_int]),
     "tcsfm_set_graph_replay": (C.c_int, [_P, C.c_int]),
     "tcsfm_graph_replay_counts": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

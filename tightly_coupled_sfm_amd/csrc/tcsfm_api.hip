@@ -17,6 +17,7 @@
 #include "dense_ref_kernel.h"
 #include "scale_kernel.h"
 #include "posenet_kernel.h"
+#include "depthnet_kernel.h"
 
 using namespace tc;
 
@@ -3128,6 +3129,327 @@ int tcsfm_solve_pose_iteratively(tcsfm_handle h, tcsfm_posenet *pn, int num_iter
     DeviceGuard dev_guard(h->device);
     if (int rc_ = pending_error(h)) return rc_;
     return pose_loop(h, pn, num_iter, B, S, tgt, srcs, depth_t, depth_s, K, poses_out, stacked_out, nullptr);
+}
+
+// ---- depth network (models/depth_w_access.py, num_scales = 1): ResNet18 encoder + U-Net decoder ------------------------------
+}  // extern "C"   (the depth network's host helpers are templates)
+
+namespace {
+struct DnLayer {
+    int cin = 0, cout = 0, coutp = 0, ks = 0, stride = 1, pad = 0, up = 0, reflect = 0, epi = DN_EPI_NONE;
+    int ih = 0, iw = 0, oh = 0, ow = 0;
+    int nb = 1, pb = 1, kw = 1;         // work split: a function of the layer's geometry only (never of N)
+    std::string wname, bname, bn;       // state_dict names: conv weight, conv bias ("" = none), BatchNorm prefix ("" = none)
+    dn_f4 *w4 = nullptr;
+    float *bias = nullptr;
+};
+const int DN_SKIP_C[5] = {64, 64, 128, 256, 512};
+}  // namespace
+
+struct tcsfm_depthnet {
+    tcsfm_ctx *h = nullptr;
+    int max_images = 0, loaded = 0;
+    std::vector<DnLayer> L;             // [0] conv1, then the encoder's block convolutions, then the decoder (order of dn_layers)
+    int enc_end = 0;                    // index of the first decoder layer
+    float *pw = nullptr, *pb = nullptr; // predict_disps.0 weight [1,8,3,3] / bias [1]
+    float *skip[5] = {};                // tcsfm_depthnet_forward's own skips, NHWC
+    float *pool = nullptr, *t1 = nullptr, *t2 = nullptr, *ds = nullptr;   // encoder scratch, N * H * W * 4 floats each
+    float *u = nullptr, *x = nullptr;   // decoder scratch, N * H * W * 32 floats each
+};
+
+namespace {
+void dn_split(DnLayer &l) {
+    const int npix = l.oh * l.ow, cb = l.coutp / 16;
+    if (npix >= 4096) { l.nb = std::min(4, cb); l.pb = 2; l.kw = 1; }
+    else if (npix >= 1024) { l.nb = std::min(2, cb); l.pb = 1; l.kw = 4; }
+    else { l.nb = 1; l.pb = 1; l.kw = 4; }
+}
+
+DnLayer dn_layer(int cin, int cout, int ks, int stride, int ih, int iw, int up, int reflect, int epi, const std::string &w,
+                 const std::string &b, const std::string &bn) {
+    DnLayer l;
+    l.cin = cin; l.cout = cout; l.coutp = (cout + 15) / 16 * 16; l.ks = ks; l.stride = stride; l.pad = (ks - 1) / 2;
+    l.up = up; l.reflect = reflect; l.epi = epi; l.ih = ih; l.iw = iw;
+    const int vh = ih << up, vw = iw << up;
+    l.oh = (vh + 2 * l.pad - ks) / stride + 1; l.ow = (vw + 2 * l.pad - ks) / stride + 1;
+    l.wname = w; l.bname = b; l.bn = bn;
+    dn_split(l);
+    return l;
+}
+
+// the network's convolutions in evaluation order
+void dn_layers(tcsfm_depthnet *dn) {
+    const int H = dn->h->H, W = dn->h->W;
+    const std::string E = "encoder.encoder.";
+    auto &L = dn->L;
+    L.clear();
+    L.push_back(dn_layer(3, 64, 7, 2, H, W, 0, 0, DN_EPI_RELU, E + "conv1.weight", "", E + "bn1"));
+    L.back().oh = H / 2; L.back().ow = W / 2;
+    int h = H / 4, w = W / 4, c = 64;
+    for (int li = 1; li <= 4; li++) {
+        const int co = 64 << (li - 1 > 0 ? li - 1 : 0);
+        for (int b = 0; b < 2; b++) {
+            const std::string pre = E + "layer" + std::to_string(li) + "." + std::to_string(b) + ".";
+            const int s = (b == 0 && li > 1) ? 2 : 1;
+            L.push_back(dn_layer(c, co, 3, s, h, w, 0, 0, DN_EPI_RELU, pre + "conv1.weight", "", pre + "bn1"));
+            const int oh = L.back().oh, ow = L.back().ow;
+            L.push_back(dn_layer(co, co, 3, 1, oh, ow, 0, 0, DN_EPI_RES_RELU, pre + "conv2.weight", "", pre + "bn2"));
+            if (s == 2) L.push_back(dn_layer(c, co, 1, 2, h, w, 0, 0, DN_EPI_NONE, pre + "downsample.0.weight", "", pre + "downsample.1"));
+            h = oh; w = ow; c = co;
+        }
+    }
+    dn->enc_end = (int)L.size();
+    static const int planes[6] = {512, 256, 128, 64, 64, 32};
+    for (int i = 0; i < 5; i++) {
+        const std::string u = "depth_upconvs." + std::to_string(i) + ".1.conv.", ic = "iconvs." + std::to_string(i) + ".0.conv.";
+        L.push_back(dn_layer(planes[i], planes[i + 1], 3, 1, h, w, 1, 1, i < 4 ? DN_EPI_ELU_ADD : DN_EPI_ELU, u + "weight", u + "bias", ""));
+        h *= 2; w *= 2;
+        L.push_back(dn_layer(planes[i + 1], planes[i + 1], 3, 1, h, w, 0, 1, DN_EPI_ELU, ic + "weight", ic + "bias", ""));
+    }
+    L.push_back(dn_layer(32, 8, 3, 1, h, w, 0, 1, DN_EPI_ELU, "feature_convs.0.0.conv.weight", "feature_convs.0.0.conv.bias", ""));
+}
+
+void dn_free(tcsfm_depthnet *dn) {
+    for (DnLayer &l : dn->L) { if (l.w4) (void)hipFree(l.w4); if (l.bias) (void)hipFree(l.bias); l.w4 = nullptr; l.bias = nullptr; }
+    float *bufs[] = {dn->pw, dn->pb, dn->skip[0], dn->skip[1], dn->skip[2], dn->skip[3], dn->skip[4], dn->pool, dn->t1, dn->t2, dn->ds, dn->u, dn->x};
+    for (float *p : bufs) if (p) (void)hipFree(p);
+}
+
+template <int KS, int NB, int PB, int KW>
+void dn_launch(const DnLayer &l, const DnConvParams &P, int N, hipStream_t s) {
+    dim3 grid((l.oh * l.ow + 16 * PB * (4 / KW) - 1) / (16 * PB * (4 / KW)), l.coutp / (16 * NB), N);
+    hipLaunchKernelGGL((k_dn_conv<KS, NB, PB, KW>), grid, dim3(256), 0, s, P);
+}
+
+template <int KS>
+void dn_launch_ks(const DnLayer &l, const DnConvParams &P, int N, hipStream_t s) {
+    if (l.kw == 1 && l.pb == 2) {
+        if (l.nb == 4) dn_launch<KS, 4, 2, 1>(l, P, N, s);
+        else if (l.nb == 2) dn_launch<KS, 2, 2, 1>(l, P, N, s);
+        else dn_launch<KS, 1, 2, 1>(l, P, N, s);
+    } else if (l.nb == 2) dn_launch<KS, 2, 1, 4>(l, P, N, s);
+    else dn_launch<KS, 1, 1, 4>(l, P, N, s);
+}
+
+void dn_conv(tcsfm_depthnet *dn, int li, int N, const float *in, const float *res, float *out) {
+    const DnLayer &l = dn->L[li];
+    DnConvParams P;
+    P.in = in; P.w4 = l.w4; P.bias = l.bias; P.res = res; P.out = out;
+    P.cin = l.cin; P.cout = l.cout; P.coutp = l.coutp; P.ih = l.ih; P.iw = l.iw; P.oh = l.oh; P.ow = l.ow;
+    P.stride = l.stride; P.pad = l.pad; P.up = l.up; P.reflect = l.reflect; P.epi = l.epi;
+    if (l.ks == 1) dn_launch_ks<1>(l, P, N, dn->h->stream);
+    else dn_launch_ks<3>(l, P, N, dn->h->stream);
+}
+
+int dn_encode(tcsfm_depthnet *dn, int N, const float *imgs, int flip, float *const sk[5]) {
+    tcsfm_ctx *h = dn->h;
+    const DnLayer &c1 = dn->L[0];
+    DnConv1Params P1;
+    P1.img = imgs; P1.w4 = c1.w4; P1.bias = c1.bias; P1.out = sk[0]; P1.ih = h->H; P1.iw = h->W; P1.oh = c1.oh; P1.ow = c1.ow; P1.flip = flip ? 1 : 0;
+    hipLaunchKernelGGL(k_dn_conv1<2>, dim3((c1.oh * c1.ow + 127) / 128, 1, N), dim3(256), 0, h->stream, P1);
+    const int ph = c1.oh / 2, pw = c1.ow / 2;
+    const long long pool_thr = (long long)N * ph * pw * 16;
+    hipLaunchKernelGGL(k_dn_maxpool, dim3((unsigned)((pool_thr + 255) / 256)), dim3(256), 0, h->stream, (const float *)sk[0], dn->pool, N, 64, c1.oh, c1.ow, ph, pw);
+    const float *x = dn->pool;
+    int li = 1;
+    for (int stage = 1; stage <= 4; stage++)
+        for (int b = 0; b < 2; b++) {
+            const bool down = b == 0 && stage > 1;
+            float *out = b == 1 ? sk[stage] : (x == dn->t2 ? dn->pool : dn->t2);
+            dn_conv(dn, li, N, x, nullptr, dn->t1);                                   // conv1 + bn1 + relu
+            const float *ident = x;
+            if (down) { dn_conv(dn, li + 2, N, x, nullptr, dn->ds); ident = dn->ds; }  // downsample.0 + downsample.1
+            dn_conv(dn, li + 1, N, dn->t1, ident, out);                               // conv2 + bn2 + identity, relu
+            li += down ? 3 : 2;
+            x = out;
+        }
+    HIPCHK(h, hipGetLastError());
+    return TCSFM_OK;
+}
+
+int dn_decode(tcsfm_depthnet *dn, int N, const float *const sk[5], float *disp) {
+    tcsfm_ctx *h = dn->h;
+    const float *x = sk[4];
+    int li = dn->enc_end;
+    for (int i = 0; i < 5; i++) {
+        dn_conv(dn, li, N, x, i < 4 ? sk[3 - i] : nullptr, dn->u);       // ELU(conv3x3_reflect(up2(x)) + b) (+ skip)
+        dn_conv(dn, li + 1, N, dn->u, nullptr, dn->x);                   // ELU(conv3x3_reflect(.) + b)
+        x = dn->x; li += 2;
+    }
+    dn_conv(dn, li, N, dn->x, nullptr, dn->u);                           // feature_convs.0: 32 -> 8, ELU
+    const long long npx = (long long)N * h->H * h->W;
+    hipLaunchKernelGGL(k_dn_predict, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, (const float *)dn->u, (const float *)dn->pw,
+                       (const float *)dn->pb, disp, N, h->H, h->W);
+    HIPCHK(h, hipGetLastError());
+    return TCSFM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void tcsfm_depthnet_destroy(tcsfm_depthnet *dn) {
+    if (!dn) return;
+    DeviceGuard dev_guard(dn->h->device);
+    dn_free(dn);
+    delete dn;
+}
+
+int tcsfm_depthnet_create(tcsfm_handle h, int max_images, tcsfm_depthnet **out) {
+    if (!h || !out) return TCSFM_E_ARG;
+    *out = nullptr;
+    if (max_images < 1 || max_images > 4096) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_create: max_images out of range");
+    if (h->H % 32 || h->W % 32 || h->H < 32 || h->W < 32)
+        return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_create: the handle's H and W must be multiples of 32 (the decoder's skip additions need them)");
+    DeviceGuard dev_guard(h->device);
+    tcsfm_depthnet *dn = new tcsfm_depthnet();
+    dn->h = h; dn->max_images = max_images;
+    dn_layers(dn);
+    hipError_t e = hipSuccess;
+    for (DnLayer &l : dn->L) {
+        const size_t nw4 = (l.ks == 7 ? 11 : (size_t)l.ks * l.ks * (l.cin / 16)) * 4 * l.coutp;
+        if (e == hipSuccess) e = hipMalloc((void **)&l.w4, nw4 * sizeof(dn_f4));
+        if (e == hipSuccess) e = hipMalloc((void **)&l.bias, l.coutp * sizeof(float));
+    }
+    const size_t N = (size_t)max_images, hw = (size_t)h->H * h->W;
+    if (e == hipSuccess) e = hipMalloc((void **)&dn->pw, 72 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&dn->pb, sizeof(float));
+    for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipMalloc((void **)&dn->skip[k], N * (hw >> (2 * (k + 1))) * DN_SKIP_C[k] * sizeof(float));
+    float **enc[] = {&dn->pool, &dn->t1, &dn->t2, &dn->ds};
+    for (float **p : enc) if (e == hipSuccess) e = hipMalloc((void **)p, N * hw * 4 * sizeof(float));       // (H/4)(W/4) x 64 = H W x 4
+    if (e == hipSuccess) e = hipMalloc((void **)&dn->u, N * hw * 32 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&dn->x, N * hw * 32 * sizeof(float));
+    if (e != hipSuccess) { tcsfm_depthnet_destroy(dn); return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_depthnet_create: allocation failed"); }
+    *out = dn;
+    return TCSFM_OK;
+}
+
+int tcsfm_depthnet_load(tcsfm_depthnet *dn, int n, const char *const names[], const float *const host_ptrs[], const int64_t *shapes) {
+    if (!dn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = dn->h;
+    if (n < 0 || (n > 0 && (!names || !host_ptrs || !shapes))) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_load: NULL argument");
+    for (int i = 0; i < n; i++) {
+        if (!names[i]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_load: NULL name");
+        if (!strncmp(names[i], "feature_convs.1.", 16) || !strncmp(names[i], "predict_disps.1.", 16)) {
+            h->err = std::string("tcsfm_depthnet_load: ") + names[i] + ": num_scales > 1 is not supported";
+            return TCSFM_E_ARG;
+        }
+    }
+    auto find = [&](const std::string &key, std::vector<int64_t> shape, const float **ptr) -> int {
+        for (int i = 0; i < n; i++)
+            if (key == names[i]) {
+                bool ok = host_ptrs[i] != nullptr;
+                for (int d = 0; d < 4; d++) ok = ok && shapes[4 * i + d] == (d < (int)shape.size() ? shape[d] : 0);
+                if (!ok) {
+                    std::string s = "(";
+                    for (size_t d = 0; d < shape.size(); d++) s += (d ? "," : "") + std::to_string(shape[d]);
+                    h->err = "tcsfm_depthnet_load: " + key + ": missing data or wrong shape (expected " + s + "))";
+                    if (key == "predict_disps.0.0.conv.weight" && shapes[4 * i + 1] != 8) h->err += ": num_scales > 1 is not supported";
+                    return TCSFM_E_ARG;
+                }
+                *ptr = host_ptrs[i];
+                return TCSFM_OK;
+            }
+        h->err = "tcsfm_depthnet_load: " + key + ": missing";
+        return TCSFM_E_ARG;
+    };
+    DeviceGuard dev_guard(h->device);
+    // fold + lay out every layer on the host (float64 fold, deterministic), then copy
+    std::vector<std::vector<float>> w4s(dn->L.size()), biases(dn->L.size());
+    for (size_t li = 0; li < dn->L.size(); li++) {
+        const DnLayer &l = dn->L[li];
+        const float *w = nullptr, *cb = nullptr, *g = nullptr, *be = nullptr, *rm = nullptr, *rv = nullptr;
+        int rc;
+        if ((rc = find(l.wname, {l.cout, l.cin, l.ks, l.ks}, &w))) return rc;
+        if (!l.bname.empty() && (rc = find(l.bname, {l.cout}, &cb))) return rc;
+        if (!l.bn.empty()) {
+            if ((rc = find(l.bn + ".weight", {l.cout}, &g)) || (rc = find(l.bn + ".bias", {l.cout}, &be)) ||
+                (rc = find(l.bn + ".running_mean", {l.cout}, &rm)) || (rc = find(l.bn + ".running_var", {l.cout}, &rv))) return rc;
+        }
+        std::vector<double> sc(l.cout, 1.0), sh(l.cout, 0.0);
+        for (int co = 0; co < l.cout; co++) {
+            if (g) { sc[co] = (double)g[co] / sqrt((double)rv[co] + 1e-5); sh[co] = (double)be[co] - (double)rm[co] * sc[co]; }
+            if (cb) sh[co] += (double)cb[co] * sc[co];
+        }
+        auto W = [&](int co, int ci, int ky, int kx) { return (float)((double)w[(((size_t)co * l.cin + ci) * l.ks + ky) * l.ks + kx] * sc[co]); };
+        std::vector<float> &o = w4s[li];
+        if (l.ks == 7) {        // first layer: (g, kq) -> (ci, ky) = combo 2 g + (kq >> 1), kx = 4 (kq & 1) + t
+            o.assign((size_t)11 * 4 * l.coutp * 4, 0.f);
+            for (int gq = 0; gq < 44; gq++) {
+                const int gg = gq >> 2, kq = gq & 3, combo = 2 * gg + (kq >> 1);
+                if (combo >= 21) continue;
+                const int ci = combo / 7, ky = combo % 7;
+                for (int co = 0; co < l.cout; co++)
+                    for (int t = 0; t < 4; t++) {
+                        const int kx = 4 * (kq & 1) + t;
+                        if (kx < 7) o[((size_t)(gg * 4 + kq) * l.coutp + co) * 4 + t] = W(co, ci, ky, kx);
+                    }
+            }
+        } else {
+            const int c16n = l.cin / 16;
+            o.assign((size_t)l.ks * l.ks * c16n * 4 * l.coutp * 4, 0.f);
+            for (int tap = 0; tap < l.ks * l.ks; tap++)
+                for (int c16 = 0; c16 < c16n; c16++)
+                    for (int kq = 0; kq < 4; kq++)
+                        for (int co = 0; co < l.cout; co++)
+                            for (int t = 0; t < 4; t++)
+                                o[((size_t)((tap * c16n + c16) * 4 + kq) * l.coutp + co) * 4 + t] = W(co, c16 * 16 + 4 * kq + t, tap / l.ks, tap % l.ks);
+        }
+        biases[li].assign(l.coutp, 0.f);
+        for (int co = 0; co < l.cout; co++) biases[li][co] = (float)sh[co];
+    }
+    const float *pw = nullptr, *pb = nullptr;
+    int rc;
+    if ((rc = find("predict_disps.0.0.conv.weight", {1, 8, 3, 3}, &pw)) || (rc = find("predict_disps.0.0.conv.bias", {1}, &pb))) return rc;
+    if (int rc_q = drain_queued(h)) return rc_q;
+    HIPCHK(h, hipStreamSynchronize(h->stream));     // weights may be in use by earlier calls on the stream
+    for (size_t li = 0; li < dn->L.size(); li++) {
+        HIPCHK(h, hipMemcpy(dn->L[li].w4, w4s[li].data(), w4s[li].size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(dn->L[li].bias, biases[li].data(), biases[li].size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    HIPCHK(h, hipMemcpy(dn->pw, pw, 72 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(dn->pb, pb, sizeof(float), hipMemcpyHostToDevice));
+    dn->loaded = 1;
+    return TCSFM_OK;
+}
+
+static int dn_check(tcsfm_depthnet *dn, int N, const char *fn) {
+    tcsfm_ctx *h = dn->h;
+    if (!dn->loaded) { h->err = std::string(fn) + ": no weights loaded"; return TCSFM_E_ARG; }
+    if (N < 1 || N > dn->max_images) { h->err = std::string(fn) + ": N out of range (1 .. max_images)"; return TCSFM_E_ARG; }
+    return TCSFM_OK;
+}
+
+int tcsfm_depthnet_encode(tcsfm_depthnet *dn, int N, const float *imgs, int flip, float *const skips_out[5]) {
+    if (!dn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = dn->h;
+    if (int rc = dn_check(dn, N, "tcsfm_depthnet_encode")) return rc;
+    if (!imgs || !skips_out) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode: NULL argument");
+    for (int k = 0; k < 5; k++) if (!skips_out[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode: NULL skip buffer");
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    return dn_encode(dn, N, imgs, flip, skips_out);
+}
+
+int tcsfm_depthnet_decode(tcsfm_depthnet *dn, int N, const float *const skips_in[5], float *disp_out) {
+    if (!dn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = dn->h;
+    if (int rc = dn_check(dn, N, "tcsfm_depthnet_decode")) return rc;
+    if (!skips_in || !disp_out) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode: NULL argument");
+    for (int k = 0; k < 5; k++) if (!skips_in[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode: NULL skip buffer");
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    return dn_decode(dn, N, skips_in, disp_out);
+}
+
+int tcsfm_depthnet_forward(tcsfm_depthnet *dn, int N, const float *imgs, int flip, float *disp_out) {
+    if (!dn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = dn->h;
+    if (int rc = dn_check(dn, N, "tcsfm_depthnet_forward")) return rc;
+    if (!imgs || !disp_out) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_forward: NULL argument");
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    if (int rc = dn_encode(dn, N, imgs, flip, dn->skip)) return rc;
+    return dn_decode(dn, N, dn->skip, disp_out);
 }
 
 void tcsfm_pose_to_matrix(const double pose[6], double T[12]) { tc::pose_to_T(pose, T); }

@@ -173,12 +173,18 @@ class DepthOptimizer:
                                    and self._refine_mode() == "pose" and o.get("param", "se3") == "se3") else 0.0)
 
     def _disparities(self, imgs):
-        """depth net forward in the reference's two call forms (optimizer.py:146-147) or a plain callable"""
+        """depth net forward in the reference's two call forms (optimizer.py:146-147) or a plain callable.  options['library_depth_net']
+        = True runs a reference depth module on the library's own kernels (depthnet.DepthNetHIP, created once per module)"""
+        net = self.depth_model
+        if self.options.get("library_depth_net", False):
+            from ._shared import get_engine
+            from .depthnet import library_depthnet
+            net = library_depthnet(self.depth_model, get_engine(imgs.shape[2], imgs.shape[3], 1), imgs.shape[0]) or self.depth_model
         try:
-            _, skips = self.depth_model(x=imgs, return_disp=False, epoch=50)
-            disparities, _ = self.depth_model(x=None, skips=skips, epoch=50)
+            _, skips = net(x=imgs, return_disp=False, epoch=50)
+            disparities, _ = net(x=None, skips=skips, epoch=50)
         except TypeError:
-            disparities, _ = self.depth_model(imgs)
+            disparities, _ = net(imgs)
         return disparities[0]
 
     # -- the reference's coupled pose initialisation, warp done by the HIP library -------------------------------
