@@ -388,6 +388,37 @@ int tcsfm_depthnet_encode(tcsfm_depthnet *dn, int N, const float *imgs, int flip
 int tcsfm_depthnet_decode(tcsfm_depthnet *dn, int N, const float *const skips_in[5], float *disp_out);
 int tcsfm_depthnet_forward(tcsfm_depthnet *dn, int N, const float *imgs, int flip, float *disp_out);
 
+/* ---- depth network: training (weight tuning) ----------------------------------------------------------------------------
+ * The exact fp32 gradient of the network above (BatchNorm with its running statistics, num_scales = 1) for the reference's
+ * test-time weight tuning (Adam on the encoder's, all or the decoder's weights) and bottleneck tuning (gradients of the skips).
+ * A training forward runs the kernels of tcsfm_depthnet_encode / _decode unchanged (its skips and disparity are bit-identical to
+ * theirs) and keeps the activations the backward needs in a caller-owned tape; the backward reads the tape only.
+ *   tcsfm_depthnet_load_device    as tcsfm_depthnet_load (same names, checks and refusals), but the tensors are DEVICE pointers and
+ *                                 the call is asynchronous on the handle's stream: the parameters are copied into the instance and
+ *                                 re-folded on the device (float64, the host fold's bits).  Call it again after every parameter
+ *                                 update (an optimiser step); there is no host round trip.  The training calls below need it.
+ *   tcsfm_depthnet_tape_size      floats of the encoder's and the decoder's tapes for N images (about 6.5 M and 17.4 M per 640 x 192
+ *                                 image)
+ *   tcsfm_depthnet_encode_train   imgs [N,3,H,W] -> skips_out[5] (as tcsfm_depthnet_encode, no mirroring) and the encoder tape
+ *   tcsfm_depthnet_decode_train   skips_in[5] -> disp_out [N,1,H,W] and the decoder tape
+ *   tcsfm_depthnet_decode_backward  decoder tape, d_disp [N,1,H,W] -> d_skips[k] [N,h_k,w_k,C_k] NHWC for every non-NULL entry (d_skips
+ *                                 itself may be NULL), and the gradients of the n_grads decoder parameters names[i] (state_dict names)
+ *                                 into grads[i] (device, reference layout [co,ci,kh,kw] / [c]); outputs are overwritten
+ *   tcsfm_depthnet_encode_backward  encoder tape, d_skips[5] (NULL entries: zero) -> gradients of the n_grads encoder parameters
+ * Only what is requested is computed: a parameter that is not named gets no kernel, and the data gradient stops below the lowest
+ * requested parameter or skip.  Running statistics have no gradient (refused, as are unknown names and names of the other half).
+ * Calls with N > max_images run in groups of max_images; weight gradients of the groups are summed in group order.  Weight gradients
+ * are reduced in a fixed order (no float atomics): two calls on the same inputs give the same bits, and an image's skip gradients do
+ * not depend on the other images of the call.  All calls are asynchronous on the handle's stream. */
+int tcsfm_depthnet_load_device(tcsfm_depthnet *dn, int n, const char *const names[], const float *const dev_ptrs[], const int64_t *shapes);
+int tcsfm_depthnet_tape_size(tcsfm_depthnet *dn, int N, int64_t *enc_floats, int64_t *dec_floats);
+int tcsfm_depthnet_encode_train(tcsfm_depthnet *dn, int N, const float *imgs, float *const skips_out[5], float *tape);
+int tcsfm_depthnet_decode_train(tcsfm_depthnet *dn, int N, const float *const skips_in[5], float *disp_out, float *tape);
+int tcsfm_depthnet_decode_backward(tcsfm_depthnet *dn, int N, const float *tape, const float *d_disp, float *const d_skips[5], int n_grads,
+                                   const char *const names[], float *const grads[]);
+int tcsfm_depthnet_encode_backward(tcsfm_depthnet *dn, int N, const float *tape, const float *const d_skips[5], int n_grads,
+                                   const char *const names[], float *const grads[]);
+
 /* ---- lanes: several refinements in flight (streaming a sequence) ----------------------------------
  * The reference's driver refines one window after another (run_sequential_optimization.py:186-247: DataLoader batch -> H2D ->
  * optimize_window); consecutive windows do not depend on each other.  A B=1 refinement leaves the GPU idle between its short

@@ -140,6 +140,12 @@ _SIGNATURES = {
     "tcsfm_depthnet_encode": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     "tcsfm_depthnet_decode": (C.c_int, [_P, C.c_int, _P, _P]),
     "tcsfm_depthnet_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "tcsfm_depthnet_load_device": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "tcsfm_depthnet_tape_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tcsfm_depthnet_encode_train": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "tcsfm_depthnet_decode_train": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "tcsfm_depthnet_decode_backward": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P]),
+    "tcsfm_depthnet_encode_backward": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P]),
     "tcsfm_set_lanes": (C.c_int, [_P, C.c_int]),
     "tcsfm_set_graph_replay": (C.c_int, [_P, C.c_int]),
     "tcsfm_graph_replay_counts": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

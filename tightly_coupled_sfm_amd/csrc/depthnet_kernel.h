@@ -29,6 +29,7 @@ struct DnConvParams {
     const float *bias;      // [coutp] (BatchNorm folded)
     const float *res;       // [N][oh][ow][cout]: residual (DN_EPI_RES_RELU, before the ReLU) or skip (DN_EPI_ELU_ADD, after the ELU)
     float *out;             // [N][oh][ow][cout]
+    float *aux;             // DN_EPI_ELU_ADD: the ELU value before the skip add (training tape; NULL: not stored)
     int cin, cout, coutp;   // coutp = cout rounded up to 16 (the weight image's width; channels >= cout are zero and not stored)
     int ih, iw, oh, ow;
     int stride, pad, up, reflect, epi;
@@ -159,7 +160,12 @@ __global__ __launch_bounds__(256) void k_dn_conv(DnConvParams P) {
                     case DN_EPI_RELU: v = fmaxf(v, 0.f); break;
                     case DN_EPI_RES_RELU: v = fmaxf(v + P.res[o], 0.f); break;
                     case DN_EPI_ELU: v = dn_elu(v); break;
-                    case DN_EPI_ELU_ADD: v = dn_elu(v) + P.res[o]; break;
+                    case DN_EPI_ELU_ADD: {
+                        const float e = dn_elu(v);
+                        if (P.aux) P.aux[o] = e;
+                        v = e + P.res[o];
+                        break;
+                    }
                     default: break;
                 }
                 P.out[o] = v;

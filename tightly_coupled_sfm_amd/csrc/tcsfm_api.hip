@@ -18,6 +18,7 @@
 #include "scale_kernel.h"
 #include "posenet_kernel.h"
 #include "depthnet_kernel.h"
+#include "depthnet_grad_kernel.h"
 
 using namespace tc;
 
@@ -3142,6 +3143,13 @@ struct DnLayer {
     std::string wname, bname, bn;       // state_dict names: conv weight, conv bias ("" = none), BatchNorm prefix ("" = none)
     dn_f4 *w4 = nullptr;
     float *bias = nullptr;
+    // training (tcsfm_depthnet_load_device): the transposed weight image of the data gradient (not for conv1), the raw parameters'
+    // snapshot (w [cout][cin][ks][ks], then conv bias, gamma, beta, mean, var [cout] each) and the folded-gradient accumulators
+    // (dw' [cout][cin ks ks], db' [cout])
+    dn_f4 *wt4 = nullptr;
+    float *raw = nullptr, *gw = nullptr, *gb = nullptr;
+    int taps() const { return ks * ks; }
+    size_t nw() const { return (size_t)cout * cin * ks * ks; }
 };
 const int DN_SKIP_C[5] = {64, 64, 128, 256, 512};
 }  // namespace
@@ -3155,6 +3163,12 @@ struct tcsfm_depthnet {
     float *skip[5] = {};                // tcsfm_depthnet_forward's own skips, NHWC
     float *pool = nullptr, *t1 = nullptr, *t2 = nullptr, *ds = nullptr;   // encoder scratch, N * H * W * 4 floats each
     float *u = nullptr, *x = nullptr;   // decoder scratch, N * H * W * 32 floats each
+    // training state (allocated by the first tcsfm_depthnet_load_device)
+    int train_loaded = 0;
+    float *tbuf = nullptr;              // one allocation: the layers' raw / gw / gb regions and the head's gradient accumulator
+    float *hacc = nullptr;              // head: d predict_disps weight [72] + bias [1]
+    float *part = nullptr, *bpart = nullptr, *hpart = nullptr;   // weight / bias / head partials of one image group
+    float *gA = nullptr, *gB = nullptr, *gC = nullptr, *gD = nullptr, *gV = nullptr;   // data-gradient scratch
 };
 
 namespace {
@@ -3211,7 +3225,9 @@ void dn_layers(tcsfm_depthnet *dn) {
 
 void dn_free(tcsfm_depthnet *dn) {
     for (DnLayer &l : dn->L) { if (l.w4) (void)hipFree(l.w4); if (l.bias) (void)hipFree(l.bias); l.w4 = nullptr; l.bias = nullptr; }
-    float *bufs[] = {dn->pw, dn->pb, dn->skip[0], dn->skip[1], dn->skip[2], dn->skip[3], dn->skip[4], dn->pool, dn->t1, dn->t2, dn->ds, dn->u, dn->x};
+    for (DnLayer &l : dn->L) { if (l.wt4) (void)hipFree(l.wt4); l.wt4 = nullptr; }
+    float *bufs[] = {dn->pw, dn->pb, dn->skip[0], dn->skip[1], dn->skip[2], dn->skip[3], dn->skip[4], dn->pool, dn->t1, dn->t2, dn->ds, dn->u, dn->x,
+                     dn->tbuf, dn->part, dn->bpart, dn->hpart, dn->gA, dn->gB, dn->gC, dn->gD, dn->gV};
     for (float *p : bufs) if (p) (void)hipFree(p);
 }
 
@@ -3231,10 +3247,10 @@ void dn_launch_ks(const DnLayer &l, const DnConvParams &P, int N, hipStream_t s)
     else dn_launch<KS, 1, 1, 4>(l, P, N, s);
 }
 
-void dn_conv(tcsfm_depthnet *dn, int li, int N, const float *in, const float *res, float *out) {
+void dn_conv(tcsfm_depthnet *dn, int li, int N, const float *in, const float *res, float *out, float *aux = nullptr) {
     const DnLayer &l = dn->L[li];
     DnConvParams P;
-    P.in = in; P.w4 = l.w4; P.bias = l.bias; P.res = res; P.out = out;
+    P.in = in; P.w4 = l.w4; P.bias = l.bias; P.res = res; P.out = out; P.aux = aux;
     P.cin = l.cin; P.cout = l.cout; P.coutp = l.coutp; P.ih = l.ih; P.iw = l.iw; P.oh = l.oh; P.ow = l.ow;
     P.stride = l.stride; P.pad = l.pad; P.up = l.up; P.reflect = l.reflect; P.epi = l.epi;
     if (l.ks == 1) dn_launch_ks<1>(l, P, N, dn->h->stream);
@@ -3283,6 +3299,55 @@ int dn_decode(tcsfm_depthnet *dn, int N, const float *const sk[5], float *disp) 
     HIPCHK(h, hipGetLastError());
     return TCSFM_OK;
 }
+
+// the tensors of a state_dict by name for every layer (names / shapes checked; the error names the key)
+struct DnSrc { const float *w = nullptr, *cb = nullptr, *g = nullptr, *be = nullptr, *rm = nullptr, *rv = nullptr; };
+int dn_lookup(tcsfm_depthnet *dn, const char *fn, int n, const char *const names[], const float *const ptrs[], const int64_t *shapes,
+              std::vector<DnSrc> &src, const float **pw, const float **pb) {
+    tcsfm_ctx *h = dn->h;
+    const std::string pre = std::string(fn) + ": ";
+    if (n < 0 || (n > 0 && (!names || !ptrs || !shapes))) return fail(h, TCSFM_E_ARG, (pre + "NULL argument").c_str());
+    for (int i = 0; i < n; i++) {
+        if (!names[i]) return fail(h, TCSFM_E_ARG, (pre + "NULL name").c_str());
+        if (!strncmp(names[i], "feature_convs.1.", 16) || !strncmp(names[i], "predict_disps.1.", 16)) {
+            h->err = pre + names[i] + ": num_scales > 1 is not supported";
+            return TCSFM_E_ARG;
+        }
+    }
+    auto find = [&](const std::string &key, std::vector<int64_t> shape, const float **ptr) -> int {
+        for (int i = 0; i < n; i++)
+            if (key == names[i]) {
+                bool ok = ptrs[i] != nullptr;
+                for (int d = 0; d < 4; d++) ok = ok && shapes[4 * i + d] == (d < (int)shape.size() ? shape[d] : 0);
+                if (!ok) {
+                    std::string s = "(";
+                    for (size_t d = 0; d < shape.size(); d++) s += (d ? "," : "") + std::to_string(shape[d]);
+                    h->err = pre + key + ": missing data or wrong shape (expected " + s + "))";
+                    if (key == "predict_disps.0.0.conv.weight" && shapes[4 * i + 1] != 8) h->err += ": num_scales > 1 is not supported";
+                    return TCSFM_E_ARG;
+                }
+                *ptr = ptrs[i];
+                return TCSFM_OK;
+            }
+        h->err = pre + key + ": missing";
+        return TCSFM_E_ARG;
+    };
+    src.assign(dn->L.size(), DnSrc());
+    for (size_t li = 0; li < dn->L.size(); li++) {
+        const DnLayer &l = dn->L[li];
+        DnSrc &p = src[li];
+        int rc;
+        if ((rc = find(l.wname, {l.cout, l.cin, l.ks, l.ks}, &p.w))) return rc;
+        if (!l.bname.empty() && (rc = find(l.bname, {l.cout}, &p.cb))) return rc;
+        if (!l.bn.empty()) {
+            if ((rc = find(l.bn + ".weight", {l.cout}, &p.g)) || (rc = find(l.bn + ".bias", {l.cout}, &p.be)) ||
+                (rc = find(l.bn + ".running_mean", {l.cout}, &p.rm)) || (rc = find(l.bn + ".running_var", {l.cout}, &p.rv))) return rc;
+        }
+    }
+    int rc;
+    if ((rc = find("predict_disps.0.0.conv.weight", {1, 8, 3, 3}, pw)) || (rc = find("predict_disps.0.0.conv.bias", {1}, pb))) return rc;
+    return TCSFM_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3326,45 +3391,15 @@ int tcsfm_depthnet_create(tcsfm_handle h, int max_images, tcsfm_depthnet **out) 
 int tcsfm_depthnet_load(tcsfm_depthnet *dn, int n, const char *const names[], const float *const host_ptrs[], const int64_t *shapes) {
     if (!dn) return TCSFM_E_ARG;
     tcsfm_ctx *h = dn->h;
-    if (n < 0 || (n > 0 && (!names || !host_ptrs || !shapes))) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_load: NULL argument");
-    for (int i = 0; i < n; i++) {
-        if (!names[i]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_load: NULL name");
-        if (!strncmp(names[i], "feature_convs.1.", 16) || !strncmp(names[i], "predict_disps.1.", 16)) {
-            h->err = std::string("tcsfm_depthnet_load: ") + names[i] + ": num_scales > 1 is not supported";
-            return TCSFM_E_ARG;
-        }
-    }
-    auto find = [&](const std::string &key, std::vector<int64_t> shape, const float **ptr) -> int {
-        for (int i = 0; i < n; i++)
-            if (key == names[i]) {
-                bool ok = host_ptrs[i] != nullptr;
-                for (int d = 0; d < 4; d++) ok = ok && shapes[4 * i + d] == (d < (int)shape.size() ? shape[d] : 0);
-                if (!ok) {
-                    std::string s = "(";
-                    for (size_t d = 0; d < shape.size(); d++) s += (d ? "," : "") + std::to_string(shape[d]);
-                    h->err = "tcsfm_depthnet_load: " + key + ": missing data or wrong shape (expected " + s + "))";
-                    if (key == "predict_disps.0.0.conv.weight" && shapes[4 * i + 1] != 8) h->err += ": num_scales > 1 is not supported";
-                    return TCSFM_E_ARG;
-                }
-                *ptr = host_ptrs[i];
-                return TCSFM_OK;
-            }
-        h->err = "tcsfm_depthnet_load: " + key + ": missing";
-        return TCSFM_E_ARG;
-    };
+    std::vector<DnSrc> src;
+    const float *pw = nullptr, *pb = nullptr;
+    if (int rc = dn_lookup(dn, "tcsfm_depthnet_load", n, names, host_ptrs, shapes, src, &pw, &pb)) return rc;
     DeviceGuard dev_guard(h->device);
     // fold + lay out every layer on the host (float64 fold, deterministic), then copy
     std::vector<std::vector<float>> w4s(dn->L.size()), biases(dn->L.size());
     for (size_t li = 0; li < dn->L.size(); li++) {
         const DnLayer &l = dn->L[li];
-        const float *w = nullptr, *cb = nullptr, *g = nullptr, *be = nullptr, *rm = nullptr, *rv = nullptr;
-        int rc;
-        if ((rc = find(l.wname, {l.cout, l.cin, l.ks, l.ks}, &w))) return rc;
-        if (!l.bname.empty() && (rc = find(l.bname, {l.cout}, &cb))) return rc;
-        if (!l.bn.empty()) {
-            if ((rc = find(l.bn + ".weight", {l.cout}, &g)) || (rc = find(l.bn + ".bias", {l.cout}, &be)) ||
-                (rc = find(l.bn + ".running_mean", {l.cout}, &rm)) || (rc = find(l.bn + ".running_var", {l.cout}, &rv))) return rc;
-        }
+        const float *w = src[li].w, *cb = src[li].cb, *g = src[li].g, *be = src[li].be, *rm = src[li].rm, *rv = src[li].rv;
         std::vector<double> sc(l.cout, 1.0), sh(l.cout, 0.0);
         for (int co = 0; co < l.cout; co++) {
             if (g) { sc[co] = (double)g[co] / sqrt((double)rv[co] + 1e-5); sh[co] = (double)be[co] - (double)rm[co] * sc[co]; }
@@ -3397,9 +3432,6 @@ int tcsfm_depthnet_load(tcsfm_depthnet *dn, int n, const char *const names[], co
         biases[li].assign(l.coutp, 0.f);
         for (int co = 0; co < l.cout; co++) biases[li][co] = (float)sh[co];
     }
-    const float *pw = nullptr, *pb = nullptr;
-    int rc;
-    if ((rc = find("predict_disps.0.0.conv.weight", {1, 8, 3, 3}, &pw)) || (rc = find("predict_disps.0.0.conv.bias", {1}, &pb))) return rc;
     if (int rc_q = drain_queued(h)) return rc_q;
     HIPCHK(h, hipStreamSynchronize(h->stream));     // weights may be in use by earlier calls on the stream
     for (size_t li = 0; li < dn->L.size(); li++) {
@@ -3409,6 +3441,7 @@ int tcsfm_depthnet_load(tcsfm_depthnet *dn, int n, const char *const names[], co
     HIPCHK(h, hipMemcpy(dn->pw, pw, 72 * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(dn->pb, pb, sizeof(float), hipMemcpyHostToDevice));
     dn->loaded = 1;
+    dn->train_loaded = 0;               // the training snapshot (tcsfm_depthnet_load_device) no longer matches the weights
     return TCSFM_OK;
 }
 
@@ -3450,6 +3483,541 @@ int tcsfm_depthnet_forward(tcsfm_depthnet *dn, int N, const float *imgs, int fli
     DeviceGuard dev_guard(h->device);
     if (int rc = dn_encode(dn, N, imgs, flip, dn->skip)) return rc;
     return dn_decode(dn, N, dn->skip, disp_out);
+}
+
+}  // extern "C"   (the depth network's training helpers)
+
+namespace {
+// ---- depth network training: tape layout, device re-fold, data / weight gradients ------------------------------------------
+// The tape of N images is a list of entries, each [N][per-image size] (entry-major), so a group of images [i0, i1) of a chunked call
+// is a pointer offset in every entry.
+struct DnTape {
+    std::vector<size_t> sz, off;        // per-image floats of each entry; offset of each entry for N images
+    float *base = nullptr;
+    int N = 0;
+    float *at(int k, int i0) const { return base + off[k] + (size_t)i0 * sz[k]; }
+    size_t total() const { size_t t = 0; for (size_t s : sz) t += s; return t * N; }
+};
+
+void dn_tape_layout(const tcsfm_depthnet *dn, int dec, int N, float *base, DnTape &t) {
+    const int H = dn->h->H, W = dn->h->W;
+    const size_t hw = (size_t)H * W;
+    t.sz.clear();
+    if (!dec) {
+        // images, conv1's output (skip 0), the pooled map, then per block: conv1's output, the block's output
+        const DnLayer &c1 = dn->L[0];
+        t.sz.push_back(3 * hw);
+        t.sz.push_back((size_t)c1.oh * c1.ow * 64);
+        t.sz.push_back((size_t)(c1.oh / 2) * (c1.ow / 2) * 64);
+        for (int li = 1; li < dn->enc_end;) {
+            const DnLayer &a = dn->L[li];
+            const bool down = a.stride == 2;
+            t.sz.push_back((size_t)a.oh * a.ow * a.cout);
+            t.sz.push_back((size_t)a.oh * a.ow * a.cout);
+            li += down ? 3 : 2;
+        }
+    } else {
+        // skip 4, then per up-step i: the ELU before the skip add (i < 4), up-conv output, iconv output; features; disparity
+        const DnLayer &u0 = dn->L[dn->enc_end];
+        t.sz.push_back((size_t)u0.ih * u0.iw * u0.cin);
+        for (int i = 0; i < 5; i++) {
+            const DnLayer &u = dn->L[dn->enc_end + 2 * i];
+            const size_t s = (size_t)u.oh * u.ow * u.cout;
+            if (i < 4) t.sz.push_back(s);
+            t.sz.push_back(s);
+            t.sz.push_back(s);
+        }
+        t.sz.push_back(hw * 8);
+        t.sz.push_back(hw);
+    }
+    t.off.assign(t.sz.size(), 0);
+    size_t o = 0;
+    for (size_t k = 0; k < t.sz.size(); k++) { t.off[k] = o; o += t.sz[k] * N; }
+    t.base = base; t.N = N;
+}
+
+int dn_wchunk(int npix) { return npix <= 2048 ? npix : 2048; }     // weight-gradient K chunk (pixels of one image): geometry only
+int dn_nchunk(int npix) { const int c = dn_wchunk(npix); return (npix + c - 1) / c; }
+size_t dn_cinT(const DnLayer &l) { return l.ks == 7 ? 147 : (size_t)l.cin * l.taps(); }
+
+// the padded virtual grid of a reflect-padded / up-sampled layer (the data gradient's lane grid before k_dnb_fold)
+void dn_padded_grid(const DnLayer &l, int &gh, int &gw) { gh = (l.ih << l.up) + 2 * l.pad; gw = (l.iw << l.up) + 2 * l.pad; }
+
+int dn_train_alloc(tcsfm_depthnet *dn) {
+    if (dn->tbuf) return TCSFM_OK;
+    tcsfm_ctx *h = dn->h;
+    const size_t N = dn->max_images, hw = (size_t)h->H * h->W;
+    size_t tot = 0, part = 0, bpart = 0, gv = 0;
+    for (const DnLayer &l : dn->L) {
+        tot += l.nw() + 5 * (size_t)l.cout + l.nw() + l.cout;
+        const int npix = l.oh * l.ow;
+        part = std::max(part, N * dn_nchunk(npix) * l.cout * dn_cinT(l));
+        bpart = std::max(bpart, N * dn_nchunk(npix) * l.cout);
+        if (l.reflect) { int gh, gw; dn_padded_grid(l, gh, gw); gv = std::max(gv, N * gh * gw * l.cin); }
+    }
+    tot += 73;
+    hipError_t e = hipMalloc((void **)&dn->tbuf, tot * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&dn->part, part * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&dn->bpart, bpart * sizeof(float));
+    const int hch = (int)((hw + DNB_HEAD_CHUNK - 1) / DNB_HEAD_CHUNK);
+    if (e == hipSuccess) e = hipMalloc((void **)&dn->hpart, N * hch * 73 * sizeof(float));
+    float **g32[] = {&dn->gA, &dn->gB, &dn->gC};
+    for (float **p : g32) if (e == hipSuccess) e = hipMalloc((void **)p, N * hw * 32 * sizeof(float));    // the largest activation: H W x 32
+    if (e == hipSuccess) e = hipMalloc((void **)&dn->gD, N * hw * 4 * sizeof(float));                      // a downsample's input grid
+    if (e == hipSuccess) e = hipMalloc((void **)&dn->gV, gv * sizeof(float));
+    size_t o = 0;
+    for (DnLayer &l : dn->L) {
+        l.raw = dn->tbuf + o; o += l.nw() + 5 * (size_t)l.cout;
+        l.gw = dn->tbuf + o; o += l.nw();
+        l.gb = dn->tbuf + o; o += l.cout;
+        if (l.ks != 7 && e == hipSuccess) {
+            const size_t n4 = (size_t)l.taps() * l.coutp * l.cin;      // floats / 4 ... in dn_f4 units: taps * coutp/16 * 4 * cin
+            e = hipMalloc((void **)&l.wt4, n4 / 4 * sizeof(dn_f4) * 1);
+            if (e == hipSuccess) e = hipMemsetAsync(l.wt4, 0, n4 * sizeof(float), h->stream);   // rows of channels >= cout stay zero
+        }
+        if (e == hipSuccess) {
+            const size_t nw4 = (l.ks == 7 ? 11 : (size_t)l.ks * l.ks * (l.cin / 16)) * 4 * l.coutp;
+            e = hipMemsetAsync(l.w4, 0, nw4 * sizeof(dn_f4), h->stream);
+        }
+    }
+    dn->hacc = dn->tbuf + o;
+    if (e != hipSuccess) {
+        for (DnLayer &l : dn->L) { if (l.wt4) (void)hipFree(l.wt4); l.wt4 = nullptr; l.raw = l.gw = l.gb = nullptr; }
+        float **bufs[] = {&dn->tbuf, &dn->part, &dn->bpart, &dn->hpart, &dn->gA, &dn->gB, &dn->gC, &dn->gD, &dn->gV};
+        for (float **p : bufs) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_depthnet_load_device: allocation failed");
+    }
+    return TCSFM_OK;
+}
+
+unsigned dn_blocks(long long threads) { return (unsigned)((threads + 255) / 256); }
+
+template <int KS, int NB, int PB, int KW>
+void dnb_dgrad_launch(int gpix, int cin, const DnDgradParams &P, int N, hipStream_t s) {
+    dim3 grid((gpix + 16 * PB * (4 / KW) - 1) / (16 * PB * (4 / KW)), cin / (16 * NB), N);
+    hipLaunchKernelGGL((k_dnb_dgrad<KS, NB, PB, KW>), grid, dim3(256), 0, s, P);
+}
+
+template <int KS>
+void dnb_dgrad_ks(int gpix, int cin, const DnDgradParams &P, int N, hipStream_t s) {
+    // the forward's split rule (dn_split) on the lane grid and the input channel blocks
+    const int cb = cin / 16;
+    if (gpix >= 4096) {
+        const int nb = std::min(4, cb);
+        if (nb == 4) dnb_dgrad_launch<KS, 4, 2, 1>(gpix, cin, P, N, s);
+        else if (nb == 2) dnb_dgrad_launch<KS, 2, 2, 1>(gpix, cin, P, N, s);
+        else dnb_dgrad_launch<KS, 1, 2, 1>(gpix, cin, P, N, s);
+    } else if (gpix >= 1024 && cb >= 2) dnb_dgrad_launch<KS, 2, 1, 4>(gpix, cin, P, N, s);
+    else dnb_dgrad_launch<KS, 1, 1, 4>(gpix, cin, P, N, s);
+}
+
+// data gradient of layer l from dz: direct (input grid, fused adds + derivative) or onto the padded virtual grid (then k_dnb_fold)
+void dnb_dgrad(tcsfm_depthnet *dn, int li, int N, const float *dz, float *out, bool direct, const float *add1, const float *add2,
+               const float *y, int act) {
+    const DnLayer &l = dn->L[li];
+    DnDgradParams P;
+    P.dz = dz; P.wt4 = l.wt4; P.out = out; P.add1 = add1; P.add2 = add2; P.y = y; P.act = act;
+    P.cin = l.cin; P.cout = l.cout; P.coutp = l.coutp; P.oh = l.oh; P.ow = l.ow; P.stride = l.stride; P.direct = direct ? 1 : 0;
+    if (direct) { P.gh = l.ih; P.gw = l.iw; P.goff = l.pad; }
+    else { dn_padded_grid(l, P.gh, P.gw); P.goff = 0; }
+    if (l.ks == 1) dnb_dgrad_ks<1>(P.gh * P.gw, l.cin, P, N, dn->h->stream);
+    else dnb_dgrad_ks<3>(P.gh * P.gw, l.cin, P, N, dn->h->stream);
+}
+
+void dnb_fold(tcsfm_depthnet *dn, int li, int N, const float *src, const float *add, const float *y, int act, float *out, float *raw_out) {
+    DnFoldParams F;
+    const DnLayer *l = li >= 0 ? &dn->L[li] : nullptr;
+    F.src = src; F.add = add; F.y = y; F.act = act; F.out = out; F.raw_out = raw_out; F.N = N;
+    F.C = l->cin; F.ih = l->ih; F.iw = l->iw; F.up = l->up; F.pad = l->pad; F.reflect = l->reflect;
+    dn_padded_grid(*l, F.gh, F.gw);
+    hipLaunchKernelGGL(k_dnb_fold, dim3(dn_blocks((long long)N * F.ih * F.iw * (F.C / 4))), dim3(256), 0, dn->h->stream, F);
+}
+
+// (src + add) * act'(y) elementwise on an [N][h][w][C] map (C % 4 == 0)
+void dnb_ew(tcsfm_depthnet *dn, int N, int C, int hh, int ww, const float *src, const float *add, const float *y, int act, float *out) {
+    DnFoldParams F;
+    F.src = src; F.add = add; F.y = y; F.act = act; F.out = out; F.raw_out = nullptr; F.N = N;
+    F.C = C; F.ih = hh; F.iw = ww; F.gh = hh; F.gw = ww; F.up = 0; F.pad = 0; F.reflect = 0;
+    hipLaunchKernelGGL(k_dnb_fold, dim3(dn_blocks((long long)N * hh * ww * (C / 4))), dim3(256), 0, dn->h->stream, F);
+}
+
+// weight (wneed) and bias (bneed) gradients of the folded layer into l.gw / l.gb (accumulate: add to them)
+void dnb_wgrad(tcsfm_depthnet *dn, int li, int N, const float *dz, const float *x, bool wneed, bool bneed, int accumulate) {
+    DnLayer &l = dn->L[li];
+    hipStream_t s = dn->h->stream;
+    const int npix = l.oh * l.ow, chunk = dn_wchunk(npix), nch = dn_nchunk(npix), parts = N * nch;
+    if (wneed) {
+        DnWgradParams P;
+        P.dz = dz; P.x = x; P.part = dn->part; P.cin = l.cin; P.cout = l.cout; P.ih = l.ih; P.iw = l.iw; P.oh = l.oh; P.ow = l.ow;
+        P.stride = l.stride; P.pad = l.pad; P.up = l.up; P.reflect = l.reflect; P.chunk = chunk; P.nchunk = nch;
+        if (l.ks == 7) hipLaunchKernelGGL((k_dnb_wgrad<7, 2, true>), dim3(parts, 2, l.coutp / 32), dim3(256), 0, s, P);
+        else if (l.ks == 1) hipLaunchKernelGGL((k_dnb_wgrad<1, 2, false>), dim3(parts, l.cin / 16, l.coutp / 32), dim3(256), 0, s, P);
+        else if (l.coutp % 32 == 0) hipLaunchKernelGGL((k_dnb_wgrad<9, 2, false>), dim3(parts, l.cin / 16, l.coutp / 32), dim3(256), 0, s, P);
+        else hipLaunchKernelGGL((k_dnb_wgrad<9, 1, false>), dim3(parts, l.cin / 16, l.coutp / 16), dim3(256), 0, s, P);
+        const long long E = (long long)l.cout * dn_cinT(l);
+        hipLaunchKernelGGL(k_dnb_wsum, dim3(dn_blocks(E)), dim3(256), 0, s, (const float *)dn->part, l.gw, E, parts, accumulate);
+    }
+    if (bneed) {
+        hipLaunchKernelGGL(k_dnb_bgrad, dim3(parts), dim3(256), 0, s, dz, dn->bpart, l.cout, npix, chunk, nch);
+        hipLaunchKernelGGL(k_dnb_wsum, dim3(dn_blocks(l.cout)), dim3(256), 0, s, (const float *)dn->bpart, l.gb, (long long)l.cout, parts, accumulate);
+    }
+}
+
+// requested parameter gradients, by layer
+struct DnReq {
+    float *w = nullptr, *cb = nullptr, *g = nullptr, *be = nullptr;
+    bool wneed() const { return w || g; }
+    bool bneed() const { return cb || g || be; }
+    bool any() const { return w || cb || g || be; }
+};
+
+// names -> per-layer requests (decoder: layers >= enc_end and the head; encoder: the others)
+int dn_requests(tcsfm_depthnet *dn, const char *fn, bool dec, int n, const char *const names[], float *const grads[],
+                std::vector<DnReq> &req, float **hw, float **hb) {
+    tcsfm_ctx *h = dn->h;
+    req.assign(dn->L.size(), DnReq());
+    *hw = *hb = nullptr;
+    if (n < 0 || (n > 0 && (!names || !grads))) return fail(h, TCSFM_E_ARG, (std::string(fn) + ": NULL argument").c_str());
+    for (int i = 0; i < n; i++) {
+        if (!names[i] || !grads[i]) return fail(h, TCSFM_E_ARG, (std::string(fn) + ": NULL name or gradient buffer").c_str());
+        const std::string k = names[i];
+        float **slot = nullptr;
+        bool mine = false;
+        for (size_t li = 0; li < dn->L.size() && !slot; li++) {
+            DnLayer &l = dn->L[li];
+            const bool d = (int)li >= dn->enc_end;
+            if (k == l.wname) slot = &req[li].w;
+            else if (!l.bname.empty() && k == l.bname) slot = &req[li].cb;
+            else if (!l.bn.empty() && k == l.bn + ".weight") slot = &req[li].g;
+            else if (!l.bn.empty() && k == l.bn + ".bias") slot = &req[li].be;
+            else if (!l.bn.empty() && (k == l.bn + ".running_mean" || k == l.bn + ".running_var")) {
+                h->err = std::string(fn) + ": " + k + ": running statistics have no gradient";
+                return TCSFM_E_ARG;
+            }
+            if (slot) mine = d == dec;
+        }
+        if (!slot && k == "predict_disps.0.0.conv.weight") { slot = hw; mine = dec; }
+        if (!slot && k == "predict_disps.0.0.conv.bias") { slot = hb; mine = dec; }
+        if (!slot || !mine) {
+            h->err = std::string(fn) + ": " + k + (slot ? ": not a parameter of this half of the network" : ": unknown parameter");
+            return TCSFM_E_ARG;
+        }
+        *slot = grads[i];
+    }
+    return TCSFM_OK;
+}
+
+// the chain rule through the fold and the reference layout, for every requested layer
+void dn_param_out(tcsfm_depthnet *dn, const std::vector<DnReq> &req, int lo, int hi) {
+    for (int li = lo; li < hi; li++) {
+        const DnReq &r = req[li];
+        if (!r.any()) continue;
+        DnLayer &l = dn->L[li];
+        const float *w = l.raw, *v = l.raw + l.nw();
+        const bool bn = !l.bn.empty();
+        hipLaunchKernelGGL(k_dnb_param_grad, dim3(dn_blocks(l.cout)), dim3(256), 0, dn->h->stream, (const float *)l.gw, (const float *)l.gb, w,
+                           bn ? v + l.cout : nullptr, v + 3 * l.cout, v + 4 * l.cout, r.w, r.cb, r.g, r.be, l.cout, (int)l.nw() / l.cout);
+    }
+}
+
+int dn_encode_train(tcsfm_depthnet *dn, int N, const float *imgs, const DnTape &t, int i0, float *const sk[5]) {
+    tcsfm_ctx *h = dn->h;
+    HIPCHK(h, hipMemcpyAsync(t.at(0, i0), imgs, (size_t)N * t.sz[0] * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    const DnLayer &c1 = dn->L[0];
+    DnConv1Params P1;
+    P1.img = imgs; P1.w4 = c1.w4; P1.bias = c1.bias; P1.out = t.at(1, i0); P1.ih = h->H; P1.iw = h->W; P1.oh = c1.oh; P1.ow = c1.ow; P1.flip = 0;
+    hipLaunchKernelGGL(k_dn_conv1<2>, dim3((c1.oh * c1.ow + 127) / 128, 1, N), dim3(256), 0, h->stream, P1);
+    const int ph = c1.oh / 2, pw = c1.ow / 2;
+    const long long pool_thr = (long long)N * ph * pw * 16;
+    hipLaunchKernelGGL(k_dn_maxpool, dim3((unsigned)((pool_thr + 255) / 256)), dim3(256), 0, h->stream, (const float *)t.at(1, i0), t.at(2, i0), N, 64,
+                       c1.oh, c1.ow, ph, pw);
+    const float *x = t.at(2, i0);
+    int li = 1, e = 3;
+    for (int stage = 1; stage <= 4; stage++)
+        for (int b = 0; b < 2; b++) {
+            const bool down = b == 0 && stage > 1;
+            float *t1 = t.at(e, i0), *out = t.at(e + 1, i0);
+            dn_conv(dn, li, N, x, nullptr, t1);
+            const float *ident = x;
+            if (down) { dn_conv(dn, li + 2, N, x, nullptr, dn->ds); ident = dn->ds; }
+            dn_conv(dn, li + 1, N, t1, ident, out);
+            li += down ? 3 : 2; e += 2;
+            x = out;
+            if (b == 1) HIPCHK(h, hipMemcpyAsync(sk[stage], out, (size_t)N * t.sz[e - 1] * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        }
+    HIPCHK(h, hipMemcpyAsync(sk[0], t.at(1, i0), (size_t)N * t.sz[1] * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipGetLastError());
+    return TCSFM_OK;
+}
+
+int dn_decode_train(tcsfm_depthnet *dn, int N, const float *const sk[5], float *disp, const DnTape &t, int i0) {
+    tcsfm_ctx *h = dn->h;
+    HIPCHK(h, hipMemcpyAsync(t.at(0, i0), sk[4], (size_t)N * t.sz[0] * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    const float *x = sk[4];
+    int li = dn->enc_end, e = 1;
+    for (int i = 0; i < 5; i++) {
+        float *aux = i < 4 ? t.at(e++, i0) : nullptr;
+        float *u = t.at(e++, i0), *xo = t.at(e++, i0);
+        dn_conv(dn, li, N, x, i < 4 ? sk[3 - i] : nullptr, u, aux);
+        dn_conv(dn, li + 1, N, u, nullptr, xo);
+        x = xo; li += 2;
+    }
+    float *f = t.at(e, i0), *dt = t.at(e + 1, i0);
+    dn_conv(dn, li, N, x, nullptr, f);
+    const long long npx = (long long)N * h->H * h->W;
+    hipLaunchKernelGGL(k_dn_predict, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, (const float *)f, (const float *)dn->pw,
+                       (const float *)dn->pb, dt, N, h->H, h->W);
+    HIPCHK(h, hipMemcpyAsync(disp, dt, (size_t)npx * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipGetLastError());
+    return TCSFM_OK;
+}
+
+// decoder backward of one image group.  Layer positions: up_i = enc_end + 2 i, iconv_i = enc_end + 2 i + 1, feature conv, head.
+int dn_decode_backward(tcsfm_depthnet *dn, int N, const DnTape &t, int i0, const float *ddisp, float *const dsk[5],
+                       const std::vector<DnReq> &req, bool head_req, int accumulate) {
+    tcsfm_ctx *h = dn->h;
+    const int E = dn->enc_end, F = (int)dn->L.size() - 1, HEAD = F + 1, H = h->H, W = h->W;
+    // lowest position whose data gradient is needed: below the lowest requested parameter, or where a requested skip's gradient leaves
+    int low = HEAD + 1;
+    for (int li = E; li <= F; li++) if (req[li].any()) { low = std::min(low, li); break; }
+    if (head_req) low = std::min(low, HEAD);
+    int skip_src = HEAD + 1;                    // the data gradient of layers >= skip_src must run
+    if (dsk[4]) skip_src = E;
+    for (int i = 0; i < 4 && skip_src > E; i++) if (dsk[3 - i]) skip_src = std::min(skip_src, E + 2 * i + 1);
+    auto need_dgrad = [&](int pos) { return low < pos || skip_src <= pos; };
+    const int ntape = (int)t.sz.size();
+    float *f = t.at(ntape - 2, i0), *disp = t.at(ntape - 1, i0);
+    const long long npx = (long long)N * H * W;
+    if (head_req) {
+        const int hch = (H * W + DNB_HEAD_CHUNK - 1) / DNB_HEAD_CHUNK;
+        hipLaunchKernelGGL(k_dnb_head_wgrad, dim3(N * hch), dim3(128), 0, h->stream, (const float *)f, (const float *)disp, ddisp, dn->hpart, H, W, hch);
+        hipLaunchKernelGGL(k_dnb_wsum, dim3(1), dim3(256), 0, h->stream, (const float *)dn->hpart, dn->hacc, 73LL, N * hch, accumulate);
+    }
+    if (!need_dgrad(HEAD)) return TCSFM_OK;
+    float *cur = dn->gA, *nxt = dn->gB;
+    hipLaunchKernelGGL(k_dnb_head, dim3(dn_blocks(npx)), dim3(256), 0, h->stream, (const float *)f, (const float *)disp, ddisp, (const float *)dn->pw, cur, N, H, W);
+    // tape entries: 0 = skip 4; up-step i: aux (i < 4), u, x
+    auto u_at = [&](int i) { return t.at(1 + 3 * i + 1, i0); };
+    auto aux_at = [&](int i) { return t.at(1 + 3 * i, i0); };
+    auto x_at = [&](int i) { return i < 4 ? t.at(1 + 3 * i + 2, i0) : t.at(1 + 3 * 4 + 1, i0); };
+    for (int li = F; li >= E && need_dgrad(li + 1); li--) {
+        const int rel = li - E, i = rel / 2;
+        const bool feat = li == F, up = !feat && rel % 2 == 0;
+        const float *in = feat ? x_at(4) : (up ? (i ? x_at(i - 1) : t.at(0, i0)) : (i < 4 ? u_at(i) : t.at(1 + 3 * 4, i0)));
+        if (req[li].any()) dnb_wgrad(dn, li, N, cur, in, req[li].wneed(), req[li].bneed(), accumulate);
+        if (!need_dgrad(li)) break;
+        dnb_dgrad(dn, li, N, cur, dn->gV, false, nullptr, nullptr, nullptr, DN_ACT_NONE);
+        if (feat) dnb_fold(dn, li, N, dn->gV, nullptr, x_at(4), DN_ACT_ELU, nxt, nullptr);
+        else if (!up) dnb_fold(dn, li, N, dn->gV, nullptr, i < 4 ? aux_at(i) : t.at(1 + 3 * 4, i0), DN_ACT_ELU, nxt, i < 4 ? dsk[3 - i] : nullptr);
+        else if (i > 0) dnb_fold(dn, li, N, dn->gV, nullptr, x_at(i - 1), DN_ACT_ELU, nxt, nullptr);
+        else dnb_fold(dn, li, N, dn->gV, nullptr, nullptr, DN_ACT_NONE, nullptr, dsk[4]);
+        std::swap(cur, nxt);
+    }
+    HIPCHK(h, hipGetLastError());
+    return TCSFM_OK;
+}
+
+// encoder backward of one image group (dsk[k] NULL: no gradient on skip k)
+int dn_encode_backward(tcsfm_depthnet *dn, int N, const DnTape &t, int i0, const float *const dsk[5], const std::vector<DnReq> &req, int accumulate) {
+    tcsfm_ctx *h = dn->h;
+    struct Blk { int li, down, h_e, t1_e, out_e, skip_in; };
+    std::vector<Blk> blk;
+    int li = 1, e = 3;
+    for (int stage = 1; stage <= 4; stage++)
+        for (int b = 0; b < 2; b++) {
+            const int down = b == 0 && stage > 1;
+            blk.push_back({li, down, b == 0 ? (stage == 1 ? 2 : e - 1) : e - 1, e, e + 1, b == 0 && stage > 1 ? stage - 1 : -1});
+            li += down ? 3 : 2; e += 2;
+        }
+    // is anything requested in blocks < j (or conv1)?
+    std::vector<int> before(blk.size() + 1, 0);
+    before[0] = req[0].any();
+    for (size_t j = 0; j < blk.size(); j++) {
+        const Blk &B = blk[j];
+        before[j + 1] = before[j] || req[B.li].any() || req[B.li + 1].any() || (B.down && req[B.li + 2].any());
+    }
+    if (!before[blk.size()]) return TCSFM_OK;
+    float *dz2 = dn->gA, *dz1 = dn->gB, *nx = dn->gC;
+    const Blk &last = blk.back();
+    const DnLayer &l4 = dn->L[last.li + 1];
+    dnb_ew(dn, N, l4.cout, l4.oh, l4.ow, dsk[4], nullptr, t.at(last.out_e, i0), DN_ACT_RELU, dz2);
+    for (int j = (int)blk.size() - 1; j >= 0; j--) {
+        const Blk &B = blk[j];
+        const float *hin = t.at(B.h_e, i0), *t1 = t.at(B.t1_e, i0);
+        const int c1 = B.li, c2 = B.li + 1, ds = B.li + 2;
+        if (req[c2].any()) dnb_wgrad(dn, c2, N, dz2, t1, req[c2].wneed(), req[c2].bneed(), accumulate);
+        if (B.down && req[ds].any()) dnb_wgrad(dn, ds, N, dz2, hin, req[ds].wneed(), req[ds].bneed(), accumulate);
+        if (!(req[c1].any() || before[j])) break;
+        dnb_dgrad(dn, c2, N, dz2, dz1, true, nullptr, nullptr, t1, DN_ACT_RELU);
+        if (req[c1].any()) dnb_wgrad(dn, c1, N, dz1, hin, req[c1].wneed(), req[c1].bneed(), accumulate);
+        if (!before[j]) break;
+        if (B.down) dnb_dgrad(dn, ds, N, dz2, dn->gD, true, nullptr, nullptr, nullptr, DN_ACT_NONE);
+        const bool pool_in = j == 0;
+        dnb_dgrad(dn, c1, N, dz1, nx, true, B.down ? dn->gD : dz2, B.skip_in >= 0 ? dsk[B.skip_in] : nullptr, hin,
+                  pool_in ? DN_ACT_NONE : DN_ACT_RELU);
+        std::swap(dz2, nx);
+    }
+    if (req[0].any()) {
+        // dz2 holds the pooled map's gradient: max-pool backward + skip 0 + ReLU, then conv1's weight gradient from the images
+        const DnLayer &c1 = dn->L[0];
+        const long long thr = (long long)N * c1.oh * c1.ow * 16;
+        hipLaunchKernelGGL(k_dnb_maxpool, dim3(dn_blocks(thr)), dim3(256), 0, h->stream, (const float *)t.at(1, i0), (const float *)dz2, dsk[0], nx, N, 64,
+                           c1.oh, c1.ow, c1.oh / 2, c1.ow / 2);
+        dnb_wgrad(dn, 0, N, nx, t.at(0, i0), req[0].wneed(), req[0].bneed(), accumulate);
+    }
+    HIPCHK(h, hipGetLastError());
+    return TCSFM_OK;
+}
+
+int dn_check_train(tcsfm_depthnet *dn, int N, const char *fn) {
+    tcsfm_ctx *h = dn->h;
+    if (!dn->train_loaded) { h->err = std::string(fn) + ": no parameters loaded with tcsfm_depthnet_load_device"; return TCSFM_E_ARG; }
+    if (N < 1) { h->err = std::string(fn) + ": N out of range"; return TCSFM_E_ARG; }
+    return TCSFM_OK;
+}
+
+// skip k of images [i0, ...) inside a caller's NHWC skip tensor of N images
+template <typename P>
+P dn_skip_at(const tcsfm_depthnet *dn, P base, int k, int i0) {
+    return base ? base + (size_t)i0 * (((size_t)dn->h->H * dn->h->W) >> (2 * (k + 1))) * DN_SKIP_C[k] : nullptr;
+}
+}  // namespace
+
+extern "C" {
+
+int tcsfm_depthnet_load_device(tcsfm_depthnet *dn, int n, const char *const names[], const float *const dev_ptrs[], const int64_t *shapes) {
+    if (!dn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = dn->h;
+    std::vector<DnSrc> src;
+    const float *pw = nullptr, *pb = nullptr;
+    if (int rc = dn_lookup(dn, "tcsfm_depthnet_load_device", n, names, dev_ptrs, shapes, src, &pw, &pb)) return rc;
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    if (int rc = dn_train_alloc(dn)) return rc;
+    hipStream_t s = h->stream;
+    for (size_t li = 0; li < dn->L.size(); li++) {
+        DnLayer &l = dn->L[li];
+        const DnSrc &p = src[li];
+        float *v = l.raw + l.nw();
+        HIPCHK(h, hipMemcpyAsync(l.raw, p.w, l.nw() * sizeof(float), hipMemcpyDeviceToDevice, s));
+        const float *vs[5] = {p.cb, p.g, p.be, p.rm, p.rv};
+        for (int k = 0; k < 5; k++)
+            if (vs[k]) HIPCHK(h, hipMemcpyAsync(v + (size_t)k * l.cout, vs[k], l.cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+        const bool bn = p.g != nullptr;
+        hipLaunchKernelGGL(k_dnb_fold_params, dim3(dn_blocks((long long)l.nw())), dim3(256), 0, s, (const float *)l.raw, p.cb ? (const float *)v : nullptr,
+                           bn ? (const float *)v + l.cout : nullptr, (const float *)v + 2 * l.cout, (const float *)v + 3 * l.cout,
+                           (const float *)v + 4 * l.cout, l.w4, l.wt4, l.bias, l.cout, l.cin, l.ks, l.coutp);
+    }
+    HIPCHK(h, hipMemcpyAsync(dn->pw, pw, 72 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(dn->pb, pb, sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipGetLastError());
+    dn->loaded = 1;
+    dn->train_loaded = 1;
+    return TCSFM_OK;
+}
+
+int tcsfm_depthnet_tape_size(tcsfm_depthnet *dn, int N, int64_t *enc_floats, int64_t *dec_floats) {
+    if (!dn) return TCSFM_E_ARG;
+    if (N < 1 || !enc_floats || !dec_floats) return fail(dn->h, TCSFM_E_ARG, "tcsfm_depthnet_tape_size: bad argument");
+    DnTape t;
+    dn_tape_layout(dn, 0, N, nullptr, t);
+    *enc_floats = (int64_t)t.total();
+    dn_tape_layout(dn, 1, N, nullptr, t);
+    *dec_floats = (int64_t)t.total();
+    return TCSFM_OK;
+}
+
+int tcsfm_depthnet_encode_train(tcsfm_depthnet *dn, int N, const float *imgs, float *const skips_out[5], float *tape) {
+    if (!dn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = dn->h;
+    if (int rc = dn_check_train(dn, N, "tcsfm_depthnet_encode_train")) return rc;
+    if (!imgs || !skips_out || !tape) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode_train: NULL argument");
+    for (int k = 0; k < 5; k++) if (!skips_out[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode_train: NULL skip buffer");
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    DnTape t;
+    dn_tape_layout(dn, 0, N, tape, t);
+    const size_t hw = (size_t)h->H * h->W;
+    for (int i0 = 0; i0 < N; i0 += dn->max_images) {
+        const int n = std::min(N - i0, dn->max_images);
+        float *sk[5];
+        for (int k = 0; k < 5; k++) sk[k] = dn_skip_at(dn, skips_out[k], k, i0);
+        if (int rc = dn_encode_train(dn, n, imgs + (size_t)i0 * 3 * hw, t, i0, sk)) return rc;
+    }
+    return TCSFM_OK;
+}
+
+int tcsfm_depthnet_decode_train(tcsfm_depthnet *dn, int N, const float *const skips_in[5], float *disp_out, float *tape) {
+    if (!dn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = dn->h;
+    if (int rc = dn_check_train(dn, N, "tcsfm_depthnet_decode_train")) return rc;
+    if (!skips_in || !disp_out || !tape) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode_train: NULL argument");
+    for (int k = 0; k < 5; k++) if (!skips_in[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode_train: NULL skip buffer");
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    DnTape t;
+    dn_tape_layout(dn, 1, N, tape, t);
+    const size_t hw = (size_t)h->H * h->W;
+    for (int i0 = 0; i0 < N; i0 += dn->max_images) {
+        const int n = std::min(N - i0, dn->max_images);
+        const float *sk[5];
+        for (int k = 0; k < 5; k++) sk[k] = dn_skip_at(dn, skips_in[k], k, i0);
+        if (int rc = dn_decode_train(dn, n, sk, disp_out + (size_t)i0 * hw, t, i0)) return rc;
+    }
+    return TCSFM_OK;
+}
+
+int tcsfm_depthnet_decode_backward(tcsfm_depthnet *dn, int N, const float *tape, const float *d_disp, float *const d_skips[5], int n_grads,
+                                   const char *const names[], float *const grads[]) {
+    if (!dn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = dn->h;
+    const char *fn = "tcsfm_depthnet_decode_backward";
+    if (int rc = dn_check_train(dn, N, fn)) return rc;
+    if (!tape || !d_disp) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode_backward: NULL argument");
+    std::vector<DnReq> req;
+    float *hw_ = nullptr, *hb_ = nullptr;
+    if (int rc = dn_requests(dn, fn, true, n_grads, names, grads, req, &hw_, &hb_)) return rc;
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    DnTape t;
+    dn_tape_layout(dn, 1, N, const_cast<float *>(tape), t);
+    const size_t hw = (size_t)h->H * h->W;
+    for (int i0 = 0; i0 < N; i0 += dn->max_images) {
+        const int n = std::min(N - i0, dn->max_images);
+        float *dsk[5];
+        for (int k = 0; k < 5; k++) dsk[k] = d_skips ? dn_skip_at(dn, d_skips[k], k, i0) : nullptr;
+        if (int rc = dn_decode_backward(dn, n, t, i0, d_disp + (size_t)i0 * hw, dsk, req, hw_ || hb_, i0 > 0)) return rc;
+    }
+    dn_param_out(dn, req, dn->enc_end, (int)dn->L.size());
+    if (hw_) HIPCHK(h, hipMemcpyAsync(hw_, dn->hacc, 72 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    if (hb_) HIPCHK(h, hipMemcpyAsync(hb_, dn->hacc + 72, sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipGetLastError());
+    return TCSFM_OK;
+}
+
+int tcsfm_depthnet_encode_backward(tcsfm_depthnet *dn, int N, const float *tape, const float *const d_skips[5], int n_grads,
+                                   const char *const names[], float *const grads[]) {
+    if (!dn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = dn->h;
+    const char *fn = "tcsfm_depthnet_encode_backward";
+    if (int rc = dn_check_train(dn, N, fn)) return rc;
+    if (!tape) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode_backward: NULL argument");
+    std::vector<DnReq> req;
+    float *hw_ = nullptr, *hb_ = nullptr;
+    if (int rc = dn_requests(dn, fn, false, n_grads, names, grads, req, &hw_, &hb_)) return rc;
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    DnTape t;
+    dn_tape_layout(dn, 0, N, const_cast<float *>(tape), t);
+    for (int i0 = 0; i0 < N; i0 += dn->max_images) {
+        const int n = std::min(N - i0, dn->max_images);
+        const float *dsk[5];
+        for (int k = 0; k < 5; k++) dsk[k] = d_skips ? dn_skip_at(dn, d_skips[k], k, i0) : nullptr;
+        if (int rc = dn_encode_backward(dn, n, t, i0, dsk, req, i0 > 0)) return rc;
+    }
+    dn_param_out(dn, req, 0, dn->enc_end);
+    HIPCHK(h, hipGetLastError());
+    return TCSFM_OK;
 }
 
 void tcsfm_pose_to_matrix(const double pose[6], double T[12]) { tc::pose_to_T(pose, T); }
