@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, REPO
+import operator_inputs as OI
 import parity_util as PU
 
 torch = pytest.importorskip("torch")
@@ -81,10 +82,16 @@ def test_photometric_vs_reference_golden(name):
         vbad = wv[k] != g["f64_valid"][k]
         if vbad.any():      # exact-tie border pixels at the identity pose / a handful of fp32 ties
             assert vbad.mean() <= 0.003 or not vbad[1:-1, 1:-1].any()
-            continue
-        assert _maxabs(diff[k], g["f64_diff"][k]) < 3e-5
-        assert _maxabs(weight[k], g["f64_weight"][k]) < 1e-4
-        assert (mask[k] != g["f64_mask"][k]).mean() <= 0.003
+        # no pair is skipped: a pixel whose validity was decided differently is left out together with its 3 x 3 neighbourhood (the
+        # SSIM window of a neighbour reads the flipped reconstruction), and such pixels are capped (tests/operator_inputs.py).  The
+        # cap is on interior pixels: at the golden's identity pose every border sample sits exactly on the validity limit, and any
+        # order of operations decides those ties its own way (the float64 oracle itself differs from the reference's float64 run at
+        # 2 of 128 and 56 of 960 border pixels there, its fp32 build at 27 of 128) -- the assertion above is the rule for them
+        assert vbad[1:-1, 1:-1].sum() <= OI.decision_cap(vbad.size), (name, k, int(vbad.sum()))
+        ok = ~OI.dilate3(vbad)
+        assert _maxabs(diff[k][ok], g["f64_diff"][k][ok]) < 3e-5
+        assert _maxabs(weight[k][ok], g["f64_weight"][k][ok]) < 1e-4
+        assert (mask[k] != g["f64_mask"][k])[ok].mean() <= 0.003     # (the combined mask holds the validity: same exclusion)
 
 
 def test_batched_fwd_inv_stack_vs_solve_pose_iteratively():
