@@ -455,6 +455,15 @@ int tcsfm_debug_check_guards(int *n_allocations, int *n_damaged);
 /* ... and its self-test: writes four bytes past the end of a scratch allocation of its own and says whether the bands caught it
  * (*detected = 1 / 0; -1: guards are off) */
 int tcsfm_debug_guard_selftest(int *detected);
+/* Read-out of the PoseNet's most recent evaluation on `pn`, for layer-by-layer tests (layer = 1..7):
+ *   tcsfm_debug_posenet_layer   raw_out [N, oh*ow, cout] (device, NHWC) = the layer's raw convolution output (+ bias; K-split partial sums
+ *                               already combined), scsh_out [N, cout, 2] (device) = the GroupNorm (scale, shift) pairs its consumer applies:
+ *                               a = relu(raw * scale + shift).  Either may be NULL.  N <= the images of that evaluation.  Ordered on the
+ *                               handle's stream.
+ *   tcsfm_debug_posenet_split   the layer's output size and the work split an N-image call uses (tcsfm_posenet_forward): output-channel
+ *                               blocks of 16 per wave, K split, pixel blocks of 16 per wave.  Any out-pointer may be NULL. */
+int tcsfm_debug_posenet_layer(tcsfm_posenet *pn, int layer, int N, float *raw_out, float *scsh_out);
+int tcsfm_debug_posenet_split(tcsfm_posenet *pn, int layer, int N, int *oh, int *ow, int *nb, int *ks, int *pb);
 int tcsfm_refine_window_async(tcsfm_handle h, int lane, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
                               const float *depth_t, const float *depth_s, const float *K, const float *pose_in,
                               const float *log_scale_in, float *pose_out, float *log_scale_out, float *stats_out);

@@ -94,7 +94,7 @@ struct PnConvParams {
     const pn_f4 *w4;              // prepared weights
     const float *bias;            // [COUT] or null
     float *out;                   // [ksplit][N][OH][OW][COUT] raw output (+ bias when ksplit == 1)
-    float *part;                  // ksplit == 1: [N][tiles][COUT][2] per-workgroup (sum, sum of squares) of the outputs, for GroupNorm
+    float *part;                  // ksplit == 1: [N][tiles][COUT][2] per-workgroup (sum, sum of squares) of the outputs less bias, for GroupNorm
     PnLayer L;
     int N;
 };
@@ -248,13 +248,13 @@ __global__ __launch_bounds__(256) void k_pn_conv(PnConvParams P) {
 #pragma unroll
             for (int r = 0; r < 4; r++)
                 if (prow0 + r < npix) {
-                    const float v = acc[p][b][r] + bs;
-                    out[(size_t)(prow0 + r) * L.cout + co] = v;
-                    s1 += v; s2 += v * v;
+                    const float a = acc[p][b][r];
+                    out[(size_t)(prow0 + r) * L.cout + co] = a + bs;
+                    s1 += a; s2 += a * a;      // about the bias (k_pn_stats puts it back in double): a large bias must not eat the squares' digits
                 }
         }
-        // GroupNorm partial sums of this workgroup's 64 PB pixels, per channel: the 4 row groups of the wave (lanes m, m+16, m+32,
-        // m+48), then the 4 waves through LDS, both in fixed order
+        // GroupNorm partial sums of this workgroup's 64 PB pixels, per channel, of the outputs WITHOUT their bias: the 4 row groups of
+        // the wave (lanes m, m+16, m+32, m+48), then the 4 waves through LDS, both in fixed order
         s1 += __shfl_xor(s1, 16, 64); s2 += __shfl_xor(s2, 16, 64);
         s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
         if (kq == 0) { wsum[wave][b * 16 + m][0] = s1; wsum[wave][b * 16 + m][1] = s2; }
@@ -392,9 +392,9 @@ __global__ __launch_bounds__(256) void k_pn_conv1(PnConvParams P) {
         for (int q = 0; q < 4; q++) {
             const int ox = ox0 + wave * 16 + 4 * kq + q, oy = oy0 + r;
             if (ox < L.ow && oy < L.oh) {
-                const float v = acc[r][q] + bs;
-                out[((size_t)oy * L.ow + ox) * L.cout + m] = v;
-                s1 += v; s2 += v * v;
+                const float a = acc[r][q];
+                out[((size_t)oy * L.ow + ox) * L.cout + m] = a + bs;
+                s1 += a; s2 += a * a;          // about the bias, as in k_pn_conv
             }
         }
     s1 += __shfl_xor(s1, 16, 64); s2 += __shfl_xor(s2, 16, 64);
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(256) void k_pn_conv1(PnConvParams P) {
 }
 
 struct PnStatsParams {
-    const float *part;      // ksplit == 1: [N][tiles][cout][2] partial sums written by the convolution's epilogue
+    const float *part;      // ksplit == 1: [N][tiles][cout][2] partial sums (of the outputs without bias) written by the convolution's epilogue
     int tiles;
     float *out;             // [ksplit][N][npix][cout] raw (reduced in place into split 0 when ksplit > 1)
     const float *bias;      // [cout] or null (added here when ksplit > 1)
@@ -431,9 +431,15 @@ __global__ __launch_bounds__(256) void k_pn_stats(PnStatsParams P) {
     const int total = P.npix * cg;
     if (P.ksplit == 1 && P.part != nullptr) {       // fixed-order sum of the workgroup partials of this group's channels
         const float *pp = P.part + (size_t)n * P.tiles * P.cout * 2;
+        // the partial sums are those of x - bias[c] (fp32 sums of squares about a large bias lose var's digits to mean^2: with group
+        // means at 3..10 standard deviations the activations were up to 20 x further from float64 than fp32 torch's); in double:
+        // sum x = S1 + n b,  sum x^2 = S2 + 2 b S1 + n b^2
         for (int e = tid; e < P.tiles * cg; e += 256) {
             const int t = e / cg, c = g * cg + (e - t * cg);
-            s += (double)pp[((size_t)t * P.cout + c) * 2]; q += (double)pp[((size_t)t * P.cout + c) * 2 + 1];
+            const double b = P.bias ? (double)P.bias[c] : 0.0;
+            const double p1 = (double)pp[((size_t)t * P.cout + c) * 2], p2 = (double)pp[((size_t)t * P.cout + c) * 2 + 1];
+            s += p1; q += p2 + 2.0 * b * p1;
+            if (t == 0) { s += P.npix * b; q += P.npix * b * b; }
         }
     } else
     for (int e0 = tid; e0 < total; e0 += 1024) {       // 4 elements per trip: their loads (all K-split planes) are independent

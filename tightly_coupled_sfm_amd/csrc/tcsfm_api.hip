@@ -2891,6 +2891,7 @@ int tcsfm_profile_kernel_busy(tcsfm_handle h, double *ms_busy, int64_t *launches
 struct tcsfm_posenet {
     tcsfm_ctx *h = nullptr;
     int max_images = 0, loaded = 0;
+    int last_N = 0;              // images of the most recent evaluation (tcsfm_debug_posenet_layer reads its activations)
     PnLayer L[7];
     int nb_cfg[2][7] = {}, ks_cfg[2][7] = {};   // (output-channel blocks per wave, K split) per layer: [0] few images (latency), [1] many
     pn_f4 *w4[7] = {};
@@ -3030,28 +3031,35 @@ int tcsfm_posenet_load(tcsfm_posenet *pn, const float *const conv_w[7], const fl
 }
 
 namespace {
+// work split of layer l (0-based) in a call over N images: channel blocks per wave, K split, pixel blocks per wave
+void pn_split(const tcsfm_posenet *pn, int l, int N, int *nb, int *ks, int *pb) {
+    const int cfg = N <= 4 ? 0 : 1;
+    const PnLayer &L = pn->L[l];
+    *nb = pn->nb_cfg[cfg][l]; *ks = pn->ks_cfg[cfg][l];
+    // two pixel blocks per wave in the many-images regime where a layer has pixels to spare (posenet_kernel.h k_pn_conv PB): a fixed
+    // function of the regime and the layer, so results stay bit-identical for every batch within a regime
+    // (A/B on one box, KITTI odometry sequence at 8 / 12 windows per call: layers 2-5 with two blocks 3 632-3 640 / 3 702-3 710 windows/s,
+    // layer 2 only 3 609-3 637 / 3 621-3 626, none 3 504-3 510)
+    static const int pb_min_px = getenv("TCSFM_PN_PB_MIN_PIXELS") ? atoi(getenv("TCSFM_PN_PB_MIN_PIXELS")) : 64;        // (measurement hook)
+    *pb = (cfg == 1 && l > 0 && *nb >= 2 && L.oh * L.ow >= pb_min_px) ? 2 : 1;
+}
+
 // the seven convolutions + statistics passes + head of one PoseNet evaluation on N samples; the first layer reads
 // (imgA | imgB) per sample (strides in floats; window indexing when win_B > 0)
 int pn_run(tcsfm_posenet *pn, int N, const float *imgA, long long strideA, const float *imgB, long long strideB, int win_B, int win_S,
            float *pose, int accumulate, float *stacked, int it, int iters, const WinOff *wo = nullptr) {
     tcsfm_ctx *h = pn->h;
-    const int cfg = N <= 4 ? 0 : 1;
+    pn->last_N = N;
     for (int l = 0; l < 7; l++) {
         PnLayer L = pn->L[l];
-        L.ksplit = pn->ks_cfg[cfg][l];
-        const int nb = pn->nb_cfg[cfg][l];
+        int nb, pb;
+        pn_split(pn, l, N, &nb, &L.ksplit, &pb);
         PnConvParams P;
         memset(&P, 0, sizeof(P));
         P.imgA = imgA; P.imgB = imgB; P.strideA = strideA; P.strideB = strideB; P.win_B = win_B; P.win_S = win_S;
         if (wo) P.win_off = *wo;
         P.in = l > 0 ? pn->act[l - 1] : nullptr; P.scsh = l > 0 ? pn->scsh[l - 1] : nullptr;
         P.w4 = pn->w4[l]; P.bias = pn->bias[l]; P.out = pn->act[l]; P.part = L.ksplit == 1 ? pn->part[l] : nullptr; P.L = L; P.N = N;
-        // two pixel blocks per wave in the many-images regime where a layer has pixels to spare (posenet_kernel.h k_pn_conv PB): a fixed
-        // function of the regime and the layer, so results stay bit-identical for every batch within a regime
-        // (A/B on one box, KITTI odometry sequence at 8 / 12 windows per call: layers 2-5 with two blocks 3 632-3 640 / 3 702-3 710 windows/s,
-        // layer 2 only 3 609-3 637 / 3 621-3 626, none 3 504-3 510)
-        static const int pb_min_px = getenv("TCSFM_PN_PB_MIN_PIXELS") ? atoi(getenv("TCSFM_PN_PB_MIN_PIXELS")) : 64;        // (measurement hook)
-        const int pb = (cfg == 1 && l > 0 && nb >= 2 && L.oh * L.ow >= pb_min_px) ? 2 : 1;
         dim3 grid((L.oh * L.ow + 64 * pb - 1) / (64 * pb), L.cout / (16 * nb), N * L.ksplit);
         if (l == 0) {            // LDS-staged first layer: one workgroup per 64-pixel segment of two output rows
             grid = dim3(((L.oh + 1) / 2) * ((L.ow + 63) / 64), 1, N);
@@ -3089,6 +3097,33 @@ int tcsfm_posenet_forward(tcsfm_posenet *pn, int N, const float *imgs, float *po
     DeviceGuard dev_guard(h->device);
     const long long hw = (long long)h->H * h->W;
     return pn_run(pn, N, imgs, 6 * hw, imgs + 3 * hw, 6 * hw, 0, 0, pose_out, 0, nullptr, 0, 1);
+}
+
+int tcsfm_debug_posenet_split(tcsfm_posenet *pn, int layer, int N, int *oh, int *ow, int *nb, int *ks, int *pb) {
+    if (!pn) return TCSFM_E_ARG;
+    if (layer < 1 || layer > 7 || N < 1 || N > pn->max_images) return fail(pn->h, TCSFM_E_ARG, "tcsfm_debug_posenet_split: bad layer or N");
+    int nb_, ks_, pb_;
+    pn_split(pn, layer - 1, N, &nb_, &ks_, &pb_);
+    if (oh) *oh = pn->L[layer - 1].oh;
+    if (ow) *ow = pn->L[layer - 1].ow;
+    if (nb) *nb = nb_;
+    if (ks) *ks = ks_;
+    if (pb) *pb = pb_;
+    return TCSFM_OK;
+}
+
+int tcsfm_debug_posenet_layer(tcsfm_posenet *pn, int layer, int N, float *raw_out, float *scsh_out) {
+    if (!pn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = pn->h;
+    if (layer < 1 || layer > 7) return fail(h, TCSFM_E_ARG, "tcsfm_debug_posenet_layer: layer out of range");
+    if (N < 1 || N > pn->last_N) return fail(h, TCSFM_E_ARG, "tcsfm_debug_posenet_layer: N exceeds the most recent evaluation");
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    const PnLayer &L = pn->L[layer - 1];
+    // K-split plane 0 holds the reduced sums (+ bias) once k_pn_stats has run: [last_N][npix][cout], the first N samples of it
+    if (raw_out) HIPCHK(h, hipMemcpyAsync(raw_out, pn->act[layer - 1], (size_t)N * L.oh * L.ow * L.cout * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    if (scsh_out) HIPCHK(h, hipMemcpyAsync(scsh_out, pn->scsh[layer - 1], (size_t)N * L.cout * 2 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    return TCSFM_OK;
 }
 
 // the coupled loop of train_mono.py:64-80 on context `h` (the handle or one of its lanes; pn->h == h): network, warps, corrections

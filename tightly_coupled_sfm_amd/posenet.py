@@ -93,6 +93,24 @@ class PoseNetHIP:
         e._call(self.lib.tcsfm_posenet_forward(self._pn, N, e._p(imgs), e._p(out)))
         return out
 
+    def split(self, layer: int, N: int):
+        """tcsfm_debug_posenet_split: (oh, ow, nb, ks, pb) of layer 1..7 in a call over N images"""
+        v = [C.c_int(0) for _ in range(5)]
+        self.eng._call(self.lib.tcsfm_debug_posenet_split(self._pn, int(layer), int(N), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def layer(self, layer: int, N: int):
+        """tcsfm_debug_posenet_layer: layer 1..7 of the most recent evaluation -> (raw convolution output [N,cout,oh,ow],
+        GroupNorm (scale, shift) [N,cout,2]); the layer's activation is relu(raw * scale + shift)"""
+        e = self.eng
+        e._bind()
+        oh, ow = self.split(layer, N)[:2]
+        cout = [16, 32, 64, 128, 256, 256, 256][int(layer) - 1]
+        raw = torch.empty((int(N), oh, ow, cout), device=e.dev, dtype=torch.float32)
+        scsh = torch.empty((int(N), cout, 2), device=raw.device, dtype=torch.float32)
+        e._call(self.lib.tcsfm_debug_posenet_layer(self._pn, int(layer), int(N), e._p(raw), e._p(scsh)))
+        return raw.permute(0, 3, 1, 2), scsh
+
     def odometry_sequence(self, frames, depths, K, opts=None, sources: int = 1, iterations: int = 4, ring: int = 0, windows_per_call: int = 0,
                           target_pos: int = 0):
         """tcsfm_odometry_sequence: for every window of a sequence (frames [T,3,H,W] / depths [T,1,H,W] CPU tensors, pinned for
