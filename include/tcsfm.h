@@ -464,6 +464,12 @@ int tcsfm_debug_guard_selftest(int *detected);
  *                               blocks of 16 per wave, K split, pixel blocks of 16 per wave.  Any out-pointer may be NULL. */
 int tcsfm_debug_posenet_layer(tcsfm_posenet *pn, int layer, int N, float *raw_out, float *scsh_out);
 int tcsfm_debug_posenet_split(tcsfm_posenet *pn, int layer, int N, int *oh, int *ow, int *nb, int *ks, int *pb);
+/* Read-out of the depth network's work split, for layer-by-layer tests: convolution `layer` in evaluation order (0 = conv1; per
+ * BasicBlock conv1, conv2 and, in a stride-2 block, the 1x1 downsample; depth_upconvs.i, iconvs.i for i = 0..4; feature_convs.0 --
+ * 33 - 2 = 31 entries, the max pool and the head have no split) -> kernel size, output size and the k_dn_conv instance it launches:
+ * output-channel blocks of 16 per wave, pixel blocks of 16 per wave, waves sharing K.  conv1 runs k_dn_conv1 whatever nb / pb / kw
+ * say.  The split depends on the handle's H and W only.  Any out-pointer may be NULL. */
+int tcsfm_debug_depthnet_split(tcsfm_depthnet *dn, int layer, int *ks, int *oh, int *ow, int *nb, int *pb, int *kw);
 int tcsfm_refine_window_async(tcsfm_handle h, int lane, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
                               const float *depth_t, const float *depth_s, const float *K, const float *pose_in,
                               const float *log_scale_in, float *pose_out, float *log_scale_out, float *stats_out);

@@ -142,6 +142,7 @@ _SIGNATURES = {
     "tcsfm_depthnet_encode": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     "tcsfm_depthnet_decode": (C.c_int, [_P, C.c_int, _P, _P]),
     "tcsfm_depthnet_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "tcsfm_debug_depthnet_split": (C.c_int, [_P, C.c_int] + [C.POINTER(C.c_int)] * 6),
     "tcsfm_depthnet_load_device": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "tcsfm_depthnet_tape_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tcsfm_depthnet_encode_train": (C.c_int, [_P, C.c_int, _P, _P, _P]),

@@ -3520,6 +3520,19 @@ int tcsfm_depthnet_forward(tcsfm_depthnet *dn, int N, const float *imgs, int fli
     return dn_decode(dn, N, dn->skip, disp_out);
 }
 
+int tcsfm_debug_depthnet_split(tcsfm_depthnet *dn, int layer, int *ks, int *oh, int *ow, int *nb, int *pb, int *kw) {
+    if (!dn) return TCSFM_E_ARG;
+    if (layer < 0 || layer >= (int)dn->L.size()) return fail(dn->h, TCSFM_E_ARG, "tcsfm_debug_depthnet_split: layer out of range");
+    const DnLayer &l = dn->L[layer];
+    if (ks) *ks = l.ks;
+    if (oh) *oh = l.oh;
+    if (ow) *ow = l.ow;
+    if (nb) *nb = l.nb;
+    if (pb) *pb = l.pb;
+    if (kw) *kw = l.kw;
+    return TCSFM_OK;
+}
+
 }  // extern "C"   (the depth network's training helpers)
 
 namespace {

@@ -97,6 +97,12 @@ class DepthNetHIP:
         """the 'depth_state_dict' entry of a reference checkpoint file, or of `<dir>/best_model/best_model.pt` / `<dir>/checkpoint.pt`"""
         return self.load(read_depth_state_dict(path, load_best))
 
+    def split(self, layer: int):
+        """tcsfm_debug_depthnet_split: (ks, oh, ow, nb, pb, kw) of convolution `layer` (0 = conv1, evaluation order)"""
+        v = [C.c_int() for _ in range(6)]
+        self.eng._call(self.lib.tcsfm_debug_depthnet_split(self._dn, int(layer), *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     def _skip_shapes(self, N):
         e = self.eng
         return [(N, e.H >> (k + 1), e.W >> (k + 1), c) for k, c in enumerate(SKIP_CHANNELS)]
