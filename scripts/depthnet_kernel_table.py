@@ -11,7 +11,7 @@ N, H, W = 5, 192, 640
 
 
 def layers():
-    """(name, multiply-adds per image) in launch order (tcsfm_api.hip dn_encode / dn_decode)"""
+    """(name, multiply-adds per image) in launch order (depthnet_host.h dn_encode / dn_decode)"""
     out = [("conv1+bn1+relu", 64 * 3 * 49 * (H // 2) * (W // 2)), ("maxpool", 0)]
     for p, ci, co, s, ds in dt._blocks():
         sc = {64: 4, 128: 8, 256: 16, 512: 32}[co]

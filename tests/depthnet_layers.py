@@ -4,7 +4,7 @@ max_over_rms, hold) is tests/posenet_layers.py's.
 
 LAUNCHES: the forward is 33 launches -- conv1, the max pool, 16 BasicBlock convolutions and 3 1x1 downsamples, 5 up-convolutions,
 5 iconvs, feature_convs.0 and the sigmoid head.  The training forward (tcsfm_depthnet_encode_train / _decode_train) runs the same
-kernels and leaves every launch's input and output in its tapes (tcsfm_api.hip dn_tape_layout), except a downsample's output, which
+kernels and leaves every launch's input and output in its tapes (depthnet_host.h dn_tape_layout), except a downsample's output, which
 only the block's second convolution reads.  checks() pairs every launch with the tape entries it read and wrote.
 
 ISOLATED reference of a launch: the layer alone, in float64, on the library's OWN fp32 tape entry, with BatchNorm folded in float64
@@ -57,7 +57,7 @@ def gamma_n(n):
 
 # ---- the convolutions in the library's order (dn_layers) and the work split rule (dn_split), restated --------------------------------
 def layers(H, W):
-    """the 31 convolutions of tcsfm_api.hip dn_layers, in its order: dicts(name, kind, cin, cout, ks, stride, up, reflect, ih, iw, oh,
+    """the 31 convolutions of depthnet_host.h dn_layers, in its order: dicts(name, kind, cin, cout, ks, stride, up, reflect, ih, iw, oh,
     ow, w, b (conv bias key or None), bn (BatchNorm prefix or None))"""
     out = []
 

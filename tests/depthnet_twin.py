@@ -110,7 +110,7 @@ def forward(sd, x, calibrate: bool = False, return_skips: bool = False):
 
 
 def encoder_tape_shapes(H: int, W: int):
-    """per-image shapes of the encoder tape's entries (tcsfm_api.hip dn_tape_layout): images [3,H,W], conv1's output (skip 0)
+    """per-image shapes of the encoder tape's entries (depthnet_host.h dn_tape_layout): images [3,H,W], conv1's output (skip 0)
     [H/2,W/2,64], the max-pooled map [H/4,W/4,64], then for each of the eight BasicBlocks its conv1 output and its block output,
     [h,w,c] each (NHWC, both after their ReLU)"""
     shp = [(3, H, W), (H // 2, W // 2, 64), (H // 4, W // 4, 64)]

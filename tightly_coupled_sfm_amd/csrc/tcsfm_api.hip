@@ -1250,8 +1250,7 @@ constexpr decltype(&dense_ref_run<1>) dense_ref_runs[JMAXS] = {dense_ref_run<1>,
 }  // namespace
 
 // =================================================================================================
-extern "C" {
-
+// Entry points: include/tcsfm.h declares every one of them extern "C", so the definitions below have C linkage.
 static int flush_pending(tcsfm_ctx *h);
 static int join_coalesce_lanes(tcsfm_ctx *h);
 // Calls noted by the *_queued entry points are launched -- and the handle's stream ordered behind the merged sequences that ran on lanes --
@@ -1725,7 +1724,6 @@ static int refine_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, in
 // The kernels, their order and their arguments are exactly those of the plain path (`body`): results are bit-identical.
 // kind: 0 pose refinement, 1 dense refinement (the joint dense mode, which forks its inverse pairs onto a second stream when it runs
 // plainly, keeps them on the captured stream: every graph is one chain of launches).
-extern "C++" {
 template <class Body>
 static int replay_or_run(tcsfm_ctx *h, const tcsfm_opts *o, int kind, int N, int win_B, int win_S, const void *const *ptrs, const float *K,
                          bool bypass, Body body) {
@@ -1797,7 +1795,6 @@ static int replay_or_run(tcsfm_ctx *h, const tcsfm_opts *o, int kind, int N, int
     }
     return body();
 }
-}  // extern "C++"
 
 static int refine_impl(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int win_S, const float *tgt, const float *src,
                        const float *depth_t, const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in,
@@ -2459,13 +2456,7 @@ int tcsfm_refine_dense_window_async(tcsfm_handle h, int lane, const tcsfm_opts *
     return TCSFM_OK;
 }
 
-// (the PoseNet section further down)
-struct tcsfm_posenet;
-static int pose_loop(tcsfm_ctx *h, tcsfm_posenet *pn, int num_iter, int B, int S, const float *tgt, const float *srcs, const float *depth_t,
-                     const float *depth_s, const float *K, float *poses_out, float *stacked_out, const WinOff *wo);
-static tcsfm_posenet *pn_for_lane(tcsfm_posenet *pn, tcsfm_ctx *c);
-static bool pn_usable(const tcsfm_posenet *pn, const tcsfm_ctx *h, int images);
-static int pn_max_images(const tcsfm_posenet *pn);
+#include "posenet_host.h"
 
 // The reference's sequential driver (run_sequential_optimization.py:186-247) as ONE call: see include/tcsfm.h.  With `pn` the initial
 // poses of every window come from the coupled PoseNet loop (train_mono.py:64-80) on the window's lane instead of from the caller.
@@ -2486,7 +2477,7 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     WinOff wo;
     wo.on = 1;
     for (int s_ = 0; s_ < TC_MAX_SRC_OFF; s_++) wo.off[s_] = s_ < tp ? s_ : s_ + 1;     // source s = frame w + off[s], relative to the window's first frame
-    if (pn && (num_iter < 1 || !pn_usable(pn, h, N) || o_in->depth_is_disp))
+    if (pn && (num_iter < 1 || pn->h != h || !pn->loaded || N > pn->max_images || o_in->depth_is_disp))
         return fail(h, TCSFM_E_ARG, "tcsfm_odometry_sequence: needs a loaded PoseNet of this handle with max_images >= 2*S, num_iter >= 1 and depths (not disparities)");
     tcsfm_opts o = *o_in;
     o.host_ptrs = 0;                                   // the lanes work on the device ring; this call does the staging itself
@@ -2497,7 +2488,7 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     // runs on 2 S WB images at a third of the time per image.
     int WB = windows_per_call > 0 ? windows_per_call : 8;
     WB = std::min(WB, std::min(h->max_pairs / N, nwin));
-    if (pn) WB = std::min(WB, pn_max_images(pn) / N);
+    if (pn) WB = std::min(WB, pn->max_images / N);
     while (ring > 0 && WB > 1 && ring < WB + S + (ring >= WB + S + 8 ? 4 : 1)) WB--;      // an explicit small ring bounds the windows per call
     int rc = check_common(h, &o, N * WB);
     if (rc) return rc;
@@ -2887,1186 +2878,7 @@ int tcsfm_profile_kernel_busy(tcsfm_handle h, double *ms_busy, int64_t *launches
     return TCSFM_OK;
 }
 
-// ---- PoseNet (models/pose_models.py:88-147) and the coupled pose loop (train_mono.py:64-80) ---------------------------------
-struct tcsfm_posenet {
-    tcsfm_ctx *h = nullptr;
-    int max_images = 0, loaded = 0;
-    int last_N = 0;              // images of the most recent evaluation (tcsfm_debug_posenet_layer reads its activations)
-    PnLayer L[7];
-    int nb_cfg[2][7] = {}, ks_cfg[2][7] = {};   // (output-channel blocks per wave, K split) per layer: [0] few images (latency), [1] many
-    pn_f4 *w4[7] = {};
-    float *bias[7] = {}, *gamma[7] = {}, *beta[7] = {};
-    float *act[7] = {}, *scsh[7] = {}, *part[7] = {};
-    float *head_w = nullptr, *head_b = nullptr, *raw = nullptr;
-    float *in_buf = nullptr;     // [max_images,6,H,W] (tgt * valid | img_rec) written by the warp kernel
-    float *pose = nullptr;       // [max_images,6] running pose of the coupled loop
-    // tcsfm_odometry_sequence runs the network on the handle's lanes: clone k works on lane k with its own activations and
-    // borrows this object's weights
-    bool owns_weights = true;
-    std::vector<tcsfm_posenet *> clones;
-};
-
-void tcsfm_posenet_destroy(tcsfm_posenet *pn) {
-    if (!pn) return;
-    for (tcsfm_posenet *c : pn->clones) tcsfm_posenet_destroy(c);
-    DeviceGuard dev_guard(pn->h->device);
-    for (int l = 0; l < 7; l++) {
-        void *weights[] = {pn->w4[l], pn->bias[l], pn->gamma[l], pn->beta[l]}, *scratch[] = {pn->act[l], pn->scsh[l], pn->part[l]};
-        if (pn->owns_weights) for (void *p : weights) if (p) (void)hipFree(p);
-        for (void *p : scratch) if (p) (void)hipFree(p);
-    }
-    void *weights[] = {pn->head_w, pn->head_b, pn->raw}, *scratch[] = {pn->in_buf, pn->pose};
-    if (pn->owns_weights) for (void *p : weights) if (p) (void)hipFree(p);
-    for (void *p : scratch) if (p) (void)hipFree(p);
-    delete pn;
-}
-
-// activations, statistics and loop buffers of one PoseNet instance (layer geometry and work split already filled in)
-static hipError_t pn_alloc_scratch(tcsfm_posenet *pn) {
-    hipError_t e = hipSuccess;
-    const int max_images = pn->max_images;
-    for (int l = 0; l < 7 && e == hipSuccess; l++) {
-        const PnLayer &L = pn->L[l];
-        e = hipMalloc((void **)&pn->act[l], (size_t)L.ksplit * max_images * L.oh * L.ow * L.cout * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void **)&pn->scsh[l], (size_t)max_images * L.cout * 2 * sizeof(float));
-        if (e == hipSuccess && (pn->ks_cfg[0][l] == 1 || pn->ks_cfg[1][l] == 1))
-            e = hipMalloc((void **)&pn->part[l], (size_t)max_images * std::max((L.oh * L.ow + 63) / 64, L.oh * ((L.ow + 63) / 64)) * L.cout * 2 * sizeof(float));
-    }
-    if (e == hipSuccess) e = hipMalloc((void **)&pn->in_buf, (size_t)max_images * 6 * pn->h->H * pn->h->W * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&pn->pose, (size_t)max_images * 6 * sizeof(float));
-    return e;
-}
-
-// the instance that runs `pn`'s network on lane context `c` (lane 0 = pn itself)
-static tcsfm_posenet *pn_for_lane(tcsfm_posenet *pn, tcsfm_ctx *c) {
-    if (pn->h == c) return pn;
-    for (tcsfm_posenet *q : pn->clones)
-        if (q->h == c) return q;
-    tcsfm_posenet *q = new tcsfm_posenet(*pn);          // geometry, work split, weight pointers
-    q->h = c; q->owns_weights = false; q->clones.clear();
-    for (int l = 0; l < 7; l++) q->act[l] = q->scsh[l] = q->part[l] = nullptr;
-    q->in_buf = q->pose = nullptr;
-    if (pn_alloc_scratch(q) != hipSuccess) { tcsfm_posenet_destroy(q); return nullptr; }
-    pn->clones.push_back(q);
-    return q;
-}
-
-static bool pn_usable(const tcsfm_posenet *pn, const tcsfm_ctx *h, int images) { return pn && pn->h == h && pn->loaded && images <= pn->max_images; }
-static int pn_max_images(const tcsfm_posenet *pn) { return pn->max_images; }
-
-int tcsfm_posenet_create(tcsfm_handle h, int max_images, tcsfm_posenet **out) {
-    if (!h || !out) return TCSFM_E_ARG;
-    *out = nullptr;
-    if (max_images < 1 || max_images > 4096) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_create: max_images out of range");
-    DeviceGuard dev_guard(h->device);
-    tcsfm_posenet *pn = new tcsfm_posenet();
-    pn->h = h; pn->max_images = max_images;
-    static const int chans[8] = {6, 16, 32, 64, 128, 256, 256, 256}, ksz[7] = {7, 5, 3, 3, 3, 3, 3};
-    int ih = h->H, iw = h->W;
-    hipError_t e = hipSuccess;
-    size_t wmax = 0;
-    for (int l = 0; l < 7; l++) {
-        PnLayer &L = pn->L[l];
-        L.cin = chans[l]; L.cout = chans[l + 1]; L.ks = ksz[l]; L.pad = (ksz[l] - 1) / 2;
-        L.ih = ih; L.iw = iw; L.oh = (ih + 2 * L.pad - L.ks) / 2 + 1; L.ow = (iw + 2 * L.pad - L.ks) / 2 + 1;
-        L.kgroups = l == 0 ? 21 : L.ks * L.ks * L.cin / 16;
-        // Work split of a layer = (output-channel blocks of 16 per wave, K split).  A wave's K loop is a serial chain of loads and
-        // matrix-core steps, and a window's fwd + inv pair is only 2 images: with 4 channel blocks per wave and K whole the small
-        // layers ran on ~100 waves of ~300 dependent MFMAs each (15 us per layer whatever its size).  Two fixed regimes, chosen by
-        // the number of images only (results do not depend on anything else):
-        //   few images (N <= 4): as few channel blocks per wave as it takes to have ~800 waves for N = 2, then K split until they
-        //                        exist or a wave's loop is down to 8 groups;
-        //   many images:         up to 4 channel blocks per wave, K split only for the late layers (few output pixels).
-        {
-            const int pxb = (L.oh * L.ow + 15) / 16, cb = L.cout / 16;
-            int nb = std::min(cb, 4), ks = 1;
-            while (nb > 1 && pxb * (cb / nb) * 2 < 768) nb /= 2;
-            while (ks < 16 && pxb * (cb / nb) * 2 * ks < 768 && L.kgroups / (2 * ks) >= 8) ks *= 2;
-            pn->nb_cfg[0][l] = l == 0 ? 1 : nb; pn->ks_cfg[0][l] = l == 0 ? 1 : ks;
-            pn->nb_cfg[1][l] = L.cout >= 64 ? 4 : cb;
-            pn->ks_cfg[1][l] = L.oh * L.ow <= 512 ? std::min(16, (L.kgroups + 23) / 24) : 1;
-        }
-        L.ksplit = std::max(pn->ks_cfg[0][l], pn->ks_cfg[1][l]);     // allocation; the launch sets the split it uses
-        if (L.oh < 1 || L.ow < 1) { tcsfm_posenet_destroy(pn); return fail(h, TCSFM_E_ARG, "tcsfm_posenet_create: image too small for seven stride-2 layers"); }
-        const size_t nw4 = (size_t)L.kgroups * 4 * L.cout;
-        if (e == hipSuccess) e = hipMalloc((void **)&pn->w4[l], nw4 * sizeof(pn_f4));
-        if (e == hipSuccess) e = hipMalloc((void **)&pn->bias[l], L.cout * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void **)&pn->gamma[l], L.cout * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void **)&pn->beta[l], L.cout * sizeof(float));
-        wmax = std::max(wmax, (size_t)L.cout * L.cin * L.ks * L.ks);
-        ih = L.oh; iw = L.ow;
-    }
-    if (e == hipSuccess) e = hipMalloc((void **)&pn->head_w, 6 * 256 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&pn->head_b, 6 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&pn->raw, wmax * sizeof(float));
-    if (e == hipSuccess) e = pn_alloc_scratch(pn);
-    if (e != hipSuccess) { tcsfm_posenet_destroy(pn); return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_posenet_create: allocation failed"); }
-    *out = pn;
-    return TCSFM_OK;
-}
-
-int tcsfm_posenet_load(tcsfm_posenet *pn, const float *const conv_w[7], const float *const conv_b[7], const float *const gn_w[7],
-                       const float *const gn_b[7], const float *head_w, const float *head_b) {
-    if (!pn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = pn->h;
-    if (!conv_w || !head_w || !head_b) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_load: NULL argument");
-    DeviceGuard dev_guard(h->device);
-    for (int l = 0; l < 7; l++) {
-        const PnLayer &L = pn->L[l];
-        if (!conv_w[l]) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_load: NULL convolution weight");
-        const size_t nw = (size_t)L.cout * L.cin * L.ks * L.ks;
-        HIPCHK(h, hipMemcpyAsync(pn->raw, conv_w[l], nw * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_pn_prep, dim3(L.cout), dim3(256), 0, h->stream, (const float *)pn->raw, pn->w4[l], L.cin, L.cout, L.ks, l == 0 ? 1 : 0, 1);
-        HIPCHK(h, hipStreamSynchronize(h->stream));    // pn->raw is reused by the next layer; loading happens once per model
-        std::vector<float> ones(L.cout, 1.f), zeros(L.cout, 0.f);
-        HIPCHK(h, hipMemcpy(pn->bias[l], conv_b && conv_b[l] ? conv_b[l] : zeros.data(), L.cout * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(pn->gamma[l], gn_w && gn_w[l] ? gn_w[l] : ones.data(), L.cout * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(pn->beta[l], gn_b && gn_b[l] ? gn_b[l] : zeros.data(), L.cout * sizeof(float), hipMemcpyHostToDevice));
-    }
-    HIPCHK(h, hipMemcpy(pn->head_w, head_w, 6 * 256 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(pn->head_b, head_b, 6 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(h, hipGetLastError());
-    pn->loaded = 1;
-    return TCSFM_OK;
-}
-
-namespace {
-// work split of layer l (0-based) in a call over N images: channel blocks per wave, K split, pixel blocks per wave
-void pn_split(const tcsfm_posenet *pn, int l, int N, int *nb, int *ks, int *pb) {
-    const int cfg = N <= 4 ? 0 : 1;
-    const PnLayer &L = pn->L[l];
-    *nb = pn->nb_cfg[cfg][l]; *ks = pn->ks_cfg[cfg][l];
-    // two pixel blocks per wave in the many-images regime where a layer has pixels to spare (posenet_kernel.h k_pn_conv PB): a fixed
-    // function of the regime and the layer, so results stay bit-identical for every batch within a regime
-    // (A/B on one box, KITTI odometry sequence at 8 / 12 windows per call: layers 2-5 with two blocks 3 632-3 640 / 3 702-3 710 windows/s,
-    // layer 2 only 3 609-3 637 / 3 621-3 626, none 3 504-3 510)
-    static const int pb_min_px = getenv("TCSFM_PN_PB_MIN_PIXELS") ? atoi(getenv("TCSFM_PN_PB_MIN_PIXELS")) : 64;        // (measurement hook)
-    *pb = (cfg == 1 && l > 0 && *nb >= 2 && L.oh * L.ow >= pb_min_px) ? 2 : 1;
-}
-
-// the seven convolutions + statistics passes + head of one PoseNet evaluation on N samples; the first layer reads
-// (imgA | imgB) per sample (strides in floats; window indexing when win_B > 0)
-int pn_run(tcsfm_posenet *pn, int N, const float *imgA, long long strideA, const float *imgB, long long strideB, int win_B, int win_S,
-           float *pose, int accumulate, float *stacked, int it, int iters, const WinOff *wo = nullptr) {
-    tcsfm_ctx *h = pn->h;
-    pn->last_N = N;
-    for (int l = 0; l < 7; l++) {
-        PnLayer L = pn->L[l];
-        int nb, pb;
-        pn_split(pn, l, N, &nb, &L.ksplit, &pb);
-        PnConvParams P;
-        memset(&P, 0, sizeof(P));
-        P.imgA = imgA; P.imgB = imgB; P.strideA = strideA; P.strideB = strideB; P.win_B = win_B; P.win_S = win_S;
-        if (wo) P.win_off = *wo;
-        P.in = l > 0 ? pn->act[l - 1] : nullptr; P.scsh = l > 0 ? pn->scsh[l - 1] : nullptr;
-        P.w4 = pn->w4[l]; P.bias = pn->bias[l]; P.out = pn->act[l]; P.part = L.ksplit == 1 ? pn->part[l] : nullptr; P.L = L; P.N = N;
-        dim3 grid((L.oh * L.ow + 64 * pb - 1) / (64 * pb), L.cout / (16 * nb), N * L.ksplit);
-        if (l == 0) {            // LDS-staged first layer: one workgroup per 64-pixel segment of two output rows
-            grid = dim3(((L.oh + 1) / 2) * ((L.ow + 63) / 64), 1, N);
-            hipLaunchKernelGGL(k_pn_conv1, grid, dim3(256), 0, h->stream, P);
-        } else if (nb == 1) hipLaunchKernelGGL((k_pn_conv<1, false>), grid, dim3(256), 0, h->stream, P);
-        else if (nb == 2 && pb == 2) hipLaunchKernelGGL((k_pn_conv<2, false, 2>), grid, dim3(256), 0, h->stream, P);
-        else if (nb == 2) hipLaunchKernelGGL((k_pn_conv<2, false>), grid, dim3(256), 0, h->stream, P);
-        else if (pb == 2) hipLaunchKernelGGL((k_pn_conv<4, false, 2>), grid, dim3(256), 0, h->stream, P);
-        else hipLaunchKernelGGL((k_pn_conv<4, false>), grid, dim3(256), 0, h->stream, P);
-        // GroupNorm statistics (+ K-split combination) as their own launch.  Round 3 measured the alternative -- statistics, K-split
-        // combination and the head in the convolutions' tails by the last-arriver ticket protocol, 7 launches instead of 15: every
-        // convolution became 6-8 us SLOWER (ticket round trips, acquire, serial tail of the last workgroup), 127.5 vs 119 us per
-        // evaluation (profiles/r03_posenet_fused_tail_kernel_stats.csv, _timing.jsonl) -- a separate 16 N-workgroup pass is faster.
-        PnStatsParams S;
-        S.part = P.part; S.tiles = (int)grid.x;
-        S.out = pn->act[l]; S.bias = pn->bias[l]; S.gamma = pn->gamma[l]; S.beta = pn->beta[l]; S.scsh = pn->scsh[l];
-        S.N = N; S.npix = L.oh * L.ow; S.cout = L.cout; S.ksplit = L.ksplit;
-        hipLaunchKernelGGL(k_pn_stats, dim3(N, 16), dim3(256), 0, h->stream, S);
-    }
-    PnHeadParams Hd;
-    Hd.x = pn->act[6]; Hd.scsh = pn->scsh[6]; Hd.w = pn->head_w; Hd.b = pn->head_b; Hd.pose = pose; Hd.stacked = stacked;
-    Hd.npix = pn->L[6].oh * pn->L[6].ow; Hd.accumulate = accumulate; Hd.it = it; Hd.iters = iters;
-    hipLaunchKernelGGL(k_pn_head, dim3(N), dim3(256), 0, h->stream, Hd);
-    HIPCHK(h, hipGetLastError());
-    return TCSFM_OK;
-}
-}  // namespace
-
-int tcsfm_posenet_forward(tcsfm_posenet *pn, int N, const float *imgs, float *pose_out) {
-    if (!pn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = pn->h;
-    if (!pn->loaded) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_forward: no weights loaded");
-    if (N < 1 || N > pn->max_images || !imgs || !pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_forward: bad argument");
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    const long long hw = (long long)h->H * h->W;
-    return pn_run(pn, N, imgs, 6 * hw, imgs + 3 * hw, 6 * hw, 0, 0, pose_out, 0, nullptr, 0, 1);
-}
-
-int tcsfm_debug_posenet_split(tcsfm_posenet *pn, int layer, int N, int *oh, int *ow, int *nb, int *ks, int *pb) {
-    if (!pn) return TCSFM_E_ARG;
-    if (layer < 1 || layer > 7 || N < 1 || N > pn->max_images) return fail(pn->h, TCSFM_E_ARG, "tcsfm_debug_posenet_split: bad layer or N");
-    int nb_, ks_, pb_;
-    pn_split(pn, layer - 1, N, &nb_, &ks_, &pb_);
-    if (oh) *oh = pn->L[layer - 1].oh;
-    if (ow) *ow = pn->L[layer - 1].ow;
-    if (nb) *nb = nb_;
-    if (ks) *ks = ks_;
-    if (pb) *pb = pb_;
-    return TCSFM_OK;
-}
-
-int tcsfm_debug_posenet_layer(tcsfm_posenet *pn, int layer, int N, float *raw_out, float *scsh_out) {
-    if (!pn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = pn->h;
-    if (layer < 1 || layer > 7) return fail(h, TCSFM_E_ARG, "tcsfm_debug_posenet_layer: layer out of range");
-    if (N < 1 || N > pn->last_N) return fail(h, TCSFM_E_ARG, "tcsfm_debug_posenet_layer: N exceeds the most recent evaluation");
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    const PnLayer &L = pn->L[layer - 1];
-    // K-split plane 0 holds the reduced sums (+ bias) once k_pn_stats has run: [last_N][npix][cout], the first N samples of it
-    if (raw_out) HIPCHK(h, hipMemcpyAsync(raw_out, pn->act[layer - 1], (size_t)N * L.oh * L.ow * L.cout * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    if (scsh_out) HIPCHK(h, hipMemcpyAsync(scsh_out, pn->scsh[layer - 1], (size_t)N * L.cout * 2 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    return TCSFM_OK;
-}
-
-// the coupled loop of train_mono.py:64-80 on context `h` (the handle or one of its lanes; pn->h == h): network, warps, corrections
-static int pose_loop(tcsfm_ctx *h, tcsfm_posenet *pn, int num_iter, int B, int S, const float *tgt, const float *srcs, const float *depth_t,
-                     const float *depth_s, const float *K, float *poses_out, float *stacked_out, const WinOff *wo) {
-    const int N = 2 * B * S;
-    int rc;
-    tcsfm_opts o; tcsfm_default_opts(&o);
-    if ((rc = check_intrinsics(h, &o, K, B))) return rc;
-    const long long hw = (long long)h->H * h->W;
-    // full_poses = pose_model(cat(tgt | src ; src | tgt)), train_mono.py:54-64 -- the pairs are formed by indexing
-    if ((rc = pn_run(pn, N, tgt, 3 * hw, srcs, 3 * hw, B, S, pn->pose, 0, stacked_out, 0, num_iter, wo))) return rc;
-    for (int it = 1; it < num_iter; it++) {
-        // inverse_warp2(src, d_t, d_s, -full_poses, K) with the next network input (tgt * valid | img_rec) written by the warp
-        // itself (train_mono.py:69-76), then full_poses += pose_model(new_imgs) (:77-78)
-        InitParams I = init_params(h, &o, N, pn->pose, nullptr, K, 0);
-        I.K_mod = B;
-        hipLaunchKernelGGL(k_init, dim3((N + 63) / 64), dim3(64), 0, h->stream, I);
-        WarpParams W;
-        memset(&W, 0, sizeof(W));
-        W.src = srcs; W.depth_t = depth_t; W.depth_s = depth_s; W.pc = h->pconst; W.tgt = tgt; W.posenet_in = pn->in_buf;
-        W.H = h->H; W.W = h->W; W.win_B = B; W.win_S = S;
-        if (wo) W.win_off = *wo;
-        hipLaunchKernelGGL(k_warp, dim3((unsigned)((hw + 255) / 256), N), dim3(256), 0, h->stream, W);
-        if ((rc = pn_run(pn, N, pn->in_buf, 6 * hw, pn->in_buf + 3 * hw, 6 * hw, 0, 0, pn->pose, 1, stacked_out, it, num_iter))) return rc;
-    }
-    HIPCHK(h, hipMemcpyAsync(poses_out, pn->pose, (size_t)N * 6 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    return TCSFM_OK;
-}
-
-int tcsfm_solve_pose_iteratively(tcsfm_handle h, tcsfm_posenet *pn, int num_iter, int B, int S, const float *tgt, const float *srcs,
-                                 const float *depth_t, const float *depth_s, const float *K, float *poses_out, float *stacked_out) {
-    if (!h || !pn || pn->h != h) return TCSFM_E_ARG;
-    if (!pn->loaded) return fail(h, TCSFM_E_ARG, "tcsfm_solve_pose_iteratively: no weights loaded");
-    const int N = 2 * B * S;
-    if (num_iter < 1 || B < 1 || S < 1 || N > pn->max_images || N > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_solve_pose_iteratively: sizes out of range");
-    if (!tgt || !srcs || !depth_t || !depth_s || !K || !poses_out) return fail(h, TCSFM_E_ARG, "tcsfm_solve_pose_iteratively: NULL argument");
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
-    return pose_loop(h, pn, num_iter, B, S, tgt, srcs, depth_t, depth_s, K, poses_out, stacked_out, nullptr);
-}
-
-// ---- depth network (models/depth_w_access.py, num_scales = 1): ResNet18 encoder + U-Net decoder ------------------------------
-}  // extern "C"   (the depth network's host helpers are templates)
-
-namespace {
-struct DnLayer {
-    int cin = 0, cout = 0, coutp = 0, ks = 0, stride = 1, pad = 0, up = 0, reflect = 0, epi = DN_EPI_NONE;
-    int ih = 0, iw = 0, oh = 0, ow = 0;
-    int nb = 1, pb = 1, kw = 1;         // work split: a function of the layer's geometry only (never of N)
-    std::string wname, bname, bn;       // state_dict names: conv weight, conv bias ("" = none), BatchNorm prefix ("" = none)
-    dn_f4 *w4 = nullptr;
-    float *bias = nullptr;
-    // training (tcsfm_depthnet_load_device): the transposed weight image of the data gradient (not for conv1), the raw parameters'
-    // snapshot (w [cout][cin][ks][ks], then conv bias, gamma, beta, mean, var [cout] each) and the folded-gradient accumulators
-    // (dw' [cout][cin ks ks], db' [cout])
-    dn_f4 *wt4 = nullptr;
-    float *raw = nullptr, *gw = nullptr, *gb = nullptr;
-    int taps() const { return ks * ks; }
-    size_t nw() const { return (size_t)cout * cin * ks * ks; }
-};
-const int DN_SKIP_C[5] = {64, 64, 128, 256, 512};
-}  // namespace
-
-struct tcsfm_depthnet {
-    tcsfm_ctx *h = nullptr;
-    int max_images = 0, loaded = 0;
-    std::vector<DnLayer> L;             // [0] conv1, then the encoder's block convolutions, then the decoder (order of dn_layers)
-    int enc_end = 0;                    // index of the first decoder layer
-    float *pw = nullptr, *pb = nullptr; // predict_disps.0 weight [1,8,3,3] / bias [1]
-    float *skip[5] = {};                // tcsfm_depthnet_forward's own skips, NHWC
-    float *pool = nullptr, *t1 = nullptr, *t2 = nullptr, *ds = nullptr;   // encoder scratch, N * H * W * 4 floats each
-    float *u = nullptr, *x = nullptr;   // decoder scratch, N * H * W * 32 floats each
-    // training state (allocated by the first tcsfm_depthnet_load_device)
-    int train_loaded = 0;
-    float *tbuf = nullptr;              // one allocation: the layers' raw / gw / gb regions and the head's gradient accumulator
-    float *hacc = nullptr;              // head: d predict_disps weight [72] + bias [1]
-    float *part = nullptr, *bpart = nullptr, *hpart = nullptr;   // weight / bias / head partials of one image group
-    float *gA = nullptr, *gB = nullptr, *gC = nullptr, *gD = nullptr, *gV = nullptr;   // data-gradient scratch
-};
-
-namespace {
-void dn_split(DnLayer &l) {
-    const int npix = l.oh * l.ow, cb = l.coutp / 16;
-    if (npix >= 4096) { l.nb = std::min(4, cb); l.pb = 2; l.kw = 1; }
-    else if (npix >= 1024) { l.nb = std::min(2, cb); l.pb = 1; l.kw = 4; }
-    else { l.nb = 1; l.pb = 1; l.kw = 4; }
-}
-
-DnLayer dn_layer(int cin, int cout, int ks, int stride, int ih, int iw, int up, int reflect, int epi, const std::string &w,
-                 const std::string &b, const std::string &bn) {
-    DnLayer l;
-    l.cin = cin; l.cout = cout; l.coutp = (cout + 15) / 16 * 16; l.ks = ks; l.stride = stride; l.pad = (ks - 1) / 2;
-    l.up = up; l.reflect = reflect; l.epi = epi; l.ih = ih; l.iw = iw;
-    const int vh = ih << up, vw = iw << up;
-    l.oh = (vh + 2 * l.pad - ks) / stride + 1; l.ow = (vw + 2 * l.pad - ks) / stride + 1;
-    l.wname = w; l.bname = b; l.bn = bn;
-    dn_split(l);
-    return l;
-}
-
-// the network's convolutions in evaluation order
-void dn_layers(tcsfm_depthnet *dn) {
-    const int H = dn->h->H, W = dn->h->W;
-    const std::string E = "encoder.encoder.";
-    auto &L = dn->L;
-    L.clear();
-    L.push_back(dn_layer(3, 64, 7, 2, H, W, 0, 0, DN_EPI_RELU, E + "conv1.weight", "", E + "bn1"));
-    L.back().oh = H / 2; L.back().ow = W / 2;
-    int h = H / 4, w = W / 4, c = 64;
-    for (int li = 1; li <= 4; li++) {
-        const int co = 64 << (li - 1 > 0 ? li - 1 : 0);
-        for (int b = 0; b < 2; b++) {
-            const std::string pre = E + "layer" + std::to_string(li) + "." + std::to_string(b) + ".";
-            const int s = (b == 0 && li > 1) ? 2 : 1;
-            L.push_back(dn_layer(c, co, 3, s, h, w, 0, 0, DN_EPI_RELU, pre + "conv1.weight", "", pre + "bn1"));
-            const int oh = L.back().oh, ow = L.back().ow;
-            L.push_back(dn_layer(co, co, 3, 1, oh, ow, 0, 0, DN_EPI_RES_RELU, pre + "conv2.weight", "", pre + "bn2"));
-            if (s == 2) L.push_back(dn_layer(c, co, 1, 2, h, w, 0, 0, DN_EPI_NONE, pre + "downsample.0.weight", "", pre + "downsample.1"));
-            h = oh; w = ow; c = co;
-        }
-    }
-    dn->enc_end = (int)L.size();
-    static const int planes[6] = {512, 256, 128, 64, 64, 32};
-    for (int i = 0; i < 5; i++) {
-        const std::string u = "depth_upconvs." + std::to_string(i) + ".1.conv.", ic = "iconvs." + std::to_string(i) + ".0.conv.";
-        L.push_back(dn_layer(planes[i], planes[i + 1], 3, 1, h, w, 1, 1, i < 4 ? DN_EPI_ELU_ADD : DN_EPI_ELU, u + "weight", u + "bias", ""));
-        h *= 2; w *= 2;
-        L.push_back(dn_layer(planes[i + 1], planes[i + 1], 3, 1, h, w, 0, 1, DN_EPI_ELU, ic + "weight", ic + "bias", ""));
-    }
-    L.push_back(dn_layer(32, 8, 3, 1, h, w, 0, 1, DN_EPI_ELU, "feature_convs.0.0.conv.weight", "feature_convs.0.0.conv.bias", ""));
-}
-
-void dn_free(tcsfm_depthnet *dn) {
-    for (DnLayer &l : dn->L) { if (l.w4) (void)hipFree(l.w4); if (l.bias) (void)hipFree(l.bias); l.w4 = nullptr; l.bias = nullptr; }
-    for (DnLayer &l : dn->L) { if (l.wt4) (void)hipFree(l.wt4); l.wt4 = nullptr; }
-    float *bufs[] = {dn->pw, dn->pb, dn->skip[0], dn->skip[1], dn->skip[2], dn->skip[3], dn->skip[4], dn->pool, dn->t1, dn->t2, dn->ds, dn->u, dn->x,
-                     dn->tbuf, dn->part, dn->bpart, dn->hpart, dn->gA, dn->gB, dn->gC, dn->gD, dn->gV};
-    for (float *p : bufs) if (p) (void)hipFree(p);
-}
-
-template <int KS, int NB, int PB, int KW>
-void dn_launch(const DnLayer &l, const DnConvParams &P, int N, hipStream_t s) {
-    dim3 grid((l.oh * l.ow + 16 * PB * (4 / KW) - 1) / (16 * PB * (4 / KW)), l.coutp / (16 * NB), N);
-    hipLaunchKernelGGL((k_dn_conv<KS, NB, PB, KW>), grid, dim3(256), 0, s, P);
-}
-
-template <int KS>
-void dn_launch_ks(const DnLayer &l, const DnConvParams &P, int N, hipStream_t s) {
-    if (l.kw == 1 && l.pb == 2) {
-        if (l.nb == 4) dn_launch<KS, 4, 2, 1>(l, P, N, s);
-        else if (l.nb == 2) dn_launch<KS, 2, 2, 1>(l, P, N, s);
-        else dn_launch<KS, 1, 2, 1>(l, P, N, s);
-    } else if (l.nb == 2) dn_launch<KS, 2, 1, 4>(l, P, N, s);
-    else dn_launch<KS, 1, 1, 4>(l, P, N, s);
-}
-
-void dn_conv(tcsfm_depthnet *dn, int li, int N, const float *in, const float *res, float *out, float *aux = nullptr) {
-    const DnLayer &l = dn->L[li];
-    DnConvParams P;
-    P.in = in; P.w4 = l.w4; P.bias = l.bias; P.res = res; P.out = out; P.aux = aux;
-    P.cin = l.cin; P.cout = l.cout; P.coutp = l.coutp; P.ih = l.ih; P.iw = l.iw; P.oh = l.oh; P.ow = l.ow;
-    P.stride = l.stride; P.pad = l.pad; P.up = l.up; P.reflect = l.reflect; P.epi = l.epi;
-    if (l.ks == 1) dn_launch_ks<1>(l, P, N, dn->h->stream);
-    else dn_launch_ks<3>(l, P, N, dn->h->stream);
-}
-
-int dn_encode(tcsfm_depthnet *dn, int N, const float *imgs, int flip, float *const sk[5]) {
-    tcsfm_ctx *h = dn->h;
-    const DnLayer &c1 = dn->L[0];
-    DnConv1Params P1;
-    P1.img = imgs; P1.w4 = c1.w4; P1.bias = c1.bias; P1.out = sk[0]; P1.ih = h->H; P1.iw = h->W; P1.oh = c1.oh; P1.ow = c1.ow; P1.flip = flip ? 1 : 0;
-    hipLaunchKernelGGL(k_dn_conv1<2>, dim3((c1.oh * c1.ow + 127) / 128, 1, N), dim3(256), 0, h->stream, P1);
-    const int ph = c1.oh / 2, pw = c1.ow / 2;
-    const long long pool_thr = (long long)N * ph * pw * 16;
-    hipLaunchKernelGGL(k_dn_maxpool, dim3((unsigned)((pool_thr + 255) / 256)), dim3(256), 0, h->stream, (const float *)sk[0], dn->pool, N, 64, c1.oh, c1.ow, ph, pw);
-    const float *x = dn->pool;
-    int li = 1;
-    for (int stage = 1; stage <= 4; stage++)
-        for (int b = 0; b < 2; b++) {
-            const bool down = b == 0 && stage > 1;
-            float *out = b == 1 ? sk[stage] : (x == dn->t2 ? dn->pool : dn->t2);
-            dn_conv(dn, li, N, x, nullptr, dn->t1);                                   // conv1 + bn1 + relu
-            const float *ident = x;
-            if (down) { dn_conv(dn, li + 2, N, x, nullptr, dn->ds); ident = dn->ds; }  // downsample.0 + downsample.1
-            dn_conv(dn, li + 1, N, dn->t1, ident, out);                               // conv2 + bn2 + identity, relu
-            li += down ? 3 : 2;
-            x = out;
-        }
-    HIPCHK(h, hipGetLastError());
-    return TCSFM_OK;
-}
-
-int dn_decode(tcsfm_depthnet *dn, int N, const float *const sk[5], float *disp) {
-    tcsfm_ctx *h = dn->h;
-    const float *x = sk[4];
-    int li = dn->enc_end;
-    for (int i = 0; i < 5; i++) {
-        dn_conv(dn, li, N, x, i < 4 ? sk[3 - i] : nullptr, dn->u);       // ELU(conv3x3_reflect(up2(x)) + b) (+ skip)
-        dn_conv(dn, li + 1, N, dn->u, nullptr, dn->x);                   // ELU(conv3x3_reflect(.) + b)
-        x = dn->x; li += 2;
-    }
-    dn_conv(dn, li, N, dn->x, nullptr, dn->u);                           // feature_convs.0: 32 -> 8, ELU
-    const long long npx = (long long)N * h->H * h->W;
-    hipLaunchKernelGGL(k_dn_predict, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, (const float *)dn->u, (const float *)dn->pw,
-                       (const float *)dn->pb, disp, N, h->H, h->W);
-    HIPCHK(h, hipGetLastError());
-    return TCSFM_OK;
-}
-
-// the tensors of a state_dict by name for every layer (names / shapes checked; the error names the key)
-struct DnSrc { const float *w = nullptr, *cb = nullptr, *g = nullptr, *be = nullptr, *rm = nullptr, *rv = nullptr; };
-int dn_lookup(tcsfm_depthnet *dn, const char *fn, int n, const char *const names[], const float *const ptrs[], const int64_t *shapes,
-              std::vector<DnSrc> &src, const float **pw, const float **pb) {
-    tcsfm_ctx *h = dn->h;
-    const std::string pre = std::string(fn) + ": ";
-    if (n < 0 || (n > 0 && (!names || !ptrs || !shapes))) return fail(h, TCSFM_E_ARG, (pre + "NULL argument").c_str());
-    for (int i = 0; i < n; i++) {
-        if (!names[i]) return fail(h, TCSFM_E_ARG, (pre + "NULL name").c_str());
-        if (!strncmp(names[i], "feature_convs.1.", 16) || !strncmp(names[i], "predict_disps.1.", 16)) {
-            h->err = pre + names[i] + ": num_scales > 1 is not supported";
-            return TCSFM_E_ARG;
-        }
-    }
-    auto find = [&](const std::string &key, std::vector<int64_t> shape, const float **ptr) -> int {
-        for (int i = 0; i < n; i++)
-            if (key == names[i]) {
-                bool ok = ptrs[i] != nullptr;
-                for (int d = 0; d < 4; d++) ok = ok && shapes[4 * i + d] == (d < (int)shape.size() ? shape[d] : 0);
-                if (!ok) {
-                    std::string s = "(";
-                    for (size_t d = 0; d < shape.size(); d++) s += (d ? "," : "") + std::to_string(shape[d]);
-                    h->err = pre + key + ": missing data or wrong shape (expected " + s + "))";
-                    if (key == "predict_disps.0.0.conv.weight" && shapes[4 * i + 1] != 8) h->err += ": num_scales > 1 is not supported";
-                    return TCSFM_E_ARG;
-                }
-                *ptr = ptrs[i];
-                return TCSFM_OK;
-            }
-        h->err = pre + key + ": missing";
-        return TCSFM_E_ARG;
-    };
-    src.assign(dn->L.size(), DnSrc());
-    for (size_t li = 0; li < dn->L.size(); li++) {
-        const DnLayer &l = dn->L[li];
-        DnSrc &p = src[li];
-        int rc;
-        if ((rc = find(l.wname, {l.cout, l.cin, l.ks, l.ks}, &p.w))) return rc;
-        if (!l.bname.empty() && (rc = find(l.bname, {l.cout}, &p.cb))) return rc;
-        if (!l.bn.empty()) {
-            if ((rc = find(l.bn + ".weight", {l.cout}, &p.g)) || (rc = find(l.bn + ".bias", {l.cout}, &p.be)) ||
-                (rc = find(l.bn + ".running_mean", {l.cout}, &p.rm)) || (rc = find(l.bn + ".running_var", {l.cout}, &p.rv))) return rc;
-        }
-    }
-    int rc;
-    if ((rc = find("predict_disps.0.0.conv.weight", {1, 8, 3, 3}, pw)) || (rc = find("predict_disps.0.0.conv.bias", {1}, pb))) return rc;
-    return TCSFM_OK;
-}
-}  // namespace
-
-extern "C" {
-
-void tcsfm_depthnet_destroy(tcsfm_depthnet *dn) {
-    if (!dn) return;
-    DeviceGuard dev_guard(dn->h->device);
-    dn_free(dn);
-    delete dn;
-}
-
-int tcsfm_depthnet_create(tcsfm_handle h, int max_images, tcsfm_depthnet **out) {
-    if (!h || !out) return TCSFM_E_ARG;
-    *out = nullptr;
-    if (max_images < 1 || max_images > 4096) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_create: max_images out of range");
-    if (h->H % 32 || h->W % 32 || h->H < 32 || h->W < 32)
-        return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_create: the handle's H and W must be multiples of 32 (the decoder's skip additions need them)");
-    DeviceGuard dev_guard(h->device);
-    tcsfm_depthnet *dn = new tcsfm_depthnet();
-    dn->h = h; dn->max_images = max_images;
-    dn_layers(dn);
-    hipError_t e = hipSuccess;
-    for (DnLayer &l : dn->L) {
-        const size_t nw4 = (l.ks == 7 ? 11 : (size_t)l.ks * l.ks * (l.cin / 16)) * 4 * l.coutp;
-        if (e == hipSuccess) e = hipMalloc((void **)&l.w4, nw4 * sizeof(dn_f4));
-        if (e == hipSuccess) e = hipMalloc((void **)&l.bias, l.coutp * sizeof(float));
-    }
-    const size_t N = (size_t)max_images, hw = (size_t)h->H * h->W;
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->pw, 72 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->pb, sizeof(float));
-    for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipMalloc((void **)&dn->skip[k], N * (hw >> (2 * (k + 1))) * DN_SKIP_C[k] * sizeof(float));
-    float **enc[] = {&dn->pool, &dn->t1, &dn->t2, &dn->ds};
-    for (float **p : enc) if (e == hipSuccess) e = hipMalloc((void **)p, N * hw * 4 * sizeof(float));       // (H/4)(W/4) x 64 = H W x 4
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->u, N * hw * 32 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->x, N * hw * 32 * sizeof(float));
-    if (e != hipSuccess) { tcsfm_depthnet_destroy(dn); return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_depthnet_create: allocation failed"); }
-    *out = dn;
-    return TCSFM_OK;
-}
-
-int tcsfm_depthnet_load(tcsfm_depthnet *dn, int n, const char *const names[], const float *const host_ptrs[], const int64_t *shapes) {
-    if (!dn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = dn->h;
-    std::vector<DnSrc> src;
-    const float *pw = nullptr, *pb = nullptr;
-    if (int rc = dn_lookup(dn, "tcsfm_depthnet_load", n, names, host_ptrs, shapes, src, &pw, &pb)) return rc;
-    DeviceGuard dev_guard(h->device);
-    // fold + lay out every layer on the host (float64 fold, deterministic), then copy
-    std::vector<std::vector<float>> w4s(dn->L.size()), biases(dn->L.size());
-    for (size_t li = 0; li < dn->L.size(); li++) {
-        const DnLayer &l = dn->L[li];
-        const float *w = src[li].w, *cb = src[li].cb, *g = src[li].g, *be = src[li].be, *rm = src[li].rm, *rv = src[li].rv;
-        std::vector<double> sc(l.cout, 1.0), sh(l.cout, 0.0);
-        for (int co = 0; co < l.cout; co++) {
-            if (g) { sc[co] = (double)g[co] / sqrt((double)rv[co] + 1e-5); sh[co] = (double)be[co] - (double)rm[co] * sc[co]; }
-            if (cb) sh[co] += (double)cb[co] * sc[co];
-        }
-        auto W = [&](int co, int ci, int ky, int kx) { return (float)((double)w[(((size_t)co * l.cin + ci) * l.ks + ky) * l.ks + kx] * sc[co]); };
-        std::vector<float> &o = w4s[li];
-        if (l.ks == 7) {        // first layer: (g, kq) -> (ci, ky) = combo 2 g + (kq >> 1), kx = 4 (kq & 1) + t
-            o.assign((size_t)11 * 4 * l.coutp * 4, 0.f);
-            for (int gq = 0; gq < 44; gq++) {
-                const int gg = gq >> 2, kq = gq & 3, combo = 2 * gg + (kq >> 1);
-                if (combo >= 21) continue;
-                const int ci = combo / 7, ky = combo % 7;
-                for (int co = 0; co < l.cout; co++)
-                    for (int t = 0; t < 4; t++) {
-                        const int kx = 4 * (kq & 1) + t;
-                        if (kx < 7) o[((size_t)(gg * 4 + kq) * l.coutp + co) * 4 + t] = W(co, ci, ky, kx);
-                    }
-            }
-        } else {
-            const int c16n = l.cin / 16;
-            o.assign((size_t)l.ks * l.ks * c16n * 4 * l.coutp * 4, 0.f);
-            for (int tap = 0; tap < l.ks * l.ks; tap++)
-                for (int c16 = 0; c16 < c16n; c16++)
-                    for (int kq = 0; kq < 4; kq++)
-                        for (int co = 0; co < l.cout; co++)
-                            for (int t = 0; t < 4; t++)
-                                o[((size_t)((tap * c16n + c16) * 4 + kq) * l.coutp + co) * 4 + t] = W(co, c16 * 16 + 4 * kq + t, tap / l.ks, tap % l.ks);
-        }
-        biases[li].assign(l.coutp, 0.f);
-        for (int co = 0; co < l.cout; co++) biases[li][co] = (float)sh[co];
-    }
-    if (int rc_q = drain_queued(h)) return rc_q;
-    HIPCHK(h, hipStreamSynchronize(h->stream));     // weights may be in use by earlier calls on the stream
-    for (size_t li = 0; li < dn->L.size(); li++) {
-        HIPCHK(h, hipMemcpy(dn->L[li].w4, w4s[li].data(), w4s[li].size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(dn->L[li].bias, biases[li].data(), biases[li].size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    HIPCHK(h, hipMemcpy(dn->pw, pw, 72 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(dn->pb, pb, sizeof(float), hipMemcpyHostToDevice));
-    dn->loaded = 1;
-    dn->train_loaded = 0;               // the training snapshot (tcsfm_depthnet_load_device) no longer matches the weights
-    return TCSFM_OK;
-}
-
-static int dn_check(tcsfm_depthnet *dn, int N, const char *fn) {
-    tcsfm_ctx *h = dn->h;
-    if (!dn->loaded) { h->err = std::string(fn) + ": no weights loaded"; return TCSFM_E_ARG; }
-    if (N < 1 || N > dn->max_images) { h->err = std::string(fn) + ": N out of range (1 .. max_images)"; return TCSFM_E_ARG; }
-    return TCSFM_OK;
-}
-
-int tcsfm_depthnet_encode(tcsfm_depthnet *dn, int N, const float *imgs, int flip, float *const skips_out[5]) {
-    if (!dn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = dn->h;
-    if (int rc = dn_check(dn, N, "tcsfm_depthnet_encode")) return rc;
-    if (!imgs || !skips_out) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode: NULL argument");
-    for (int k = 0; k < 5; k++) if (!skips_out[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode: NULL skip buffer");
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    return dn_encode(dn, N, imgs, flip, skips_out);
-}
-
-int tcsfm_depthnet_decode(tcsfm_depthnet *dn, int N, const float *const skips_in[5], float *disp_out) {
-    if (!dn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = dn->h;
-    if (int rc = dn_check(dn, N, "tcsfm_depthnet_decode")) return rc;
-    if (!skips_in || !disp_out) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode: NULL argument");
-    for (int k = 0; k < 5; k++) if (!skips_in[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode: NULL skip buffer");
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    return dn_decode(dn, N, skips_in, disp_out);
-}
-
-int tcsfm_depthnet_forward(tcsfm_depthnet *dn, int N, const float *imgs, int flip, float *disp_out) {
-    if (!dn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = dn->h;
-    if (int rc = dn_check(dn, N, "tcsfm_depthnet_forward")) return rc;
-    if (!imgs || !disp_out) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_forward: NULL argument");
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    if (int rc = dn_encode(dn, N, imgs, flip, dn->skip)) return rc;
-    return dn_decode(dn, N, dn->skip, disp_out);
-}
-
-int tcsfm_debug_depthnet_split(tcsfm_depthnet *dn, int layer, int *ks, int *oh, int *ow, int *nb, int *pb, int *kw) {
-    if (!dn) return TCSFM_E_ARG;
-    if (layer < 0 || layer >= (int)dn->L.size()) return fail(dn->h, TCSFM_E_ARG, "tcsfm_debug_depthnet_split: layer out of range");
-    const DnLayer &l = dn->L[layer];
-    if (ks) *ks = l.ks;
-    if (oh) *oh = l.oh;
-    if (ow) *ow = l.ow;
-    if (nb) *nb = l.nb;
-    if (pb) *pb = l.pb;
-    if (kw) *kw = l.kw;
-    return TCSFM_OK;
-}
-
-}  // extern "C"   (the depth network's training helpers)
-
-namespace {
-// ---- depth network training: tape layout, device re-fold, data / weight gradients ------------------------------------------
-// The tape of N images is a list of entries, each [N][per-image size] (entry-major), so a group of images [i0, i1) of a chunked call
-// is a pointer offset in every entry.
-struct DnTape {
-    std::vector<size_t> sz, off;        // per-image floats of each entry; offset of each entry for N images
-    float *base = nullptr;
-    int N = 0;
-    float *at(int k, int i0) const { return base + off[k] + (size_t)i0 * sz[k]; }
-    size_t total() const { size_t t = 0; for (size_t s : sz) t += s; return t * N; }
-};
-
-void dn_tape_layout(const tcsfm_depthnet *dn, int dec, int N, float *base, DnTape &t) {
-    const int H = dn->h->H, W = dn->h->W;
-    const size_t hw = (size_t)H * W;
-    t.sz.clear();
-    if (!dec) {
-        // images, conv1's output (skip 0), the pooled map, then per block: conv1's output, the block's output
-        const DnLayer &c1 = dn->L[0];
-        t.sz.push_back(3 * hw);
-        t.sz.push_back((size_t)c1.oh * c1.ow * 64);
-        t.sz.push_back((size_t)(c1.oh / 2) * (c1.ow / 2) * 64);
-        for (int li = 1; li < dn->enc_end;) {
-            const DnLayer &a = dn->L[li];
-            const bool down = a.stride == 2;
-            t.sz.push_back((size_t)a.oh * a.ow * a.cout);
-            t.sz.push_back((size_t)a.oh * a.ow * a.cout);
-            li += down ? 3 : 2;
-        }
-    } else {
-        // skip 4, then per up-step i: the ELU before the skip add (i < 4), up-conv output, iconv output; features; disparity
-        const DnLayer &u0 = dn->L[dn->enc_end];
-        t.sz.push_back((size_t)u0.ih * u0.iw * u0.cin);
-        for (int i = 0; i < 5; i++) {
-            const DnLayer &u = dn->L[dn->enc_end + 2 * i];
-            const size_t s = (size_t)u.oh * u.ow * u.cout;
-            if (i < 4) t.sz.push_back(s);
-            t.sz.push_back(s);
-            t.sz.push_back(s);
-        }
-        t.sz.push_back(hw * 8);
-        t.sz.push_back(hw);
-    }
-    t.off.assign(t.sz.size(), 0);
-    size_t o = 0;
-    for (size_t k = 0; k < t.sz.size(); k++) { t.off[k] = o; o += t.sz[k] * N; }
-    t.base = base; t.N = N;
-}
-
-int dn_wchunk(int npix) { return npix <= 2048 ? npix : 2048; }     // weight-gradient K chunk (pixels of one image): geometry only
-int dn_nchunk(int npix) { const int c = dn_wchunk(npix); return (npix + c - 1) / c; }
-size_t dn_cinT(const DnLayer &l) { return l.ks == 7 ? 147 : (size_t)l.cin * l.taps(); }
-
-// the padded virtual grid of a reflect-padded / up-sampled layer (the data gradient's lane grid before k_dnb_fold)
-void dn_padded_grid(const DnLayer &l, int &gh, int &gw) { gh = (l.ih << l.up) + 2 * l.pad; gw = (l.iw << l.up) + 2 * l.pad; }
-
-int dn_train_alloc(tcsfm_depthnet *dn) {
-    if (dn->tbuf) return TCSFM_OK;
-    tcsfm_ctx *h = dn->h;
-    const size_t N = dn->max_images, hw = (size_t)h->H * h->W;
-    size_t tot = 0, part = 0, bpart = 0, gv = 0;
-    for (const DnLayer &l : dn->L) {
-        tot += l.nw() + 5 * (size_t)l.cout + l.nw() + l.cout;
-        const int npix = l.oh * l.ow;
-        part = std::max(part, N * dn_nchunk(npix) * l.cout * dn_cinT(l));
-        bpart = std::max(bpart, N * dn_nchunk(npix) * l.cout);
-        if (l.reflect) { int gh, gw; dn_padded_grid(l, gh, gw); gv = std::max(gv, N * gh * gw * l.cin); }
-    }
-    tot += 73;
-    hipError_t e = hipMalloc((void **)&dn->tbuf, tot * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->part, part * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->bpart, bpart * sizeof(float));
-    const int hch = (int)((hw + DNB_HEAD_CHUNK - 1) / DNB_HEAD_CHUNK);
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->hpart, N * hch * 73 * sizeof(float));
-    float **g32[] = {&dn->gA, &dn->gB, &dn->gC};
-    for (float **p : g32) if (e == hipSuccess) e = hipMalloc((void **)p, N * hw * 32 * sizeof(float));    // the largest activation: H W x 32
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->gD, N * hw * 4 * sizeof(float));                      // a downsample's input grid
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->gV, gv * sizeof(float));
-    size_t o = 0;
-    for (DnLayer &l : dn->L) {
-        l.raw = dn->tbuf + o; o += l.nw() + 5 * (size_t)l.cout;
-        l.gw = dn->tbuf + o; o += l.nw();
-        l.gb = dn->tbuf + o; o += l.cout;
-        if (l.ks != 7 && e == hipSuccess) {
-            const size_t n4 = (size_t)l.taps() * l.coutp * l.cin;      // floats / 4 ... in dn_f4 units: taps * coutp/16 * 4 * cin
-            e = hipMalloc((void **)&l.wt4, n4 / 4 * sizeof(dn_f4) * 1);
-            if (e == hipSuccess) e = hipMemsetAsync(l.wt4, 0, n4 * sizeof(float), h->stream);   // rows of channels >= cout stay zero
-        }
-        if (e == hipSuccess) {
-            const size_t nw4 = (l.ks == 7 ? 11 : (size_t)l.ks * l.ks * (l.cin / 16)) * 4 * l.coutp;
-            e = hipMemsetAsync(l.w4, 0, nw4 * sizeof(dn_f4), h->stream);
-        }
-    }
-    dn->hacc = dn->tbuf + o;
-    if (e != hipSuccess) {
-        for (DnLayer &l : dn->L) { if (l.wt4) (void)hipFree(l.wt4); l.wt4 = nullptr; l.raw = l.gw = l.gb = nullptr; }
-        float **bufs[] = {&dn->tbuf, &dn->part, &dn->bpart, &dn->hpart, &dn->gA, &dn->gB, &dn->gC, &dn->gD, &dn->gV};
-        for (float **p : bufs) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_depthnet_load_device: allocation failed");
-    }
-    return TCSFM_OK;
-}
-
-unsigned dn_blocks(long long threads) { return (unsigned)((threads + 255) / 256); }
-
-template <int KS, int NB, int PB, int KW>
-void dnb_dgrad_launch(int gpix, int cin, const DnDgradParams &P, int N, hipStream_t s) {
-    dim3 grid((gpix + 16 * PB * (4 / KW) - 1) / (16 * PB * (4 / KW)), cin / (16 * NB), N);
-    hipLaunchKernelGGL((k_dnb_dgrad<KS, NB, PB, KW>), grid, dim3(256), 0, s, P);
-}
-
-template <int KS>
-void dnb_dgrad_ks(int gpix, int cin, const DnDgradParams &P, int N, hipStream_t s) {
-    // the forward's split rule (dn_split) on the lane grid and the input channel blocks
-    const int cb = cin / 16;
-    if (gpix >= 4096) {
-        const int nb = std::min(4, cb);
-        if (nb == 4) dnb_dgrad_launch<KS, 4, 2, 1>(gpix, cin, P, N, s);
-        else if (nb == 2) dnb_dgrad_launch<KS, 2, 2, 1>(gpix, cin, P, N, s);
-        else dnb_dgrad_launch<KS, 1, 2, 1>(gpix, cin, P, N, s);
-    } else if (gpix >= 1024 && cb >= 2) dnb_dgrad_launch<KS, 2, 1, 4>(gpix, cin, P, N, s);
-    else dnb_dgrad_launch<KS, 1, 1, 4>(gpix, cin, P, N, s);
-}
-
-// data gradient of layer l from dz: direct (input grid, fused adds + derivative) or onto the padded virtual grid (then k_dnb_fold)
-void dnb_dgrad(tcsfm_depthnet *dn, int li, int N, const float *dz, float *out, bool direct, const float *add1, const float *add2,
-               const float *y, int act) {
-    const DnLayer &l = dn->L[li];
-    DnDgradParams P;
-    P.dz = dz; P.wt4 = l.wt4; P.out = out; P.add1 = add1; P.add2 = add2; P.y = y; P.act = act;
-    P.cin = l.cin; P.cout = l.cout; P.coutp = l.coutp; P.oh = l.oh; P.ow = l.ow; P.stride = l.stride; P.direct = direct ? 1 : 0;
-    if (direct) { P.gh = l.ih; P.gw = l.iw; P.goff = l.pad; }
-    else { dn_padded_grid(l, P.gh, P.gw); P.goff = 0; }
-    if (l.ks == 1) dnb_dgrad_ks<1>(P.gh * P.gw, l.cin, P, N, dn->h->stream);
-    else dnb_dgrad_ks<3>(P.gh * P.gw, l.cin, P, N, dn->h->stream);
-}
-
-void dnb_fold(tcsfm_depthnet *dn, int li, int N, const float *src, const float *add, const float *y, int act, float *out, float *raw_out) {
-    DnFoldParams F;
-    const DnLayer *l = li >= 0 ? &dn->L[li] : nullptr;
-    F.src = src; F.add = add; F.y = y; F.act = act; F.out = out; F.raw_out = raw_out; F.N = N;
-    F.C = l->cin; F.ih = l->ih; F.iw = l->iw; F.up = l->up; F.pad = l->pad; F.reflect = l->reflect;
-    dn_padded_grid(*l, F.gh, F.gw);
-    hipLaunchKernelGGL(k_dnb_fold, dim3(dn_blocks((long long)N * F.ih * F.iw * (F.C / 4))), dim3(256), 0, dn->h->stream, F);
-}
-
-// (src + add) * act'(y) elementwise on an [N][h][w][C] map (C % 4 == 0)
-void dnb_ew(tcsfm_depthnet *dn, int N, int C, int hh, int ww, const float *src, const float *add, const float *y, int act, float *out) {
-    DnFoldParams F;
-    F.src = src; F.add = add; F.y = y; F.act = act; F.out = out; F.raw_out = nullptr; F.N = N;
-    F.C = C; F.ih = hh; F.iw = ww; F.gh = hh; F.gw = ww; F.up = 0; F.pad = 0; F.reflect = 0;
-    hipLaunchKernelGGL(k_dnb_fold, dim3(dn_blocks((long long)N * hh * ww * (C / 4))), dim3(256), 0, dn->h->stream, F);
-}
-
-// weight (wneed) and bias (bneed) gradients of the folded layer into l.gw / l.gb (accumulate: add to them)
-void dnb_wgrad(tcsfm_depthnet *dn, int li, int N, const float *dz, const float *x, bool wneed, bool bneed, int accumulate) {
-    DnLayer &l = dn->L[li];
-    hipStream_t s = dn->h->stream;
-    const int npix = l.oh * l.ow, chunk = dn_wchunk(npix), nch = dn_nchunk(npix), parts = N * nch;
-    if (wneed) {
-        DnWgradParams P;
-        P.dz = dz; P.x = x; P.part = dn->part; P.cin = l.cin; P.cout = l.cout; P.ih = l.ih; P.iw = l.iw; P.oh = l.oh; P.ow = l.ow;
-        P.stride = l.stride; P.pad = l.pad; P.up = l.up; P.reflect = l.reflect; P.chunk = chunk; P.nchunk = nch;
-        if (l.ks == 7) hipLaunchKernelGGL((k_dnb_wgrad<7, 2, true>), dim3(parts, 2, l.coutp / 32), dim3(256), 0, s, P);
-        else if (l.ks == 1) hipLaunchKernelGGL((k_dnb_wgrad<1, 2, false>), dim3(parts, l.cin / 16, l.coutp / 32), dim3(256), 0, s, P);
-        else if (l.coutp % 32 == 0) hipLaunchKernelGGL((k_dnb_wgrad<9, 2, false>), dim3(parts, l.cin / 16, l.coutp / 32), dim3(256), 0, s, P);
-        else hipLaunchKernelGGL((k_dnb_wgrad<9, 1, false>), dim3(parts, l.cin / 16, l.coutp / 16), dim3(256), 0, s, P);
-        const long long E = (long long)l.cout * dn_cinT(l);
-        hipLaunchKernelGGL(k_dnb_wsum, dim3(dn_blocks(E)), dim3(256), 0, s, (const float *)dn->part, l.gw, E, parts, accumulate);
-    }
-    if (bneed) {
-        hipLaunchKernelGGL(k_dnb_bgrad, dim3(parts), dim3(256), 0, s, dz, dn->bpart, l.cout, npix, chunk, nch);
-        hipLaunchKernelGGL(k_dnb_wsum, dim3(dn_blocks(l.cout)), dim3(256), 0, s, (const float *)dn->bpart, l.gb, (long long)l.cout, parts, accumulate);
-    }
-}
-
-// requested parameter gradients, by layer
-struct DnReq {
-    float *w = nullptr, *cb = nullptr, *g = nullptr, *be = nullptr;
-    bool wneed() const { return w || g; }
-    bool bneed() const { return cb || g || be; }
-    bool any() const { return w || cb || g || be; }
-};
-
-// names -> per-layer requests (decoder: layers >= enc_end and the head; encoder: the others)
-int dn_requests(tcsfm_depthnet *dn, const char *fn, bool dec, int n, const char *const names[], float *const grads[],
-                std::vector<DnReq> &req, float **hw, float **hb) {
-    tcsfm_ctx *h = dn->h;
-    req.assign(dn->L.size(), DnReq());
-    *hw = *hb = nullptr;
-    if (n < 0 || (n > 0 && (!names || !grads))) return fail(h, TCSFM_E_ARG, (std::string(fn) + ": NULL argument").c_str());
-    for (int i = 0; i < n; i++) {
-        if (!names[i] || !grads[i]) return fail(h, TCSFM_E_ARG, (std::string(fn) + ": NULL name or gradient buffer").c_str());
-        const std::string k = names[i];
-        float **slot = nullptr;
-        bool mine = false;
-        for (size_t li = 0; li < dn->L.size() && !slot; li++) {
-            DnLayer &l = dn->L[li];
-            const bool d = (int)li >= dn->enc_end;
-            if (k == l.wname) slot = &req[li].w;
-            else if (!l.bname.empty() && k == l.bname) slot = &req[li].cb;
-            else if (!l.bn.empty() && k == l.bn + ".weight") slot = &req[li].g;
-            else if (!l.bn.empty() && k == l.bn + ".bias") slot = &req[li].be;
-            else if (!l.bn.empty() && (k == l.bn + ".running_mean" || k == l.bn + ".running_var")) {
-                h->err = std::string(fn) + ": " + k + ": running statistics have no gradient";
-                return TCSFM_E_ARG;
-            }
-            if (slot) mine = d == dec;
-        }
-        if (!slot && k == "predict_disps.0.0.conv.weight") { slot = hw; mine = dec; }
-        if (!slot && k == "predict_disps.0.0.conv.bias") { slot = hb; mine = dec; }
-        if (!slot || !mine) {
-            h->err = std::string(fn) + ": " + k + (slot ? ": not a parameter of this half of the network" : ": unknown parameter");
-            return TCSFM_E_ARG;
-        }
-        *slot = grads[i];
-    }
-    return TCSFM_OK;
-}
-
-// the chain rule through the fold and the reference layout, for every requested layer
-void dn_param_out(tcsfm_depthnet *dn, const std::vector<DnReq> &req, int lo, int hi) {
-    for (int li = lo; li < hi; li++) {
-        const DnReq &r = req[li];
-        if (!r.any()) continue;
-        DnLayer &l = dn->L[li];
-        const float *w = l.raw, *v = l.raw + l.nw();
-        const bool bn = !l.bn.empty();
-        hipLaunchKernelGGL(k_dnb_param_grad, dim3(dn_blocks(l.cout)), dim3(256), 0, dn->h->stream, (const float *)l.gw, (const float *)l.gb, w,
-                           bn ? v + l.cout : nullptr, v + 3 * l.cout, v + 4 * l.cout, r.w, r.cb, r.g, r.be, l.cout, (int)l.nw() / l.cout);
-    }
-}
-
-int dn_encode_train(tcsfm_depthnet *dn, int N, const float *imgs, const DnTape &t, int i0, float *const sk[5]) {
-    tcsfm_ctx *h = dn->h;
-    HIPCHK(h, hipMemcpyAsync(t.at(0, i0), imgs, (size_t)N * t.sz[0] * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    const DnLayer &c1 = dn->L[0];
-    DnConv1Params P1;
-    P1.img = imgs; P1.w4 = c1.w4; P1.bias = c1.bias; P1.out = t.at(1, i0); P1.ih = h->H; P1.iw = h->W; P1.oh = c1.oh; P1.ow = c1.ow; P1.flip = 0;
-    hipLaunchKernelGGL(k_dn_conv1<2>, dim3((c1.oh * c1.ow + 127) / 128, 1, N), dim3(256), 0, h->stream, P1);
-    const int ph = c1.oh / 2, pw = c1.ow / 2;
-    const long long pool_thr = (long long)N * ph * pw * 16;
-    hipLaunchKernelGGL(k_dn_maxpool, dim3((unsigned)((pool_thr + 255) / 256)), dim3(256), 0, h->stream, (const float *)t.at(1, i0), t.at(2, i0), N, 64,
-                       c1.oh, c1.ow, ph, pw);
-    const float *x = t.at(2, i0);
-    int li = 1, e = 3;
-    for (int stage = 1; stage <= 4; stage++)
-        for (int b = 0; b < 2; b++) {
-            const bool down = b == 0 && stage > 1;
-            float *t1 = t.at(e, i0), *out = t.at(e + 1, i0);
-            dn_conv(dn, li, N, x, nullptr, t1);
-            const float *ident = x;
-            if (down) { dn_conv(dn, li + 2, N, x, nullptr, dn->ds); ident = dn->ds; }
-            dn_conv(dn, li + 1, N, t1, ident, out);
-            li += down ? 3 : 2; e += 2;
-            x = out;
-            if (b == 1) HIPCHK(h, hipMemcpyAsync(sk[stage], out, (size_t)N * t.sz[e - 1] * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-        }
-    HIPCHK(h, hipMemcpyAsync(sk[0], t.at(1, i0), (size_t)N * t.sz[1] * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipGetLastError());
-    return TCSFM_OK;
-}
-
-int dn_decode_train(tcsfm_depthnet *dn, int N, const float *const sk[5], float *disp, const DnTape &t, int i0) {
-    tcsfm_ctx *h = dn->h;
-    HIPCHK(h, hipMemcpyAsync(t.at(0, i0), sk[4], (size_t)N * t.sz[0] * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    const float *x = sk[4];
-    int li = dn->enc_end, e = 1;
-    for (int i = 0; i < 5; i++) {
-        float *aux = i < 4 ? t.at(e++, i0) : nullptr;
-        float *u = t.at(e++, i0), *xo = t.at(e++, i0);
-        dn_conv(dn, li, N, x, i < 4 ? sk[3 - i] : nullptr, u, aux);
-        dn_conv(dn, li + 1, N, u, nullptr, xo);
-        x = xo; li += 2;
-    }
-    float *f = t.at(e, i0), *dt = t.at(e + 1, i0);
-    dn_conv(dn, li, N, x, nullptr, f);
-    const long long npx = (long long)N * h->H * h->W;
-    hipLaunchKernelGGL(k_dn_predict, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, (const float *)f, (const float *)dn->pw,
-                       (const float *)dn->pb, dt, N, h->H, h->W);
-    HIPCHK(h, hipMemcpyAsync(disp, dt, (size_t)npx * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipGetLastError());
-    return TCSFM_OK;
-}
-
-// decoder backward of one image group.  Layer positions: up_i = enc_end + 2 i, iconv_i = enc_end + 2 i + 1, feature conv, head.
-int dn_decode_backward(tcsfm_depthnet *dn, int N, const DnTape &t, int i0, const float *ddisp, float *const dsk[5],
-                       const std::vector<DnReq> &req, bool head_req, int accumulate) {
-    tcsfm_ctx *h = dn->h;
-    const int E = dn->enc_end, F = (int)dn->L.size() - 1, HEAD = F + 1, H = h->H, W = h->W;
-    // lowest position whose data gradient is needed: below the lowest requested parameter, or where a requested skip's gradient leaves
-    int low = HEAD + 1;
-    for (int li = E; li <= F; li++) if (req[li].any()) { low = std::min(low, li); break; }
-    if (head_req) low = std::min(low, HEAD);
-    int skip_src = HEAD + 1;                    // the data gradient of layers >= skip_src must run
-    if (dsk[4]) skip_src = E;
-    for (int i = 0; i < 4 && skip_src > E; i++) if (dsk[3 - i]) skip_src = std::min(skip_src, E + 2 * i + 1);
-    auto need_dgrad = [&](int pos) { return low < pos || skip_src <= pos; };
-    const int ntape = (int)t.sz.size();
-    float *f = t.at(ntape - 2, i0), *disp = t.at(ntape - 1, i0);
-    const long long npx = (long long)N * H * W;
-    if (head_req) {
-        const int hch = (H * W + DNB_HEAD_CHUNK - 1) / DNB_HEAD_CHUNK;
-        hipLaunchKernelGGL(k_dnb_head_wgrad, dim3(N * hch), dim3(128), 0, h->stream, (const float *)f, (const float *)disp, ddisp, dn->hpart, H, W, hch);
-        hipLaunchKernelGGL(k_dnb_wsum, dim3(1), dim3(256), 0, h->stream, (const float *)dn->hpart, dn->hacc, 73LL, N * hch, accumulate);
-    }
-    if (!need_dgrad(HEAD)) return TCSFM_OK;
-    float *cur = dn->gA, *nxt = dn->gB;
-    hipLaunchKernelGGL(k_dnb_head, dim3(dn_blocks(npx)), dim3(256), 0, h->stream, (const float *)f, (const float *)disp, ddisp, (const float *)dn->pw, cur, N, H, W);
-    // tape entries: 0 = skip 4; up-step i: aux (i < 4), u, x
-    auto u_at = [&](int i) { return t.at(1 + 3 * i + 1, i0); };
-    auto aux_at = [&](int i) { return t.at(1 + 3 * i, i0); };
-    auto x_at = [&](int i) { return i < 4 ? t.at(1 + 3 * i + 2, i0) : t.at(1 + 3 * 4 + 1, i0); };
-    for (int li = F; li >= E && need_dgrad(li + 1); li--) {
-        const int rel = li - E, i = rel / 2;
-        const bool feat = li == F, up = !feat && rel % 2 == 0;
-        const float *in = feat ? x_at(4) : (up ? (i ? x_at(i - 1) : t.at(0, i0)) : (i < 4 ? u_at(i) : t.at(1 + 3 * 4, i0)));
-        if (req[li].any()) dnb_wgrad(dn, li, N, cur, in, req[li].wneed(), req[li].bneed(), accumulate);
-        if (!need_dgrad(li)) break;
-        dnb_dgrad(dn, li, N, cur, dn->gV, false, nullptr, nullptr, nullptr, DN_ACT_NONE);
-        if (feat) dnb_fold(dn, li, N, dn->gV, nullptr, x_at(4), DN_ACT_ELU, nxt, nullptr);
-        else if (!up) dnb_fold(dn, li, N, dn->gV, nullptr, i < 4 ? aux_at(i) : t.at(1 + 3 * 4, i0), DN_ACT_ELU, nxt, i < 4 ? dsk[3 - i] : nullptr);
-        else if (i > 0) dnb_fold(dn, li, N, dn->gV, nullptr, x_at(i - 1), DN_ACT_ELU, nxt, nullptr);
-        else dnb_fold(dn, li, N, dn->gV, nullptr, nullptr, DN_ACT_NONE, nullptr, dsk[4]);
-        std::swap(cur, nxt);
-    }
-    HIPCHK(h, hipGetLastError());
-    return TCSFM_OK;
-}
-
-// encoder backward of one image group (dsk[k] NULL: no gradient on skip k)
-int dn_encode_backward(tcsfm_depthnet *dn, int N, const DnTape &t, int i0, const float *const dsk[5], const std::vector<DnReq> &req, int accumulate) {
-    tcsfm_ctx *h = dn->h;
-    struct Blk { int li, down, h_e, t1_e, out_e, skip_in; };
-    std::vector<Blk> blk;
-    int li = 1, e = 3;
-    for (int stage = 1; stage <= 4; stage++)
-        for (int b = 0; b < 2; b++) {
-            const int down = b == 0 && stage > 1;
-            blk.push_back({li, down, b == 0 ? (stage == 1 ? 2 : e - 1) : e - 1, e, e + 1, b == 0 && stage > 1 ? stage - 1 : -1});
-            li += down ? 3 : 2; e += 2;
-        }
-    // is anything requested in blocks < j (or conv1)?
-    std::vector<int> before(blk.size() + 1, 0);
-    before[0] = req[0].any();
-    for (size_t j = 0; j < blk.size(); j++) {
-        const Blk &B = blk[j];
-        before[j + 1] = before[j] || req[B.li].any() || req[B.li + 1].any() || (B.down && req[B.li + 2].any());
-    }
-    if (!before[blk.size()]) return TCSFM_OK;
-    float *dz2 = dn->gA, *dz1 = dn->gB, *nx = dn->gC;
-    const Blk &last = blk.back();
-    const DnLayer &l4 = dn->L[last.li + 1];
-    dnb_ew(dn, N, l4.cout, l4.oh, l4.ow, dsk[4], nullptr, t.at(last.out_e, i0), DN_ACT_RELU, dz2);
-    for (int j = (int)blk.size() - 1; j >= 0; j--) {
-        const Blk &B = blk[j];
-        const float *hin = t.at(B.h_e, i0), *t1 = t.at(B.t1_e, i0);
-        const int c1 = B.li, c2 = B.li + 1, ds = B.li + 2;
-        if (req[c2].any()) dnb_wgrad(dn, c2, N, dz2, t1, req[c2].wneed(), req[c2].bneed(), accumulate);
-        if (B.down && req[ds].any()) dnb_wgrad(dn, ds, N, dz2, hin, req[ds].wneed(), req[ds].bneed(), accumulate);
-        if (!(req[c1].any() || before[j])) break;
-        dnb_dgrad(dn, c2, N, dz2, dz1, true, nullptr, nullptr, t1, DN_ACT_RELU);
-        if (req[c1].any()) dnb_wgrad(dn, c1, N, dz1, hin, req[c1].wneed(), req[c1].bneed(), accumulate);
-        if (!before[j]) break;
-        if (B.down) dnb_dgrad(dn, ds, N, dz2, dn->gD, true, nullptr, nullptr, nullptr, DN_ACT_NONE);
-        const bool pool_in = j == 0;
-        dnb_dgrad(dn, c1, N, dz1, nx, true, B.down ? dn->gD : dz2, B.skip_in >= 0 ? dsk[B.skip_in] : nullptr, hin,
-                  pool_in ? DN_ACT_NONE : DN_ACT_RELU);
-        std::swap(dz2, nx);
-    }
-    if (req[0].any()) {
-        // dz2 holds the pooled map's gradient: max-pool backward + skip 0 + ReLU, then conv1's weight gradient from the images
-        const DnLayer &c1 = dn->L[0];
-        const long long thr = (long long)N * c1.oh * c1.ow * 16;
-        hipLaunchKernelGGL(k_dnb_maxpool, dim3(dn_blocks(thr)), dim3(256), 0, h->stream, (const float *)t.at(1, i0), (const float *)dz2, dsk[0], nx, N, 64,
-                           c1.oh, c1.ow, c1.oh / 2, c1.ow / 2);
-        dnb_wgrad(dn, 0, N, nx, t.at(0, i0), req[0].wneed(), req[0].bneed(), accumulate);
-    }
-    HIPCHK(h, hipGetLastError());
-    return TCSFM_OK;
-}
-
-int dn_check_train(tcsfm_depthnet *dn, int N, const char *fn) {
-    tcsfm_ctx *h = dn->h;
-    if (!dn->train_loaded) { h->err = std::string(fn) + ": no parameters loaded with tcsfm_depthnet_load_device"; return TCSFM_E_ARG; }
-    if (N < 1) { h->err = std::string(fn) + ": N out of range"; return TCSFM_E_ARG; }
-    return TCSFM_OK;
-}
-
-// skip k of images [i0, ...) inside a caller's NHWC skip tensor of N images
-template <typename P>
-P dn_skip_at(const tcsfm_depthnet *dn, P base, int k, int i0) {
-    return base ? base + (size_t)i0 * (((size_t)dn->h->H * dn->h->W) >> (2 * (k + 1))) * DN_SKIP_C[k] : nullptr;
-}
-}  // namespace
-
-extern "C" {
-
-int tcsfm_depthnet_load_device(tcsfm_depthnet *dn, int n, const char *const names[], const float *const dev_ptrs[], const int64_t *shapes) {
-    if (!dn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = dn->h;
-    std::vector<DnSrc> src;
-    const float *pw = nullptr, *pb = nullptr;
-    if (int rc = dn_lookup(dn, "tcsfm_depthnet_load_device", n, names, dev_ptrs, shapes, src, &pw, &pb)) return rc;
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    if (int rc = dn_train_alloc(dn)) return rc;
-    hipStream_t s = h->stream;
-    for (size_t li = 0; li < dn->L.size(); li++) {
-        DnLayer &l = dn->L[li];
-        const DnSrc &p = src[li];
-        float *v = l.raw + l.nw();
-        HIPCHK(h, hipMemcpyAsync(l.raw, p.w, l.nw() * sizeof(float), hipMemcpyDeviceToDevice, s));
-        const float *vs[5] = {p.cb, p.g, p.be, p.rm, p.rv};
-        for (int k = 0; k < 5; k++)
-            if (vs[k]) HIPCHK(h, hipMemcpyAsync(v + (size_t)k * l.cout, vs[k], l.cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-        const bool bn = p.g != nullptr;
-        hipLaunchKernelGGL(k_dnb_fold_params, dim3(dn_blocks((long long)l.nw())), dim3(256), 0, s, (const float *)l.raw, p.cb ? (const float *)v : nullptr,
-                           bn ? (const float *)v + l.cout : nullptr, (const float *)v + 2 * l.cout, (const float *)v + 3 * l.cout,
-                           (const float *)v + 4 * l.cout, l.w4, l.wt4, l.bias, l.cout, l.cin, l.ks, l.coutp);
-    }
-    HIPCHK(h, hipMemcpyAsync(dn->pw, pw, 72 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(dn->pb, pb, sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIPCHK(h, hipGetLastError());
-    dn->loaded = 1;
-    dn->train_loaded = 1;
-    return TCSFM_OK;
-}
-
-int tcsfm_depthnet_tape_size(tcsfm_depthnet *dn, int N, int64_t *enc_floats, int64_t *dec_floats) {
-    if (!dn) return TCSFM_E_ARG;
-    if (N < 1 || !enc_floats || !dec_floats) return fail(dn->h, TCSFM_E_ARG, "tcsfm_depthnet_tape_size: bad argument");
-    DnTape t;
-    dn_tape_layout(dn, 0, N, nullptr, t);
-    *enc_floats = (int64_t)t.total();
-    dn_tape_layout(dn, 1, N, nullptr, t);
-    *dec_floats = (int64_t)t.total();
-    return TCSFM_OK;
-}
-
-int tcsfm_depthnet_encode_train(tcsfm_depthnet *dn, int N, const float *imgs, float *const skips_out[5], float *tape) {
-    if (!dn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = dn->h;
-    if (int rc = dn_check_train(dn, N, "tcsfm_depthnet_encode_train")) return rc;
-    if (!imgs || !skips_out || !tape) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode_train: NULL argument");
-    for (int k = 0; k < 5; k++) if (!skips_out[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode_train: NULL skip buffer");
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    DnTape t;
-    dn_tape_layout(dn, 0, N, tape, t);
-    const size_t hw = (size_t)h->H * h->W;
-    for (int i0 = 0; i0 < N; i0 += dn->max_images) {
-        const int n = std::min(N - i0, dn->max_images);
-        float *sk[5];
-        for (int k = 0; k < 5; k++) sk[k] = dn_skip_at(dn, skips_out[k], k, i0);
-        if (int rc = dn_encode_train(dn, n, imgs + (size_t)i0 * 3 * hw, t, i0, sk)) return rc;
-    }
-    return TCSFM_OK;
-}
-
-int tcsfm_depthnet_decode_train(tcsfm_depthnet *dn, int N, const float *const skips_in[5], float *disp_out, float *tape) {
-    if (!dn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = dn->h;
-    if (int rc = dn_check_train(dn, N, "tcsfm_depthnet_decode_train")) return rc;
-    if (!skips_in || !disp_out || !tape) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode_train: NULL argument");
-    for (int k = 0; k < 5; k++) if (!skips_in[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode_train: NULL skip buffer");
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    DnTape t;
-    dn_tape_layout(dn, 1, N, tape, t);
-    const size_t hw = (size_t)h->H * h->W;
-    for (int i0 = 0; i0 < N; i0 += dn->max_images) {
-        const int n = std::min(N - i0, dn->max_images);
-        const float *sk[5];
-        for (int k = 0; k < 5; k++) sk[k] = dn_skip_at(dn, skips_in[k], k, i0);
-        if (int rc = dn_decode_train(dn, n, sk, disp_out + (size_t)i0 * hw, t, i0)) return rc;
-    }
-    return TCSFM_OK;
-}
-
-int tcsfm_depthnet_decode_backward(tcsfm_depthnet *dn, int N, const float *tape, const float *d_disp, float *const d_skips[5], int n_grads,
-                                   const char *const names[], float *const grads[]) {
-    if (!dn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = dn->h;
-    const char *fn = "tcsfm_depthnet_decode_backward";
-    if (int rc = dn_check_train(dn, N, fn)) return rc;
-    if (!tape || !d_disp) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode_backward: NULL argument");
-    std::vector<DnReq> req;
-    float *hw_ = nullptr, *hb_ = nullptr;
-    if (int rc = dn_requests(dn, fn, true, n_grads, names, grads, req, &hw_, &hb_)) return rc;
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    DnTape t;
-    dn_tape_layout(dn, 1, N, const_cast<float *>(tape), t);
-    const size_t hw = (size_t)h->H * h->W;
-    for (int i0 = 0; i0 < N; i0 += dn->max_images) {
-        const int n = std::min(N - i0, dn->max_images);
-        float *dsk[5];
-        for (int k = 0; k < 5; k++) dsk[k] = d_skips ? dn_skip_at(dn, d_skips[k], k, i0) : nullptr;
-        if (int rc = dn_decode_backward(dn, n, t, i0, d_disp + (size_t)i0 * hw, dsk, req, hw_ || hb_, i0 > 0)) return rc;
-    }
-    dn_param_out(dn, req, dn->enc_end, (int)dn->L.size());
-    if (hw_) HIPCHK(h, hipMemcpyAsync(hw_, dn->hacc, 72 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    if (hb_) HIPCHK(h, hipMemcpyAsync(hb_, dn->hacc + 72, sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipGetLastError());
-    return TCSFM_OK;
-}
-
-int tcsfm_depthnet_encode_backward(tcsfm_depthnet *dn, int N, const float *tape, const float *const d_skips[5], int n_grads,
-                                   const char *const names[], float *const grads[]) {
-    if (!dn) return TCSFM_E_ARG;
-    tcsfm_ctx *h = dn->h;
-    const char *fn = "tcsfm_depthnet_encode_backward";
-    if (int rc = dn_check_train(dn, N, fn)) return rc;
-    if (!tape) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode_backward: NULL argument");
-    std::vector<DnReq> req;
-    float *hw_ = nullptr, *hb_ = nullptr;
-    if (int rc = dn_requests(dn, fn, false, n_grads, names, grads, req, &hw_, &hb_)) return rc;
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    DnTape t;
-    dn_tape_layout(dn, 0, N, const_cast<float *>(tape), t);
-    for (int i0 = 0; i0 < N; i0 += dn->max_images) {
-        const int n = std::min(N - i0, dn->max_images);
-        const float *dsk[5];
-        for (int k = 0; k < 5; k++) dsk[k] = d_skips ? dn_skip_at(dn, d_skips[k], k, i0) : nullptr;
-        if (int rc = dn_encode_backward(dn, n, t, i0, dsk, req, i0 > 0)) return rc;
-    }
-    dn_param_out(dn, req, 0, dn->enc_end);
-    HIPCHK(h, hipGetLastError());
-    return TCSFM_OK;
-}
+#include "depthnet_host.h"
 
 void tcsfm_pose_to_matrix(const double pose[6], double T[12]) { tc::pose_to_T(pose, T); }
 void tcsfm_matrix_to_pose(const double T[12], double pose[6]) { tc::T_to_pose(T, pose); }
@@ -4074,5 +2886,3 @@ void tcsfm_se3_exp(const double xi[6], double T[12]) { tc::se3_exp(xi, T); }
 void tcsfm_se3_log(const double T[12], double xi[6]) { tc::se3_log(T, xi); }
 void tcsfm_se3_mul(const double A[12], const double B[12], double C[12]) { tc::se3_mul(A, B, C); }
 void tcsfm_se3_inv(const double A[12], double B[12]) { tc::se3_inv(A, B); }
-
-}  // extern "C"

@@ -37,6 +37,18 @@ def is_reference_depthnet(module) -> bool:
             and "feature_convs.1.0.conv.weight" not in sd and tuple(sd["predict_disps.0.0.conv.weight"].shape) == (1, 8, 3, 3))
 
 
+def named_table(named):
+    """the library's by-name tables from [(name, contiguous float32 torch tensor or numpy array)]: (n, names, pointers, shapes [n,4]
+    int64, zero-padded), the last three as void pointers that keep their arrays alive"""
+    n = len(named)
+    names = (C.c_char_p * max(n, 1))(*[k.encode() for k, _ in named])
+    ptrs = (C.c_void_p * max(n, 1))(*[a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data for _, a in named])
+    shapes = np.zeros((max(n, 1), 4), dtype=np.int64)
+    for i, (_, a) in enumerate(named):
+        shapes[i, :a.ndim] = a.shape
+    return n, C.cast(names, C.c_void_p), C.cast(ptrs, C.c_void_p), shapes.ctypes.data_as(C.c_void_p)
+
+
 class DepthNetHIP:
     """depth_model.forward on the engine's GPU.  `params`: a reference depth_model (nn.Module) or its state_dict / a dict of numpy
     arrays under the same names.  Calls with more than max_images images run in chunks (an image's result does not depend on the
@@ -73,24 +85,16 @@ class DepthNetHIP:
 
     def load(self, params):
         sd = params.state_dict() if hasattr(params, "state_dict") else params
-        names, keep = [], []
+        named = []
         for k, v in sd.items():
             if k.endswith("num_batches_tracked") or k.startswith("fc.") or ".fc." in k:
                 continue
             a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
             if a.ndim > 4:
                 raise ValueError(f"{k}: {a.ndim}-dimensional tensor")
-            names.append(k.encode())
-            keep.append(np.ascontiguousarray(a, dtype=np.float32))
-        n = len(names)
-        cnames = (C.c_char_p * max(n, 1))(*names)
-        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in keep])
-        shapes = np.zeros((max(n, 1), 4), dtype=np.int64)
-        for i, a in enumerate(keep):
-            shapes[i, :a.ndim] = a.shape
+            named.append((k, np.ascontiguousarray(a, dtype=np.float32)))
         self.eng._bind()
-        self.eng._call(self.lib.tcsfm_depthnet_load(self._dn, n, C.cast(cnames, C.c_void_p), C.cast(ptrs, C.c_void_p),
-                                                    shapes.ctypes.data_as(C.c_void_p)))
+        self.eng._call(self.lib.tcsfm_depthnet_load(self._dn, *named_table(named)))
         return self
 
     def load_checkpoint(self, path: str, load_best: bool = True):

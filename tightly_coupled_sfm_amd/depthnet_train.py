@@ -10,7 +10,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .depthnet import SKIP_CHANNELS, DepthNetHIP
+from .depthnet import SKIP_CHANNELS, DepthNetHIP, named_table
 
 _ENC = "encoder.encoder."
 _PLANES = [512, 256, 128, 64, 64, 32]
@@ -74,25 +74,16 @@ class _Native:
 
     def load(self, named):
         """named: [(name, contiguous float32 device tensor)]"""
-        n = len(named)
-        names = (C.c_char_p * n)(*[k.encode() for k, _ in named])
-        ptrs = (C.c_void_p * n)(*[t.data_ptr() for _, t in named])
-        shapes = np.zeros((n, 4), dtype=np.int64)
-        for i, (_, t) in enumerate(named):
-            shapes[i, :t.dim()] = t.shape
         self.eng._bind()
-        self.eng._call(self.lib.tcsfm_depthnet_load_device(self.dn, n, C.cast(names, C.c_void_p), C.cast(ptrs, C.c_void_p),
-                                                           shapes.ctypes.data_as(C.c_void_p)))
+        self.eng._call(self.lib.tcsfm_depthnet_load_device(self.dn, *named_table(named)))
 
     @staticmethod
     def ptrs(ts):
         return (C.c_void_p * len(ts))(*[(t.data_ptr() if t is not None else None) for t in ts])
 
     def grads_call(self, fn, N, pre_args, named_out):
-        names = (C.c_char_p * max(1, len(named_out)))(*[k.encode() for k, _ in named_out])
-        outs = (C.c_void_p * max(1, len(named_out)))(*[t.data_ptr() for _, t in named_out])
         self.eng._bind()
-        self.eng._call(fn(self.dn, N, *pre_args, len(named_out), C.cast(names, C.c_void_p), C.cast(outs, C.c_void_p)))
+        self.eng._call(fn(self.dn, N, *pre_args, *named_table(named_out)[:3]))
 
 
 def _check_stamp(ctx):
