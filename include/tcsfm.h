@@ -173,6 +173,16 @@ int tcsfm_smooth_loss(tcsfm_handle h, const tcsfm_opts *o, int N, const float *d
 int tcsfm_warp(tcsfm_handle h, const tcsfm_opts *o, int N, const float *src, const float *depth_t, const float *depth_s,
                const float *pose, const float *K, float *img_rec, float *valid, float *proj_depth, float *comp_depth);
 
+/* backward of tcsfm_warp (models/stn.py:234-273 under autograd): the inputs of tcsfm_warp and the cotangents of img_rec, proj_depth and
+ * comp_depth (each may be NULL = zero) -> the gradients with respect to depth_t, depth_s [N,1,H,W] and to THIS call's `pose` argument
+ * [N,6] (each may be NULL = not wanted; what is not wanted is not computed).  `valid` is not differentiable; the image and the
+ * intrinsics take no gradient.  Every requested output is fully written (zeros where nothing flows) and is bit-reproducible: the
+ * bilinear cell, the out-of-range sentinel and the Z clamp are recomputed exactly as tcsfm_warp takes them. */
+int tcsfm_warp_backward(tcsfm_handle h, const tcsfm_opts *o, int N,
+        const float *src, const float *depth_t, const float *depth_s, const float *pose, const float *K,
+        const float *g_rec, const float *g_proj_depth, const float *g_comp_depth,
+        float *d_depth_t, float *d_depth_s, float *d_pose);
+
 /* The coupled-iteration input assembly of solve_pose_iteratively, train_mono.py:73-77, fused into the warp:
  * posenet_in [N,6,H,W] = (tgt * valid_mask, img_rec) for the next PoseNet call; valid [N,1,H,W] optional. */
 int tcsfm_warp_posenet_input(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *src, const float *depth_t,

@@ -117,6 +117,7 @@ _SIGNATURES = {
     "tcsfm_smooth_loss": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P]),
     "tcsfm_ssim": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P]),
     "tcsfm_warp": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 9),
+    "tcsfm_warp_backward": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 11),
     "tcsfm_warp_posenet_input": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 8),
     "tcsfm_photometric": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 12),
     "tcsfm_loss_surface": (C.c_int, [_P, C.POINTER(Opts)] + [_P] * 5 + [C.c_int, _P, _P]),

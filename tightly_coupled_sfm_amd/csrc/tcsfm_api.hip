@@ -19,6 +19,7 @@
 #include "posenet_kernel.h"
 #include "depthnet_kernel.h"
 #include "depthnet_grad_kernel.h"
+#include "warp_grad_kernel.h"
 
 using namespace tc;
 
@@ -127,6 +128,11 @@ struct tcsfm_ctx {
     hipStream_t aux_stream = nullptr;  // joint dense mode: the inverse pairs' refinement runs beside the forward group's (fork / join by events)
     hipEvent_t aux_fork = nullptr, aux_join = nullptr;
     float *sel_maps = nullptr;   // dense window modes: the forward pairs' diff | valid maps, [2][max_pairs][H*W], allocated on first use
+    // tcsfm_warp_backward (warp_grad_kernel.h), allocated on first use: workgroup records of the pose gradient [max_pairs][blocks][12],
+    // fixed-point scatter sums [max_pairs][H*W], per-item max |g_proj_depth| (bit patterns)
+    double *wgrad_rec = nullptr;
+    long long *wgrad_fix = nullptr;
+    unsigned *wgrad_gmax = nullptr;
     unsigned *scale_keys = nullptr, *scale_hist = nullptr;   // scale recovery scratch (keys, 256 bins + 4 state words)
     long long *dbg_stamps = nullptr;  // TCSFM_DEBUG_STAMPS=1: 8 wall-clock stamps of the last k_solve launch (100 MHz ticks)
     std::vector<HostStage> stage;
@@ -1366,7 +1372,7 @@ void tcsfm_destroy(tcsfm_handle h) {
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
     void *ptrs[] = {h->stamp_buf, h->tgtpack, h->srcpack, h->depth_work, h->partials, h->blockrec, h->tickets, h->state, h->pconst, h->lin_out,
                     h->jrec, h->jrec_acc, h->jblockrec, h->jdepth_acc, h->jstate, h->jdelta, h->jpart, h->jtick, h->dref_norms, h->dref_ext, h->dref_export, h->qres_rho, h->qres_rec, h->pose_lin, h->dref_smooth, h->jrec_src, h->jstate_src, h->jdelta_src, h->dref_ext_src, h->qres_rho_src, h->qres_rec_src,
-                    h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept, h->dbg_stamps,
+                    h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept, h->dbg_stamps, h->wgrad_rec, h->wgrad_fix, h->wgrad_gmax,
                     h->seq_fpack, h->seq_fdepth, h->pair_idx, h->seq_img, h->seq_depth, h->seq_pose_in, h->seq_pose_out, h->seq_ls_out, h->seq_K, h->seq_dense, h->seq_dense_tmp};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -1485,6 +1491,55 @@ int tcsfm_warp_posenet_input(tcsfm_handle h, const tcsfm_opts *o, int N, const f
     P.win_B = 0; P.win_S = 0;
     hipLaunchKernelGGL(k_warp, dim3((unsigned)((hw + 255) / 256), N), dim3(256), 0, h->stream, P);
     HIPCHK(h, hipGetLastError());
+    return st.finish();
+}
+
+int tcsfm_warp_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const float *src, const float *depth_t, const float *depth_s,
+                        const float *pose, const float *K, const float *g_rec, const float *g_proj_depth, const float *g_comp_depth,
+                        float *d_depth_t, float *d_depth_s, float *d_pose) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    int rc = check_common(h, o, N);
+    if (rc) return rc;
+    if (!src || !depth_t || !depth_s || !pose || !K) return fail(h, TCSFM_E_ARG, "tcsfm_warp_backward: NULL input");
+    Staging st(h, o);
+    if (st.rc) return st.rc;
+    if ((rc = check_intrinsics(h, o, K, N))) return rc;
+    if (o->depth_is_disp) return fail(h, TCSFM_E_ARG, "tcsfm_warp_backward takes depth maps (call tcsfm_disp_to_depth first)");
+    const size_t hw = (size_t)h->H * h->W;
+    const unsigned nblk = (unsigned)((hw + 255) / 256);
+    const float *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
+    const float *d_pose_in = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
+    const float *d_grec = st.in(g_rec, N * 3 * hw), *d_gpd = st.in(g_proj_depth, N * hw), *d_gcd = st.in(g_comp_depth, N * hw);
+    float *o_dt = st.out(d_depth_t, N * hw), *o_ds = st.out(d_depth_s, N * hw), *o_pose = st.out(d_pose, (size_t)N * 6);
+    if (st.rc) return st.rc;
+    if (!o_dt && !o_ds && !o_pose) return st.finish();
+    if (o_pose && !h->wgrad_rec) HIPCHK(h, hipMalloc((void **)&h->wgrad_rec, (size_t)h->max_pairs * nblk * 12 * sizeof(double)));
+    if (o_ds && d_gpd && !h->wgrad_fix) HIPCHK(h, hipMalloc((void **)&h->wgrad_fix, (size_t)h->max_pairs * hw * sizeof(long long)));
+    if (o_ds && d_gpd && !h->wgrad_gmax) HIPCHK(h, hipMalloc((void **)&h->wgrad_gmax, (size_t)h->max_pairs * sizeof(unsigned)));
+    const dim3 grid(nblk, N);
+    if (o_ds && !d_gpd) HIPCHK(h, hipMemsetAsync(o_ds, 0, N * hw * sizeof(float), h->stream));      // nothing flows into the source depth
+    if (!o_dt && !o_pose && !(o_ds && d_gpd)) return st.finish();                                   // ... and nothing else is wanted: no kernel at all
+    if ((rc = run_init(h, o, N, d_pose_in, nullptr, d_K, 0))) return rc;
+    if (o_ds && d_gpd) {
+        int lg_hw = 0;
+        while (((size_t)1 << lg_hw) < hw) lg_hw++;
+        HIPCHK(h, hipMemsetAsync(h->wgrad_fix, 0, N * hw * sizeof(long long), h->stream));
+        HIPCHK(h, hipMemsetAsync(h->wgrad_gmax, 0, (size_t)N * sizeof(unsigned), h->stream));
+        hipLaunchKernelGGL(k_warp_gmax, grid, dim3(256), 0, h->stream, d_gpd, h->wgrad_gmax, (int)hw);
+        WarpScatterParams S;
+        S.depth_t = d_dt; S.pc = h->pconst; S.g_pd = d_gpd; S.gmax = h->wgrad_gmax; S.fix = h->wgrad_fix; S.H = h->H; S.W = h->W; S.lg_hw = lg_hw;
+        hipLaunchKernelGGL(k_warp_scatter, grid, dim3(256), 0, h->stream, S);
+        hipLaunchKernelGGL(k_warp_fix_out, grid, dim3(256), 0, h->stream, (const long long *)h->wgrad_fix, (const unsigned *)h->wgrad_gmax, o_ds, (int)hw, lg_hw);
+        HIPCHK(h, hipGetLastError());
+    }
+    if (o_dt || o_pose) {
+        WarpGradParams P;
+        P.src = d_src; P.depth_t = d_dt; P.depth_s = d_ds; P.pc = h->pconst; P.st = h->state; P.g_rec = d_grec; P.g_pd = d_gpd; P.g_cd = d_gcd;
+        P.d_depth_t = o_dt; P.blockrec = o_pose ? h->wgrad_rec : nullptr; P.H = h->H; P.W = h->W;
+        hipLaunchKernelGGL(k_warp_bwd, grid, dim3(256), 0, h->stream, P);
+        if (o_pose) hipLaunchKernelGGL(k_warp_pose_tail, dim3(N), dim3(64), 0, h->stream, (const double *)h->wgrad_rec, (int)nblk, d_pose_in, d_K, o_pose);
+        HIPCHK(h, hipGetLastError());
+    }
     return st.finish();
 }
 

@@ -200,6 +200,29 @@ class Engine:
                                        self._p(intrinsics), self._p(rec), self._p(valid), self._p(pd), self._p(cd)))
         return rec, valid, pd, cd
 
+    def inverse_warp2_backward(self, img, depth, ref_depth, pose, intrinsics, g_rec=None, g_pd=None, g_cd=None, want=(True, True, True)):
+        """backward of inverse_warp2 (tcsfm_warp_backward): the forward's arguments, the cotangents of the reconstruction, the
+        projected and the computed depth (None = zero) -> (d_depth, d_ref_depth, d_pose), None where ``want`` is False.  ``pose``
+        and d_pose are in the reference's convention, as in inverse_warp2.  No gradient exists for img and intrinsics."""
+        self._bind()
+        N = img.shape[0]
+        H, W = self.H, self.W
+        img = _chk(img, (N, 3, H, W), "img"); depth = _chk(depth, (N, 1, H, W), "depth")
+        ref_depth = _chk(ref_depth, (N, 1, H, W), "ref_depth"); intrinsics = _chk(intrinsics, (N, 3, 3), "intrinsics")
+        pose6 = _chk(pose[:, 0:6].contiguous(), (N, 6), "pose")
+        neg = (-pose6).contiguous()
+        g_rec = None if g_rec is None else _chk(g_rec, (N, 3, H, W), "g_rec")
+        g_pd = None if g_pd is None else _chk(g_pd, (N, 1, H, W), "g_pd")
+        g_cd = None if g_cd is None else _chk(g_cd, (N, 1, H, W), "g_cd")
+        d_depth = torch.empty_like(depth) if want[0] else None
+        d_ref = torch.empty_like(ref_depth) if want[1] else None
+        d_neg = torch.empty_like(neg) if want[2] else None
+        o = default_opts()
+        self._call(self.lib.tcsfm_warp_backward(self._h, C.byref(o), N, self._p(img), self._p(depth), self._p(ref_depth), self._p(neg),
+                                                self._p(intrinsics), self._p(g_rec), self._p(g_pd), self._p(g_cd),
+                                                self._p(d_depth), self._p(d_ref), self._p(d_neg)))
+        return d_depth, d_ref, (None if d_neg is None else -d_neg)     # the ABI's pose is -pose: so is its gradient
+
     def posenet_input(self, target_img, source_img, target_depth, source_depth, pose, intrinsics):
         """(tgt * valid | img_rec) [N,6,H,W] for the next PoseNet call of the coupled iteration (train_mono.py:73-77);
         `pose` is the estimate so far in the reference convention (the warp uses -pose like train_mono.py:80)."""
