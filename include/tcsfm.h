@@ -183,6 +183,27 @@ int tcsfm_warp_backward(tcsfm_handle h, const tcsfm_opts *o, int N,
         const float *g_rec, const float *g_proj_depth, const float *g_comp_depth,
         float *d_depth_t, float *d_depth_s, float *d_pose);
 
+/* backward of the residual assembly behind tcsfm_photometric's differentiable outputs (train_mono.py:84-92, helpers.py:8-23 under
+ * autograd), the kernel alone:  diff = mean_c(w_l1 clamp|rec - tgt| + w_ssim SSIM(tgt, rec)),  weight = 1 - clamp(|cd - pd| / (cd + pd)).
+ * tgt, img_rec [N,3,H,W], proj_depth, comp_depth [N,1,H,W] and the cotangents of diff and weight [N,1,H,W] (each may be NULL = zero)
+ * -> the gradients with respect to img_rec, proj_depth and comp_depth (each may be NULL = not wanted).  A requested output is fully
+ * written; without the cotangent that feeds it, it is zeroed and no kernel is launched.  torch's conventions: sgn(0) = 0, a clamp
+ * passes its gradient on the closed interval.  One gather kernel, no atomics: bit-reproducible.  w_l1, w_ssim from opts. */
+int tcsfm_photometric_maps_backward(tcsfm_handle h, const tcsfm_opts *o, int N,
+        const float *tgt, const float *img_rec, const float *proj_depth, const float *comp_depth,
+        const float *g_diff, const float *g_weight,
+        float *g_rec, float *g_proj_depth, float *g_comp_depth);
+
+/* backward of tcsfm_photometric's differentiable outputs: its inputs and the cotangents of diff, weight [N,1,H,W] and img_rec
+ * [N,3,H,W] (each may be NULL = zero) -> the gradients with respect to depth_t, depth_s [N,1,H,W] and to THIS call's `pose` argument
+ * [N,6] (the reference's convention, as in tcsfm_photometric; each may be NULL = not wanted).  The warp is run forward into the handle's
+ * scratch, then the assembly's backward, then the launches of tcsfm_warp_backward.  The masks, the images and the intrinsics take no
+ * gradient; opts.depth_is_disp is refused as in tcsfm_warp_backward.  Bit-reproducible. */
+int tcsfm_photometric_backward(tcsfm_handle h, const tcsfm_opts *o, int N,
+        const float *tgt, const float *src, const float *depth_t, const float *depth_s, const float *pose, const float *K,
+        const float *g_diff, const float *g_weight, const float *g_img_rec,
+        float *d_depth_t, float *d_depth_s, float *d_pose);
+
 /* The coupled-iteration input assembly of solve_pose_iteratively, train_mono.py:73-77, fused into the warp:
  * posenet_in [N,6,H,W] = (tgt * valid_mask, img_rec) for the next PoseNet call; valid [N,1,H,W] optional. */
 int tcsfm_warp_posenet_input(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *src, const float *depth_t,

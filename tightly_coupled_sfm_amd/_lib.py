@@ -120,6 +120,8 @@ _SIGNATURES = {
     "tcsfm_warp_backward": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 11),
     "tcsfm_warp_posenet_input": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 8),
     "tcsfm_photometric": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 12),
+    "tcsfm_photometric_maps_backward": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 9),
+    "tcsfm_photometric_backward": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 12),
     "tcsfm_loss_surface": (C.c_int, [_P, C.POINTER(Opts)] + [_P] * 5 + [C.c_int, _P, _P]),
     "tcsfm_linearize": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 10),
     "tcsfm_linearize_window": (C.c_int, [_P, C.POINTER(Opts), C.c_int, C.c_int] + [_P] * 10),

@@ -18,6 +18,8 @@
 //                   constants of the next iteration.
 //   k_warp        inverse_warp2 drop-in (stn.py:234-273), planar in / planar out (+ the next PoseNet input, train_mono.py:73-77).
 //   k_warp_bwd, k_warp_pose_tail, k_warp_gmax, k_warp_scatter, k_warp_fix_out: the backward pass of k_warp (warp_grad_kernel.h).
+//   k_photo_bwd, k_warp_fwd64: the backward pass of the residual assembly (diff_img, weight_mask of tcsfm_photometric) and the warp
+//                   forward its chain starts from: photo_grad_kernel.h.
 //   k_ssim, k_disp_to_depth: SSIM_Loss / disp_to_depth drop-ins.  dense_kernel.h, scale_kernel.h: dense mode, DNet scale.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -20,6 +20,7 @@
 #include "depthnet_kernel.h"
 #include "depthnet_grad_kernel.h"
 #include "warp_grad_kernel.h"
+#include "photo_grad_kernel.h"
 
 using namespace tc;
 
@@ -133,6 +134,9 @@ struct tcsfm_ctx {
     double *wgrad_rec = nullptr;
     long long *wgrad_fix = nullptr;
     unsigned *wgrad_gmax = nullptr;
+    // tcsfm_photometric_backward (photo_grad_kernel.h), allocated on first use: the warp's forward (img_rec | proj_depth | comp_depth) and
+    // the cotangents that reach it (g_rec | g_proj_depth | g_comp_depth), each [max_pairs][5][H*W]
+    float *pgrad_fwd = nullptr, *pgrad_cot = nullptr;
     unsigned *scale_keys = nullptr, *scale_hist = nullptr;   // scale recovery scratch (keys, 256 bins + 4 state words)
     long long *dbg_stamps = nullptr;  // TCSFM_DEBUG_STAMPS=1: 8 wall-clock stamps of the last k_solve launch (100 MHz ticks)
     std::vector<HostStage> stage;
@@ -1372,7 +1376,7 @@ void tcsfm_destroy(tcsfm_handle h) {
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
     void *ptrs[] = {h->stamp_buf, h->tgtpack, h->srcpack, h->depth_work, h->partials, h->blockrec, h->tickets, h->state, h->pconst, h->lin_out,
                     h->jrec, h->jrec_acc, h->jblockrec, h->jdepth_acc, h->jstate, h->jdelta, h->jpart, h->jtick, h->dref_norms, h->dref_ext, h->dref_export, h->qres_rho, h->qres_rec, h->pose_lin, h->dref_smooth, h->jrec_src, h->jstate_src, h->jdelta_src, h->dref_ext_src, h->qres_rho_src, h->qres_rec_src,
-                    h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept, h->dbg_stamps, h->wgrad_rec, h->wgrad_fix, h->wgrad_gmax,
+                    h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept, h->dbg_stamps, h->wgrad_rec, h->wgrad_fix, h->wgrad_gmax, h->pgrad_fwd, h->pgrad_cot,
                     h->seq_fpack, h->seq_fdepth, h->pair_idx, h->seq_img, h->seq_depth, h->seq_pose_in, h->seq_pose_out, h->seq_ls_out, h->seq_K, h->seq_dense, h->seq_dense_tmp};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -1494,32 +1498,22 @@ int tcsfm_warp_posenet_input(tcsfm_handle h, const tcsfm_opts *o, int N, const f
     return st.finish();
 }
 
-int tcsfm_warp_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const float *src, const float *depth_t, const float *depth_s,
-                        const float *pose, const float *K, const float *g_rec, const float *g_proj_depth, const float *g_comp_depth,
-                        float *d_depth_t, float *d_depth_s, float *d_pose) {
-    if (int rc_q = drain_queued(h)) return rc_q;
-    int rc = check_common(h, o, N);
-    if (rc) return rc;
-    if (!src || !depth_t || !depth_s || !pose || !K) return fail(h, TCSFM_E_ARG, "tcsfm_warp_backward: NULL input");
-    Staging st(h, o);
-    if (st.rc) return st.rc;
-    if ((rc = check_intrinsics(h, o, K, N))) return rc;
-    if (o->depth_is_disp) return fail(h, TCSFM_E_ARG, "tcsfm_warp_backward takes depth maps (call tcsfm_disp_to_depth first)");
+// The launches of the warp's backward on device pointers (shared by tcsfm_warp_backward and tcsfm_photometric_backward): cotangents may
+// be null (= zero), outputs may be null (= not wanted).  `inited`: run_init has already formed this call's pair constants.
+static int warp_backward_dev(tcsfm_ctx *h, const tcsfm_opts *o, int N, const float *d_src, const float *d_dt, const float *d_ds,
+                             const float *d_pose_in, const float *d_K, const float *d_grec, const float *d_gpd, const float *d_gcd,
+                             float *o_dt, float *o_ds, float *o_pose, bool inited) {
+    int rc;
     const size_t hw = (size_t)h->H * h->W;
     const unsigned nblk = (unsigned)((hw + 255) / 256);
-    const float *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
-    const float *d_pose_in = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
-    const float *d_grec = st.in(g_rec, N * 3 * hw), *d_gpd = st.in(g_proj_depth, N * hw), *d_gcd = st.in(g_comp_depth, N * hw);
-    float *o_dt = st.out(d_depth_t, N * hw), *o_ds = st.out(d_depth_s, N * hw), *o_pose = st.out(d_pose, (size_t)N * 6);
-    if (st.rc) return st.rc;
-    if (!o_dt && !o_ds && !o_pose) return st.finish();
+    if (!o_dt && !o_ds && !o_pose) return TCSFM_OK;
     if (o_pose && !h->wgrad_rec) HIPCHK(h, hipMalloc((void **)&h->wgrad_rec, (size_t)h->max_pairs * nblk * 12 * sizeof(double)));
     if (o_ds && d_gpd && !h->wgrad_fix) HIPCHK(h, hipMalloc((void **)&h->wgrad_fix, (size_t)h->max_pairs * hw * sizeof(long long)));
     if (o_ds && d_gpd && !h->wgrad_gmax) HIPCHK(h, hipMalloc((void **)&h->wgrad_gmax, (size_t)h->max_pairs * sizeof(unsigned)));
     const dim3 grid(nblk, N);
     if (o_ds && !d_gpd) HIPCHK(h, hipMemsetAsync(o_ds, 0, N * hw * sizeof(float), h->stream));      // nothing flows into the source depth
-    if (!o_dt && !o_pose && !(o_ds && d_gpd)) return st.finish();                                   // ... and nothing else is wanted: no kernel at all
-    if ((rc = run_init(h, o, N, d_pose_in, nullptr, d_K, 0))) return rc;
+    if (!o_dt && !o_pose && !(o_ds && d_gpd)) return TCSFM_OK;                                      // ... and nothing else is wanted: no kernel at all
+    if (!inited && (rc = run_init(h, o, N, d_pose_in, nullptr, d_K, 0))) return rc;
     if (o_ds && d_gpd) {
         int lg_hw = 0;
         while (((size_t)1 << lg_hw) < hw) lg_hw++;
@@ -1540,6 +1534,109 @@ int tcsfm_warp_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const float 
         if (o_pose) hipLaunchKernelGGL(k_warp_pose_tail, dim3(N), dim3(64), 0, h->stream, (const double *)h->wgrad_rec, (int)nblk, d_pose_in, d_K, o_pose);
         HIPCHK(h, hipGetLastError());
     }
+    return TCSFM_OK;
+}
+
+int tcsfm_warp_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const float *src, const float *depth_t, const float *depth_s,
+                        const float *pose, const float *K, const float *g_rec, const float *g_proj_depth, const float *g_comp_depth,
+                        float *d_depth_t, float *d_depth_s, float *d_pose) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    int rc = check_common(h, o, N);
+    if (rc) return rc;
+    if (!src || !depth_t || !depth_s || !pose || !K) return fail(h, TCSFM_E_ARG, "tcsfm_warp_backward: NULL input");
+    Staging st(h, o);
+    if (st.rc) return st.rc;
+    if ((rc = check_intrinsics(h, o, K, N))) return rc;
+    if (o->depth_is_disp) return fail(h, TCSFM_E_ARG, "tcsfm_warp_backward takes depth maps (call tcsfm_disp_to_depth first)");
+    const size_t hw = (size_t)h->H * h->W;
+    const float *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
+    const float *d_pose_in = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
+    const float *d_grec = st.in(g_rec, N * 3 * hw), *d_gpd = st.in(g_proj_depth, N * hw), *d_gcd = st.in(g_comp_depth, N * hw);
+    float *o_dt = st.out(d_depth_t, N * hw), *o_ds = st.out(d_depth_s, N * hw), *o_pose = st.out(d_pose, (size_t)N * 6);
+    if (st.rc) return st.rc;
+    if ((rc = warp_backward_dev(h, o, N, d_src, d_dt, d_ds, d_pose_in, d_K, d_grec, d_gpd, d_gcd, o_dt, o_ds, o_pose, false))) return rc;
+    return st.finish();
+}
+
+// k_photo_bwd on device pointers.  A requested output whose cotangent is absent is zeroed without a launch.
+static int photo_maps_backward_dev(tcsfm_ctx *h, const tcsfm_opts *o, int N, const float *d_tgt, const float *d_rec, const float *d_pd,
+                                   const float *d_cd, const float *d_gdiff, const float *d_gweight, const float *d_grec_add,
+                                   float *o_grec, float *o_gpd, float *o_gcd) {
+    const size_t hw = (size_t)h->H * h->W;
+    const bool rec_on = o_grec && d_gdiff, dep_on = (o_gpd || o_gcd) && d_gweight;
+    if (o_grec && !rec_on) HIPCHK(h, hipMemsetAsync(o_grec, 0, N * 3 * hw * sizeof(float), h->stream));
+    if (o_gpd && !dep_on) HIPCHK(h, hipMemsetAsync(o_gpd, 0, N * hw * sizeof(float), h->stream));
+    if (o_gcd && !dep_on) HIPCHK(h, hipMemsetAsync(o_gcd, 0, N * hw * sizeof(float), h->stream));
+    if (!rec_on && !dep_on) return TCSFM_OK;
+    PhotoGradParams P;
+    P.tgt = d_tgt; P.rec = d_rec; P.pd = d_pd; P.cd = d_cd;
+    P.g_diff = rec_on ? d_gdiff : nullptr; P.g_weight = dep_on ? d_gweight : nullptr; P.g_rec_add = d_grec_add;
+    P.g_rec = rec_on ? o_grec : nullptr; P.g_pd = dep_on ? o_gpd : nullptr; P.g_cd = dep_on ? o_gcd : nullptr;
+    P.H = h->H; P.W = h->W; P.wl = o->w_l1 / 3.f; P.ws = o->w_ssim / 3.f;
+    const dim3 grid((unsigned)((h->W + PG_TW - 1) / PG_TW), (unsigned)((h->H + PG_TH - 1) / PG_TH), (unsigned)N);
+    hipLaunchKernelGGL(k_photo_bwd, grid, dim3(256), 0, h->stream, P);
+    HIPCHK(h, hipGetLastError());
+    return TCSFM_OK;
+}
+
+int tcsfm_photometric_maps_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *img_rec, const float *proj_depth,
+                                    const float *comp_depth, const float *g_diff, const float *g_weight, float *g_rec, float *g_proj_depth,
+                                    float *g_comp_depth) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    int rc = check_common(h, o, N);
+    if (rc) return rc;
+    if (!tgt || !img_rec || !proj_depth || !comp_depth) return fail(h, TCSFM_E_ARG, "tcsfm_photometric_maps_backward: NULL input");
+    Staging st(h, o);
+    if (st.rc) return st.rc;
+    const size_t hw = (size_t)h->H * h->W;
+    const float *d_tgt = st.in(tgt, N * 3 * hw), *d_rec = st.in(img_rec, N * 3 * hw), *d_pd = st.in(proj_depth, N * hw), *d_cd = st.in(comp_depth, N * hw);
+    const float *d_gdiff = st.in(g_diff, N * hw), *d_gweight = st.in(g_weight, N * hw);
+    float *o_grec = st.out(g_rec, N * 3 * hw), *o_gpd = st.out(g_proj_depth, N * hw), *o_gcd = st.out(g_comp_depth, N * hw);
+    if (st.rc) return st.rc;
+    if ((rc = photo_maps_backward_dev(h, o, N, d_tgt, d_rec, d_pd, d_cd, d_gdiff, d_gweight, nullptr, o_grec, o_gpd, o_gcd))) return rc;
+    return st.finish();
+}
+
+int tcsfm_photometric_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *src, const float *depth_t,
+                               const float *depth_s, const float *pose, const float *K, const float *g_diff, const float *g_weight,
+                               const float *g_img_rec, float *d_depth_t, float *d_depth_s, float *d_pose) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    int rc = check_common(h, o, N);
+    if (rc) return rc;
+    if (!tgt || !src || !depth_t || !depth_s || !pose || !K) return fail(h, TCSFM_E_ARG, "tcsfm_photometric_backward: NULL input");
+    Staging st(h, o);
+    if (st.rc) return st.rc;
+    if ((rc = check_intrinsics(h, o, K, N))) return rc;
+    if (o->depth_is_disp) return fail(h, TCSFM_E_ARG, "tcsfm_photometric_backward takes depth maps (call tcsfm_disp_to_depth first)");
+    const size_t hw = (size_t)h->H * h->W;
+    const float *d_tgt = st.in(tgt, N * 3 * hw), *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
+    const float *d_pose_in = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
+    const float *d_gdiff = st.in(g_diff, N * hw), *d_gweight = st.in(g_weight, N * hw), *d_gimg = st.in(g_img_rec, N * 3 * hw);
+    float *o_dt = st.out(d_depth_t, N * hw), *o_ds = st.out(d_depth_s, N * hw), *o_pose = st.out(d_pose, (size_t)N * 6);
+    if (st.rc) return st.rc;
+    if (!o_dt && !o_ds && !o_pose) return st.finish();
+    // the cotangents that reach the warp: g_rec = (assembly's, from g_diff) + g_img_rec; g_proj_depth, g_comp_depth from g_weight
+    const float *w_grec = d_gimg, *w_gpd = nullptr, *w_gcd = nullptr;
+    bool inited = false;
+    if (d_gdiff || d_gweight) {
+        const size_t plane = (size_t)h->max_pairs * hw;
+        if (!h->pgrad_fwd) HIPCHK(h, hipMalloc((void **)&h->pgrad_fwd, 5 * plane * sizeof(float)));
+        if (!h->pgrad_cot) HIPCHK(h, hipMalloc((void **)&h->pgrad_cot, 5 * plane * sizeof(float)));
+        float *f_rec = h->pgrad_fwd, *f_pd = h->pgrad_fwd + 3 * plane, *f_cd = h->pgrad_fwd + 4 * plane;
+        float *c_rec = h->pgrad_cot, *c_pd = h->pgrad_cot + 3 * plane, *c_cd = h->pgrad_cot + 4 * plane;
+        if ((rc = run_init(h, o, N, d_pose_in, nullptr, d_K, 0))) return rc;
+        inited = true;
+        WarpFwd64Params P;
+        P.src = d_src; P.depth_t = d_dt; P.depth_s = d_ds; P.pc = h->pconst; P.st = h->state;
+        P.rec = d_gdiff ? f_rec : nullptr; P.pd = d_gweight ? f_pd : nullptr; P.cd = d_gweight ? f_cd : nullptr; P.H = h->H; P.W = h->W;
+        hipLaunchKernelGGL(k_warp_fwd64, dim3((unsigned)((hw + 255) / 256), N), dim3(256), 0, h->stream, P);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = photo_maps_backward_dev(h, o, N, d_tgt, f_rec, f_pd, f_cd, d_gdiff, d_gweight, d_gimg, d_gdiff ? c_rec : nullptr,
+                                          d_gweight ? c_pd : nullptr, d_gweight ? c_cd : nullptr))) return rc;
+        if (d_gdiff) w_grec = c_rec;
+        if (d_gweight) { w_gpd = c_pd; w_gcd = c_cd; }
+    }
+    if ((rc = warp_backward_dev(h, o, N, d_src, d_dt, d_ds, d_pose_in, d_K, w_grec, w_gpd, w_gcd, o_dt, o_ds, o_pose, inited))) return rc;
     return st.finish();
 }
 

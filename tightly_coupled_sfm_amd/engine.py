@@ -37,6 +37,29 @@ def _copy_opts(o: Opts) -> Opts:
     return c
 
 
+class _PhotometricError(torch.autograd.Function):
+    """Engine.compute_photometric_error under autograd: the same forward call, tcsfm_photometric_backward behind it
+    (Engine.compute_photometric_error_backward).  diff_img, weight_mask and img_rec are differentiable; every mask is not."""
+
+    @staticmethod
+    def forward(ctx, engine, opts, t, s, dt, ds, p, K):
+        diff, valid, weight, ae, am, rec = engine._photometric(t, s, dt, ds, p, K, opts)
+        ctx.engine, ctx.opts = engine, _copy_opts(opts)
+        ctx.save_for_backward(t, s, dt, ds, p, K)
+        valid_mask = am * valid
+        ctx.mark_non_differentiable(valid, ae, am, valid_mask)
+        ctx.set_materialize_grads(False)        # a cotangent autograd does not supply stays None: its path launches nothing
+        return diff, rec, weight, valid, ae, am, valid_mask
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_diff, g_rec, g_weight, *_masks):
+        t, s, dt, ds, p, K = ctx.saved_tensors
+        want = tuple(ctx.needs_input_grad[4:7])
+        d_dt, d_ds, d_p = ctx.engine.compute_photometric_error_backward(t, s, dt, ds, p, K, g_diff, g_weight, g_rec, want, ctx.opts)
+        return None, None, None, None, d_dt, d_ds, d_p, None
+
+
 class Engine:
     """One handle = one GPU + one HIP stream (include/tcsfm.h).  ``max_pairs`` directed pairs of HxW."""
 
@@ -238,9 +261,20 @@ class Engine:
                                                      self._p(K), self._p(out), None))
         return out
 
+    def _photometric(self, t, s, dt, ds, p, K, o):
+        N = t.shape[0]
+        diff, valid, weight, ae, am = (torch.empty_like(dt) for _ in range(5))
+        rec = torch.empty_like(t)
+        self._call(self.lib.tcsfm_photometric(self._h, C.byref(o), N, self._p(t), self._p(s), self._p(dt), self._p(ds), self._p(p),
+                                              self._p(K), self._p(diff), self._p(valid), self._p(weight), self._p(ae), self._p(am),
+                                              self._p(rec)))
+        return diff, valid, weight, ae, am, rec
+
     def compute_photometric_error(self, target_img, source_img, target_depth, source_depth, pose, intrinsics,
                                   opts: Optional[Opts] = None):
-        """optimization_experiments/helpers.py:8-23 -> dict with the reference's keys (+ the raw maps)."""
+        """optimization_experiments/helpers.py:8-23 -> dict with the reference's keys (+ the raw maps).  When grad is enabled and
+        target_depth, source_depth or pose requires grad, diff_img, weight_mask and img_rec carry a grad_fn (HIP backward kernels,
+        tcsfm_photometric_backward); the masks never do."""
         self._bind()
         N = target_img.shape[0]
         H, W = self.H, self.W
@@ -248,13 +282,61 @@ class Engine:
         dt = _chk(target_depth, (N, 1, H, W), "target_depth"); ds = _chk(source_depth, (N, 1, H, W), "source_depth")
         p = _chk(pose, (N, 6), "pose"); K = _chk(intrinsics, (N, 3, 3), "intrinsics")
         o = opts or default_opts()
-        diff, valid, weight, ae, am = (torch.empty_like(dt) for _ in range(5))
-        rec = torch.empty_like(t)
-        self._call(self.lib.tcsfm_photometric(self._h, C.byref(o), N, self._p(t), self._p(s), self._p(dt), self._p(ds), self._p(p),
-                                              self._p(K), self._p(diff), self._p(valid), self._p(weight), self._p(ae), self._p(am),
-                                              self._p(rec)))
-        return {"diff_img": diff, "img_rec": rec, "valid_mask": am * valid, "weight_mask": weight, "poses": pose,
+        if torch.is_grad_enabled() and any(x.requires_grad for x in (t, s, dt, ds, p, K)):
+            if t.requires_grad or s.requires_grad or K.requires_grad:
+                raise NotImplementedError("compute_photometric_error has no gradient with respect to the images or the intrinsics "
+                                          "(DESIGN.md section 7: gradients with respect to the images stay out of scope)")
+            if o.depth_is_disp:
+                raise NotImplementedError("compute_photometric_error is differentiable on depth maps only (apply disp_to_depth first)")
+            diff, rec, weight, valid, ae, am, valid_mask = _PhotometricError.apply(self, o, t, s, dt, ds, p, K)
+        else:
+            diff, valid, weight, ae, am, rec = self._photometric(t, s, dt, ds, p, K, o)
+            valid_mask = am * valid
+        return {"diff_img": diff, "img_rec": rec, "valid_mask": valid_mask, "weight_mask": weight, "poses": pose,
                 "warp_valid": valid, "auto_mask_error": ae, "auto_mask": am}
+
+    def photometric_maps_backward(self, target_img, img_rec, proj_depth, comp_depth, g_diff=None, g_weight=None, want=(True, True, True),
+                                  opts: Optional[Opts] = None):
+        """backward of the residual assembly alone (tcsfm_photometric_maps_backward): diff_img and weight_mask as functions of
+        (img_rec, projected depth, computed depth); the cotangents of the two maps (None = zero) -> (g_rec, g_proj_depth, g_comp_depth),
+        None where ``want`` is False."""
+        self._bind()
+        N = target_img.shape[0]
+        H, W = self.H, self.W
+        t = _chk(target_img, (N, 3, H, W), "target_img"); r = _chk(img_rec, (N, 3, H, W), "img_rec")
+        pd = _chk(proj_depth, (N, 1, H, W), "proj_depth"); cd = _chk(comp_depth, (N, 1, H, W), "comp_depth")
+        g_diff = None if g_diff is None else _chk(g_diff, (N, 1, H, W), "g_diff")
+        g_weight = None if g_weight is None else _chk(g_weight, (N, 1, H, W), "g_weight")
+        g_rec = torch.empty_like(r) if want[0] else None
+        g_pd = torch.empty_like(pd) if want[1] else None
+        g_cd = torch.empty_like(cd) if want[2] else None
+        o = opts or default_opts()
+        self._call(self.lib.tcsfm_photometric_maps_backward(self._h, C.byref(o), N, self._p(t), self._p(r), self._p(pd), self._p(cd),
+                                                            self._p(g_diff), self._p(g_weight), self._p(g_rec), self._p(g_pd), self._p(g_cd)))
+        return g_rec, g_pd, g_cd
+
+    def compute_photometric_error_backward(self, target_img, source_img, target_depth, source_depth, pose, intrinsics, g_diff=None,
+                                           g_weight=None, g_img_rec=None, want=(True, True, True), opts: Optional[Opts] = None):
+        """backward of compute_photometric_error (tcsfm_photometric_backward): the forward's arguments and the cotangents of diff_img,
+        weight_mask and img_rec (None = zero) -> (d_target_depth, d_source_depth, d_pose), None where ``want`` is False.  ``pose`` and
+        d_pose are in the reference's convention, as in compute_photometric_error."""
+        self._bind()
+        N = target_img.shape[0]
+        H, W = self.H, self.W
+        t = _chk(target_img, (N, 3, H, W), "target_img"); s = _chk(source_img, (N, 3, H, W), "source_img")
+        dt = _chk(target_depth, (N, 1, H, W), "target_depth"); ds = _chk(source_depth, (N, 1, H, W), "source_depth")
+        p = _chk(pose, (N, 6), "pose"); K = _chk(intrinsics, (N, 3, 3), "intrinsics")
+        g_diff = None if g_diff is None else _chk(g_diff, (N, 1, H, W), "g_diff")
+        g_weight = None if g_weight is None else _chk(g_weight, (N, 1, H, W), "g_weight")
+        g_img_rec = None if g_img_rec is None else _chk(g_img_rec, (N, 3, H, W), "g_img_rec")
+        d_dt = torch.empty_like(dt) if want[0] else None
+        d_ds = torch.empty_like(ds) if want[1] else None
+        d_p = torch.empty_like(p) if want[2] else None
+        o = opts or default_opts()
+        self._call(self.lib.tcsfm_photometric_backward(self._h, C.byref(o), N, self._p(t), self._p(s), self._p(dt), self._p(ds), self._p(p),
+                                                       self._p(K), self._p(g_diff), self._p(g_weight), self._p(g_img_rec),
+                                                       self._p(d_dt), self._p(d_ds), self._p(d_p)))
+        return d_dt, d_ds, d_p
 
     def loss_surface(self, target_img, source_img, target_depth, source_depth, intrinsics, poses, opts: Optional[Opts] = None):
         """costs of ONE pair under P candidate poses (plot_loss_surface.py:31-33,45-47) -> np.ndarray [P] float64"""

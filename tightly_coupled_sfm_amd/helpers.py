@@ -10,7 +10,9 @@ from .optimizer import avg_final_predictions, batch_post_process_disparity  # no
 
 
 def compute_photometric_error(target_img, source_img, target_depth, source_depth, pose, intrinsics):
-    """optimization_experiments/helpers.py:8-23 -> {'diff_img','img_rec','valid_mask' (validity x auto-mask),'weight_mask','poses'}"""
+    """optimization_experiments/helpers.py:8-23 -> {'diff_img','img_rec','valid_mask' (validity x auto-mask),'weight_mask','poses'}.
+    Differentiable with respect to target_depth, source_depth and pose (HIP backward kernels): diff_img, weight_mask and img_rec carry a
+    grad_fn when one of them requires grad; valid_mask never does; an image or intrinsics that require grad raise NotImplementedError."""
     N, _, H, W = target_img.shape
     r = get_engine(H, W, N).compute_photometric_error(target_img.float(), source_img.float(), target_depth.float(), source_depth.float(),
                                                       pose.float(), intrinsics.float())
