@@ -168,6 +168,32 @@ int tcsfm_ssim(tcsfm_handle h, const tcsfm_opts *o, int planes, const float *x, 
  * (options['l_smooth'], run_sequential_optimization.py:87); a logging quantity here, not a term of the Gauss-Newton cost. */
 int tcsfm_smooth_loss(tcsfm_handle h, const tcsfm_opts *o, int N, const float *disp, const float *img, double *loss_out);
 
+/* backward of disp_to_depth (utils/learning_helpers.py:77-86 under autograd, optimizer.py:241): scaled = a + b disp, depth = 1 / scaled,
+ * a = 1 / max_depth, b = 1 / min_depth - a.  The cotangents of scaled_disp and depth (a NULL one is absent and costs nothing; at least
+ * one must be given) -> g_disp = b (g_scaled - g_depth / scaled^2), n elements; `scaled` is recomputed as the forward forms it. */
+int tcsfm_disp_to_depth_backward(tcsfm_handle h, const tcsfm_opts *o, int64_t n, const float *disp, const float *g_scaled, const float *g_depth,
+        float *g_disp);
+
+/* backward of SSIM_Loss.forward (losses.py:27-41 under autograd; l_depth_init, optimizer.py:90): x, y and the cotangent of the output,
+ * `planes` images of H x W each -> the gradients with respect to x and to y (a NULL one is not wanted; at least one must be given).
+ * One gather kernel with the reflect-padding multiplicity, no atomics: bit-reproducible, and an output requested alone has the bits it
+ * has next to the other.  The clamp of losses.py:41 passes its gradient on the closed interval [0, 1] (torch's convention). */
+int tcsfm_ssim_backward(tcsfm_handle h, const tcsfm_opts *o, int planes, const float *x, const float *y, const float *g_out, float *g_x,
+        float *g_y);
+
+/* get_smooth_loss (losses.py:43-61; l_smooth, optimizer.py:93) without leaving the device: loss_out is ONE float and stats_out [N,3]
+ * doubles (per image: mean disparity, sum of the x terms, sum of the y terms -- what tcsfm_smooth_loss_backward needs), both in device
+ * memory (host memory under opts.host_ptrs).  With device pointers the call neither synchronises the stream nor copies to the host: it
+ * can be captured.  The value is tcsfm_smooth_loss's to the rounding of a float (the same partial sums, added per image). */
+int tcsfm_smooth_loss_device(tcsfm_handle h, const tcsfm_opts *o, int N, const float *disp, const float *img, float *loss_out,
+        double *stats_out);
+
+/* backward of get_smooth_loss (losses.py:43-61 under autograd) with respect to disp: disp, img, the stats of tcsfm_smooth_loss_device
+ * on the same inputs and the cotangent of the scalar (one float, device memory unless opts.host_ptrs) -> g_disp [N,1,H,W].  sgn(0) = 0
+ * on an edge between equal disparities; the coupling through the per-image mean is included; img takes no gradient.  One gather kernel. */
+int tcsfm_smooth_loss_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const float *disp, const float *img, const double *stats,
+        const float *g_loss, float *g_disp);
+
 /* inverse_warp2(src, depth_t, depth_s, -pose, K), models/stn.py:234-273.
  * Outputs (any may be NULL): img_rec [N,3,H,W], valid [N,1,H,W], proj_depth, comp_depth [N,1,H,W]. */
 int tcsfm_warp(tcsfm_handle h, const tcsfm_opts *o, int N, const float *src, const float *depth_t, const float *depth_s,

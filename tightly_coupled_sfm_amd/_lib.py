@@ -116,6 +116,10 @@ _SIGNATURES = {
     "tcsfm_disp_to_depth": (C.c_int, [_P, C.POINTER(Opts), C.c_int64, _P, _P, _P]),
     "tcsfm_smooth_loss": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P]),
     "tcsfm_ssim": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P]),
+    "tcsfm_disp_to_depth_backward": (C.c_int, [_P, C.POINTER(Opts), C.c_int64, _P, _P, _P, _P]),
+    "tcsfm_ssim_backward": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P, _P, _P]),
+    "tcsfm_smooth_loss_device": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P, _P]),
+    "tcsfm_smooth_loss_backward": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P, _P, _P]),
     "tcsfm_warp": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 9),
     "tcsfm_warp_backward": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 11),
     "tcsfm_warp_posenet_input": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 8),

@@ -20,6 +20,8 @@
 //   k_warp_bwd, k_warp_pose_tail, k_warp_gmax, k_warp_scatter, k_warp_fix_out: the backward pass of k_warp (warp_grad_kernel.h).
 //   k_photo_bwd, k_warp_fwd64: the backward pass of the residual assembly (diff_img, weight_mask of tcsfm_photometric) and the warp
 //                   forward its chain starts from: photo_grad_kernel.h.
+//   k_disp_to_depth_bwd, k_ssim_bwd, k_smooth_reduce, k_smooth_bwd: the backward passes of disp_to_depth, SSIM_Loss and get_smooth_loss
+//                   and the smoothness scalar on the device: loss_grad_kernel.h.
 //   k_ssim, k_disp_to_depth: SSIM_Loss / disp_to_depth drop-ins.  dense_kernel.h, scale_kernel.h: dense mode, DNet scale.
 #pragma once
 #include <hip/hip_runtime.h>

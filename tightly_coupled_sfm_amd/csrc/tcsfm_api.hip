@@ -21,6 +21,7 @@
 #include "depthnet_grad_kernel.h"
 #include "warp_grad_kernel.h"
 #include "photo_grad_kernel.h"
+#include "loss_grad_kernel.h"
 
 using namespace tc;
 
@@ -1448,6 +1449,46 @@ int tcsfm_ssim(tcsfm_handle h, const tcsfm_opts *o, int planes, const float *x, 
     return st.finish();
 }
 
+int tcsfm_disp_to_depth_backward(tcsfm_handle h, const tcsfm_opts *o, int64_t n, const float *disp, const float *g_scaled, const float *g_depth,
+                                 float *g_disp) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    if (!h) return TCSFM_E_ARG;
+    if (!o || !disp || !g_disp || n < 1) return fail(h, TCSFM_E_ARG, "tcsfm_disp_to_depth_backward: bad argument");
+    if (!g_scaled && !g_depth) return fail(h, TCSFM_E_ARG, "tcsfm_disp_to_depth_backward: no cotangent given");
+    if (!(o->min_depth > 0 && o->max_depth > o->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
+    Staging st(h, o);
+    const float *d_in = st.in(disp, (size_t)n), *d_gs = st.in(g_scaled, (size_t)n), *d_gd = st.in(g_depth, (size_t)n);
+    float *d_out = st.out(g_disp, (size_t)n);
+    if (st.rc) return st.rc;
+    // float4 accesses need 16-byte alignment of every array in use: otherwise the scalar tail takes everything
+    const bool aligned = (((uintptr_t)d_in | (uintptr_t)d_gs | (uintptr_t)d_gd | (uintptr_t)d_out) & 15) == 0;
+    const long long n4 = aligned ? (long long)(n / 4) : 0, threads = n4 + ((long long)n - 4 * n4);
+    hipLaunchKernelGGL(k_disp_to_depth_bwd, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, d_in, d_gs, d_gd, d_out,
+                       (long long)n, n4, 1.f / o->max_depth, 1.f / o->min_depth);
+    HIPCHK(h, hipGetLastError());
+    return st.finish();
+}
+
+int tcsfm_ssim_backward(tcsfm_handle h, const tcsfm_opts *o, int planes, const float *x, const float *y, const float *g_out, float *g_x,
+                        float *g_y) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    if (!h) return TCSFM_E_ARG;
+    if (!o || !x || !y || !g_out || planes < 1) return fail(h, TCSFM_E_ARG, "tcsfm_ssim_backward: bad argument");
+    if (!g_x && !g_y) return fail(h, TCSFM_E_ARG, "tcsfm_ssim_backward: no output wanted");
+    if (planes > 65535) return fail(h, TCSFM_E_ARG, "tcsfm_ssim_backward: more than 65535 planes");
+    Staging st(h, o);
+    const size_t hw = (size_t)h->H * h->W, n = hw * planes;
+    SsimGradParams P;
+    P.x = st.in(x, n); P.y = st.in(y, n); P.g_out = st.in(g_out, n);
+    P.g_x = st.out(g_x, n); P.g_y = st.out(g_y, n);
+    P.H = h->H; P.W = h->W;
+    if (st.rc) return st.rc;
+    const dim3 grid((unsigned)((h->W + PG_TW - 1) / PG_TW), (unsigned)((h->H + PG_TH - 1) / PG_TH), (unsigned)planes);
+    hipLaunchKernelGGL(k_ssim_bwd, grid, dim3(256), 0, h->stream, P);
+    HIPCHK(h, hipGetLastError());
+    return st.finish();
+}
+
 int tcsfm_warp(tcsfm_handle h, const tcsfm_opts *o, int N, const float *src, const float *depth_t, const float *depth_s,
                const float *pose, const float *K, float *img_rec, float *valid, float *proj_depth, float *comp_depth) {
     if (int rc_q = drain_queued(h)) return rc_q;
@@ -2033,6 +2074,51 @@ int tcsfm_smooth_loss(tcsfm_handle h, const tcsfm_opts *o, int N, const float *d
     for (size_t i = 0; i < hp.size(); i += 2) { sx += hp[i]; sy += hp[i + 1]; }
     *loss_out = sx / ((double)N * h->H * (h->W - 1)) + sy / ((double)N * (h->H - 1) * h->W);
     return TCSFM_OK;
+}
+
+int tcsfm_smooth_loss_device(tcsfm_handle h, const tcsfm_opts *o, int N, const float *disp, const float *img, float *loss_out,
+                             double *stats_out) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    int rc = check_common(h, o, N);
+    if (rc) return rc;
+    if (!disp || !img || !loss_out || !stats_out) return fail(h, TCSFM_E_ARG, "tcsfm_smooth_loss_device: NULL argument");
+    if (h->H < 2 || h->W < 2) return fail(h, TCSFM_E_ARG, "tcsfm_smooth_loss_device: image too small");
+    Staging st(h, o);
+    const size_t hw = (size_t)h->H * h->W;
+    const int nb = (int)((hw + 255) / 256);
+    const float *d_disp = st.in(disp, N * hw), *d_img = st.in(img, N * 3 * hw);
+    float *d_loss = st.out(loss_out, (size_t)1);
+    double *d_stats = st.out(stats_out, (size_t)N * 3);
+    // scratch as in tcsfm_smooth_loss: N means (double) + N * nb * 2 partial sums
+    float *scratch = (float *)st.scratch(((size_t)N * 2 + (size_t)N * nb * 2) * sizeof(float));
+    if (st.rc) return st.rc;
+    double *mean = reinterpret_cast<double *>(scratch);
+    float *partial = scratch + (size_t)N * 2;
+    hipLaunchKernelGGL(k_smooth_mean, dim3(N), dim3(1024), 0, h->stream, d_disp, (int)hw, mean);
+    hipLaunchKernelGGL(k_smooth, dim3(nb, N), dim3(256), 0, h->stream, d_disp, d_img, (const double *)mean, h->H, h->W, partial);
+    hipLaunchKernelGGL(k_smooth_reduce, dim3(1), dim3(256), 0, h->stream, (const float *)partial, (const double *)mean, N, nb, h->H, h->W,
+                       d_stats, d_loss);
+    HIPCHK(h, hipGetLastError());
+    return st.finish();          // (device pointers: no copy, no synchronisation)
+}
+
+int tcsfm_smooth_loss_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const float *disp, const float *img, const double *stats,
+                               const float *g_loss, float *g_disp) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    int rc = check_common(h, o, N);
+    if (rc) return rc;
+    if (!disp || !img || !stats || !g_loss || !g_disp) return fail(h, TCSFM_E_ARG, "tcsfm_smooth_loss_backward: NULL argument");
+    if (h->H < 2 || h->W < 2) return fail(h, TCSFM_E_ARG, "tcsfm_smooth_loss_backward: image too small");
+    Staging st(h, o);
+    const size_t hw = (size_t)h->H * h->W;
+    SmoothGradParams P;
+    P.disp = st.in(disp, N * hw); P.img = st.in(img, N * 3 * hw); P.stats = st.in(stats, (size_t)N * 3); P.g_loss = st.in(g_loss, (size_t)1);
+    P.g_disp = st.out(g_disp, N * hw);
+    P.H = h->H; P.W = h->W; P.N = N;
+    if (st.rc) return st.rc;
+    hipLaunchKernelGGL(k_smooth_bwd, dim3((unsigned)((hw + 255) / 256), N), dim3(256), 0, h->stream, P);
+    HIPCHK(h, hipGetLastError());
+    return st.finish();
 }
 
 // shared body of tcsfm_refine_dense (win_B == 0) and tcsfm_refine_dense_window

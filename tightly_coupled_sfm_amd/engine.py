@@ -60,6 +60,70 @@ class _PhotometricError(torch.autograd.Function):
         return None, None, None, None, d_dt, d_ds, d_p, None
 
 
+def _cot(g):
+    return None if g is None else g.contiguous()
+
+
+class _DispToDepth(torch.autograd.Function):
+    """Engine.disp_to_depth under autograd: the same forward kernel, tcsfm_disp_to_depth_backward behind it."""
+
+    @staticmethod
+    def forward(ctx, engine, d, min_depth, max_depth):
+        ctx.engine, ctx.range = engine, (min_depth, max_depth)
+        ctx.save_for_backward(d)
+        ctx.set_materialize_grads(False)        # a cotangent autograd does not supply stays None: its path costs nothing
+        return engine._disp_to_depth(d, min_depth, max_depth)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_scaled, g_depth):
+        if g_scaled is None and g_depth is None:
+            return None, None, None, None
+        d, = ctx.saved_tensors
+        return None, ctx.engine.disp_to_depth_backward(d, *ctx.range, _cot(g_scaled), _cot(g_depth)), None, None
+
+
+class _SSIMLoss(torch.autograd.Function):
+    """Engine.ssim_loss under autograd: the same forward kernel, tcsfm_ssim_backward behind it."""
+
+    @staticmethod
+    def forward(ctx, engine, x, y):
+        ctx.engine = engine
+        ctx.save_for_backward(x, y)
+        ctx.set_materialize_grads(False)
+        return engine._ssim(x, y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        if g_out is None:
+            return None, None, None
+        x, y = ctx.saved_tensors
+        g_x, g_y = ctx.engine.ssim_loss_backward(x, y, _cot(g_out), tuple(ctx.needs_input_grad[1:3]))
+        return None, g_x, g_y
+
+
+class _SmoothLoss(torch.autograd.Function):
+    """losses.get_smooth_loss under autograd: tcsfm_smooth_loss_device forward (the scalar stays on the device),
+    tcsfm_smooth_loss_backward behind it.  img takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, engine, disp, img):
+        loss, stats = engine.smooth_loss_device(disp, img)
+        ctx.engine = engine
+        ctx.save_for_backward(disp, img, stats)
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        if g_loss is None:
+            return None, None, None
+        disp, img, stats = ctx.saved_tensors
+        return None, ctx.engine.smooth_loss_backward(disp, img, stats, _cot(g_loss)), None
+
+
 class Engine:
     """One handle = one GPU + one HIP stream (include/tcsfm.h).  ``max_pairs`` directed pairs of HxW."""
 
@@ -177,26 +241,65 @@ class Engine:
         return C.c_void_p(t.data_ptr())
 
     # -- reference-function drop-ins -----------------------------------------------------------
-    def disp_to_depth(self, disp: torch.Tensor, min_depth: float, max_depth: float):
-        """utils/learning_helpers.py:77-86 -> (scaled_disp, depth)"""
-        self._bind()
-        d = disp.contiguous()
-        if d.dtype != torch.float32 or not d.is_cuda:
-            raise TypeError("disp must be a float32 GPU tensor")
+    def _disp_to_depth(self, d, min_depth, max_depth):
         s, z = torch.empty_like(d), torch.empty_like(d)
         o = default_opts(min_depth=min_depth, max_depth=max_depth)
         self._call(self.lib.tcsfm_disp_to_depth(self._h, C.byref(o), d.numel(), self._p(d), self._p(s), self._p(z)))
         return s, z
 
+    def disp_to_depth(self, disp: torch.Tensor, min_depth: float, max_depth: float):
+        """utils/learning_helpers.py:77-86 -> (scaled_disp, depth).  When grad is enabled and disp requires grad both carry a grad_fn
+        (tcsfm_disp_to_depth_backward); the values are the plain call's bits."""
+        self._bind()
+        d = disp.contiguous()
+        if d.dtype != torch.float32 or not d.is_cuda:
+            raise TypeError("disp must be a float32 GPU tensor")
+        if torch.is_grad_enabled() and d.requires_grad:
+            return _DispToDepth.apply(self, d, float(min_depth), float(max_depth))
+        return self._disp_to_depth(d, min_depth, max_depth)
+
+    def disp_to_depth_backward(self, disp: torch.Tensor, min_depth: float, max_depth: float, g_scaled=None, g_depth=None) -> torch.Tensor:
+        """backward of disp_to_depth (tcsfm_disp_to_depth_backward): the cotangents of scaled_disp and depth (None = absent; at least
+        one) -> g_disp, shaped as disp"""
+        self._bind()
+        d = disp.contiguous()
+        if d.dtype != torch.float32 or not d.is_cuda:
+            raise TypeError("disp must be a float32 GPU tensor")
+        g_scaled = None if g_scaled is None else _chk(g_scaled, d.shape, "g_scaled")
+        g_depth = None if g_depth is None else _chk(g_depth, d.shape, "g_depth")
+        out = torch.empty_like(d)
+        o = default_opts(min_depth=min_depth, max_depth=max_depth)
+        self._call(self.lib.tcsfm_disp_to_depth_backward(self._h, C.byref(o), d.numel(), self._p(d), self._p(g_scaled), self._p(g_depth),
+                                                         self._p(out)))
+        return out
+
+    def _ssim(self, x, y):
+        out = torch.empty_like(x)
+        o = default_opts()
+        self._call(self.lib.tcsfm_ssim(self._h, C.byref(o), x.shape[0] * x.shape[1], self._p(x), self._p(y), self._p(out)))
+        return out
+
     def ssim_loss(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        """SSIM_Loss.forward (losses.py:27-41) for [N,C,H,W] tensors"""
+        """SSIM_Loss.forward (losses.py:27-41) for [N,C,H,W] tensors.  When grad is enabled and x or y requires grad the result carries a
+        grad_fn (tcsfm_ssim_backward); the values are the plain call's bits."""
         self._bind()
         N, Cc = x.shape[0], x.shape[1]
         x = _chk(x, (N, Cc, self.H, self.W), "x"); y = _chk(y, (N, Cc, self.H, self.W), "y")
-        out = torch.empty_like(x)
-        o = default_opts()
-        self._call(self.lib.tcsfm_ssim(self._h, C.byref(o), N * Cc, self._p(x), self._p(y), self._p(out)))
-        return out
+        if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+            return _SSIMLoss.apply(self, x, y)
+        return self._ssim(x, y)
+
+    def ssim_loss_backward(self, x: torch.Tensor, y: torch.Tensor, g_out: torch.Tensor, want=(True, True)):
+        """backward of ssim_loss (tcsfm_ssim_backward): x, y and the cotangent of the output -> (g_x, g_y), None where ``want`` is False"""
+        self._bind()
+        N, Cc = x.shape[0], x.shape[1]
+        shape = (N, Cc, self.H, self.W)
+        x = _chk(x, shape, "x"); y = _chk(y, shape, "y"); g_out = _chk(g_out, shape, "g_out")
+        g_x = torch.empty_like(x) if want[0] else None
+        g_y = torch.empty_like(y) if want[1] else None
+        self._call(self.lib.tcsfm_ssim_backward(self._h, C.byref(default_opts()), N * Cc, self._p(x), self._p(y), self._p(g_out),
+                                                self._p(g_x), self._p(g_y)))
+        return g_x, g_y
 
     def smooth_loss(self, disp: torch.Tensor, img: torch.Tensor) -> float:
         """get_smooth_loss (losses.py:43-61): disp [N,1,H,W], img [N,3,H,W] -> python float"""
@@ -206,6 +309,31 @@ class Engine:
         out = C.c_double()
         self._call(self.lib.tcsfm_smooth_loss(self._h, C.byref(default_opts()), N, self._p(disp), self._p(img), C.byref(out)))
         return out.value
+
+    def smooth_loss_device(self, disp: torch.Tensor, img: torch.Tensor):
+        """get_smooth_loss without the host round trip (tcsfm_smooth_loss_device) -> (loss: 0-dim float32 tensor, stats [N,3] float64:
+        per image the mean disparity and the sums of the x and y terms, the input of smooth_loss_backward)"""
+        self._bind()
+        N = disp.shape[0]
+        disp = _chk(disp, (N, 1, self.H, self.W), "disp"); img = _chk(img, (N, 3, self.H, self.W), "img")
+        loss = torch.empty((), dtype=torch.float32, device=disp.device)
+        stats = torch.empty((N, 3), dtype=torch.float64, device=disp.device)
+        self._call(self.lib.tcsfm_smooth_loss_device(self._h, C.byref(default_opts()), N, self._p(disp), self._p(img), self._p(loss), self._p(stats)))
+        return loss, stats
+
+    def smooth_loss_backward(self, disp: torch.Tensor, img: torch.Tensor, stats: torch.Tensor, g_loss: torch.Tensor) -> torch.Tensor:
+        """backward of get_smooth_loss with respect to disp (tcsfm_smooth_loss_backward): ``stats`` from smooth_loss_device on the same
+        inputs, ``g_loss`` a float32 GPU tensor with one element -> g_disp [N,1,H,W]"""
+        self._bind()
+        N = disp.shape[0]
+        disp = _chk(disp, (N, 1, self.H, self.W), "disp"); img = _chk(img, (N, 3, self.H, self.W), "img")
+        if stats.dtype != torch.float64 or not stats.is_cuda or tuple(stats.shape) != (N, 3):
+            raise TypeError(f"stats must be a float64 GPU tensor of shape [{N}, 3]")
+        g_loss = _chk(g_loss.reshape(()), (), "g_loss")
+        out = torch.empty_like(disp)
+        self._call(self.lib.tcsfm_smooth_loss_backward(self._h, C.byref(default_opts()), N, self._p(disp), self._p(img),
+                                                       self._p(stats.contiguous()), self._p(g_loss), self._p(out)))
+        return out
 
     def inverse_warp2(self, img, depth, ref_depth, pose, intrinsics):
         """models/stn.py:234-273 with the reference's argument order; ``pose`` here is what the reference

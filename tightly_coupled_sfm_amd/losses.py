@@ -9,7 +9,9 @@ import torch
 
 class SSIM_Loss:
     """losses.py:16-41: callable like the reference's nn.Module -- SSIM_Loss()(x, y) -> clamp((1 - SSIM) / 2, 0, 1) per pixel
-    and channel, 3x3 windows over a reflect-padded image; one fused HIP kernel (tcsfm_ssim) instead of 2 pads + 5 pools."""
+    and channel, 3x3 windows over a reflect-padded image; one fused HIP kernel (tcsfm_ssim) instead of 2 pads + 5 pools.
+    Differentiable with respect to x and y (one HIP gather kernel, tcsfm_ssim_backward): the result carries a grad_fn when grad is
+    enabled and one of them requires grad; its values are the plain call's bits."""
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         from ._shared import get_engine
@@ -22,10 +24,18 @@ class SSIM_Loss:
 def get_smooth_loss(disp: torch.Tensor, img: torch.Tensor) -> torch.Tensor:
     """losses.py:43-61: edge-aware smoothness of the mean-normalised disparity.  GPU tensors of the engine's image size go
     through the HIP kernels (tcsfm_smooth_loss); anything else (CPU tensors: the golden tests of the scalar-loss mirror) through
-    the same expression in torch."""
+    the same expression in torch.  Differentiable with respect to disp on the GPU path: when grad is enabled and disp requires grad
+    the scalar is computed on the device (tcsfm_smooth_loss_device: no host round trip, within one float32 ulp of the plain value)
+    and carries a grad_fn (tcsfm_smooth_loss_backward); img requiring grad raises NotImplementedError."""
     if disp.is_cuda and disp.dim() == 4 and disp.shape[1] == 1 and img.shape[1] == 3:
         from ._shared import get_engine
         H, W = disp.shape[-2:]
+        if torch.is_grad_enabled() and (disp.requires_grad or img.requires_grad):
+            if img.requires_grad:
+                raise NotImplementedError("get_smooth_loss has no gradient with respect to img "
+                                          "(DESIGN.md section 7: gradients with respect to the images stay out of scope)")
+            from .engine import _SmoothLoss
+            return _SmoothLoss.apply(get_engine(H, W, max(1, disp.shape[0])), disp.float().contiguous(), img.float().contiguous()).to(disp.dtype)
         v = get_engine(H, W, max(1, disp.shape[0])).smooth_loss(disp.float().contiguous(), img.float().contiguous())
         return torch.tensor(v, device=disp.device, dtype=disp.dtype)
     mean_disp = disp.mean(2, True).mean(3, True)
