@@ -297,32 +297,37 @@ def e2e_inputs():
                 K=f(np.repeat(c["K"][:1], 2, 0)))
 
 
-def e2e_twin(masks, dtype="f64"):
+def e2e_twin(masks, dtype="f64", inputs=None, options=None, depth_range=None, hooks=None):
     """the chain of the GPU test in torch on the CPU: disparity leaves -> 1 / (a + b disp) -> torch_twin.photometric for the forward
     and the inverse pairs -> losses.compute_optimization_loss (its CPU path) with E2E_OPTIONS and torch_twin.ssim; `masks`: the
     library's valid_mask (validity x auto-mask, as helpers.compute_photometric_error returns it) of both directions, detached (dict
-    fwd_valid, inv_valid, numpy [2,1,H,W])
+    fwd_valid, inv_valid, numpy [2,1,H,W]).  `inputs` (default e2e_inputs()), `options` (default E2E_OPTIONS) and `depth_range`
+    (default E2E_DEPTH_RANGE) let other chains reuse it (tests/tuning_chain_inputs.py).  `hooks`: {name: callable(tensor) -> tensor}
+    applied to "repeat" (the repeated target depth) and "inv_ref_depth" (the same tensor as the inverse pairs take it): where planted
+    faults cut or alter a path
     -> (dict d_disp_t, d_disp_s; the loss as a float)"""
     dt = _dt(dtype)
-    i = e2e_inputs()
+    i = e2e_inputs() if inputs is None else inputs
+    options = E2E_OPTIONS if options is None else options
+    hook = lambda name, t: (hooks or {}).get(name, lambda a: a)(t)
     disp_t, disp_s = _T(i["disp_t"], dt).requires_grad_(), _T(i["disp_s"], dt).requires_grad_()
-    lo, hi = 1 / E2E_DEPTH_RANGE[1], 1 / E2E_DEPTH_RANGE[0]
+    lo, hi = (1 / d for d in reversed(E2E_DEPTH_RANGE if depth_range is None else depth_range))
     depth = lambda d: 1 / (lo + (hi - lo) * d)
     tgt2, src, pose, K = _T(i["tgt"], dt).repeat(2, 1, 1, 1), _T(i["src"], dt), _T(i["pose"], dt), _T(i["K"], dt)
-    dt2, ds = depth(disp_t).repeat(2, 1, 1, 1), depth(disp_s)
-    fwd, inv = tw.photometric(tgt2, src, dt2, ds, pose, K), tw.photometric(src, tgt2, ds, dt2, -pose, K)
+    dt2, ds = hook("repeat", depth(disp_t).repeat(2, 1, 1, 1)), depth(disp_s)
+    fwd, inv = tw.photometric(tgt2, src, dt2, ds, pose, K), tw.photometric(src, tgt2, ds, hook("inv_ref_depth", dt2), -pose, K)
     pack = lambda r, valid, p: dict(diff_img=r["diff"], valid_mask=_T(valid, dt), weight_mask=r["weight"], poses=p)
-    L = losses.compute_optimization_loss(E2E_OPTIONS, tgt2[:1], disp_t, _T(i["disp_init"], dt), pack(fwd, masks["fwd_valid"], pose),
+    L = losses.compute_optimization_loss(options, tgt2[:1], disp_t, _T(i["disp_init"], dt), pack(fwd, masks["fwd_valid"], pose),
                                          pack(inv, masks["inv_valid"], -pose), tw.ssim)
     L.backward()
     return dict(d_disp_t=disp_t.grad.double().numpy(), d_disp_s=disp_s.grad.double().numpy()), float(L.detach())
 
 
-def e2e_twin_masks(dtype="f64"):
+def e2e_twin_masks(dtype="f64", inputs=None, depth_range=None):
     """the masks as the twin itself takes them (the CPU test: they are not empty) -> dict as `masks` of e2e_twin"""
     dt = _dt(dtype)
-    i = e2e_inputs()
-    lo, hi = 1 / E2E_DEPTH_RANGE[1], 1 / E2E_DEPTH_RANGE[0]
+    i = e2e_inputs() if inputs is None else inputs
+    lo, hi = (1 / d for d in reversed(E2E_DEPTH_RANGE if depth_range is None else depth_range))
     depth = lambda d: 1 / (lo + (hi - lo) * _T(d, dt))
     tgt2, src, pose, K = _T(i["tgt"], dt).repeat(2, 1, 1, 1), _T(i["src"], dt), _T(i["pose"], dt), _T(i["K"], dt)
     dt2, ds = depth(i["disp_t"]).repeat(2, 1, 1, 1), depth(i["disp_s"])

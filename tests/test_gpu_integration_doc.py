@@ -1,5 +1,6 @@
 """INTEGRATION.md shows the ctypes stub a reference maintainer would paste in; this runs that exact text against the
 built library, so the documented binding cannot drift from the C ABI."""
+import copy
 import os
 import re
 
@@ -76,3 +77,24 @@ def test_documented_dense_reference_stub_runs_and_matches_engine():
     rp, rd, _ = Engine(H, W, 2 * S).refine_dense_window(t["tgt"], t["srcs"], depths[0], torch.stack(depths[1:]), t["K"], t["pose"], o, argmin=True)
     torch.cuda.synchronize()
     assert torch.equal(pose, rp) and torch.equal(depth, rd[:1]) and not torch.equal(depth, depths[0])
+
+
+def test_documented_weight_tuning_loop_runs_on_the_library():
+    """the documented epoch loop on the differentiable operators: its first loss has the bits of the composed chain of
+    tests/test_gpu_tuning_chain.py on the same inputs, the copy's encoder moves, the decoder and the original model do not"""
+    import test_gpu_tuning_chain as T
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    block = re.search(r"```python\n(# weight tuning on the library's differentiable operators.*?)```", text, re.S).group(1)
+    ns = {}
+    exec(compile(block, "INTEGRATION.md:weight_tuning", "exec"), ns)
+    shape, c = T.SMALL, T._consts(T.SMALL)
+    orig = T._orig(shape)
+    before = {k: v.clone() for k, v in orig.state_dict().items()}
+    config = dict(min_depth=T.TC.DEPTH_RANGE[0], max_depth=T.TC.DEPTH_RANGE[1])
+    model, history = ns["tune_depth_encoder"](orig, c["tgt"], [c["src"][0:1], c["src"][1:2]], c["pose"], c["K"], T.TC.OPTIONS, config, epochs=2)
+    L = T._chain(shape, T.TC.OPTIONS, copy.deepcopy(orig), T._first_pass(shape)["init"])[0]
+    assert len(history) == 2 and history[0] == float(L.detach()) and history[1] != history[0]
+    after, tuned = orig.state_dict(), model.state_dict()
+    assert all(torch.equal(after[k], before[k]) for k in before)
+    assert any(not torch.equal(tuned[k], before[k]) for k in before if k.startswith("encoder."))
+    assert all(torch.equal(tuned[k], before[k]) for k in before if not k.startswith("encoder."))
