@@ -667,6 +667,9 @@ int tcsfm_profile_kernel_busy(tcsfm_handle h, double *ms_busy, int64_t *launches
  *                                of |cd - pd| and |rec - tgt|; 2-bit codes: 0 exactly zero, 1 positive, 2 negative)
  *   decide [lin][N]      int32   LM: 1 = trial accepted (lin < n_iters) / last step kept (lin == n_iters); GN: 1
  * so that a checker can replay them and compare the continuous arithmetic at full tolerance (tests/test_gpu_parity.py).
+ * tcsfm_linearize and tcsfm_linearize_window record too: their ONE linearisation writes bits [0][N][H*W] (N = 2 S B for a window,
+ * stacked order) and leaves `decide` untouched (nothing is decided); the normal equations they return are those of exactly these
+ * decisions (tests/test_gpu_linearize_exact.py).  tcsfm_loss_surface records nothing.
  * Capacities in elements; a call that would overflow them returns TCSFM_E_ARG.  Either pointer may be NULL; (NULL, 0, NULL, 0)
  * switches the trace off.  Costs one wave-uniform branch per pixel when off. */
 int tcsfm_debug_trace(tcsfm_handle h, uint16_t *bits, int64_t bits_capacity, int32_t *decide, int64_t decide_capacity);

@@ -26,7 +26,7 @@ class OrcOpts(C.Structure):
 
 class LinOut(C.Structure):
     _fields_ = [("H", C.c_double * (MAXP * MAXP)), ("g", C.c_double * MAXP), ("cost", C.c_double),
-                ("cost_photo", C.c_double), ("cost_dc", C.c_double), ("n_mask", C.c_double)]
+                ("cost_photo", C.c_double), ("cost_dc", C.c_double), ("n_mask", C.c_double), ("gabs", C.c_double * MAXP)]
 
 
 def default_opts(**kw) -> OrcOpts:
@@ -158,8 +158,10 @@ class Oracle:
         return self.lib.orc_cost(H, W, self._p(tgt), self._p(src), self._p(depth_t), self._p(depth_s), self._p(T),
                                  self._p(K), C.c_double(log_scale), C.byref(opts))
 
-    def linearize(self, tgt, src, depth_t, depth_s, pose, K, opts=None, log_scale=0.0, rows=False, T=None):
-        """-> dict(H [np,np], g [np], cost, cost_photo, cost_dc, n_mask [, J1,J2,J3 [H,W,np], E [H,W,3], M [H,W]])."""
+    def linearize(self, tgt, src, depth_t, depth_s, pose, K, opts=None, log_scale=0.0, rows=False, T=None, bits=None):
+        """-> dict(H [np,np], g [np], cost, cost_photo, cost_dc, n_mask, gabs [np] = sum over the pixels of |their contribution to g|
+        [, J1,J2,J3 [H,W,np], E [H,W,3], M [H,W]]).  bits [H,W] uint16: replay the engine's decisions of this linearisation
+        (Engine.linearize under trace_begin(1, N)) as refine does per iterate; the flip statistics count it as linearisation 0."""
         opts = opts or default_opts()
         tgt, src, depth_t, depth_s, K = map(self._r, (tgt, src, depth_t, depth_s, K))
         _, H, W = tgt.shape
@@ -169,11 +171,13 @@ class Oracle:
         J = [np.empty((H, W, n_p), self.dt) if rows else None for _ in range(3)]
         E = np.empty((H, W, 3), self.dt) if rows else None
         M = np.empty((H, W), self.dt) if rows else None
-        self.lib.orc_linearize(H, W, self._p(tgt), self._p(src), self._p(depth_t), self._p(depth_s), self._p(T),
-                               self._p(K), C.c_double(log_scale), C.byref(opts), None, C.byref(out),
-                               self._p(J[0]), self._p(J[1]), self._p(J[2]), self._p(E), self._p(M))
+        bits, _ = self._forced(bits, None)
+        assert bits is None or bits.shape == (H, W)
+        self.lib.orc_linearize_forced(H, W, self._p(tgt), self._p(src), self._p(depth_t), self._p(depth_s), self._p(T),
+                                      self._p(K), C.c_double(log_scale), C.byref(opts), self._p(bits), C.byref(out),
+                                      self._p(J[0]), self._p(J[1]), self._p(J[2]), self._p(E), self._p(M))
         r = dict(H=np.array(out.H[:n_p * n_p]).reshape(n_p, n_p), g=np.array(out.g[:n_p]), cost=out.cost,
-                 cost_photo=out.cost_photo, cost_dc=out.cost_dc, n_mask=out.n_mask)
+                 cost_photo=out.cost_photo, cost_dc=out.cost_dc, n_mask=out.n_mask, gabs=np.array(out.gabs[:n_p]))
         if rows:
             r.update(J1=J[0], J2=J[1], J3=J[2], E=E, M=M)
         return r
@@ -413,8 +417,10 @@ class Oracle:
                                         self._p(bits), self._p(decide), None)
         return pose, ls, stats
 
-    def linearize_window(self, tgt, srcs, depth_t, depth_s, K, poses, opts=None, argmin=True, rule=0, log_scale=None):
-        """one linearisation of a whole window at `poses` [2SB,6] -> dict(H [2SB,np,np], g [2SB,np], cost, cost_photo, cost_dc, n_mask [2SB])"""
+    def linearize_window(self, tgt, srcs, depth_t, depth_s, K, poses, opts=None, argmin=True, rule=0, log_scale=None, bits=None):
+        """one linearisation of a whole window at `poses` [2SB,6] -> dict(H [2SB,np,np], g [2SB,np], gabs [2SB,np], cost, cost_photo, cost_dc,
+        n_mask [2SB]).  bits [2SB,H,W] uint16: replay the engine's decisions (Engine.linearize_window under trace_begin(1, 2SB)): the first
+        linearisation of refine_window's forced path."""
         opts = opts or default_opts()
         tgt, srcs, depth_t, depth_s, K = map(self._r, (tgt, srcs, depth_t, depth_s, K))
         S, B, _, H, W = srcs.shape
@@ -422,9 +428,12 @@ class Oracle:
         pose = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(N, 6))
         ls = None if log_scale is None else np.ascontiguousarray(np.asarray(log_scale, dtype=np.float64))
         out = (LinOut * N)()
-        self.lib.orc_linearize_window(H, W, B, S, self._p(tgt), self._p(srcs), self._p(depth_t), self._p(depth_s), self._p(K),
-                                      C.byref(opts), int(bool(argmin)), int(rule), self._p(pose), self._p(ls), out)
+        bits, _ = self._forced(bits, None)
+        assert bits is None or bits.shape == (N, H, W)
+        self.lib.orc_linearize_window_forced(H, W, B, S, self._p(tgt), self._p(srcs), self._p(depth_t), self._p(depth_s), self._p(K),
+                                             C.byref(opts), int(bool(argmin)), int(rule), self._p(pose), self._p(ls), self._p(bits), out)
         return dict(H=np.stack([np.array(o.H[:n_p * n_p]).reshape(n_p, n_p) for o in out]), g=np.stack([np.array(o.g[:n_p]) for o in out]),
+                    gabs=np.stack([np.array(o.gabs[:n_p]) for o in out]),
                     cost=np.array([o.cost for o in out]), cost_photo=np.array([o.cost_photo for o in out]),
                     cost_dc=np.array([o.cost_dc for o in out]), n_mask=np.array([o.n_mask for o in out]))
 

@@ -585,6 +585,7 @@ void orc_pixel_debug(int H, int W, const real *tgt, const real *src, const real 
 typedef struct {
     double H[MAXP * MAXP], g[MAXP];
     double cost, cost_photo, cost_dc, n_mask;
+    double gabs[MAXP];  /* sum over the pixels of |the pixel's contribution to g_j|: the size of what was summed into g_j (its condition scale) */
 } lin_t;
 
 /*
@@ -733,6 +734,7 @@ static void linearize_masked(int H, int W, const real *tgt, const real *src, con
     double a = den > 0 ? sc / den : 0.0, b = (x && x->b_dc >= 0) ? x->b_dc : op->w_dc / (double)n, eps = op->irls_eps;
     for (int i = 0; i < n; i++) {
         double am = a * M[i];
+        const double acr = (x && x->cross) ? a * (double)x->cross[i] : 0.0;
         if (x && x->cross)
             for (int j = 0; j < np; j++) out->g[j] -= a * (double)x->cross[i] * J3[i * np + j];
         double E1 = E[3 * i], E2 = E[3 * i + 1], E3 = E[3 * i + 2];
@@ -752,6 +754,7 @@ static void linearize_masked(int H, int W, const real *tgt, const real *src, con
              * to rounding, sign(cd - pd) is numerical noise -- in the reference's autograd too -- and an exact-L1 gradient is
              * not reproducible across precisions.  Same region where the IRLS curvature 1/max(dd,eps) is already quadratic. */
             out->g[j] += am * (j1 + j2) + b * fmin(1.0, E3 / eps) * j3;
+            out->gabs[j] += fabs(am * (j1 + j2) + b * fmin(1.0, E3 / eps) * j3 - acr * j3);
             double la = lxx * P->a[j] + lxy * P->b[j], lb = lxy * P->a[j] + lyy * P->b[j];
             for (int k = 0; k <= j; k++)
                 out->H[j * np + k] += la * P->a[k] + lb * P->b[k] + k3 * j3 * J3[i * np + k];
@@ -772,6 +775,17 @@ void orc_linearize(int H, int W, const real *tgt, const real *src, const real *d
                    const double T[12], const real *K, double log_scale, const orc_opts *op, const real *auto_err_in,
                    lin_t *out, real *J1o, real *J2o, real *J3o, real *Eo, real *Mo) {
     linearize_masked(H, W, tgt, src, depth_t, depth_s, T, K, log_scale, op, auto_err_in, NULL, NULL, out, J1o, J2o, J3o, Eo, Mo);
+}
+
+/* orc_linearize under the engine's decisions `bits` [H*W] of this ONE linearisation (tcsfm_linearize under tcsfm_debug_trace), exactly as
+ * refine_impl replays an iterate; the flip statistics are booked as linearisation 0.  bits NULL: orc_linearize. */
+void orc_linearize_forced(int H, int W, const real *tgt, const real *src, const real *depth_t, const real *depth_s,
+                          const double T[12], const real *K, double log_scale, const orc_opts *op, const unsigned short *bits,
+                          lin_t *out, real *J1o, real *J2o, real *J3o, real *Eo, real *Mo) {
+    g_force_bits = bits;
+    g_lin_idx = bits ? 0 : -1;
+    linearize_masked(H, W, tgt, src, depth_t, depth_s, T, K, log_scale, op, NULL, NULL, NULL, out, J1o, J2o, J3o, Eo, Mo);
+    g_force_bits = NULL; g_lin_idx = -1;
 }
 
 /* scalar cost only: the quantity generate_loss_surface sweeps, plot_loss_surface.py:31-33,45-47 */
@@ -1270,18 +1284,26 @@ void orc_refine_window(int H, int W, int B, int S, const real *tgt, const real *
     orc_refine_window_rule(H, W, B, S, tgt, srcs, depth_t, depth_s, K, op, argmin, 0, pose_io, log_scale_io, stats, NULL, NULL, NULL);
 }
 
-/* one linearisation of a whole window at the given poses: normal equations, cost and mask count of every directed pair */
-void orc_linearize_window(int H, int W, int B, int S, const real *tgt, const real *srcs, const real *depth_t, const real *depth_s,
-                          const real *K, const orc_opts *op, int argmin, int rule, const double *pose /* [2SB][6] */,
-                          const double *log_scale /* [2SB] or NULL */, lin_t *out /* [2SB] */) {
+/* one linearisation of a whole window at the given poses: normal equations, cost and mask count of every directed pair.
+ * bits [2SB][H*W] or NULL: the engine's decisions of this linearisation (tcsfm_linearize_window under tcsfm_debug_trace) -- the first
+ * linearisation of orc_refine_window_rule's forced path, selection-margin tie rule and flip statistics (linearisation 0) included */
+void orc_linearize_window_forced(int H, int W, int B, int S, const real *tgt, const real *srcs, const real *depth_t, const real *depth_s,
+                                 const real *K, const orc_opts *op, int argmin, int rule, const double *pose /* [2SB][6] */,
+                                 const double *log_scale /* [2SB] or NULL */, const unsigned short *bits, lin_t *out /* [2SB] */) {
     const int N = 2 * S * B;
     double *p = (double *)malloc(sizeof(double) * 6 * N), *ls = log_scale ? (double *)malloc(sizeof(double) * N) : NULL;
     memcpy(p, pose, sizeof(double) * 6 * N);
     if (ls) memcpy(ls, log_scale, sizeof(double) * N);
     orc_opts o1 = *op;
     if (o1.n_iters < 1) o1.n_iters = 1;
-    orc_refine_window_rule(H, W, B, S, tgt, srcs, depth_t, depth_s, K, &o1, argmin, rule, p, ls, NULL, NULL, NULL, out);
+    orc_refine_window_rule(H, W, B, S, tgt, srcs, depth_t, depth_s, K, &o1, argmin, rule, p, ls, NULL, bits, NULL, out);
     free(p); free(ls);
+}
+
+void orc_linearize_window(int H, int W, int B, int S, const real *tgt, const real *srcs, const real *depth_t, const real *depth_s,
+                          const real *K, const orc_opts *op, int argmin, int rule, const double *pose /* [2SB][6] */,
+                          const double *log_scale /* [2SB] or NULL */, lin_t *out /* [2SB] */) {
+    orc_linearize_window_forced(H, W, B, S, tgt, srcs, depth_t, depth_s, K, op, argmin, rule, pose, log_scale, NULL, out);
 }
 
 /* ------------------------------------------------------------------------- */

@@ -93,3 +93,42 @@ def test_replay_obeys_edited_decisions(oracle64):
         assert np.array_equal(q3, q1)
     want = PU.check_lm_decisions(s1, dec, default_opts(**kw))
     assert want == 0                                                              # the oracle's own decisions are what its costs imply
+
+
+# ---- the same at linearisation level: Oracle.linearize / linearize_window under bits (tests/linearize_exact_inputs.py) -----------------------
+import linearize_exact_inputs as LX
+
+LIN_REPLAY = [LX.pair_case(24, 40, refine=1, w_dc=0.15), LX.pair_case(37, 53, automask=0, weights=(1.0, 0.0)), LX.pair_case(37, 53, w_dc=0.15, automask=0, oob=1),
+              LX.window_case(17, 33, 1, 0, 0), LX.window_case(17, 33, 1, 1, 1), LX.window_case(37, 53, 0, 1, 0), LX.window_case(37, 53, 0, 0, 1)]
+
+
+@pytest.mark.parametrize("precision", ["f64", "f32"])
+@pytest.mark.parametrize("c", LIN_REPLAY, ids=[LX.case_id(c) for c in LIN_REPLAY])
+def test_linearisation_forced_with_own_bits_is_the_identity(c, precision):
+    """one linearisation forced with the oracle's own recorded decisions (refine_record, n_iters = 1; for the forward pairs of a window bit 0
+    is the selection) reproduces the unforced one bit for bit, pair and window forms, and the flip statistics count nothing"""
+    orc = LX.oracle(precision)
+    bits = LX.own_bits(c, precision)
+    if c.kind == "pair":        # bit 0 as recorded IS the mask the module derives from the photometric maps
+        for n, (t, s, dt, ds, K, pose, ls) in enumerate(LX.pair_views(c)):
+            rec = orc.refine_record(t, s, dt, ds, pose, K, LX.oracle_opts(c, n_iters=1), log_scale=ls)[3]
+            assert rec.shape == (1, c.H, c.W) and np.array_equal(rec[0], bits[n])
+    free = LX.reference(c, precision)
+    orc.flip_stats_reset()
+    forced = LX.reference(c, precision, bits)
+    fn, fh = orc.flip_stats(1)
+    assert not fn.any() and not fh.any()
+    for n in range(c.N):
+        assert set(free[n]) == {"H", "g", "gabs", "cost", "cost_photo", "cost_dc", "n_mask"}
+        for k in free[n]:
+            assert np.array_equal(free[n][k], forced[n][k]), (n, k)
+        assert forced[n]["n_mask"] == (bits[n] & 1).sum()
+        assert np.all(forced[n]["gabs"] >= np.abs(forced[n]["g"]) * (1 - 1e-12))          # |sum| <= sum |.|
+    # the replay is in control: a cleared block of mask bits changes the result and is reported as hard flips of linearisation 0
+    cut = bits.copy(); cut[:, 2:6, 3:9] &= 0xFFFE
+    gone = int((bits & 1).sum() - (cut & 1).sum())
+    orc.flip_stats_reset()
+    less = LX.reference(c, precision, cut)
+    fn, fh = orc.flip_stats(1)
+    assert gone > 0 and fn[0] == gone and sum(r["n_mask"] for r in less) == sum(r["n_mask"] for r in free) - gone
+    assert any(not np.array_equal(a["H"], b["H"]) for a, b in zip(less, free))

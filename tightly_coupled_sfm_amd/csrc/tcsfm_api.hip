@@ -492,6 +492,12 @@ int trace_check(tcsfm_ctx *h, const tcsfm_opts *o, int N) {
     if (h->trace_decide && n_lin * N > h->trace_decide_cap) return fail(h, TCSFM_E_ARG, "tcsfm_debug_trace: decide buffer too small for this call");
     return TCSFM_OK;
 }
+// tcsfm_linearize / tcsfm_linearize_window under a trace: ONE linearisation, bits [0][N][H*W]; no decision is taken, `decide` stays untouched
+int trace_lin_once(tcsfm_ctx *h, int N, LinParams &P) {
+    if (h->trace_bits && N * (long long)h->H * h->W > h->trace_bits_cap) return fail(h, TCSFM_E_ARG, "tcsfm_debug_trace: bits buffer too small for this call");
+    P.trace = h->trace_bits;
+    return TCSFM_OK;
+}
 
 int np_of(const tcsfm_opts *o) { return o->refine == TCSFM_REFINE_POSE_SCALE ? 7 : 6; }
 int nacc_of(int np) { return np == 6 ? AccLayout<6>::NACC : AccLayout<7>::NACC; }
@@ -1714,6 +1720,7 @@ static int eval_once(tcsfm_ctx *h, const tcsfm_opts *o, int N, int Nimg, const f
     if ((rc = run_init(h, o, N, d_pose, d_ls, d_K, shared))) return rc;
     LinParams P = lin_params(h, o, np);
     P.shared_image = shared;
+    if (mode == MODE_LIN && (rc = trace_lin_once(h, N, P))) return rc;      // (tcsfm_loss_surface records nothing)
     launch_lin(h, P, N, np, o->w_dc > 0.f, mode);
     HIPCHK(h, hipGetLastError());
     SolveParams S = solve_params(h, o, np, shared);
@@ -1785,6 +1792,7 @@ int tcsfm_linearize_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, co
     SolveParams Sv = solve_params(h, o, np, 0);
     if (S > 1 && o->argmin) { P.sel_B = B; P.sel_S = S; }
     apply_window_rule(h, o, B, S, N, P, Sv);
+    if ((rc = trace_lin_once(h, N, P))) return rc;
     launch_lin(h, P, N, np, o->w_dc > 0.f, MODE_LIN);
     Sv.mode = 2;
     launch_solve(h, Sv, N, np);

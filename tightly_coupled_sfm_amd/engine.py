@@ -213,8 +213,8 @@ class Engine:
         return out
 
     def trace_begin(self, n_lin: int, n_pairs: int):
-        """parity-test hook (tcsfm_debug_trace): record the discrete decisions of the following refine* calls -- per
-        linearisation and pair one uint16 per pixel (mask, warp validity, bilinear cell parity, L1 / depth-consistency sign codes:
+        """parity-test hook (tcsfm_debug_trace): record the discrete decisions of the following refine* calls (and of linearize /
+        linearize_window: trace_begin(1, N), their one linearisation is bits[0]) -- per linearisation and pair one uint16 per pixel (mask, warp validity, bilinear cell parity, L1 / depth-consistency sign codes:
         include/tcsfm.h) and the LM accept / keep decision"""
         self._trace = (torch.zeros((n_lin, n_pairs, self.H, self.W), dtype=torch.int16, device=self.dev),
                        torch.ones((n_lin, n_pairs), dtype=torch.int32, device=self.dev))
