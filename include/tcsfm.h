@@ -415,6 +415,30 @@ int tcsfm_posenet_forward(tcsfm_posenet *pn, int N, const float *imgs, float *po
 int tcsfm_solve_pose_iteratively(tcsfm_handle h, tcsfm_posenet *pn, int num_iter, int B, int S, const float *tgt, const float *srcs,
                                  const float *depth_t, const float *depth_s, const float *K, float *poses_out, float *stacked_out);
 
+/* ---- PoseNet: gradient with respect to the input ---------------------------------------------------
+ * In the coupled loop every PoseNet call after the first reads (tgt * valid | img_rec), and img_rec is the warp of the source under
+ * the current depths and pose: with the network's weights frozen (the reference's default test-time tuning mode) the depths reach
+ * the poses through the network's INPUT.  These calls differentiate the network with respect to it (csrc/posenet_grad_kernel.h);
+ * the parameters get no gradient.
+ *   tcsfm_posenet_tape_size      floats of the tape of an N-image training forward.  Layout, layer after layer (l = 1..7, npix = oh ow
+ *                                of the layer): raw [N][npix][cout] (the reduced convolution output + bias, NHWC), scsh [N][cout][2]
+ *                                (GroupNorm scale = rstd gamma, shift = beta - mean scale), mean_rstd [N][16][2] (per group; rstd cannot
+ *                                be had from scale where gamma is zero).  The images are not kept.  About 0.96 M floats per image at
+ *                                192 x 640.
+ *   tcsfm_posenet_forward_train  tcsfm_posenet_forward's launches unchanged (pose_out has its bits) + the tape (device, caller-owned,
+ *                                16-byte aligned).
+ *   tcsfm_posenet_backward       d_pose [N,6] -> d_imgs [N,6,H,W] (device, planar), with the instance's CURRENT weights (a
+ *                                tcsfm_posenet_load between forward and backward is the caller's to prevent).  The ReLU decisions are
+ *                                relu(raw * scale + shift) > 0 evaluated by one device function on the taped values; the forward's
+ *                                in-register activation can differ from it only where the activation is within an ulp of zero.
+ *                                No float atomics: results are bit-reproducible, and an image's gradient depends neither on the other
+ *                                images of the call nor on N within a forward regime (N <= 4, N > 4).  The first call after a load
+ *                                builds the transposed weight images and, once per instance, the gradient scratch.
+ * Both run asynchronously on the handle's stream; N <= max_images. */
+int tcsfm_posenet_tape_size(tcsfm_posenet *pn, int N, int64_t *floats_out);
+int tcsfm_posenet_forward_train(tcsfm_posenet *pn, int N, const float *imgs, float *pose_out, float *tape);
+int tcsfm_posenet_backward(tcsfm_posenet *pn, int N, const float *tape, const float *d_pose, float *d_imgs);
+
 /* ---- depth network --------------------------------------------------------------------------------
  * The reference's depth network (models/depth_w_access.py with num_scales = 1, the default of run_mono_training.py): a ResNet18
  * encoder on (x - 0.45) / 0.22 (conv1 7x7/2 + BN + ReLU -> skip 0, maxpool 3x3/2, layer1..layer4 of BasicBlocks -> skips 1..4;
@@ -521,6 +545,11 @@ int tcsfm_debug_guard_selftest(int *detected);
  *                               blocks of 16 per wave, K split, pixel blocks of 16 per wave.  Any out-pointer may be NULL. */
 int tcsfm_debug_posenet_layer(tcsfm_posenet *pn, int layer, int N, float *raw_out, float *scsh_out);
 int tcsfm_debug_posenet_split(tcsfm_posenet *pn, int layer, int N, int *oh, int *ow, int *nb, int *ks, int *pb);
+/* Read-out of one layer (1..7) of a tcsfm_posenet_forward_train tape over N images: raw_out [N, oh*ow, cout], scsh_out [N, cout, 2],
+ * mean_rstd_out [N, 16, 2] as taped, and act_out [N, oh*ow, cout] = the activation relu(raw * scale + shift) as the backward's own
+ * device function evaluates it: act_out > 0 are exactly the ReLU decisions tcsfm_posenet_backward takes.  Any out-pointer may be NULL. */
+int tcsfm_debug_posenet_tape_layer(tcsfm_posenet *pn, int N, const float *tape, int layer, float *raw_out, float *scsh_out,
+                                   float *mean_rstd_out, float *act_out);
 /* Read-out of the depth network's work split, for layer-by-layer tests: convolution `layer` in evaluation order (0 = conv1; per
  * BasicBlock conv1, conv2 and, in a stride-2 block, the 1x1 downsample; depth_upconvs.i, iconvs.i for i = 0..4; feature_convs.0 --
  * 33 - 2 = 31 entries, the max pool and the head have no split) -> kernel size, output size and the k_dn_conv instance it launches:

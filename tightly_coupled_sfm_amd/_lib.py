@@ -143,6 +143,10 @@ _SIGNATURES = {
     "tcsfm_debug_posenet_layer": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "tcsfm_debug_posenet_split": (C.c_int, [_P, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5),
     "tcsfm_solve_pose_iteratively": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int] + [_P] * 7),
+    "tcsfm_posenet_tape_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
+    "tcsfm_posenet_forward_train": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "tcsfm_posenet_backward": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "tcsfm_debug_posenet_tape_layer": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
     "tcsfm_depthnet_create": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "tcsfm_depthnet_destroy": (None, [_P]),
     "tcsfm_depthnet_load": (C.c_int, [_P, C.c_int, _P, _P, _P]),

@@ -20,6 +20,12 @@ struct tcsfm_posenet {
     // borrows this object's weights
     bool owns_weights = true;
     std::vector<tcsfm_posenet *> clones;
+    // tcsfm_posenet_backward (posenet_grad_host.h), all built at the first backward after a load: the transposed images of the
+    // prepared weights (layer 1: the plain [ky][kx][ci][co] image), two gradient maps [max_images][largest layer output] and the
+    // per-group sums [max_images][16][2]
+    pn_f4 *wt4[7] = {};
+    int wt_valid = 0;
+    float *gbuf[2] = {}, *gss = nullptr;
 };
 
 void tcsfm_posenet_destroy(tcsfm_posenet *pn) {
@@ -34,6 +40,11 @@ void tcsfm_posenet_destroy(tcsfm_posenet *pn) {
     void *weights[] = {pn->head_w, pn->head_b, pn->raw}, *scratch[] = {pn->in_buf, pn->pose};
     if (pn->owns_weights) for (void *p : weights) if (p) (void)hipFree(p);
     for (void *p : scratch) if (p) (void)hipFree(p);
+    if (pn->owns_weights) {
+        for (int l = 0; l < 7; l++) if (pn->wt4[l]) (void)hipFree(pn->wt4[l]);
+        void *grad[] = {pn->gbuf[0], pn->gbuf[1], pn->gss};
+        for (void *p : grad) if (p) (void)hipFree(p);
+    }
     delete pn;
 }
 
@@ -62,6 +73,8 @@ static tcsfm_posenet *pn_for_lane(tcsfm_posenet *pn, tcsfm_ctx *c) {
     q->h = c; q->owns_weights = false; q->clones.clear();
     for (int l = 0; l < 7; l++) q->act[l] = q->scsh[l] = q->part[l] = nullptr;
     q->in_buf = q->pose = nullptr;
+    for (int l = 0; l < 7; l++) q->wt4[l] = nullptr;
+    q->gbuf[0] = q->gbuf[1] = q->gss = nullptr; q->wt_valid = 0;
     if (pn_alloc_scratch(q) != hipSuccess) { tcsfm_posenet_destroy(q); return nullptr; }
     pn->clones.push_back(q);
     return q;
@@ -140,6 +153,7 @@ int tcsfm_posenet_load(tcsfm_posenet *pn, const float *const conv_w[7], const fl
     HIPCHK(h, hipMemcpy(pn->head_b, head_b, 6 * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(h, hipGetLastError());
     pn->loaded = 1;
+    pn->wt_valid = 0;        // the backward's transposed images follow w4: rebuilt at the next tcsfm_posenet_backward
     return TCSFM_OK;
 }
 
@@ -157,12 +171,29 @@ void pn_split(const tcsfm_posenet *pn, int l, int N, int *nb, int *ks, int *pb) 
     *pb = (cfg == 1 && l > 0 && *nb >= 2 && L.oh * L.ow >= pb_min_px) ? 2 : 1;
 }
 
+// The tape of a training forward over N images (tcsfm_posenet_forward_train), layer after layer: the reduced raw output
+// [N][npix][cout], the (scale, shift) pairs [N][cout][2], the groups' (mean, rstd) [N][16][2].  Offsets in floats; returns the total.
+struct PnTapeLayer { size_t raw, scsh, mr; };
+size_t pn_tape_layout(const tcsfm_posenet *pn, int N, PnTapeLayer t[7]) {
+    size_t o = 0;
+    for (int l = 0; l < 7; l++) {
+        const PnLayer &L = pn->L[l];
+        t[l].raw = o; o += (size_t)N * L.oh * L.ow * L.cout;
+        t[l].scsh = o; o += (size_t)N * L.cout * 2;
+        t[l].mr = o; o += (size_t)N * 32;
+    }
+    return o;
+}
+
 // the seven convolutions + statistics passes + head of one PoseNet evaluation on N samples; the first layer reads
-// (imgA | imgB) per sample (strides in floats; window indexing when win_B > 0)
+// (imgA | imgB) per sample (strides in floats; window indexing when win_B > 0).  tape: the same launches, and what the backward
+// needs is copied out layer by layer (pn_tape_layout)
 int pn_run(tcsfm_posenet *pn, int N, const float *imgA, long long strideA, const float *imgB, long long strideB, int win_B, int win_S,
-           float *pose, int accumulate, float *stacked, int it, int iters, const WinOff *wo = nullptr) {
+           float *pose, int accumulate, float *stacked, int it, int iters, const WinOff *wo = nullptr, float *tape = nullptr) {
     tcsfm_ctx *h = pn->h;
     pn->last_N = N;
+    PnTapeLayer tl[7];
+    if (tape) pn_tape_layout(pn, N, tl);
     for (int l = 0; l < 7; l++) {
         PnLayer L = pn->L[l];
         int nb, pb;
@@ -190,7 +221,12 @@ int pn_run(tcsfm_posenet *pn, int N, const float *imgA, long long strideA, const
         S.part = P.part; S.tiles = (int)grid.x;
         S.out = pn->act[l]; S.bias = pn->bias[l]; S.gamma = pn->gamma[l]; S.beta = pn->beta[l]; S.scsh = pn->scsh[l];
         S.N = N; S.npix = L.oh * L.ow; S.cout = L.cout; S.ksplit = L.ksplit;
+        S.mr = tape ? tape + tl[l].mr : nullptr;
         hipLaunchKernelGGL(k_pn_stats, dim3(N, 16), dim3(256), 0, h->stream, S);
+        if (tape) {          // K-split plane 0 holds the reduced sums once the statistics pass has run
+            HIPCHK(h, hipMemcpyAsync(tape + tl[l].raw, pn->act[l], (size_t)N * L.oh * L.ow * L.cout * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(tape + tl[l].scsh, pn->scsh[l], (size_t)N * L.cout * 2 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        }
     }
     PnHeadParams Hd;
     Hd.x = pn->act[6]; Hd.scsh = pn->scsh[6]; Hd.w = pn->head_w; Hd.b = pn->head_b; Hd.pose = pose; Hd.stacked = stacked;

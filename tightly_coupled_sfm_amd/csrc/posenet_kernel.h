@@ -418,6 +418,7 @@ struct PnStatsParams {
     const float *bias;      // [cout] or null (added here when ksplit > 1)
     const float *gamma, *beta;   // [cout] GroupNorm affine, or null (1, 0)
     float *scsh;            // [N][cout][2]
+    float *mr;              // optional [N][16][2]: the group's (mean, rstd), kept by the training forward (null: not stored)
     int N, npix, cout, ksplit;
 };
 
@@ -482,6 +483,7 @@ __global__ __launch_bounds__(256) void k_pn_stats(PnStatsParams P) {
     for (int o = 128; o > 0; o >>= 1) { if (tid < o) { r1[tid] += r1[tid + o]; r2[tid] += r2[tid + o]; } __syncthreads(); }
     const double mean = r1[0] / total, var = fmax(r2[0] / total - mean * mean, 0.0);
     const float rstd = (float)(1.0 / sqrt(var + 1e-5));
+    if (P.mr != nullptr && tid == 0) { P.mr[((size_t)n * 16 + g) * 2] = (float)mean; P.mr[((size_t)n * 16 + g) * 2 + 1] = rstd; }
     if (tid < cg) {
         const int c = g * cg + tid;
         const float sc = rstd * (P.gamma ? P.gamma[c] : 1.f);

@@ -124,6 +124,30 @@ class _SmoothLoss(torch.autograd.Function):
         return None, ctx.engine.smooth_loss_backward(disp, img, stats, _cot(g_loss)), None
 
 
+class _PoseNetInput(torch.autograd.Function):
+    """Engine.posenet_input under autograd: the same forward kernel; the cotangent of the reconstruction (channels 3..5) goes through
+    tcsfm_warp_backward (Engine.inverse_warp2_backward).  Channels 0..2 are tgt * valid: the validity mask is not differentiable
+    and the images take no gradient, so they carry none."""
+
+    @staticmethod
+    def forward(ctx, engine, t, s, dt, ds, p, K):
+        out = engine.posenet_input(t, s, dt, ds, p, K)
+        ctx.engine = engine
+        ctx.save_for_backward(s.contiguous(), dt.contiguous(), ds.contiguous(), p.contiguous(), K.contiguous())
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None, None, None
+        s, dt, ds, p, K = ctx.saved_tensors
+        # the warp is inverse_warp2(src, d_t, d_s, -pose, K) (train_mono.py:80): the gradient of -pose, negated, is the pose's
+        d_dt, d_ds, d_neg = ctx.engine.inverse_warp2_backward(s, dt, ds, -p, K, g_rec=g[:, 3:6].contiguous(), want=tuple(ctx.needs_input_grad[3:6]))
+        return None, None, None, d_dt, d_ds, (None if d_neg is None else -d_neg), None
+
+
 class Engine:
     """One handle = one GPU + one HIP stream (include/tcsfm.h).  ``max_pairs`` directed pairs of HxW."""
 
@@ -376,7 +400,8 @@ class Engine:
 
     def posenet_input(self, target_img, source_img, target_depth, source_depth, pose, intrinsics):
         """(tgt * valid | img_rec) [N,6,H,W] for the next PoseNet call of the coupled iteration (train_mono.py:73-77);
-        `pose` is the estimate so far in the reference convention (the warp uses -pose like train_mono.py:80)."""
+        `pose` is the estimate so far in the reference convention (the warp uses -pose like train_mono.py:80).  Never carries a
+        grad_fn: posenet_input_autograd is the differentiable form."""
         self._bind()
         N = target_img.shape[0]
         H, W = self.H, self.W
@@ -388,6 +413,15 @@ class Engine:
         self._call(self.lib.tcsfm_warp_posenet_input(self._h, C.byref(o), N, self._p(t), self._p(s), self._p(dt), self._p(ds), self._p(p),
                                                      self._p(K), self._p(out), None))
         return out
+
+    def posenet_input_autograd(self, target_img, source_img, target_depth, source_depth, pose, intrinsics):
+        """posenet_input with a grad_fn towards the depths and the pose: the same forward kernel (the same bits); channels 3..5 (the
+        reconstruction) go back through the warp's HIP backward (tcsfm_warp_backward), channels 0..2 (tgt * valid) carry no gradient
+        because the validity mask is not differentiable.  Images or intrinsics that require grad raise NotImplementedError."""
+        if target_img.requires_grad or source_img.requires_grad or intrinsics.requires_grad:
+            raise NotImplementedError("posenet_input has no gradient with respect to the images or the intrinsics "
+                                      "(DESIGN.md section 7: gradients with respect to the images stay out of scope)")
+        return _PoseNetInput.apply(self, target_img, source_img, target_depth, source_depth, pose, intrinsics)
 
     def _photometric(self, t, s, dt, ds, p, K, o):
         N = t.shape[0]

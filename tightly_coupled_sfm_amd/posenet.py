@@ -36,9 +36,37 @@ def is_reference_posenet(module) -> bool:
     return all(k in sd for k in need) and tuple(sd["conv1.0.weight"].shape) == (16, 6, 7, 7) and tuple(sd["pose_pred.weight"].shape[:2]) == (6, 256)
 
 
+class _PoseNetInputGrad(torch.autograd.Function):
+    """PoseNetHIP.__call__ under autograd: tcsfm_posenet_forward_train / tcsfm_posenet_backward.  Differentiable with respect to the
+    images only: the weights are the library's frozen copy (the reference's default tuning mode, optimize_depth_encoder)."""
+
+    @staticmethod
+    def forward(ctx, net, imgs):
+        pose, tape = net.forward_train(imgs)
+        ctx.net, ctx.stamp = net, net._stamp
+        ctx.save_for_backward(tape)
+        ctx.set_materialize_grads(False)
+        return pose
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_pose):
+        if g_pose is None:
+            return None, None
+        ctx.net._check_stamp(ctx.stamp)
+        tape, = ctx.saved_tensors
+        return None, ctx.net.backward(tape, g_pose.contiguous())
+
+
 class PoseNetHIP:
     """pose_model.forward on the engine's GPU.  `params`: a reference pose_model (nn.Module) or its state_dict / a dict of
-    numpy arrays under the same names."""
+    numpy arrays under the same names.
+
+    Under autograd (grad enabled and ``imgs.requires_grad``) the pose carries a grad_fn: the gradient with respect to the IMAGES
+    (csrc/posenet_grad_kernel.h).  The parameters get no gradient -- they are the library's frozen copy, as in the reference's
+    default test-time tuning mode; tuning the pose network's weights (optimize_pose_weights_all) is out of scope."""
+
+    _stamp = 0               # counts load() calls: a backward refuses a tape made with other weights
 
     def __init__(self, engine: Engine, max_images: int, params=None):
         self.eng, self.lib = engine, engine.lib
@@ -76,7 +104,13 @@ class PoseNetHIP:
         hw, hb = arr("pose_pred.weight").reshape(6, 256).copy(), arr("pose_pred.bias")
         self.eng._bind()
         self.eng._call(self.lib.tcsfm_posenet_load(self._pn, cw, cb, gw, gb, hw.ctypes.data_as(C.c_void_p), hb.ctypes.data_as(C.c_void_p)))
+        self._stamp += 1
         return self
+
+    def _check_stamp(self, stamp):
+        if stamp != self._stamp:
+            raise RuntimeError("PoseNetHIP: the weights were loaded again between this forward and its backward: the tape belongs "
+                               "to the earlier weights (run the forward again)")
 
     def load_checkpoint(self, path: str, load_best: bool = True):
         """The reference's checkpoint files (utils/learning_helpers.py:20-48: `torch.save` of a dict whose 'pose_state_dict' entry is
@@ -84,14 +118,59 @@ class PoseNetHIP:
         self.load(read_pose_state_dict(path, load_best))
 
     def __call__(self, imgs: torch.Tensor) -> torch.Tensor:
-        """pose_model(imgs): imgs [N,6,H,W] -> [N,6]"""
+        """pose_model(imgs): imgs [N,6,H,W] -> [N,6]; with a grad_fn (towards imgs only) when grad is enabled and imgs requires grad"""
         e = self.eng
         e._bind()
         N = imgs.shape[0]
         imgs = _chk(imgs, (N, 6, e.H, e.W), "imgs")
+        if torch.is_grad_enabled() and imgs.requires_grad:
+            return _PoseNetInputGrad.apply(self, imgs)
         out = torch.empty((N, 6), device=imgs.device, dtype=torch.float32)
         e._call(self.lib.tcsfm_posenet_forward(self._pn, N, e._p(imgs), e._p(out)))
         return out
+
+    def tape_size(self, N: int) -> int:
+        n = C.c_int64(0)
+        self.eng._call(self.lib.tcsfm_posenet_tape_size(self._pn, int(N), C.byref(n)))
+        return int(n.value)
+
+    def forward_train(self, imgs: torch.Tensor):
+        """tcsfm_posenet_forward_train: imgs [N,6,H,W] -> (pose [N,6] with the bits of __call__, tape) -- the tape (a flat float32
+        tensor, layout in include/tcsfm.h) is what backward needs; the images themselves are not kept"""
+        e = self.eng
+        e._bind()
+        N = imgs.shape[0]
+        imgs = _chk(imgs.detach(), (N, 6, e.H, e.W), "imgs")
+        pose = torch.empty((N, 6), device=imgs.device, dtype=torch.float32)
+        tape = torch.empty((self.tape_size(N),), device=imgs.device, dtype=torch.float32)
+        e._call(self.lib.tcsfm_posenet_forward_train(self._pn, N, e._p(imgs), e._p(pose), e._p(tape)))
+        return pose, tape
+
+    def backward(self, tape: torch.Tensor, d_pose: torch.Tensor) -> torch.Tensor:
+        """tcsfm_posenet_backward: the tape of forward_train and the pose's cotangent [N,6] -> d_imgs [N,6,H,W], with the current weights"""
+        e = self.eng
+        e._bind()
+        N = d_pose.shape[0]
+        d_pose = _chk(d_pose, (N, 6), "d_pose")
+        tape = _chk(tape, (self.tape_size(N),), "tape")
+        d_imgs = torch.empty((N, 6, e.H, e.W), device=d_pose.device, dtype=torch.float32)
+        e._call(self.lib.tcsfm_posenet_backward(self._pn, N, e._p(tape), e._p(d_pose), e._p(d_imgs)))
+        return d_imgs
+
+    def tape_layer(self, tape: torch.Tensor, layer: int, N: int):
+        """tcsfm_debug_posenet_tape_layer: layer 1..7 of a tape -> (raw [N,cout,oh,ow], scsh [N,cout,2], mean_rstd [N,16,2],
+        act [N,cout,oh,ow]); act > 0 are the ReLU decisions backward takes"""
+        e = self.eng
+        e._bind()
+        oh, ow = self.split(layer, N)[:2]
+        cout = [16, 32, 64, 128, 256, 256, 256][int(layer) - 1]
+        tape = _chk(tape, (self.tape_size(N),), "tape")
+        raw = torch.empty((int(N), oh, ow, cout), device=tape.device, dtype=torch.float32)
+        act = torch.empty_like(raw)
+        scsh = torch.empty((int(N), cout, 2), device=tape.device, dtype=torch.float32)
+        mr = torch.empty((int(N), 16, 2), device=tape.device, dtype=torch.float32)
+        e._call(self.lib.tcsfm_debug_posenet_tape_layer(self._pn, int(N), e._p(tape), int(layer), e._p(raw), e._p(scsh), e._p(mr), e._p(act)))
+        return raw.permute(0, 3, 1, 2), scsh, mr, act.permute(0, 3, 1, 2)
 
     def split(self, layer: int, N: int):
         """tcsfm_debug_posenet_split: (oh, ow, nb, ks, pb) of layer 1..7 in a call over N images"""

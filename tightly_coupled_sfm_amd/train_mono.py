@@ -8,6 +8,13 @@ residual assembly of every directed pair, forward and inverse, of a window.
     between its calls still runs in the library: the (target x valid | reconstruction) input of the next call is written by the
     warp kernel itself (:73-77).
   * the residual maps of all 2 S B directed pairs come from one fused launch (:82-100).
+  * Under autograd -- grad enabled, a depth that requires grad, num_iter > 1 and a pose model the library evaluates -- the loop runs
+    as the composition of two autograd Functions per iteration, Engine.posenet_input_autograd (the warp, HIP backward
+    tcsfm_warp_backward) and PoseNetHIP.__call__ (HIP backward tcsfm_posenet_backward, towards the network's input): the same
+    kernels as the fused loop, so stacked_poses, the poses and every map of `outputs` have its bits, and they carry the gradient the
+    reference's loss.backward() follows through the poses.  The first call does not depend on the depths and stays plain.  The pose
+    model's PARAMETERS get no gradient (their .grad stays None, whatever their requires_grad says): the library evaluates a frozen
+    copy, which is the reference's default tuning mode (optimize_depth_encoder); optimize_pose_weights_all is out of scope.
 """
 from __future__ import annotations
 
@@ -50,7 +57,16 @@ def solve_pose_iteratively(num_iter, depths, pose_model, target_img, source_img_
     d_s = torch.cat([source_depths, target_depths], 0).contiguous()
     tgt, src = imgs[:, 0:3].contiguous(), imgs[:, 3:6].contiguous()
     net = _library_posenet(pose_model, eng, 2 * split)
-    if net is not None:       # network, warps and corrections of all iterations inside the library (:64-80)
+    if net is not None and num_iter > 1 and torch.is_grad_enabled() and any(d.requires_grad for d in depths):
+        with torch.no_grad():
+            full_poses = net(imgs.contiguous())                                                                    # :64, no depth in it
+        stacked = [full_poses]
+        for _ in range(num_iter - 1):                                                                              # :73-80
+            new_imgs = eng.posenet_input_autograd(tgt, src, d_t, d_s, full_poses, K)
+            full_poses = full_poses + net(new_imgs)
+            stacked.append(full_poses)
+        stacked_poses = torch.stack(stacked, 1)
+    elif net is not None:     # network, warps and corrections of all iterations inside the library (:64-80)
         full_poses, stacked_poses = net.solve_pose_iteratively(num_iter, target_img.float(), [s.float() for s in source_img_list],
                                                                depths[0].float(), [d.float() for d in depths[1:]], intrinsics.float())
     else:
