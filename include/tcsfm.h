@@ -419,7 +419,7 @@ int tcsfm_solve_pose_iteratively(tcsfm_handle h, tcsfm_posenet *pn, int num_iter
  * In the coupled loop every PoseNet call after the first reads (tgt * valid | img_rec), and img_rec is the warp of the source under
  * the current depths and pose: with the network's weights frozen (the reference's default test-time tuning mode) the depths reach
  * the poses through the network's INPUT.  These calls differentiate the network with respect to it (csrc/posenet_grad_kernel.h);
- * the parameters get no gradient.
+ * the parameters' gradient is the next section's.
  *   tcsfm_posenet_tape_size      floats of the tape of an N-image training forward.  Layout, layer after layer (l = 1..7, npix = oh ow
  *                                of the layer): raw [N][npix][cout] (the reduced convolution output + bias, NHWC), scsh [N][cout][2]
  *                                (GroupNorm scale = rstd gamma, shift = beta - mean scale), mean_rstd [N][16][2] (per group; rstd cannot
@@ -438,6 +438,31 @@ int tcsfm_solve_pose_iteratively(tcsfm_handle h, tcsfm_posenet *pn, int num_iter
 int tcsfm_posenet_tape_size(tcsfm_posenet *pn, int N, int64_t *floats_out);
 int tcsfm_posenet_forward_train(tcsfm_posenet *pn, int N, const float *imgs, float *pose_out, float *tape);
 int tcsfm_posenet_backward(tcsfm_posenet *pn, int N, const float *tape, const float *d_pose, float *d_imgs);
+
+/* ---- PoseNet: gradient with respect to the parameters -----------------------------------------------
+ * The reference's optimize_pose_weights_all mode (optimization_experiments/optimizer.py:187-189) puts the pose model's parameters
+ * into the optimiser and backpropagates through solve_pose_iteratively into them (csrc/posenet_wgrad_kernel.h).
+ *   tcsfm_posenet_load_device    tcsfm_posenet_load from DEVICE pointers (same layouts, same NULL conventions), asynchronous on the
+ *                                handle's stream: no host staging and no synchronisation, so that a reload after every optimiser step
+ *                                is cheap.  The prepared weights have the bits tcsfm_posenet_load gives for the same values; the
+ *                                backward's transposed weight images are rebuilt at the next backward.  Both loads keep a copy of the
+ *                                raw weights per owning instance (the chain rule through the weight standardisation reads it).
+ *   tcsfm_posenet_param_backward one backward walk: every layer's dz feeds the data gradient and the parameter gradients.
+ *                                imgs [N,6,H,W]: the images of the forward (the tape does not hold them), read only when
+ *                                conv_w_g[0] is asked for.  d_imgs may be NULL (then layer 1's data gradient is skipped); when given
+ *                                it has the bits of tcsfm_posenet_backward.  Every gradient pointer and every table may be NULL:
+ *                                work nobody asked for is skipped, down to stopping the walk at the lowest layer that is needed.
+ *                                Outputs (device) are OVERWRITTEN, in the reference's layouts: conv_w_g[l] [cout,cin,k,k] (the
+ *                                gradient of the RAW weight, conv2d_wn's standardisation differentiated), conv_b_g / gn_w_g /
+ *                                gn_b_g[l] [cout], head_w_g [6,256], head_b_g [6].  Exact fp32 products on the matrix cores, per-channel
+ *                                and per-filter sums in double, no float atomics, fixed summation order: bit-reproducible.  Uses
+ *                                the instance's CURRENT weights, as tcsfm_posenet_backward does.  N <= max_images; lane clones are
+ *                                refused. */
+int tcsfm_posenet_load_device(tcsfm_posenet *pn, const float *const conv_w[7], const float *const conv_b[7], const float *const gn_w[7],
+                              const float *const gn_b[7], const float *head_w, const float *head_b);
+int tcsfm_posenet_param_backward(tcsfm_posenet *pn, int N, const float *imgs, const float *tape, const float *d_pose, float *d_imgs,
+                                 float *const conv_w_g[7], float *const conv_b_g[7], float *const gn_w_g[7], float *const gn_b_g[7],
+                                 float *head_w_g, float *head_b_g);
 
 /* ---- depth network --------------------------------------------------------------------------------
  * The reference's depth network (models/depth_w_access.py with num_scales = 1, the default of run_mono_training.py): a ResNet18

@@ -147,6 +147,8 @@ _SIGNATURES = {
     "tcsfm_posenet_forward_train": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "tcsfm_posenet_backward": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "tcsfm_debug_posenet_tape_layer": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
+    "tcsfm_posenet_load_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "tcsfm_posenet_param_backward": (C.c_int, [_P, C.c_int] + [_P] * 10),
     "tcsfm_depthnet_create": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "tcsfm_depthnet_destroy": (None, [_P]),
     "tcsfm_depthnet_load": (C.c_int, [_P, C.c_int, _P, _P, _P]),

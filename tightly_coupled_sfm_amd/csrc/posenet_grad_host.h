@@ -1,4 +1,5 @@
-// Host side of the PoseNet's input gradient (posenet_grad_kernel.h): the training forward with its tape and the backward walk.
+// Host side of the PoseNet's gradients: the training forward with its tape and the backward walk that gives the input gradient
+// (posenet_grad_kernel.h) and, for tcsfm_posenet_param_backward, the parameter gradients (posenet_wgrad_kernel.h, posenet_wgrad_host.h).
 // Part of tcsfm_api.hip, the library's only translation unit: included after posenet_host.h (tcsfm_posenet, pn_run, pn_tape_layout)
 // and depthnet_host.h, whose data-gradient dispatch (dn_split, dn_launch_ks<DnDgradKernel, KS>) layers 2..7 share.
 #pragma once
@@ -63,34 +64,42 @@ int tcsfm_posenet_forward_train(tcsfm_posenet *pn, int N, const float *imgs, flo
     return pn_run(pn, N, imgs, 6 * hw, imgs + 3 * hw, 6 * hw, 0, 0, pose_out, 0, nullptr, 0, 1, nullptr, tape);
 }
 
-int tcsfm_posenet_backward(tcsfm_posenet *pn, int N, const float *tape, const float *d_pose, float *d_imgs) {
-    if (!pn) return TCSFM_E_ARG;
+namespace {
+// The backward walk, shared by tcsfm_posenet_backward (req null) and tcsfm_posenet_param_backward: one dz per layer feeds the data
+// gradient and, where asked for, the parameter gradients.  d_imgs null: layer 1's data gradient is skipped.
+int pnb_walk(tcsfm_posenet *pn, int N, const float *imgs, const float *tape, const float *d_pose, float *d_imgs, const PnwReq *req) {
     tcsfm_ctx *h = pn->h;
-    if (int rc = pn_check_train(pn, N, "tcsfm_posenet_backward")) return rc;
-    if (!tape) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_backward: tape is NULL");
-    if (((uintptr_t)tape & 15) != 0) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_backward: tape must be 16-byte aligned");
-    if (!d_pose) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_backward: d_pose is NULL");
-    if (!d_imgs) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_backward: d_imgs is NULL");
-    if (int rc_q = drain_queued(h)) return rc_q;
-    DeviceGuard dev_guard(h->device);
-    if (int rc = pnb_prepare(pn)) return rc;
     PnTapeLayer tl[7];
     pn_tape_layout(pn, N, tl);
     hipStream_t s = h->stream;
     float *da = pn->gbuf[0], *nxt = pn->gbuf[1];
     const int npix7 = pn->L[6].oh * pn->L[6].ow;
+    if (req && (req->hw || req->hb))
+        hipLaunchKernelGGL(k_pnw_head, dim3(16), dim3(256), 0, s, tape + tl[6].raw, tape + tl[6].scsh, d_pose, req->hw, req->hb, N, npix7);
+    int last = 0;            // the lowest layer whose dz somebody needs
+    if (!d_imgs) {
+        last = 7;
+        for (int l = 6; l >= 0; l--)
+            if (req && (req->w[l] || req->b[l] || req->g[l] || req->be[l])) last = l;
+        if (last == 7) { HIPCHK(h, hipGetLastError()); return TCSFM_OK; }
+    }
     hipLaunchKernelGGL(k_pnb_head, dim3(dn_blocks((long long)N * npix7 * 256)), dim3(256), 0, s, d_pose, (const float *)pn->head_w, da, N, npix7);
-    for (int l = 6; l >= 0; l--) {
+    for (int l = 6; l >= last; l--) {
         const PnLayer &L = pn->L[l];
         PnbNormParams P;
         P.da = da; P.raw = tape + tl[l].raw; P.scsh = tape + tl[l].scsh; P.mr = tape + tl[l].mr; P.gamma = pn->gamma[l];
         P.ss = pn->gss; P.dz = da; P.N = N; P.npix = L.oh * L.ow; P.cout = L.cout;
+        if (req && (req->be[l] || req->g[l])) pnw_chan(pn, P, 0, req->be[l], req->g[l]);
         hipLaunchKernelGGL(k_pnb_gsum, dim3(N, 16), dim3(256), 0, s, P);
         hipLaunchKernelGGL(k_pnb_dz, dim3(dn_blocks((long long)N * P.npix * (L.cout / 4))), dim3(256), 0, s, P);
-        if (l == 0) {
-            const int hh = (L.ih + 1) / 2, wh = (L.iw + 1) / 2;
-            hipLaunchKernelGGL(k_pnb_dgrad1, dim3(dn_blocks((long long)hh * wh), 4, N), dim3(256), 0, s, (const float *)da,
-                               (const float *)reinterpret_cast<float *>(pn->wt4[0]), d_imgs, L.ih, L.iw, L.oh, L.ow);
+        if (req && req->b[l]) pnw_chan(pn, P, 1, req->b[l], nullptr);
+        if (req && req->w[l]) pnw_wgrad(pn, l, N, da, l == 0 ? imgs : tape + tl[l - 1].raw, l == 0 ? nullptr : tape + tl[l - 1].scsh, req->w[l]);
+        if (l == last) {
+            if (l == 0 && d_imgs) {
+                const int hh = (L.ih + 1) / 2, wh = (L.iw + 1) / 2;
+                hipLaunchKernelGGL(k_pnb_dgrad1, dim3(dn_blocks((long long)hh * wh), 4, N), dim3(256), 0, s, (const float *)da,
+                                   (const float *)reinterpret_cast<float *>(pn->wt4[0]), d_imgs, L.ih, L.iw, L.oh, L.ow);
+            }
             break;
         }
         // data gradient onto the layer's input grid: k_dnb_dgrad "direct" (zero padding, stride 2), nothing fused in its epilogue.
@@ -109,6 +118,44 @@ int tcsfm_posenet_backward(tcsfm_posenet *pn, int N, const float *tape, const fl
     }
     HIPCHK(h, hipGetLastError());
     return TCSFM_OK;
+}
+}  // namespace
+
+int tcsfm_posenet_backward(tcsfm_posenet *pn, int N, const float *tape, const float *d_pose, float *d_imgs) {
+    if (!pn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = pn->h;
+    if (int rc = pn_check_train(pn, N, "tcsfm_posenet_backward")) return rc;
+    if (!tape) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_backward: tape is NULL");
+    if (((uintptr_t)tape & 15) != 0) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_backward: tape must be 16-byte aligned");
+    if (!d_pose) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_backward: d_pose is NULL");
+    if (!d_imgs) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_backward: d_imgs is NULL");
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    if (int rc = pnb_prepare(pn)) return rc;
+    return pnb_walk(pn, N, nullptr, tape, d_pose, d_imgs, nullptr);
+}
+
+int tcsfm_posenet_param_backward(tcsfm_posenet *pn, int N, const float *imgs, const float *tape, const float *d_pose, float *d_imgs,
+                                 float *const conv_w_g[7], float *const conv_b_g[7], float *const gn_w_g[7], float *const gn_b_g[7],
+                                 float *head_w_g, float *head_b_g) {
+    if (!pn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = pn->h;
+    if (int rc = pn_check_train(pn, N, "tcsfm_posenet_param_backward")) return rc;
+    if (!tape) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_param_backward: tape is NULL");
+    if (((uintptr_t)tape & 15) != 0) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_param_backward: tape must be 16-byte aligned");
+    if (!d_pose) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_param_backward: d_pose is NULL");
+    PnwReq req;
+    for (int l = 0; l < 7; l++) {
+        req.w[l] = conv_w_g ? conv_w_g[l] : nullptr; req.b[l] = conv_b_g ? conv_b_g[l] : nullptr;
+        req.g[l] = gn_w_g ? gn_w_g[l] : nullptr; req.be[l] = gn_b_g ? gn_b_g[l] : nullptr;
+    }
+    req.hw = head_w_g; req.hb = head_b_g;
+    if (req.w[0] && !imgs) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_param_backward: imgs is NULL (conv1's weight gradient reads the images)");
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    if (int rc = pnb_prepare(pn)) return rc;
+    if (int rc = pnw_prepare(pn)) return rc;
+    return pnb_walk(pn, N, imgs, tape, d_pose, d_imgs, &req);
 }
 
 int tcsfm_debug_posenet_tape_layer(tcsfm_posenet *pn, int N, const float *tape, int layer, float *raw_out, float *scsh_out,

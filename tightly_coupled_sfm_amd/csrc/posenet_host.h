@@ -13,7 +13,7 @@ struct tcsfm_posenet {
     pn_f4 *w4[7] = {};
     float *bias[7] = {}, *gamma[7] = {}, *beta[7] = {};
     float *act[7] = {}, *scsh[7] = {}, *part[7] = {};
-    float *head_w = nullptr, *head_b = nullptr, *raw = nullptr;
+    float *head_w = nullptr, *head_b = nullptr;
     float *in_buf = nullptr;     // [max_images,6,H,W] (tgt * valid | img_rec) written by the warp kernel
     float *pose = nullptr;       // [max_images,6] running pose of the coupled loop
     // tcsfm_odometry_sequence runs the network on the handle's lanes: clone k works on lane k with its own activations and
@@ -26,6 +26,11 @@ struct tcsfm_posenet {
     pn_f4 *wt4[7] = {};
     int wt_valid = 0;
     float *gbuf[2] = {}, *gss = nullptr;
+    // tcsfm_posenet_param_backward (posenet_wgrad_host.h): the RAW weights of the load (conv2d_wn's chain rule needs them; kept by both
+    // load paths), and, built at the first parameter backward, the weight-gradient partials and the per-channel double partials
+    float *raww[7] = {};
+    float *wpart = nullptr;
+    double *cpart = nullptr;
 };
 
 void tcsfm_posenet_destroy(tcsfm_posenet *pn) {
@@ -37,12 +42,13 @@ void tcsfm_posenet_destroy(tcsfm_posenet *pn) {
         if (pn->owns_weights) for (void *p : weights) if (p) (void)hipFree(p);
         for (void *p : scratch) if (p) (void)hipFree(p);
     }
-    void *weights[] = {pn->head_w, pn->head_b, pn->raw}, *scratch[] = {pn->in_buf, pn->pose};
+    void *weights[] = {pn->head_w, pn->head_b, pn->raww[0], pn->raww[1], pn->raww[2], pn->raww[3], pn->raww[4], pn->raww[5], pn->raww[6]};
+    void *scratch[] = {pn->in_buf, pn->pose};
     if (pn->owns_weights) for (void *p : weights) if (p) (void)hipFree(p);
     for (void *p : scratch) if (p) (void)hipFree(p);
     if (pn->owns_weights) {
         for (int l = 0; l < 7; l++) if (pn->wt4[l]) (void)hipFree(pn->wt4[l]);
-        void *grad[] = {pn->gbuf[0], pn->gbuf[1], pn->gss};
+        void *grad[] = {pn->gbuf[0], pn->gbuf[1], pn->gss, pn->wpart, pn->cpart};
         for (void *p : grad) if (p) (void)hipFree(p);
     }
     delete pn;
@@ -75,6 +81,7 @@ static tcsfm_posenet *pn_for_lane(tcsfm_posenet *pn, tcsfm_ctx *c) {
     q->in_buf = q->pose = nullptr;
     for (int l = 0; l < 7; l++) q->wt4[l] = nullptr;
     q->gbuf[0] = q->gbuf[1] = q->gss = nullptr; q->wt_valid = 0;
+    q->wpart = nullptr; q->cpart = nullptr;
     if (pn_alloc_scratch(q) != hipSuccess) { tcsfm_posenet_destroy(q); return nullptr; }
     pn->clones.push_back(q);
     return q;
@@ -90,7 +97,6 @@ int tcsfm_posenet_create(tcsfm_handle h, int max_images, tcsfm_posenet **out) {
     static const int chans[8] = {6, 16, 32, 64, 128, 256, 256, 256}, ksz[7] = {7, 5, 3, 3, 3, 3, 3};
     int ih = h->H, iw = h->W;
     hipError_t e = hipSuccess;
-    size_t wmax = 0;
     for (int l = 0; l < 7; l++) {
         PnLayer &L = pn->L[l];
         L.cin = chans[l]; L.cout = chans[l + 1]; L.ks = ksz[l]; L.pad = (ksz[l] - 1) / 2;
@@ -119,12 +125,11 @@ int tcsfm_posenet_create(tcsfm_handle h, int max_images, tcsfm_posenet **out) {
         if (e == hipSuccess) e = hipMalloc((void **)&pn->bias[l], L.cout * sizeof(float));
         if (e == hipSuccess) e = hipMalloc((void **)&pn->gamma[l], L.cout * sizeof(float));
         if (e == hipSuccess) e = hipMalloc((void **)&pn->beta[l], L.cout * sizeof(float));
-        wmax = std::max(wmax, (size_t)L.cout * L.cin * L.ks * L.ks);
+        if (e == hipSuccess) e = hipMalloc((void **)&pn->raww[l], (size_t)L.cout * L.cin * L.ks * L.ks * sizeof(float));
         ih = L.oh; iw = L.ow;
     }
     if (e == hipSuccess) e = hipMalloc((void **)&pn->head_w, 6 * 256 * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&pn->head_b, 6 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&pn->raw, wmax * sizeof(float));
     if (e == hipSuccess) e = pn_alloc_scratch(pn);
     if (e != hipSuccess) { tcsfm_posenet_destroy(pn); return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_posenet_create: allocation failed"); }
     *out = pn;
@@ -141,9 +146,9 @@ int tcsfm_posenet_load(tcsfm_posenet *pn, const float *const conv_w[7], const fl
         const PnLayer &L = pn->L[l];
         if (!conv_w[l]) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_load: NULL convolution weight");
         const size_t nw = (size_t)L.cout * L.cin * L.ks * L.ks;
-        HIPCHK(h, hipMemcpyAsync(pn->raw, conv_w[l], nw * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_pn_prep, dim3(L.cout), dim3(256), 0, h->stream, (const float *)pn->raw, pn->w4[l], L.cin, L.cout, L.ks, l == 0 ? 1 : 0, 1);
-        HIPCHK(h, hipStreamSynchronize(h->stream));    // pn->raw is reused by the next layer; loading happens once per model
+        HIPCHK(h, hipMemcpyAsync(pn->raww[l], conv_w[l], nw * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_pn_prep, dim3(L.cout), dim3(256), 0, h->stream, (const float *)pn->raww[l], pn->w4[l], L.cin, L.cout, L.ks, l == 0 ? 1 : 0, 1);
+        HIPCHK(h, hipStreamSynchronize(h->stream));    // the caller's host arrays are free once this returns; loading happens once per model
         std::vector<float> ones(L.cout, 1.f), zeros(L.cout, 0.f);
         HIPCHK(h, hipMemcpy(pn->bias[l], conv_b && conv_b[l] ? conv_b[l] : zeros.data(), L.cout * sizeof(float), hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(pn->gamma[l], gn_w && gn_w[l] ? gn_w[l] : ones.data(), L.cout * sizeof(float), hipMemcpyHostToDevice));
@@ -154,6 +159,39 @@ int tcsfm_posenet_load(tcsfm_posenet *pn, const float *const conv_w[7], const fl
     HIPCHK(h, hipGetLastError());
     pn->loaded = 1;
     pn->wt_valid = 0;        // the backward's transposed images follow w4: rebuilt at the next tcsfm_posenet_backward
+    return TCSFM_OK;
+}
+
+// The same from DEVICE pointers, stream-ordered: no host staging and no synchronisation, cheap enough to run after every optimiser
+// step.  k_pn_prep reads the kept raw copy, as in tcsfm_posenet_load: the prepared weights have the same bits for the same values.
+int tcsfm_posenet_load_device(tcsfm_posenet *pn, const float *const conv_w[7], const float *const conv_b[7], const float *const gn_w[7],
+                              const float *const gn_b[7], const float *head_w, const float *head_b) {
+    if (!pn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = pn->h;
+    if (!conv_w || !head_w || !head_b) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_load_device: NULL argument");
+    if (!pn->owns_weights) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_load_device: pn is a lane clone");
+    for (int l = 0; l < 7; l++)
+        if (!conv_w[l]) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_load_device: NULL convolution weight");
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    hipStream_t s = h->stream;
+    for (int l = 0; l < 7; l++) {
+        const PnLayer &L = pn->L[l];
+        const size_t nw = (size_t)L.cout * L.cin * L.ks * L.ks, nc = L.cout * sizeof(float);
+        HIPCHK(h, hipMemcpyAsync(pn->raww[l], conv_w[l], nw * sizeof(float), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_pn_prep, dim3(L.cout), dim3(256), 0, s, (const float *)pn->raww[l], pn->w4[l], L.cin, L.cout, L.ks, l == 0 ? 1 : 0, 1);
+        const float *src[3] = {conv_b ? conv_b[l] : nullptr, gn_w ? gn_w[l] : nullptr, gn_b ? gn_b[l] : nullptr};
+        float *dst[3] = {pn->bias[l], pn->gamma[l], pn->beta[l]};
+        for (int k = 0; k < 3; k++) {
+            if (src[k]) HIPCHK(h, hipMemcpyAsync(dst[k], src[k], nc, hipMemcpyDeviceToDevice, s));
+            else hipLaunchKernelGGL(k_pnw_fill, dim3((L.cout + 255) / 256), dim3(256), 0, s, dst[k], L.cout, k == 1 ? 1.f : 0.f);
+        }
+    }
+    HIPCHK(h, hipMemcpyAsync(pn->head_w, head_w, 6 * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(pn->head_b, head_b, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipGetLastError());
+    pn->loaded = 1;
+    pn->wt_valid = 0;
     return TCSFM_OK;
 }
 

@@ -20,6 +20,7 @@
 #include "depthnet_kernel.h"
 #include "depthnet_grad_kernel.h"
 #include "posenet_grad_kernel.h"
+#include "posenet_wgrad_kernel.h"
 #include "warp_grad_kernel.h"
 #include "photo_grad_kernel.h"
 #include "loss_grad_kernel.h"
@@ -3126,6 +3127,7 @@ int tcsfm_profile_kernel_busy(tcsfm_handle h, double *ms_busy, int64_t *launches
 }
 
 #include "depthnet_host.h"
+#include "posenet_wgrad_host.h"
 #include "posenet_grad_host.h"
 
 void tcsfm_pose_to_matrix(const double pose[6], double T[12]) { tc::pose_to_T(pose, T); }

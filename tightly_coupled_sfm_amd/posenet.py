@@ -13,6 +13,17 @@ from . import _lib
 from .engine import Engine, _chk
 
 _CONV = ["conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7"]
+_CHANS, _KSZ = [6, 16, 32, 64, 128, 256, 256, 256], [7, 5, 3, 3, 3, 3, 3]
+PARAM_SHAPES_W = [(_CHANS[l + 1], _CHANS[l], _KSZ[l], _KSZ[l]) for l in range(7)]
+# the reference pose_model's parameters in module order: name -> shape
+PARAM_SHAPES = {}
+for _l, _c in enumerate(_CONV):
+    PARAM_SHAPES[f"{_c}.0.weight"] = PARAM_SHAPES_W[_l]
+    for _k in ("0.bias", "1.weight", "1.bias"):
+        PARAM_SHAPES[f"{_c}.{_k}"] = (_CHANS[_l + 1],)
+PARAM_SHAPES["pose_pred.weight"] = (6, 256, 1, 1)
+PARAM_SHAPES["pose_pred.bias"] = (6,)
+PARAM_NAMES = tuple(PARAM_SHAPES)
 
 
 def read_pose_state_dict(path: str, load_best: bool = True) -> dict:
@@ -63,8 +74,10 @@ class PoseNetHIP:
     numpy arrays under the same names.
 
     Under autograd (grad enabled and ``imgs.requires_grad``) the pose carries a grad_fn: the gradient with respect to the IMAGES
-    (csrc/posenet_grad_kernel.h).  The parameters get no gradient -- they are the library's frozen copy, as in the reference's
-    default test-time tuning mode; tuning the pose network's weights (optimize_pose_weights_all) is out of scope."""
+    (csrc/posenet_grad_kernel.h).  Through __call__ the parameters get no gradient -- they are the library's frozen copy, as in the
+    reference's default test-time tuning mode.  Tuning the pose network's weights (the reference's optimize_pose_weights_all) goes
+    through `param_backward` (csrc/posenet_wgrad_kernel.h: every parameter's gradient from the same tape) and `load_device` (a
+    stream-ordered reload from device tensors); posenet_train.PoseNetModule wraps both as a torch.nn.Module."""
 
     _stamp = 0               # counts load() calls: a backward refuses a tape made with other weights
 
@@ -106,6 +119,66 @@ class PoseNetHIP:
         self.eng._call(self.lib.tcsfm_posenet_load(self._pn, cw, cb, gw, gb, hw.ctypes.data_as(C.c_void_p), hb.ctypes.data_as(C.c_void_p)))
         self._stamp += 1
         return self
+
+    def load_device(self, named):
+        """tcsfm_posenet_load_device: `named` maps the reference's parameter names to contiguous float32 tensors on the engine's
+        device (conv{l}.0.bias and conv{l}.1.weight / .bias may be absent: 0, 1, 0).  Asynchronous, no host copy; same prepared
+        weights as load() of the same values."""
+        e = self.eng
+        keep = []
+
+        def one(k, shape, required):
+            if k not in named or named[k] is None:
+                if required:
+                    raise KeyError(f"PoseNetHIP.load_device: {k}: missing")
+                return None
+            t = named[k].detach()
+            if t.dim() == 4 and len(shape) == 2:
+                t = t.reshape(shape)
+            t = _chk(t, shape, k)
+            keep.append(t)
+            return e._p(t).value
+
+        def table(suffix, shapes, required=False):
+            return (C.c_void_p * 7)(*[one(f"{c}.{suffix}", shp, required) for c, shp in zip(_CONV, shapes)])
+        cw = table("0.weight", PARAM_SHAPES_W, True)
+        vec = [(sh[0],) for sh in PARAM_SHAPES_W]
+        cb, gw, gb = table("0.bias", vec), table("1.weight", vec), table("1.bias", vec)
+        hw, hb = one("pose_pred.weight", (6, 256), True), one("pose_pred.bias", (6,), True)
+        e._bind()
+        e._call(self.lib.tcsfm_posenet_load_device(self._pn, cw, cb, gw, gb, C.c_void_p(hw), C.c_void_p(hb)))
+        self._stamp += 1
+        return self
+
+    def param_backward(self, imgs, tape, d_pose, want=None, need_d_imgs=True):
+        """tcsfm_posenet_param_backward: the images and the tape of forward_train and the pose's cotangent [N,6] ->
+        (d_imgs [N,6,H,W] or None, {name: gradient}) with the current weights.  `want`: the parameter names whose gradient is
+        computed (None: all 30; names as in the reference, gradients in the parameters' own shapes, pose_pred.weight [6,256,1,1]).
+        The work of everything not asked for is skipped."""
+        e = self.eng
+        e._bind()
+        N = d_pose.shape[0]
+        d_pose = _chk(d_pose, (N, 6), "d_pose")
+        tape = _chk(tape, (self.tape_size(N),), "tape")
+        want = list(PARAM_NAMES) if want is None else list(want)
+        bad = [k for k in want if k not in PARAM_SHAPES]
+        if bad:
+            raise KeyError(f"PoseNetHIP.param_backward: unknown parameter names {bad}")
+        if "conv1.0.weight" in want:
+            if imgs is None:
+                raise ValueError("PoseNetHIP.param_backward: conv1.0.weight's gradient needs the images of the forward")
+            imgs = _chk(imgs.detach(), (N, 6, e.H, e.W), "imgs")
+        else:
+            imgs = None
+        dev = d_pose.device
+        grads = {k: torch.empty(PARAM_SHAPES[k], device=dev, dtype=torch.float32) for k in want}
+        table = lambda suffix: (C.c_void_p * 7)(*[(grads[f"{c}.{suffix}"].data_ptr() if f"{c}.{suffix}" in grads else None) for c in _CONV])
+        opt = lambda k: C.c_void_p(grads[k].data_ptr()) if k in grads else None
+        d_imgs = torch.empty((N, 6, e.H, e.W), device=dev, dtype=torch.float32) if need_d_imgs else None
+        e._call(self.lib.tcsfm_posenet_param_backward(self._pn, N, None if imgs is None else e._p(imgs), e._p(tape), e._p(d_pose),
+                                                      None if d_imgs is None else e._p(d_imgs), table("0.weight"), table("0.bias"),
+                                                      table("1.weight"), table("1.bias"), opt("pose_pred.weight"), opt("pose_pred.bias")))
+        return d_imgs, grads
 
     def _check_stamp(self, stamp):
         if stamp != self._stamp:

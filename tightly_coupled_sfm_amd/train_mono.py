@@ -12,9 +12,13 @@ residual assembly of every directed pair, forward and inverse, of a window.
     as the composition of two autograd Functions per iteration, Engine.posenet_input_autograd (the warp, HIP backward
     tcsfm_warp_backward) and PoseNetHIP.__call__ (HIP backward tcsfm_posenet_backward, towards the network's input): the same
     kernels as the fused loop, so stacked_poses, the poses and every map of `outputs` have its bits, and they carry the gradient the
-    reference's loss.backward() follows through the poses.  The first call does not depend on the depths and stays plain.  The pose
-    model's PARAMETERS get no gradient (their .grad stays None, whatever their requires_grad says): the library evaluates a frozen
-    copy, which is the reference's default tuning mode (optimize_depth_encoder); optimize_pose_weights_all is out of scope.
+    reference's loss.backward() follows through the poses.  The first call does not depend on the depths and stays plain.  A plain
+    nn.Module's PARAMETERS get no gradient (their .grad stays None, whatever their requires_grad says): the library evaluates a
+    frozen copy, which is the reference's default tuning mode (optimize_depth_encoder).
+  * The reference's optimize_pose_weights_all mode (optimizer.py:187-189) is opt-in through posenet_train.PoseNetModule: its
+    parameters live in torch, and when grad is enabled and a depth or one of ITS parameters requires grad, every call of the loop --
+    the first included, for any num_iter >= 1 -- runs through the module's autograd Function (HIP backward
+    tcsfm_posenet_param_backward: image and parameter gradients from one walk).  Same kernels, same bits as the fused loop.
 """
 from __future__ import annotations
 
@@ -22,6 +26,7 @@ import torch
 
 from ._shared import get_engine
 from .posenet import PoseNetHIP, is_reference_posenet
+from .posenet_train import PoseNetModule
 
 _NETS = {}     # id(module) -> (parameter version stamp, engine, PoseNetHIP)
 
@@ -56,8 +61,25 @@ def solve_pose_iteratively(num_iter, depths, pose_model, target_img, source_img_
     d_t = torch.cat([target_depths, source_depths], 0).contiguous()
     d_s = torch.cat([source_depths, target_depths], 0).contiguous()
     tgt, src = imgs[:, 0:3].contiguous(), imgs[:, 3:6].contiguous()
-    net = _library_posenet(pose_model, eng, 2 * split)
-    if net is not None and num_iter > 1 and torch.is_grad_enabled() and any(d.requires_grad for d in depths):
+    net = None if isinstance(pose_model, PoseNetModule) else _library_posenet(pose_model, eng, 2 * split)
+    if isinstance(pose_model, PoseNetModule):
+        # the parameters live in the module: the loop runs under autograd when a depth (num_iter > 1) or a parameter requires grad
+        # -- the first call included, whose only differentiable inputs are the parameters -- and inside the library otherwise
+        grad_on = torch.is_grad_enabled()
+        if grad_on and (any(p.requires_grad for p in pose_model.parameters()) or (num_iter > 1 and any(d.requires_grad for d in depths))):
+            full_poses = pose_model(imgs.contiguous())                                                             # :64
+            stacked = [full_poses]
+            for _ in range(num_iter - 1):                                                                          # :73-80
+                new_imgs = eng.posenet_input_autograd(tgt, src, d_t, d_s, full_poses, K)
+                full_poses = full_poses + pose_model(new_imgs)
+                stacked.append(full_poses)
+            stacked_poses = torch.stack(stacked, 1)
+        else:
+            with torch.no_grad():
+                nat = pose_model._native_for(imgs, 2 * split)
+            full_poses, stacked_poses = nat.net.solve_pose_iteratively(num_iter, target_img.float(), [s.float() for s in source_img_list],
+                                                                       depths[0].float(), [d.float() for d in depths[1:]], intrinsics.float())
+    elif net is not None and num_iter > 1 and torch.is_grad_enabled() and any(d.requires_grad for d in depths):
         with torch.no_grad():
             full_poses = net(imgs.contiguous())                                                                    # :64, no depth in it
         stacked = [full_poses]
