@@ -194,6 +194,32 @@ int tcsfm_smooth_loss_device(tcsfm_handle h, const tcsfm_opts *o, int N, const f
 int tcsfm_smooth_loss_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const float *disp, const float *img, const double *stats,
         const float *g_loss, float *g_disp);
 
+/* The window loss of the reference's epoch loop, optimizer.py:47-86, as one reduction: the forward term (with `argmin`: the per-pixel
+ * minimum over the S sources, weighted by source 0's weight map; without: 0.25 x the mean over all S B maps), 0.25 x the inverse term
+ * when `inverse`, and the depth-consistency terms opts.w_dc (1 - mean weight_mask) of the forward and, with `inverse`, the inverse side
+ * (w_dc = 0: off).  opts.automask applies the auto-mask (forward: diff_min < min_s auto_err, under `argmin` only; inverse: auto_mask).
+ * Every map is [S B,1,H,W], source-major as tcsfm_solve_pose_iteratively's callers stack them; 1 <= S <= 4.  fwd_auto_err is read under
+ * argmin && automask only, inv_auto_mask under automask only, the inverse maps when `inverse` only: NULL is accepted where a map is not
+ * read.  loss_out is ONE float and stats_out seven doubles N1, D1, N2, D2, W1, W2, n (numerator and denominator of the forward and of
+ * the inverse term, the sums of the two weight maps, the element count S B H W): what tcsfm_window_loss_backward needs.  Both are
+ * device memory (host memory under opts.host_ptrs); with device pointers the call neither synchronises nor copies to the host: it can
+ * be captured.  Products, sums and the final combination are in double with one rounding at the store; no atomics and a grid that
+ * depends on the shape only: bit-reproducible.  A zero denominator gives nan / inf as the reference's expression does.  Ties of the
+ * minimum go to the lowest source index. */
+int tcsfm_window_loss(tcsfm_handle h, const tcsfm_opts *o, int B, int S, int argmin, int inverse, const float *fwd_diff, const float *fwd_valid,
+        const float *fwd_weight, const float *fwd_auto_err, const float *inv_diff, const float *inv_valid, const float *inv_weight,
+        const float *inv_auto_mask, float *loss_out, double *stats_out);
+
+/* backward of tcsfm_window_loss (optimizer.py:47-86 under autograd): the same inputs, the stats of the forward call and the cotangent
+ * of the scalar (one float) -> the gradients with respect to the forward and inverse diff_img and weight_mask, each [S B,1,H,W] (a NULL
+ * one is not wanted; at least one must be given).  The masks and auto_err take no gradient.  One element-wise launch that recomputes
+ * the minimum, its source and the validity; each value is evaluated in double and rounded once, and an output requested alone has the
+ * bits it has next to the others.  Without `inverse` the two inverse gradients are exact zeros. */
+int tcsfm_window_loss_backward(tcsfm_handle h, const tcsfm_opts *o, int B, int S, int argmin, int inverse, const float *fwd_diff,
+        const float *fwd_valid, const float *fwd_weight, const float *fwd_auto_err, const float *inv_diff, const float *inv_valid,
+        const float *inv_weight, const float *inv_auto_mask, const double *stats, const float *g_loss, float *g_fwd_diff,
+        float *g_fwd_weight, float *g_inv_diff, float *g_inv_weight);
+
 /* inverse_warp2(src, depth_t, depth_s, -pose, K), models/stn.py:234-273.
  * Outputs (any may be NULL): img_rec [N,3,H,W], valid [N,1,H,W], proj_depth, comp_depth [N,1,H,W]. */
 int tcsfm_warp(tcsfm_handle h, const tcsfm_opts *o, int N, const float *src, const float *depth_t, const float *depth_s,

@@ -120,6 +120,8 @@ _SIGNATURES = {
     "tcsfm_ssim_backward": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P, _P, _P]),
     "tcsfm_smooth_loss_device": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P, _P]),
     "tcsfm_smooth_loss_backward": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P, _P, _P]),
+    "tcsfm_window_loss": (C.c_int, [_P, C.POINTER(Opts)] + [C.c_int] * 4 + [_P] * 10),
+    "tcsfm_window_loss_backward": (C.c_int, [_P, C.POINTER(Opts)] + [C.c_int] * 4 + [_P] * 14),
     "tcsfm_warp": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 9),
     "tcsfm_warp_backward": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 11),
     "tcsfm_warp_posenet_input": (C.c_int, [_P, C.POINTER(Opts), C.c_int] + [_P] * 8),

@@ -24,6 +24,7 @@
 #include "warp_grad_kernel.h"
 #include "photo_grad_kernel.h"
 #include "loss_grad_kernel.h"
+#include "window_loss_kernel.h"
 
 using namespace tc;
 
@@ -2127,6 +2128,79 @@ int tcsfm_smooth_loss_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const
     P.H = h->H; P.W = h->W; P.N = N;
     if (st.rc) return st.rc;
     hipLaunchKernelGGL(k_smooth_bwd, dim3((unsigned)((hw + 255) / 256), N), dim3(256), 0, h->stream, P);
+    HIPCHK(h, hipGetLastError());
+    return st.finish();
+}
+
+// the window loss (optimizer.py:47-86) and its backward: csrc/window_loss_kernel.h
+static int window_loss_args(tcsfm_handle h, const tcsfm_opts *o, const char *who, int B, int S, int argmin, int inverse, const float *fwd_diff,
+                            const float *fwd_valid, const float *fwd_weight, const float *fwd_auto_err, const float *inv_diff,
+                            const float *inv_valid, const float *inv_weight, const float *inv_auto_mask) {
+    if (!h) return TCSFM_E_ARG;
+    const std::string w(who);
+    if (S < 1 || S > WL_MAXS) return fail(h, TCSFM_E_ARG, (w + ": S must be 1 .. 4 source images per target").c_str());
+    if (B < 1) return fail(h, TCSFM_E_ARG, (w + ": B must be at least 1").c_str());
+    if (int rc = check_common(h, o, B * S)) return rc;
+    if (!(o->w_dc >= 0.f)) return fail(h, TCSFM_E_ARG, (w + ": opts.w_dc must be >= 0").c_str());
+    if (!fwd_diff || !fwd_valid || !fwd_weight || (argmin && o->automask && !fwd_auto_err))
+        return fail(h, TCSFM_E_ARG, (w + ": NULL forward map").c_str());
+    if (inverse && (!inv_diff || !inv_valid || !inv_weight || (o->automask && !inv_auto_mask)))
+        return fail(h, TCSFM_E_ARG, (w + ": NULL inverse map").c_str());
+    return TCSFM_OK;
+}
+
+static WindowLossParams window_loss_params(tcsfm_handle h, const tcsfm_opts *o, Staging &st, int B, int S, int argmin, int inverse,
+                                           const float *fwd_diff, const float *fwd_valid, const float *fwd_weight, const float *fwd_auto_err,
+                                           const float *inv_diff, const float *inv_valid, const float *inv_weight, const float *inv_auto_mask) {
+    const size_t n = (size_t)S * B * h->H * h->W;
+    WindowLossParams P;
+    P.f_diff = st.in(fwd_diff, n); P.f_valid = st.in(fwd_valid, n); P.f_weight = st.in(fwd_weight, n); P.f_ame = st.in(fwd_auto_err, n);
+    P.i_diff = st.in(inv_diff, n); P.i_valid = st.in(inv_valid, n); P.i_weight = st.in(inv_weight, n); P.i_am = st.in(inv_auto_mask, n);
+    P.B = B; P.S = S; P.hw = h->H * h->W; P.argmin = argmin ? 1 : 0; P.automask = o->automask ? 1 : 0; P.inverse = inverse ? 1 : 0;
+    P.w = (double)o->w_dc;
+    return P;
+}
+
+int tcsfm_window_loss(tcsfm_handle h, const tcsfm_opts *o, int B, int S, int argmin, int inverse, const float *fwd_diff, const float *fwd_valid,
+                      const float *fwd_weight, const float *fwd_auto_err, const float *inv_diff, const float *inv_valid,
+                      const float *inv_weight, const float *inv_auto_mask, float *loss_out, double *stats_out) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    if (int rc = window_loss_args(h, o, "tcsfm_window_loss", B, S, argmin, inverse, fwd_diff, fwd_valid, fwd_weight, fwd_auto_err, inv_diff,
+                                  inv_valid, inv_weight, inv_auto_mask)) return rc;
+    if (!loss_out || !stats_out) return fail(h, TCSFM_E_ARG, "tcsfm_window_loss: NULL output");
+    Staging st(h, o);
+    WindowLossParams P = window_loss_params(h, o, st, B, S, argmin, inverse, fwd_diff, fwd_valid, fwd_weight, fwd_auto_err, inv_diff, inv_valid,
+                                            inv_weight, inv_auto_mask);
+    float *d_loss = st.out(loss_out, (size_t)1);
+    double *d_stats = st.out(stats_out, (size_t)WL_NSTAT);
+    const int nu = (P.hw >> 2) + (P.hw & 3), per = 256 * WL_UNITS, nbx = (nu + per - 1) / per;      // the grid: a function of the shape only
+    double *partial = (double *)st.scratch((size_t)nbx * B * WL_NSUM * sizeof(double));
+    if (st.rc) return st.rc;
+    hipLaunchKernelGGL(k_window_loss, dim3(nbx, B), dim3(256), 0, h->stream, P, partial);
+    hipLaunchKernelGGL(k_window_loss_final, dim3(1), dim3(256), 0, h->stream, (const double *)partial, nbx * B, P, d_stats, d_loss);
+    HIPCHK(h, hipGetLastError());
+    return st.finish();          // (device pointers: no copy, no synchronisation)
+}
+
+int tcsfm_window_loss_backward(tcsfm_handle h, const tcsfm_opts *o, int B, int S, int argmin, int inverse, const float *fwd_diff,
+                               const float *fwd_valid, const float *fwd_weight, const float *fwd_auto_err, const float *inv_diff,
+                               const float *inv_valid, const float *inv_weight, const float *inv_auto_mask, const double *stats,
+                               const float *g_loss, float *g_fwd_diff, float *g_fwd_weight, float *g_inv_diff, float *g_inv_weight) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    if (int rc = window_loss_args(h, o, "tcsfm_window_loss_backward", B, S, argmin, inverse, fwd_diff, fwd_valid, fwd_weight, fwd_auto_err,
+                                  inv_diff, inv_valid, inv_weight, inv_auto_mask)) return rc;
+    if (!stats || !g_loss) return fail(h, TCSFM_E_ARG, "tcsfm_window_loss_backward: NULL argument");
+    if (!g_fwd_diff && !g_fwd_weight && !g_inv_diff && !g_inv_weight) return fail(h, TCSFM_E_ARG, "tcsfm_window_loss_backward: no output requested");
+    Staging st(h, o);
+    WindowLossGradParams G;
+    G.in = window_loss_params(h, o, st, B, S, argmin, inverse, fwd_diff, fwd_valid, fwd_weight, fwd_auto_err, inv_diff, inv_valid, inv_weight,
+                              inv_auto_mask);
+    const size_t n = (size_t)S * B * G.in.hw;
+    G.stats = st.in(stats, (size_t)WL_NSTAT); G.g_loss = st.in(g_loss, (size_t)1);
+    G.g_f_diff = st.out(g_fwd_diff, n); G.g_f_weight = st.out(g_fwd_weight, n); G.g_i_diff = st.out(g_inv_diff, n); G.g_i_weight = st.out(g_inv_weight, n);
+    if (st.rc) return st.rc;
+    const int nu = (G.in.hw >> 2) + (G.in.hw & 3);
+    hipLaunchKernelGGL(k_window_loss_bwd, dim3((nu + 255) / 256, B), dim3(256), 0, h->stream, G);
     HIPCHK(h, hipGetLastError());
     return st.finish();
 }

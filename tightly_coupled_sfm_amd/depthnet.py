@@ -61,13 +61,14 @@ class DepthNetHIP:
         engine._bind()
         engine._call(self.lib.tcsfm_depthnet_create(engine._h, self.max_images, C.byref(dn)))
         self._dn = dn
+        engine._adopt(self, self.lib.tcsfm_depthnet_destroy, dn)
         self.training = False
         if params is not None:
             self.load(params)
 
     def close(self):
         if getattr(self, "_dn", None):
-            self.lib.tcsfm_depthnet_destroy(self._dn)
+            self.eng._release(self)         # (a no-op when the engine was closed first: it took the network with it)
             self._dn = None
 
     def __del__(self):

@@ -124,6 +124,31 @@ class _SmoothLoss(torch.autograd.Function):
         return None, ctx.engine.smooth_loss_backward(disp, img, stats, _cot(g_loss)), None
 
 
+class _WindowLoss(torch.autograd.Function):
+    """The window loss of optimizer.py:47-86 under autograd: tcsfm_window_loss forward (the scalar stays on the device),
+    tcsfm_window_loss_backward behind it.  diff_img and weight_mask of both sides are differentiable; the masks and auto_mask_error are
+    not."""
+
+    @staticmethod
+    def forward(ctx, engine, sw, f_diff, f_weight, i_diff, i_weight, f_valid, f_ame, i_valid, i_am):
+        loss, stats = engine.window_loss(f_diff, f_valid, f_weight, f_ame, i_diff, i_valid, i_weight, i_am, **sw)
+        ctx.engine, ctx.sw = engine, dict(sw)
+        ctx.save_for_backward(f_diff, f_weight, i_diff, i_weight, f_valid, f_ame, i_valid, i_am, stats)
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        want = tuple(ctx.needs_input_grad[2:6])
+        if g_loss is None or not any(want):
+            return (None,) * 10
+        f_diff, f_weight, i_diff, i_weight, f_valid, f_ame, i_valid, i_am, stats = ctx.saved_tensors
+        g = ctx.engine.window_loss_backward(f_diff, f_valid, f_weight, f_ame, i_diff, i_valid, i_weight, i_am, stats, _cot(g_loss),
+                                            want=want, **ctx.sw)
+        return (None, None, *g, None, None, None, None)
+
+
 class _PoseNetInput(torch.autograd.Function):
     """Engine.posenet_input under autograd: the same forward kernel; the cotangent of the reconstruction (channels 3..5) goes through
     tcsfm_warp_backward (Engine.inverse_warp2_backward).  Channels 0..2 are tgt * valid: the validity mask is not differentiable
@@ -162,6 +187,7 @@ class Engine:
         if rc != 0:
             raise RuntimeError(f"tcsfm_create failed ({rc}): {self.lib.tcsfm_last_error(None).decode()}")
         self._h = h
+        self._nets = {}         # the native networks living on this handle: id -> (destroy function, pointer), see _adopt
         self.lanes = 1
         self.lanes_serial = False
         self.use_torch_stream()
@@ -170,8 +196,22 @@ class Engine:
             self.set_lanes(lanes)
 
     # -- lifetime ----------------------------------------------------------------------------
+    def _adopt(self, owner, destroy, ptr):
+        """A native network (tcsfm_depthnet / tcsfm_posenet) refers to this handle and must go before it.  Its Python owner destroys it
+        through _release; if the handle is closed first -- the garbage collector finalises the objects of an unreachable group in no
+        particular order -- close() destroys the network itself and the owner's _release finds nothing left to do."""
+        self._nets[id(owner)] = (destroy, ptr)
+
+    def _release(self, owner):
+        net = getattr(self, "_nets", {}).pop(id(owner), None)
+        if net is not None:
+            net[0](net[1])
+
     def close(self):
         if getattr(self, "_h", None):
+            for destroy, ptr in list(getattr(self, "_nets", {}).values()):
+                destroy(ptr)
+            self._nets = {}
             self.lib.tcsfm_destroy(self._h)
             self._h = None
 
@@ -358,6 +398,64 @@ class Engine:
         self._call(self.lib.tcsfm_smooth_loss_backward(self._h, C.byref(default_opts()), N, self._p(disp), self._p(img),
                                                        self._p(stats.contiguous()), self._p(g_loss), self._p(out)))
         return out
+
+    def _window_maps(self, f_diff, f_valid, f_weight, f_ame, i_diff, i_valid, i_weight, i_am, argmin, automasking, inverse):
+        """shape / dtype checks of the eight maps of the window loss -> (B S, the maps with None where the library does not read one)"""
+        if f_diff.dim() != 4:
+            raise AssertionError("wrong size for fwd diff_img, expected [S*B,1,H,W], got  {}".format(list(f_diff.shape)))
+        shape = (f_diff.shape[0], 1, self.H, self.W)
+        need = [True, True, True, bool(argmin and automasking), bool(inverse), bool(inverse), bool(inverse), bool(inverse and automasking)]
+        names = ("fwd diff_img", "fwd valid_mask", "fwd weight_mask", "fwd auto_mask_error", "inv diff_img", "inv valid_mask", "inv weight_mask",
+                 "inv auto_mask")
+        maps = []
+        for t, n, name in zip((f_diff, f_valid, f_weight, f_ame, i_diff, i_valid, i_weight, i_am), need, names):
+            if not n:
+                maps.append(None)
+                continue
+            if t is None:
+                raise ValueError(f"{name} is needed with these switches")
+            maps.append(_chk(t, shape, name))
+        return shape, maps
+
+    def window_loss(self, f_diff, f_valid, f_weight, f_ame, i_diff, i_valid, i_weight, i_am, S: int, argmin: bool = True,
+                    automasking: bool = True, inverse: bool = True, w_dc: float = 0.0):
+        """The window loss of optimizer.py:47-86 (tcsfm_window_loss): the forward term (per-pixel min over the S sources with ``argmin``),
+        0.25 x the inverse term with ``inverse``, and the depth-consistency terms with weight ``w_dc`` (0 = off).  The maps are
+        [S*B,1,H,W] float32, source-major, as solve_pose_iteratively emits them: forward diff_img, valid_mask (warp validity), weight_mask,
+        auto_mask_error, then inverse diff_img, valid_mask, weight_mask, auto_mask (None where the switches do not read one)
+        -> (loss: 0-dim float32 tensor, stats: 7 float64 = N1, D1, N2, D2, W1, W2, n, the input of window_loss_backward).  No host round
+        trip, no synchronisation."""
+        self._bind()
+        S = int(S)
+        shape, maps = self._window_maps(f_diff, f_valid, f_weight, f_ame, i_diff, i_valid, i_weight, i_am, argmin, automasking, inverse)
+        if S < 1 or shape[0] % S:
+            raise ValueError(f"{shape[0]} maps are not S = {S} sources of B targets")
+        loss = torch.empty((), dtype=torch.float32, device=f_diff.device)
+        stats = torch.empty((7,), dtype=torch.float64, device=f_diff.device)
+        o = default_opts(automask=1 if automasking else 0, w_dc=float(w_dc))
+        self._call(self.lib.tcsfm_window_loss(self._h, C.byref(o), shape[0] // S, S, int(bool(argmin)), int(bool(inverse)),
+                                              *[self._p(m) for m in maps], self._p(loss), self._p(stats)))
+        return loss, stats
+
+    def window_loss_backward(self, f_diff, f_valid, f_weight, f_ame, i_diff, i_valid, i_weight, i_am, stats, g_loss, S: int,
+                             argmin: bool = True, automasking: bool = True, inverse: bool = True, w_dc: float = 0.0,
+                             want=(True, True, True, True)):
+        """backward of window_loss (tcsfm_window_loss_backward): the same maps and switches, ``stats`` of window_loss on them and ``g_loss``, a
+        float32 GPU tensor with one element -> (g_fwd_diff, g_fwd_weight, g_inv_diff, g_inv_weight), None where ``want`` is False"""
+        self._bind()
+        S = int(S)
+        shape, maps = self._window_maps(f_diff, f_valid, f_weight, f_ame, i_diff, i_valid, i_weight, i_am, argmin, automasking, inverse)
+        if S < 1 or shape[0] % S:
+            raise ValueError(f"{shape[0]} maps are not S = {S} sources of B targets")
+        if stats.dtype != torch.float64 or not stats.is_cuda or tuple(stats.shape) != (7,):
+            raise TypeError("stats must be a float64 GPU tensor of shape [7]")
+        g_loss = _chk(g_loss.reshape(()), (), "g_loss")
+        outs = [torch.empty(shape, dtype=torch.float32, device=f_diff.device) if w else None for w in want]
+        o = default_opts(automask=1 if automasking else 0, w_dc=float(w_dc))
+        self._call(self.lib.tcsfm_window_loss_backward(self._h, C.byref(o), shape[0] // S, S, int(bool(argmin)), int(bool(inverse)),
+                                                       *[self._p(m) for m in maps], self._p(stats.contiguous()), self._p(g_loss),
+                                                       *[self._p(t) for t in outs]))
+        return tuple(outs)
 
     def inverse_warp2(self, img, depth, ref_depth, pose, intrinsics):
         """models/stn.py:234-273 with the reference's argument order; ``pose`` here is what the reference

@@ -47,17 +47,52 @@ def get_smooth_loss(disp: torch.Tensor, img: torch.Tensor) -> torch.Tensor:
     return (gdx * torch.exp(-gix)).mean() + (gdy * torch.exp(-giy)).mean()
 
 
+def _window_loss_fused(options: dict, B: int, S: int, fwd_data: dict, inv_data: dict) -> torch.Tensor:
+    """optimizer.py:47-86 as one HIP reduction (tcsfm_window_loss) with its backward (tcsfm_window_loss_backward) under autograd:
+    the forward term, the inverse term and the depth-consistency terms; [1] with diff_img_argmin, 0-dim without, as the reference."""
+    argmin, automask, inverse = bool(options["diff_img_argmin"]), bool(options["automasking"]), bool(options["l_inverse_reconstruction"])
+    w_dc = float(options["l_depth_consist_weight"]) if options["l_depth_consist"] else 0.0
+    if not 1 <= S <= 4:
+        raise ValueError(f"compute_optimization_loss(fused=True) handles 1 to 4 source images per target (got {S})")
+    maps = [fwd_data["diff_img"], fwd_data["weight_mask"], inv_data["diff_img"] if inverse else None, inv_data["weight_mask"] if inverse else None,
+            fwd_data["valid_mask"], fwd_data["auto_mask_error"] if (argmin and automask) else None, inv_data["valid_mask"] if inverse else None,
+            inv_data["auto_mask"] if (inverse and automask) else None]
+    for m in maps:
+        if m is not None and not (isinstance(m, torch.Tensor) and m.is_cuda and m.dtype == torch.float32):
+            raise ValueError("compute_optimization_loss(fused=True) needs float32 GPU maps (no fallback to the torch expression)")
+    f_diff = maps[0]
+    if f_diff.dim() != 4 or f_diff.shape[0] != S * B or f_diff.shape[1] != 1:
+        raise ValueError(f"compute_optimization_loss(fused=True): diff_img of shape {tuple(f_diff.shape)}, expected [{S * B},1,H,W]")
+    from ._shared import get_engine
+    from .engine import _WindowLoss
+    eng = get_engine(f_diff.shape[2], f_diff.shape[3], S * B)
+    maps = [None if m is None else m.contiguous() for m in maps]
+    sw = {"S": S, "argmin": argmin, "automasking": automask, "inverse": inverse, "w_dc": w_dc}
+    if torch.is_grad_enabled() and any(m is not None and m.requires_grad for m in maps[:4]):
+        loss = _WindowLoss.apply(eng, sw, *maps)
+    else:
+        loss = eng.window_loss(maps[0], maps[4], maps[1], maps[5], maps[2], maps[6], maps[3], maps[7], **sw)[0]
+    return loss.reshape(1) if argmin else loss
+
+
 def compute_optimization_loss(options: dict, target_img, target_disparity, target_disparity_init, fwd_data: dict, inv_data: dict,
-                              ssim_loss) -> torch.Tensor:
+                              ssim_loss, fused: bool = False) -> torch.Tensor:
     """optimization_experiments/optimizer.py:29-134 without the plotting branches.
 
     fwd_data / inv_data: dicts with the keys solve_pose_iteratively emits (train_mono.py:94-100): diff_img, valid_mask,
     weight_mask, auto_mask_error, auto_mask, poses -- e.g. slices of Engine.compute_photometric_error output, with
-    'valid_mask' the WARP validity (its key 'warp_valid').  ssim_loss: callable(x, y) e.g. Engine.ssim_loss."""
+    'valid_mask' the WARP validity (its key 'warp_valid').  ssim_loss: callable(x, y) e.g. Engine.ssim_loss.
+
+    fused=True: the forward, inverse and depth-consistency terms (optimizer.py:47-86) come from ONE HIP reduction, differentiable with
+    respect to diff_img and weight_mask of both sides (tcsfm_window_loss / tcsfm_window_loss_backward, double accumulation, one rounding),
+    on the shared engine of the frame size and torch's current stream; the three remaining terms are added as below.  It needs float32
+    GPU maps and at most 4 source images per target, and raises ValueError otherwise."""
     B = target_img.shape[0]
     S = options["num_source_imgs"]
     loss = 0
-    if options["diff_img_argmin"]:
+    if fused:
+        loss = _window_loss_fused(options, B, S, fwd_data, inv_data)
+    elif options["diff_img_argmin"]:
         diff = torch.cat([fwd_data["diff_img"][i * B:(i + 1) * B] for i in range(S)], 1).unsqueeze(2)
         diff_min, _ = torch.min(diff, 1)                                                        # optimizer.py:47-51
         valid_min = torch.cat([fwd_data["valid_mask"][i * B:(i + 1) * B] for i in range(S)], 1).sum(1, keepdim=True).clamp(0, 1)
@@ -68,13 +103,13 @@ def compute_optimization_loss(options: dict, target_img, target_disparity, targe
         loss = loss + (diff_min * valid_min * fwd_data["weight_mask"][0:B]).sum(3).sum(2).sum(0) / valid_min.sum(3).sum(2).sum(0)
     else:
         loss = loss + 0.25 * (fwd_data["diff_img"] * fwd_data["valid_mask"] * fwd_data["weight_mask"]).sum() / fwd_data["valid_mask"].sum()
-    inv_masked = inv_data["diff_img"] * inv_data["valid_mask"] * inv_data["weight_mask"]
-    if options["l_inverse_reconstruction"]:
+    inv_masked = None if fused else inv_data["diff_img"] * inv_data["valid_mask"] * inv_data["weight_mask"]
+    if options["l_inverse_reconstruction"] and not fused:
         if options["automasking"]:
             loss = loss + 0.25 * (inv_masked * inv_data["auto_mask"]).sum() / (inv_data["valid_mask"] * inv_data["auto_mask"]).sum()
         else:
             loss = loss + 0.25 * inv_masked.sum() / inv_data["valid_mask"].sum()
-    if options["l_depth_consist"]:
+    if options["l_depth_consist"] and not fused:
         loss = loss + options["l_depth_consist_weight"] * (1 - fwd_data["weight_mask"]).mean()
         if options["l_inverse_reconstruction"]:
             loss = loss + options["l_depth_consist_weight"] * (1 - inv_data["weight_mask"]).mean()

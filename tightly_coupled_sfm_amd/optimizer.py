@@ -19,11 +19,20 @@ by default ON THE REFERENCE'S OWN LOSS (optimizer.py:47-90: forward term with so
 consistency, l_depth_init SSIM prior; `diff_img_argmin`, `automasking`, `l_depth_consist(+_weight)`, `l_depth_init(+_weight)` honoured;
 include/tcsfm.h "REFERENCE LOSS"; up to four source images per target, so the five-frame window t-2 .. t+2 too); options['window_rule'] = 'pair'
 or solver 'lm' select the library's own joint / per-pair dense modes.
-Its weight-tuning switches (optimize_depth_encoder, ...) need autograd through the networks, which is out of scope:
-they are ignored with a warning, or refused when options['strict_legacy'] is set.
+options['weight_tuning'] = True runs the reference's OWN loop instead (optimizer.py:136-297 without the plotting branches): Adam (or SGD,
+options['optimizer']) at options['lr'] for options['epochs'] epochs over what the reference's switches select -- optimize_depth_encoder,
+optimize_depth_weights_all, optimize_depth_weights_bottleneck_beyond, optimize_depth_bottleneck_values, optimize_depth_pred,
+optimize_pose_weights_all -- with every stage between the weights and the loss on the library's differentiable operators
+(depthnet_train.DepthNetModule, posenet_train.PoseNetModule, train_mono.solve_pose_iteratively, learning_helpers.disp_to_depth,
+losses.compute_optimization_loss, whose window terms come from one fused HIP reduction unless options['fused_loss'] = False).  The models
+given to the constructor are never modified: the loop tunes deep copies where the reference does.  Extra result key `losses`.
+Without that key the weight-tuning switches (optimize_depth_encoder, ...) are ignored with a warning, or refused when
+options['strict_legacy'] is set.
 """
 from __future__ import annotations
 
+import contextlib
+import copy
 import warnings
 
 import numpy as np
@@ -34,6 +43,22 @@ from .engine import Engine, default_opts
 
 _LEGACY = ("optimize_depth_weights_bottleneck_beyond", "optimize_depth_weights_all", "optimize_depth_encoder",
            "optimize_pose_weights_all", "optimize_depth_bottleneck_values")
+
+
+_TUNING = _LEGACY + ("optimize_depth_pred",)
+
+
+@contextlib.contextmanager
+def _frozen(*modules):
+    """the parameters of modules the loop runs but does not tune take no gradient (their .grad stays as it was); restored on exit"""
+    touched = [p for m in modules if isinstance(m, torch.nn.Module) for p in m.parameters() if p.requires_grad]
+    for p in touched:
+        p.requires_grad_(False)
+    try:
+        yield
+    finally:
+        for p in touched:
+            p.requires_grad_(True)
 
 
 def process_sample_batch(data, config):
@@ -91,8 +116,13 @@ class DepthOptimizer:
         self.options, self.config, self.seq = options, config, seq
         self.pose_model = pose_model.train(False).eval()
         self.depth_model = depth_model.train(False).eval()
+        self.weight_tuning = bool(options.get("weight_tuning", False))
         legacy = [k for k in _LEGACY if options.get(k, False)]
-        if legacy:
+        if self.weight_tuning and not any(options.get(k, False) for k in _TUNING):
+            raise ValueError(f"options['weight_tuning'] needs one of the reference's switches {list(_TUNING)}")
+        if self.weight_tuning and options.get("optimizer", "adam") not in ("adam", "sgd"):
+            raise ValueError("options['optimizer'] must be 'adam' or 'sgd'")
+        if legacy and not self.weight_tuning:
             msg = (f"options {legacy} tune network weights/activations through autograd; the HIP engine refines the "
                    "pose (and depth scale) of each frame pair by Gauss-Newton instead")
             if options.get("strict_legacy", False):
@@ -106,10 +136,13 @@ class DepthOptimizer:
         sm_ok = (options.get("refine", "pose+depth" if options.get("optimize_depth_pred", False) else "pose") == "pose+depth" and
                  options.get("window_rule", "reference") != "pair" and options.get("solver", "gn") != "lm")
         ignored = [k for k in ("l_smooth", "l_pose_consist") if options.get(k, False) and not ((k == "l_pose_consist" and pc_ok) or (k == "l_smooth" and sm_ok))]
-        if ignored:   # off by default in the reference (run_sequential_optimization.py:87,89); not part of the per-pair GN cost
+        if ignored and not self.weight_tuning:   # off by default in the reference (run_sequential_optimization.py:87,89); not part of the per-pair GN cost
             warnings.warn(f"options {ignored} are not terms of the Gauss-Newton cost and are ignored "
                           "(losses.get_smooth_loss / compute_optimization_loss still evaluate them for logging)")
         self._engine = None
+        self._tuning_depth = None       # the depth model as a DepthNetModule (weight tuning), built once
+        self._tuning_pose = None        # the pose model as a PoseNetModule (optimize_pose_weights_all), built once
+        self.tuned_models = None
         self.full_results = []
         # measurement hook (bench.py `shim`): with time_engine the refine call inside optimize_window is bracketed by device synchronisations
         # and its wall time left in last_engine_call_us (off by default: the synchronisations are not free)
@@ -236,10 +269,158 @@ class DepthOptimizer:
             o += m
         return out
 
+    # -- the reference's epoch loop on the library's differentiable operators (options['weight_tuning']) --------
+    def _tuning_models(self, device, n_images, n_pairs):
+        """the depth and pose models of one window as the reference picks them (optimizer.py:174-191): deep copies where their weights
+        are tuned, the given models otherwise -> (depth_model, pose_model, the modules that stay frozen)"""
+        o = self.options
+        from .depthnet_train import DepthNetModule
+        from .posenet_train import PoseNetModule
+        if isinstance(self.depth_model, DepthNetModule):
+            depth = self.depth_model
+        else:
+            if self._tuning_depth is None or self._tuning_depth.max_images < n_images:
+                self._tuning_depth = DepthNetModule(self.depth_model, max_images=n_images).to(device)
+            depth = self._tuning_depth
+        tuned_depth = any(o.get(k, False) for k in ("optimize_depth_weights_bottleneck_beyond", "optimize_depth_weights_all", "optimize_depth_encoder"))
+        if tuned_depth:
+            depth = copy.deepcopy(depth).train(False).eval()
+        pose = self.pose_model
+        if o.get("optimize_pose_weights_all", False):
+            if not isinstance(pose, PoseNetModule):
+                if self._tuning_pose is None or self._tuning_pose.max_images < n_pairs:
+                    self._tuning_pose = PoseNetModule(pose, max_images=n_pairs).to(device)
+                pose = self._tuning_pose
+            pose = copy.deepcopy(pose).train(False).eval()
+        frozen = ([] if tuned_depth else [depth]) + ([] if o.get("optimize_pose_weights_all", False) else [pose])
+        return depth, pose, frozen
+
+    def _optimize_window_tuning(self, tup):
+        """optimizer.py:136-297 without the plotting branches"""
+        from . import helpers, learning_helpers, losses
+        from .train_mono import solve_pose_iteratively
+        o, cfg, res = self.options, self.config, {}
+        target_img, source_img_list, gt_lie_alg_list, _, _, intrinsics = tup[:6]
+        target_img, source_img_list, intrinsics = target_img.float(), [s.float() for s in source_img_list], intrinsics.float()
+        B, _, H, W = target_img.shape
+        S = len(source_img_list)
+        split, epochs, iters = S * B, int(o["epochs"]), int(cfg.get("iterations", 1))
+        if epochs < 1:
+            raise ValueError("options['epochs'] must be at least 1")
+        eng = self._eng(H, W, 2 * split)
+        unscaled = o.get("mode", "scaled") == "unscaled"
+        depth = lambda d: learning_helpers.disp_to_depth(d, cfg["min_depth"], cfg["max_depth"])[1]
+        scale = lambda d: eng.scale_recovery(d.detach().contiguous(), intrinsics.contiguous(), cfg["camera_height"] / 30.0,
+                                             pad_to_batch=int(cfg.get("minibatch", B)))
+        depth_model, pose_model, frozen = self._tuning_models(target_img.device, max((S + 1) * B, 2 * B), 2 * split)
+        self.tuned_models = (depth_model, pose_model)      # the models of the last window as the loop left them (copies where it tuned them)
+        imgs = torch.cat([target_img] + source_img_list, 0)
+
+        # first pass (optimizer.py:142-171): initial depths and poses, the l_depth_init anchor, the skips
+        with torch.no_grad():
+            _, skips = depth_model(x=imgs, return_disp=False, epoch=50)
+            disp0 = depth_model(x=None, skips=skips, epoch=50)[0][0]
+            skips = [s.clone().detach() for s in skips]
+            self.target_disparity = disp0[0:B].clone().detach()
+            disp_list0 = [disp0[i * B:(i + 1) * B] for i in range(S + 1)]
+            depths0 = [depth(d) for d in disp_list0]
+            _, _, out0 = solve_pose_iteratively(iters, depths0, pose_model, target_img, source_img_list, intrinsics, return_errors=True)
+        res["depths_init"] = [d.clone() for d in depths0]
+        stacked0 = torch.cat([out0["fwd"]["poses"], out0["inv"]["poses"]], 0)[:, :, :6]
+
+        # what the optimiser moves (optimizer.py:174-214)
+        lr, params = o["lr"], []
+        weights_all, beyond, encoder = (o.get(k, False) for k in ("optimize_depth_weights_all", "optimize_depth_weights_bottleneck_beyond",
+                                                                    "optimize_depth_encoder"))
+        if weights_all or beyond:
+            if beyond and not weights_all:         # the encoder never gets a gradient there (fixed skips): none is computed
+                for p in depth_model.encoder.parameters():
+                    p.requires_grad_(False)
+            params.append({"params": depth_model.parameters(), "lr": lr})
+        elif encoder:
+            enc = {id(p) for p in depth_model.encoder.parameters()}
+            for p in depth_model.parameters():   # (else the decoder's weight gradients are computed too)
+                p.requires_grad_(id(p) in enc)
+            params.append({"params": depth_model.encoder.parameters(), "lr": lr})
+        if o.get("optimize_pose_weights_all", False):
+            params.append({"params": pose_model.parameters(), "lr": lr})
+        disp_leaf = bottleneck = bottleneck_2 = None
+        if o.get("optimize_depth_pred", False):
+            stacked_disp = torch.cat(disp_list0, 1)
+            disp_leaf = torch.nn.functional.interpolate(stacked_disp, (int(H / 4), int(W / 4)), mode="bilinear").clone().detach().requires_grad_()
+            params.append({"params": disp_leaf, "lr": lr})
+        if o.get("optimize_depth_bottleneck_values", False):
+            bottleneck, bottleneck_2 = skips[-1].clone().detach().requires_grad_(), skips[-2].clone().detach().requires_grad_()
+            params.append({"params": bottleneck, "lr": lr})
+            params.append({"params": bottleneck_2, "lr": lr})
+        optimizer = torch.optim.Adam(params) if o.get("optimizer", "adam") == "adam" else torch.optim.SGD(params)
+
+        ssim = losses.SSIM_Loss()
+        fused = bool(o.get("fused_loss", True))
+        loss_list, pose_list, disp_avg, sf_init, sf = [], [], [], None, None
+        with _frozen(*frozen):
+            for i in range(epochs):                                                      # optimizer.py:217-274
+                optimizer.zero_grad()
+                disp = None
+                if weights_all or encoder:
+                    disp = depth_model(x=imgs, skips=None, epoch=50)[0][0]
+                if beyond:
+                    disp = depth_model(x=None, skips=skips, epoch=50)[0][0]
+                if bottleneck is not None:
+                    disp = depth_model(x=None, skips=skips[:-2] + [bottleneck_2, bottleneck], epoch=50)[0][0]
+                if disp_leaf is not None:
+                    up = torch.nn.functional.interpolate(disp_leaf, (int(disp_leaf.shape[2] * 4), int(disp_leaf.shape[3] * 4)), mode="bilinear")
+                    disp_list = [up[:, k:k + 1] for k in range(S + 1)]
+                elif disp is not None:
+                    disp_list = [disp[k * B:(k + 1) * B] for k in range(S + 1)]
+                else:                                                                    # pose weights only: the first pass's disparities
+                    disp_list = disp_list0
+                depths = [depth(d.contiguous()) for d in disp_list]
+                poses, poses_inv, outputs = solve_pose_iteratively(iters, depths, pose_model, target_img, source_img_list, intrinsics,
+                                                                   return_errors=True)
+                if unscaled and (i == 0 or i == epochs - 1):
+                    sf = scale(depths[0])
+                    sf_init = sf.clone() if i == 0 else sf_init
+                loss = losses.compute_optimization_loss(o, target_img, disp_list[0], self.target_disparity, outputs["fwd"], outputs["inv"], ssim,
+                                                        fused=fused)
+                if i < epochs - 1:              # the reference does not step after the last epoch: nothing is recomputed after it
+                    loss.backward()
+                    optimizer.step()
+                loss_list.append(loss.detach().reshape(()))
+                disp_avg.append(helpers.get_disp_for_eigen(depth_model, target_img, cfg))
+                pose_list.append(torch.cat(poses + poses_inv, 0)[:, :6].detach())
+        optimizer.zero_grad()
+
+        n_avg = int(o.get("avg_final_epochs", 1))
+        pose_avg = avg_final_predictions(pose_list, n_avg)
+        res["depths_opt"] = [d.detach() for d in depths]
+        res["stacked_poses_opt"] = outputs["fwd"]["poses"][:, :, :6].detach()
+        res["stacked_poses_inv_opt"] = outputs["inv"]["poses"][:, :, :6].detach()
+        gt = torch.cat(gt_lie_alg_list, 0) if gt_lie_alg_list[0] is not None else None
+        # everything small the drivers read on the CPU: ONE staged copy (every epoch's loss and poses included)
+        hst = self._to_host([("stacked0", stacked0), ("pose", pose_avg), ("gt", gt), ("sf", sf), ("sf_init", sf_init),
+                             ("losses", torch.stack(loss_list)), ("epoch_poses", torch.stack(pose_list))])
+        res["poses_init"], res["poses_inv_init"] = hst["stacked0"][:split, -1].clone(), hst["stacked0"][split:, -1].clone()
+        res["gt_poses"] = hst["gt"]
+        res["gt_poses_inv"] = -res["gt_poses"] if res["gt_poses"] is not None else None
+        res["stacked_poses_init"], res["stacked_poses_inv_init"] = hst["stacked0"][:split], hst["stacked0"][split:]
+        res["poses_opt"], res["poses_inv_opt"] = hst["pose"][:split], hst["pose"][split:]
+        res["scale_factor"] = hst["sf"] if unscaled else torch.FloatTensor([1])
+        res["scale_factor_init"] = hst["sf_init"] if unscaled else torch.FloatTensor([1])
+        # (float64 on the CPU, as the reference's: avg_final_predictions adds numpy arrays into a tensor, G9)
+        res["disp_opt"] = torch.as_tensor(np.ascontiguousarray(avg_final_predictions(disp_avg, n_avg), dtype=np.float64))
+        res["losses"] = hst["losses"]
+        ep = hst["epoch_poses"]
+        self.full_results = [dict(res, poses_opt=ep[k, :split], poses_inv_opt=ep[k, split:], loss=hst["losses"][k]) for k in range(epochs)]
+        return res
+
     @torch.no_grad()
     def optimize_window(self, img_idx, data):
         res = {}
         tup = data if len(data) == 11 else process_sample_batch(data, self.config)
+        if self.weight_tuning:
+            with torch.enable_grad():
+                return self._optimize_window_tuning(tup)
         target_img, source_img_list, gt_lie_alg_list, _, _, intrinsics = tup[:6]
         B, _, H, W = target_img.shape
         S = len(source_img_list)

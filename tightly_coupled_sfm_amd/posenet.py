@@ -87,12 +87,13 @@ class PoseNetHIP:
         pn = C.c_void_p()
         engine._call(self.lib.tcsfm_posenet_create(engine._h, self.max_images, C.byref(pn)))
         self._pn = pn
+        engine._adopt(self, self.lib.tcsfm_posenet_destroy, pn)
         if params is not None:
             self.load(params)
 
     def close(self):
         if getattr(self, "_pn", None):
-            self.lib.tcsfm_posenet_destroy(self._pn)
+            self.eng._release(self)         # (a no-op when the engine was closed first: it took the network with it)
             self._pn = None
 
     def __del__(self):
