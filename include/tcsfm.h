@@ -551,6 +551,48 @@ int tcsfm_depthnet_decode_backward(tcsfm_depthnet *dn, int N, const float *tape,
 int tcsfm_depthnet_encode_backward(tcsfm_depthnet *dn, int N, const float *tape, const float *const d_skips[5], int n_grads,
                                    const char *const names[], float *const grads[]);
 
+/* ---- the optimiser step of the weight-tuning loop ----------------------------------------------------------------------------
+ * The reference builds torch.optim.Adam (or SGD) over the parameters its switches select and steps it once per epoch
+ * (optimization_experiments/optimizer.py:211-214, 266-268); for every window it starts again from a deep copy of the network
+ * (:176-191).  Here both live behind the C ABI (csrc/optim_kernel.h): a caller of this header runs the whole tuning loop without
+ * PyTorch, and a window is started by putting the parameters back instead of copying the network.
+ *   tcsfm_optim_create     an optimiser of `kind` over n tensors: params[i] is a DEVICE pointer to numel[i] contiguous floats, owned by
+ *                          the caller and updated in place (4-byte alignment is enough; numel[i] = 0 is legal, does nothing, and its
+ *                          pointer may be NULL).  The moments (Adam) and the snapshot live in arenas owned by the optimiser, zeroed
+ *                          when they are allocated (the moments here, the snapshot's by the first tcsfm_optim_snapshot).
+ *   tcsfm_optim_step       ONE launch over all tensors: grads[i] (device, numel[i] floats, read only) and lr[i] are per tensor and per
+ *                          call, which covers parameter groups and schedules.  grads[i] = NULL skips tensor i and leaves its step
+ *                          count where it was -- torch's rule for `p.grad is None` (for numel[i] = 0 nothing is read: any non-NULL
+ *                          pointer counts as a gradient).  TCSFM_OPTIM_ADAM is torch.optim.Adam with weight_decay = 0 and
+ *                          amsgrad = False, per element in fp32 without contraction:
+ *                              m += (1 - beta1) (g - m);  v = beta2 v + (1 - beta2) g g;  p -= (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps))
+ *                          with bc1 = 1 - beta1^t, bc2 = 1 - beta2^t and t the tensor's own step count; 1 - beta1, 1 - beta2, lr / bc1
+ *                          and sqrt(bc2) are computed in double and rounded once -- which is why lr, beta1, beta2 and eps are doubles,
+ *                          as they are in torch: 1 - (float)0.999 is 1.3e-5 off 1 - 0.999, and exp_avg_sq with it.  TCSFM_OPTIM_SGD is torch.optim.SGD(params) as the
+ *                          reference calls it (no momentum, no weight decay): p -= lr g; beta1, beta2 and eps are ignored.  One thread
+ *                          owns an element: results are bit-reproducible.  Asynchronous on the handle's stream and launched plainly,
+ *                          outside tcsfm_set_graph_replay's captures; the tables of a step are staged per step, so steps issued back to
+ *                          back without a synchronisation each use their own gradient pointers and scalars (the gradient BUFFERS must
+ *                          stay valid and unchanged until their step has run).  After a step the networks that read the parameters are
+ *                          reloaded with tcsfm_depthnet_load_device / tcsfm_posenet_load_device: there is no other reload path.
+ *   tcsfm_optim_snapshot   keep a copy of every parameter's current values (a later snapshot replaces it)
+ *   tcsfm_optim_restore    parameters back to the snapshot's bits, moments zero, step counts zero: the optimiser and its tensors are
+ *                          what they were when the snapshot was taken by a fresh optimiser.  Refused before the first snapshot.
+ *                          Both are asynchronous on the handle's stream (the first snapshot allocates and waits for the stream once).
+ *   tcsfm_optim_get_state  tensor i's exp_avg / exp_avg_sq (numel[i] floats each, to a host or a device pointer; NULL: not wanted; an SGD
+ *                          optimiser has none and refuses non-NULL pointers) and its step count; waits for the handle's stream.
+ * TCSFM_E_ARG with a tcsfm_last_error text for: n < 1, a NULL parameter of numel > 0, a negative numel, a pointer that is not 4-byte
+ * aligned, an unknown kind, restore before snapshot.  Destroy the optimiser before its handle. */
+typedef struct tcsfm_optim tcsfm_optim;
+#define TCSFM_OPTIM_ADAM 0
+#define TCSFM_OPTIM_SGD 1
+int tcsfm_optim_create(tcsfm_handle h, int kind, int n, float *const params[], const int64_t numel[], tcsfm_optim **out);
+void tcsfm_optim_destroy(tcsfm_optim *o);
+int tcsfm_optim_step(tcsfm_optim *o, const float *const grads[], const double lr[], double beta1, double beta2, double eps);
+int tcsfm_optim_snapshot(tcsfm_optim *o);
+int tcsfm_optim_restore(tcsfm_optim *o);
+int tcsfm_optim_get_state(tcsfm_optim *o, int i, float *exp_avg_out, float *exp_avg_sq_out, int64_t *step_out);
+
 /* ---- lanes: several refinements in flight (streaming a sequence) ----------------------------------
  * The reference's driver refines one window after another (run_sequential_optimization.py:186-247: DataLoader batch -> H2D ->
  * optimize_window); consecutive windows do not depend on each other.  A B=1 refinement leaves the GPU idle between its short

@@ -97,6 +97,7 @@ PARAM_SE3, PARAM_EULER = 0, 1
 REFINE_POSE, REFINE_POSE_SCALE = 0, 1
 WINDOW_PAIR, WINDOW_REFERENCE = 0, 1
 DEPTH_FULL, DEPTH_QUARTER = 0, 1
+OPTIM_ADAM, OPTIM_SGD = 0, 1
 STAT_POSE = 4
 NSTAT = 10        # cost, cost_photo, n_mask, lambda, pose[6]  (include/tcsfm.h TCSFM_STAT_*)
 
@@ -164,6 +165,12 @@ _SIGNATURES = {
     "tcsfm_depthnet_decode_train": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "tcsfm_depthnet_decode_backward": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P]),
     "tcsfm_depthnet_encode_backward": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "tcsfm_optim_create": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.POINTER(_P)]),
+    "tcsfm_optim_destroy": (None, [_P]),
+    "tcsfm_optim_step": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double]),
+    "tcsfm_optim_snapshot": (C.c_int, [_P]),
+    "tcsfm_optim_restore": (C.c_int, [_P]),
+    "tcsfm_optim_get_state": (C.c_int, [_P, C.c_int, _P, _P, C.POINTER(C.c_int64)]),
     "tcsfm_set_lanes": (C.c_int, [_P, C.c_int]),
     "tcsfm_set_graph_replay": (C.c_int, [_P, C.c_int]),
     "tcsfm_graph_replay_counts": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -25,6 +25,7 @@
 #include "photo_grad_kernel.h"
 #include "loss_grad_kernel.h"
 #include "window_loss_kernel.h"
+#include "optim_kernel.h"
 
 using namespace tc;
 
@@ -3203,6 +3204,7 @@ int tcsfm_profile_kernel_busy(tcsfm_handle h, double *ms_busy, int64_t *launches
 #include "depthnet_host.h"
 #include "posenet_wgrad_host.h"
 #include "posenet_grad_host.h"
+#include "optim_host.h"
 
 void tcsfm_pose_to_matrix(const double pose[6], double T[12]) { tc::pose_to_T(pose, T); }
 void tcsfm_matrix_to_pose(const double T[12], double pose[6]) { tc::T_to_pose(T, pose); }

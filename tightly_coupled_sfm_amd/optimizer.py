@@ -28,6 +28,11 @@ losses.compute_optimization_loss, whose window terms come from one fused HIP red
 given to the constructor are never modified: the loop tunes deep copies where the reference does.  Extra result key `losses`.
 Without that key the weight-tuning switches (optimize_depth_encoder, ...) are ignored with a warning, or refused when
 options['strict_legacy'] is set.
+options['fused_step'] = True (needs weight_tuning; default False) takes the loop's last two steps into the library: the optimiser is an
+optim.LibraryOptimizer (one launch per step, csrc/optim_kernel.h) and the tuned network copies are made ONCE per DepthOptimizer, keep their
+native state, and are put back to their starting values at the start of every later window (snapshot / restore) instead of being
+deep-copied per window.  `tuned_models` then refers to these persistent copies: they hold the last window's tuned weights until the next
+window restores them.
 """
 from __future__ import annotations
 
@@ -59,6 +64,21 @@ def _frozen(*modules):
     finally:
         for p in touched:
             p.requires_grad_(True)
+
+
+class _Optimizers:
+    """several optimisers stepped as one (options['fused_step']: the persistent one of the network weights, the window's own leaves')"""
+
+    def __init__(self, optimizers):
+        self.optimizers = optimizers
+
+    def zero_grad(self):
+        for q in self.optimizers:
+            q.zero_grad()
+
+    def step(self):
+        for q in self.optimizers:
+            q.step()
 
 
 def process_sample_batch(data, config):
@@ -117,6 +137,9 @@ class DepthOptimizer:
         self.pose_model = pose_model.train(False).eval()
         self.depth_model = depth_model.train(False).eval()
         self.weight_tuning = bool(options.get("weight_tuning", False))
+        self.fused_step = bool(options.get("fused_step", False))
+        if self.fused_step and not self.weight_tuning:
+            raise ValueError("options['fused_step'] is the optimiser step of the weight-tuning loop: it needs options['weight_tuning'] = True")
         legacy = [k for k in _LEGACY if options.get(k, False)]
         if self.weight_tuning and not any(options.get(k, False) for k in _TUNING):
             raise ValueError(f"options['weight_tuning'] needs one of the reference's switches {list(_TUNING)}")
@@ -143,6 +166,9 @@ class DepthOptimizer:
         self._tuning_depth = None       # the depth model as a DepthNetModule (weight tuning), built once
         self._tuning_pose = None        # the pose model as a PoseNetModule (optimize_pose_weights_all), built once
         self.tuned_models = None
+        # options['fused_step']: the tuned copies (made once), what their parameters' requires_grad was, and their optimiser
+        self._fused_depth = self._fused_pose = self._fused_opt = None
+        self._fused_flags = []
         self.full_results = []
         # measurement hook (bench.py `shim`): with time_engine the refine call inside optimize_window is bracketed by device synchronisations
         # and its wall time left in last_engine_call_us (off by default: the synchronisations are not free)
@@ -283,15 +309,32 @@ class DepthOptimizer:
                 self._tuning_depth = DepthNetModule(self.depth_model, max_images=n_images).to(device)
             depth = self._tuning_depth
         tuned_depth = any(o.get(k, False) for k in ("optimize_depth_weights_bottleneck_beyond", "optimize_depth_weights_all", "optimize_depth_encoder"))
-        if tuned_depth:
-            depth = copy.deepcopy(depth).train(False).eval()
         pose = self.pose_model
-        if o.get("optimize_pose_weights_all", False):
-            if not isinstance(pose, PoseNetModule):
-                if self._tuning_pose is None or self._tuning_pose.max_images < n_pairs:
-                    self._tuning_pose = PoseNetModule(pose, max_images=n_pairs).to(device)
-                pose = self._tuning_pose
-            pose = copy.deepcopy(pose).train(False).eval()
+        if o.get("optimize_pose_weights_all", False) and not isinstance(pose, PoseNetModule):
+            if self._tuning_pose is None or self._tuning_pose.max_images < n_pairs:
+                self._tuning_pose = PoseNetModule(pose, max_images=n_pairs).to(device)
+            pose = self._tuning_pose
+        if self.fused_step:
+            # the copies live as long as this object (their native networks with them); a window starts by putting them back
+            stale = ((tuned_depth and (self._fused_depth is None or self._fused_depth.max_images < n_images)) or
+                     (o.get("optimize_pose_weights_all", False) and (self._fused_pose is None or self._fused_pose.max_images < n_pairs)))
+            if stale:
+                self._fused_opt, self._fused_flags = None, []
+                self._fused_depth = copy.deepcopy(depth).train(False).eval() if tuned_depth else None
+                self._fused_pose = copy.deepcopy(pose).train(False).eval() if o.get("optimize_pose_weights_all", False) else None
+                self._fused_flags = [(p, p.requires_grad) for m in (self._fused_depth, self._fused_pose) if m is not None for p in m.parameters()]
+            elif self._fused_opt is not None:
+                self._fused_opt.restore()
+                self._fused_opt.zero_grad()
+                for p, flag in self._fused_flags:          # (the loop's requires_grad_ edits)
+                    p.requires_grad_(flag)
+            depth = self._fused_depth if tuned_depth else depth
+            pose = self._fused_pose if o.get("optimize_pose_weights_all", False) else pose
+        else:
+            if tuned_depth:
+                depth = copy.deepcopy(depth).train(False).eval()
+            if o.get("optimize_pose_weights_all", False):
+                pose = copy.deepcopy(pose).train(False).eval()
         frozen = ([] if tuned_depth else [depth]) + ([] if o.get("optimize_pose_weights_all", False) else [pose])
         return depth, pose, frozen
 
@@ -313,7 +356,9 @@ class DepthOptimizer:
         scale = lambda d: eng.scale_recovery(d.detach().contiguous(), intrinsics.contiguous(), cfg["camera_height"] / 30.0,
                                              pad_to_batch=int(cfg.get("minibatch", B)))
         depth_model, pose_model, frozen = self._tuning_models(target_img.device, max((S + 1) * B, 2 * B), 2 * split)
-        self.tuned_models = (depth_model, pose_model)      # the models of the last window as the loop left them (copies where it tuned them)
+        # the models of the last window as the loop left them (copies where it tuned them; under options['fused_step'] the persistent
+        # copies, which the next window puts back to their starting values)
+        self.tuned_models = (depth_model, pose_model)
         imgs = torch.cat([target_img] + source_img_list, 0)
 
         # first pass (optimizer.py:142-171): initial depths and poses, the l_depth_init anchor, the skips
@@ -344,16 +389,29 @@ class DepthOptimizer:
             params.append({"params": depth_model.encoder.parameters(), "lr": lr})
         if o.get("optimize_pose_weights_all", False):
             params.append({"params": pose_model.parameters(), "lr": lr})
+        n_net_groups = len(params)               # the groups above are network weights, the ones below this window's own leaves
         disp_leaf = bottleneck = bottleneck_2 = None
         if o.get("optimize_depth_pred", False):
             stacked_disp = torch.cat(disp_list0, 1)
             disp_leaf = torch.nn.functional.interpolate(stacked_disp, (int(H / 4), int(W / 4)), mode="bilinear").clone().detach().requires_grad_()
             params.append({"params": disp_leaf, "lr": lr})
         if o.get("optimize_depth_bottleneck_values", False):
-            bottleneck, bottleneck_2 = skips[-1].clone().detach().requires_grad_(), skips[-2].clone().detach().requires_grad_()
+            # (the skips are channels-last views; the library's optimiser takes contiguous leaves: same values, same results)
+            fmt = torch.contiguous_format if self.fused_step else torch.preserve_format
+            bottleneck = skips[-1].clone(memory_format=fmt).detach().requires_grad_()
+            bottleneck_2 = skips[-2].clone(memory_format=fmt).detach().requires_grad_()
             params.append({"params": bottleneck, "lr": lr})
             params.append({"params": bottleneck_2, "lr": lr})
-        optimizer = torch.optim.Adam(params) if o.get("optimizer", "adam") == "adam" else torch.optim.SGD(params)
+        if self.fused_step:
+            from .optim import LibraryOptimizer
+            kind = "adam" if o.get("optimizer", "adam") == "adam" else "sgd"
+            if n_net_groups and self._fused_opt is None:       # first window: the copies hold their starting values
+                self._fused_opt = LibraryOptimizer(params[:n_net_groups], kind=kind, engine=eng)
+                self._fused_opt.snapshot()
+            leaves = LibraryOptimizer(params[n_net_groups:], kind=kind, engine=eng) if len(params) > n_net_groups else None
+            optimizer = _Optimizers([q for q in (self._fused_opt if n_net_groups else None, leaves) if q is not None])
+        else:
+            optimizer = torch.optim.Adam(params) if o.get("optimizer", "adam") == "adam" else torch.optim.SGD(params)
 
         ssim = losses.SSIM_Loss()
         fused = bool(o.get("fused_loss", True))
