@@ -25,6 +25,7 @@
  *     host-pointer calls and calls returning host scalars synchronise that stream before returning.
  *   - return value: 0 = ok, negative = error; tcsfm_last_error() gives the message.  Nothing throws.
  *   - one handle = one device + one stream; calls on a handle are not re-entrant.
+ *   - an output must not overlap another array of the same call, a few documented pairs excepted: see "overlapping arguments" below.
  */
 #ifndef TCSFM_H
 #define TCSFM_H
@@ -135,6 +136,45 @@ typedef struct tcsfm_opts {
 enum { TCSFM_STAT_COST = 0, TCSFM_STAT_COST_PHOTO = 1, TCSFM_STAT_NMASK = 2, TCSFM_STAT_LAMBDA = 3,
        TCSFM_STAT_POSE = 4 /* ..9: the 6-vector the row was evaluated at */, TCSFM_NSTAT = 10 };
 
+/* ---- overlapping arguments -------------------------------------------------------------------
+ * Every array argument of a call is a range of bytes (its pointer and the extent its description gives).  A call whose OUTPUT range
+ * overlaps an input range or another output range of the SAME call -- partially counts -- is REFUSED with TCSFM_E_ARG before anything is
+ * enqueued: tcsfm_last_error() says "<entry>: <out> overlaps <other>", no buffer is touched and the handle stays usable.  The exceptions
+ * below are HONOURED: the call returns exactly the bits of the same call on disjoint copies.  NULL arguments and zero-length arrays
+ * take part in nothing; inputs may share memory with each other freely.
+ *   1. Poses.  pose_out at the base address of pose_in (pose_init for the sequence calls): the initial poses are consumed by the first
+ *      launch, the refined ones are written by the last (the sequence calls hold pose_init on the device before the first window is
+ *      issued and write pose_out after the last has finished).
+ *   2. Dense depth.  depth_out of tcsfm_refine_dense / tcsfm_refine_dense_window (and the _async / _queued forms) may overlap depth_t
+ *      or depth_s in any way: the call then leaves depth_out alone until a final stream-ordered copy from the work buffer (a queued
+ *      call of this kind is not merged: it flushes what is waiting and runs at once).  depth_out over any other input is refused.
+ *   3. Element-wise entries, output at the base address of one input -- where a thread loads everything it needs from the elements it
+ *      owns before its first store: the pairs of tcsfm_disp_to_depth and tcsfm_disp_to_depth_backward below.  Every other operator
+ *      gathers from neighbours or from projected positions (SSIM, smoothness, warp, photometric) or re-reads an input after a store
+ *      (window loss): in-place forms of those are refused, not patched with scratch copies.
+ *   4. opts.host_ptrs != 0.  The library stages the arrays: inputs go up before the first launch, outputs come back after the last,
+ *      so an output may overlap an INPUT of the call in any way.  Two outputs sharing memory are refused in every mode.  The sequence
+ *      calls always take host pointers but STREAM them (frames go up while results come back): only item 1 applies to them.
+ *   5. Overlap between the arguments of two DIFFERENT calls (queued calls waiting for their flush, calls on different lanes) is
+ *      outside this contract: the caller's buffers must stay valid and unchanged until the calls that use them have completed.
+ * The honoured pairs, entry by entry (`=`: same base address, `~`: any overlap; device pointers):
+ *   tcsfm_disp_to_depth: scaled_disp = disp, depth = disp
+ *   tcsfm_disp_to_depth_backward: g_disp = disp, g_disp = g_scaled, g_disp = g_depth
+ *   tcsfm_refine: pose_out = pose_in
+ *   tcsfm_refine_window: pose_out = pose_in
+ *   tcsfm_refine_window_async: pose_out = pose_in
+ *   tcsfm_refine_window_queued: pose_out = pose_in
+ *   tcsfm_refine_window_scale_queued: pose_out = pose_in
+ *   tcsfm_refine_dense: pose_out = pose_in, depth_out ~ depth_t, depth_out ~ depth_s
+ *   tcsfm_refine_dense_window: pose_out = pose_in, depth_out ~ depth_t, depth_out ~ depth_s
+ *   tcsfm_refine_dense_window_async: pose_out = pose_in, depth_out ~ depth_t, depth_out ~ depth_s
+ *   tcsfm_refine_dense_window_queued: pose_out = pose_in, depth_out ~ depth_t, depth_out ~ depth_s
+ *   tcsfm_refine_sequence: pose_out = pose_init
+ *   tcsfm_refine_dense_sequence: pose_out = pose_init
+ * (end of the honoured pairs; tcsfm_odometry_sequence takes no initial poses.)  The parameter tables of the networks and of the
+ * optimiser (skips_out[5], d_skips[5], grads[], conv_w_g[7] ..., params[]) contribute one range per non-NULL element; the optimiser's
+ * parameters are outputs of every step (two tensors of one optimiser must not share memory, a gradient must not lie on a parameter). */
+
 /* ---- lifetime ------------------------------------------------------------------------------- */
 
 /* Allocates all device scratch for up to max_pairs directed pairs of H x W images on `device`.
@@ -157,7 +197,8 @@ int tcsfm_algorithmic_bytes_per_pixel(const tcsfm_opts *o);
 
 /* ---- reference-function drop-ins (a1, a5, a7, a12) -------------------------------------------- */
 
-/* disp_to_depth, utils/learning_helpers.py:77-86.  n elements; scaled/depth may be NULL. */
+/* disp_to_depth, utils/learning_helpers.py:77-86.  n elements; scaled/depth may be NULL.  Either output may sit on disp ("overlapping
+ * arguments"); the two outputs must not share memory. */
 int tcsfm_disp_to_depth(tcsfm_handle h, const tcsfm_opts *o, int64_t n, const float *disp, float *scaled_disp, float *depth);
 
 /* SSIM_Loss.forward(x, y), losses.py:27-41: `planes` = N*C images of H x W each (reflect pad 1, 3x3 means, clamp). */
@@ -170,7 +211,8 @@ int tcsfm_smooth_loss(tcsfm_handle h, const tcsfm_opts *o, int N, const float *d
 
 /* backward of disp_to_depth (utils/learning_helpers.py:77-86 under autograd, optimizer.py:241): scaled = a + b disp, depth = 1 / scaled,
  * a = 1 / max_depth, b = 1 / min_depth - a.  The cotangents of scaled_disp and depth (a NULL one is absent and costs nothing; at least
- * one must be given) -> g_disp = b (g_scaled - g_depth / scaled^2), n elements; `scaled` is recomputed as the forward forms it. */
+ * one must be given) -> g_disp = b (g_scaled - g_depth / scaled^2), n elements; `scaled` is recomputed as the forward forms it.  g_disp may
+ * sit on any one of the three inputs ("overlapping arguments"). */
 int tcsfm_disp_to_depth_backward(tcsfm_handle h, const tcsfm_opts *o, int64_t n, const float *disp, const float *g_scaled, const float *g_depth,
         float *g_disp);
 
@@ -295,7 +337,7 @@ int tcsfm_linearize_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, co
 /* Refine N directed pairs: replaces the epoch loop of DepthOptimizer.optimize_window
  * (optimization_experiments/optimizer.py:217-274) for the pose / pose+scale unknowns with
  * o->n_iters Gauss-Newton (or LM) iterations on the reference's residual.
- *   pose_in       [N,6] initial pose (e.g. PoseNet output);  pose_out [N,6] refined pose (may alias pose_in)
+ *   pose_in       [N,6] initial pose (e.g. PoseNet output);  pose_out [N,6] refined pose (may sit on pose_in: "overlapping arguments" above)
  *   log_scale_in  [N] or NULL (start at 0), log_scale_out [N] or NULL: only read/written when refine == POSE_SCALE
  *   stats_out     [N,n_iters+1,TCSFM_NSTAT] or NULL */
 int tcsfm_refine(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *src, const float *depth_t,
@@ -326,7 +368,8 @@ int tcsfm_refine_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const
  * Schur elimination of the depth block, 6x6 reduced pose system, back-substitution.  depth_t is the initial target depth
  * (or sigmoid disparity with depth_is_disp); depth_out [N,1,H,W] receives the refined DEPTH.  w_dc must be 0 (the depth prior of
  * opts.prior_depth regularises instead).  With TCSFM_SOLVER_LM the pose block is Marquardt-damped and a trial that does not
- * lower the cost is rolled back -- pose AND depth map -- before the step is recomputed from the accepted linearisation. */
+ * lower the cost is rolled back -- pose AND depth map -- before the step is recomputed from the accepted linearisation.
+ * pose_out may sit on pose_in, and depth_out may overlap depth_t or depth_s in any way ("overlapping arguments"). */
 int tcsfm_refine_dense(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *src, const float *depth_t,
                        const float *depth_s, const float *K, const float *pose_in, float *pose_out, float *depth_out,
                        float *stats_out);
@@ -373,7 +416,8 @@ int tcsfm_refine_dense(tcsfm_handle h, const tcsfm_opts *o, int N, const float *
  *     (the forward pairs' mask / min-over-sources selection and its count K_f; the inverse pairs' 6 x 6 systems, K_i and the adjoint
  *     scatter, whose two parts are summed without their factors so that no count has to precede it), the joint kernel, one launch
  *     that solves the targets' 6S x 6S systems and the inverse pairs' 6 x 6 systems, the back-substitution (five with the quarter-
- *     resolution unknown) -- and a call issues no memset or copy: csrc/dense_ref_kernel.h. */
+ *     resolution unknown) -- and a call issues no memset or copy: csrc/dense_ref_kernel.h.  (A call whose depth_out overlaps depth_t or
+ *     depth_s -- honoured, "overlapping arguments" -- ends with one copy: its depth_out is written last.) */
 int tcsfm_refine_dense_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
                               const float *depth_t, const float *depth_s, const float *K, const float *pose_in, float *pose_out,
                               float *depth_out, float *stats_out);
@@ -724,7 +768,8 @@ int tcsfm_refine_dense_window_queued(tcsfm_handle h, const tcsfm_opts *o, int B,
  * reference's batch-summed normalisers (optimizer.py:69,79) are taken over the windows of ONE CALL: windows_per_call plays the
  * role of the reference's config['minibatch'] (run_sequential_optimization.py:186 hands optimize_window a DataLoader batch of that
  * many windows), results depend on it exactly as the reference's loss depends on the minibatch, and are bit-identical to
- * tcsfm_refine_window calls over the same groups of windows; windows_per_call = 1 gives the per-window loss. */
+ * tcsfm_refine_window calls over the same groups of windows; windows_per_call = 1 gives the per-window loss.
+ * pose_out may sit on pose_init; no other output may overlap another array of the call ("overlapping arguments"). */
 int tcsfm_refine_sequence(tcsfm_handle h, const tcsfm_opts *o, int T, int S, const float *frames, const float *depths, const float *K,
                           const float *pose_init, float *pose_out, float *log_scale_out, int ring, int windows_per_call, int target_pos);
 /* The same loop with the reference's pose initialisation inside it: for every window the coupled PoseNet loop of

@@ -451,7 +451,7 @@ struct DnReq {
 
 // names -> per-layer requests (decoder: layers >= enc_end and the head; encoder: the others)
 int dn_requests(tcsfm_depthnet *dn, const char *fn, bool dec, int n, const char *const names[], float *const grads[],
-                std::vector<DnReq> &req, float **hw, float **hb) {
+                std::vector<DnReq> &req, float **hw, float **hb, ArgRanges *ranges = nullptr) {
     tcsfm_ctx *h = dn->h;
     req.assign(dn->L.size(), DnReq());
     *hw = *hb = nullptr;
@@ -461,6 +461,7 @@ int dn_requests(tcsfm_depthnet *dn, const char *fn, bool dec, int n, const char 
         const std::string k = names[i];
         float **slot = nullptr;
         bool mine = false;
+        size_t count = 0;
         for (size_t li = 0; li < dn->L.size() && !slot; li++) {
             DnLayer &l = dn->L[li];
             const bool d = (int)li >= dn->enc_end;
@@ -472,17 +473,24 @@ int dn_requests(tcsfm_depthnet *dn, const char *fn, bool dec, int n, const char 
                 h->err = std::string(fn) + ": " + k + ": running statistics have no gradient";
                 return TCSFM_E_ARG;
             }
-            if (slot) mine = d == dec;
+            if (slot) { mine = d == dec; count = slot == &req[li].w ? l.nw() : (size_t)l.cout; }
         }
-        if (!slot && k == "predict_disps.0.0.conv.weight") { slot = hw; mine = dec; }
-        if (!slot && k == "predict_disps.0.0.conv.bias") { slot = hb; mine = dec; }
+        if (!slot && k == "predict_disps.0.0.conv.weight") { slot = hw; mine = dec; count = DN_HEAD_W; }
+        if (!slot && k == "predict_disps.0.0.conv.bias") { slot = hb; mine = dec; count = 1; }
         if (!slot || !mine) {
             h->err = std::string(fn) + ": " + k + (slot ? ": not a parameter of this half of the network" : ": unknown parameter");
             return TCSFM_E_ARG;
         }
         *slot = grads[i];
+        if (ranges) ranges->out("grads", grads[i], count * sizeof(float), i);
     }
     return TCSFM_OK;
+}
+
+// the five skip maps of N images as ranges of a call (include/tcsfm.h: skip k = [N, H >> (k+1), W >> (k+1), C_k]); a null table or entry is skipped
+void dn_skip_ranges(const tcsfm_depthnet *dn, int N, const char *name, const float *const sk[5], bool out, ArgRanges &a) {
+    for (int k = 0; sk && k < 5; k++)
+        a.add(name, k, sk[k], (size_t)N * (dn->h->H >> (k + 1)) * (dn->h->W >> (k + 1)) * DN_SKIP_C[k] * sizeof(float), out);
 }
 
 // the chain rule through the fold and the reference layout, for every requested layer
@@ -682,6 +690,12 @@ int tcsfm_depthnet_encode(tcsfm_depthnet *dn, int N, const float *imgs, int flip
     if (int rc = dn_check(dn, N, "tcsfm_depthnet_encode")) return rc;
     if (!imgs || !skips_out) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode: NULL argument");
     for (int k = 0; k < 5; k++) if (!skips_out[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode: NULL skip buffer");
+    {
+        ArgRanges a;
+        a.in("imgs", imgs, (size_t)N * 3 * h->H * h->W * sizeof(float));
+        dn_skip_ranges(dn, N, "skips_out", skips_out, true, a);
+        if (int rc = check_overlap(h, "tcsfm_depthnet_encode", a)) return rc;
+    }
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     return dn_encode(dn, N, imgs, flip, dn_enc_scratch(dn, skips_out));
@@ -693,6 +707,12 @@ int tcsfm_depthnet_decode(tcsfm_depthnet *dn, int N, const float *const skips_in
     if (int rc = dn_check(dn, N, "tcsfm_depthnet_decode")) return rc;
     if (!skips_in || !disp_out) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode: NULL argument");
     for (int k = 0; k < 5; k++) if (!skips_in[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode: NULL skip buffer");
+    {
+        ArgRanges a;
+        dn_skip_ranges(dn, N, "skips_in", skips_in, false, a);
+        a.out("disp_out", disp_out, (size_t)N * h->H * h->W * sizeof(float));
+        if (int rc = check_overlap(h, "tcsfm_depthnet_decode", a)) return rc;
+    }
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     return dn_decode(dn, N, skips_in, dn_dec_scratch(dn, disp_out));
@@ -703,6 +723,12 @@ int tcsfm_depthnet_forward(tcsfm_depthnet *dn, int N, const float *imgs, int fli
     tcsfm_ctx *h = dn->h;
     if (int rc = dn_check(dn, N, "tcsfm_depthnet_forward")) return rc;
     if (!imgs || !disp_out) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_forward: NULL argument");
+    {
+        ArgRanges a;
+        a.in("imgs", imgs, (size_t)N * 3 * h->H * h->W * sizeof(float));
+        a.out("disp_out", disp_out, (size_t)N * h->H * h->W * sizeof(float));
+        if (int rc = check_overlap(h, "tcsfm_depthnet_forward", a)) return rc;
+    }
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     if (int rc = dn_encode(dn, N, imgs, flip, dn_enc_scratch(dn, dn->skip))) return rc;
@@ -767,6 +793,13 @@ int tcsfm_depthnet_encode_train(tcsfm_depthnet *dn, int N, const float *imgs, fl
     if (int rc = dn_check_train(dn, N, "tcsfm_depthnet_encode_train")) return rc;
     if (!imgs || !skips_out || !tape) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode_train: NULL argument");
     for (int k = 0; k < 5; k++) if (!skips_out[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode_train: NULL skip buffer");
+    {
+        ArgRanges a;
+        a.in("imgs", imgs, (size_t)N * 3 * h->H * h->W * sizeof(float));
+        dn_skip_ranges(dn, N, "skips_out", skips_out, true, a);
+        a.out("tape", tape, dn_tape_layout(dn, 0, N, nullptr).total() * sizeof(float));
+        if (int rc = check_overlap(h, "tcsfm_depthnet_encode_train", a)) return rc;
+    }
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     return dn_for_groups(dn, 0, N, tape, skips_out, [&](int n, int i0, const DnTape &t, float *const sk[5]) -> int {
@@ -788,6 +821,13 @@ int tcsfm_depthnet_decode_train(tcsfm_depthnet *dn, int N, const float *const sk
     if (int rc = dn_check_train(dn, N, "tcsfm_depthnet_decode_train")) return rc;
     if (!skips_in || !disp_out || !tape) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode_train: NULL argument");
     for (int k = 0; k < 5; k++) if (!skips_in[k]) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode_train: NULL skip buffer");
+    {
+        ArgRanges a;
+        dn_skip_ranges(dn, N, "skips_in", skips_in, false, a);
+        a.out("disp_out", disp_out, (size_t)N * h->H * h->W * sizeof(float));
+        a.out("tape", tape, dn_tape_layout(dn, 1, N, nullptr).total() * sizeof(float));
+        if (int rc = check_overlap(h, "tcsfm_depthnet_decode_train", a)) return rc;
+    }
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     return dn_for_groups(dn, 1, N, tape, skips_in, [&](int n, int i0, const DnTape &t, const float *const sk[5]) -> int {
@@ -808,7 +848,12 @@ int tcsfm_depthnet_decode_backward(tcsfm_depthnet *dn, int N, const float *tape,
     if (!tape || !d_disp) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_decode_backward: NULL argument");
     std::vector<DnReq> req;
     float *hw_ = nullptr, *hb_ = nullptr;
-    if (int rc = dn_requests(dn, fn, true, n_grads, names, grads, req, &hw_, &hb_)) return rc;
+    ArgRanges a;
+    a.in("tape", tape, dn_tape_layout(dn, 1, N, nullptr).total() * sizeof(float));
+    a.in("d_disp", d_disp, (size_t)N * h->H * h->W * sizeof(float));
+    dn_skip_ranges(dn, N, "d_skips", d_skips, true, a);
+    if (int rc = dn_requests(dn, fn, true, n_grads, names, grads, req, &hw_, &hb_, &a)) return rc;
+    if (int rc = check_overlap(h, fn, a)) return rc;
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     if (int rc = dn_for_groups(dn, 1, N, tape, d_skips, [&](int n, int i0, const DnTape &t, float *const dsk[5]) {
@@ -830,7 +875,11 @@ int tcsfm_depthnet_encode_backward(tcsfm_depthnet *dn, int N, const float *tape,
     if (!tape) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_encode_backward: NULL argument");
     std::vector<DnReq> req;
     float *hw_ = nullptr, *hb_ = nullptr;
-    if (int rc = dn_requests(dn, fn, false, n_grads, names, grads, req, &hw_, &hb_)) return rc;
+    ArgRanges a;
+    a.in("tape", tape, dn_tape_layout(dn, 0, N, nullptr).total() * sizeof(float));
+    dn_skip_ranges(dn, N, "d_skips", d_skips, false, a);
+    if (int rc = dn_requests(dn, fn, false, n_grads, names, grads, req, &hw_, &hb_, &a)) return rc;
+    if (int rc = check_overlap(h, fn, a)) return rc;
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     if (int rc = dn_for_groups(dn, 0, N, tape, d_skips, [&](int n, int i0, const DnTape &t, const float *const dsk[5]) {

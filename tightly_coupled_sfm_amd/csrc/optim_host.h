@@ -78,6 +78,11 @@ int tcsfm_optim_create(tcsfm_handle h, int kind, int n, float *const params[], c
         nwork += ((long long)numel[i] + (long long)phase + OPT_CHUNK - 1) / OPT_CHUNK;
     }
     if (nwork > 0x7fffffffLL) return fail(h, TCSFM_E_ARG, "tcsfm_optim_create: too many elements for one optimiser");
+    {   // the tensors are updated in place by every step: two of them sharing memory would be stepped twice
+        ArgRanges a;
+        for (int i = 0; i < n; i++) a.out("params", params[i], (size_t)numel[i] * sizeof(float), i);
+        if (int rc = check_overlap(h, "tcsfm_optim_create", a)) return rc;
+    }
     if (int rc = drain_queued(h)) return rc;
     DeviceGuard dev_guard(h->device);
     tcsfm_optim *o = new tcsfm_optim();
@@ -117,6 +122,14 @@ int tcsfm_optim_step(tcsfm_optim *o, const float *const grads[], const double lr
     if (!grads || !lr) return fail(h, TCSFM_E_ARG, "tcsfm_optim_step: grads and lr are tables of n entries");
     for (int i = 0; i < o->n; i++)
         if (((uintptr_t)grads[i] & 3) != 0) return fail(h, TCSFM_E_ARG, "tcsfm_optim_step: gradient pointer is not 4-byte aligned");
+    {   // a gradient that lies on a parameter (its own or another tensor's) is read while the step rewrites it
+        ArgRanges a;
+        for (int i = 0; i < o->n; i++) {
+            a.in("grads", grads[i], (size_t)o->T[i].numel * sizeof(float), i);
+            if (grads[i]) a.out("params", o->T[i].p, (size_t)o->T[i].numel * sizeof(float), i);
+        }
+        if (int rc = check_overlap(h, "tcsfm_optim_step", a)) return rc;
+    }
     if (int rc = drain_queued(h)) return rc;
     DeviceGuard dev_guard(h->device);
     const int slot = (int)(o->seq % tcsfm_optim::kRing);
@@ -193,6 +206,11 @@ int tcsfm_optim_get_state(tcsfm_optim *o, int i, float *exp_avg_out, float *exp_
     if (step_out) *step_out = (int64_t)o->step[i];
     const size_t bytes = (size_t)o->T[i].numel * sizeof(float);
     if (!bytes || !(exp_avg_out || exp_avg_sq_out)) return TCSFM_OK;
+    {
+        ArgRanges a;
+        a.out("exp_avg_out", exp_avg_out, bytes); a.out("exp_avg_sq_out", exp_avg_sq_out, bytes);
+        if (int rc = check_overlap(h, "tcsfm_optim_get_state", a)) return rc;
+    }
     DeviceGuard dev_guard(h->device);
     if (exp_avg_out) HIPCHK(h, hipMemcpyAsync(exp_avg_out, o->T[i].m, bytes, hipMemcpyDefault, h->stream));
     if (exp_avg_sq_out) HIPCHK(h, hipMemcpyAsync(exp_avg_sq_out, o->T[i].v, bytes, hipMemcpyDefault, h->stream));

@@ -58,6 +58,14 @@ int tcsfm_posenet_forward_train(tcsfm_posenet *pn, int N, const float *imgs, flo
     if (!pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_forward_train: pose_out is NULL");
     if (!tape) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_forward_train: tape is NULL");
     if (((uintptr_t)tape & 15) != 0) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_forward_train: tape must be 16-byte aligned");
+    {
+        PnTapeLayer tl[7];
+        ArgRanges a;
+        a.in("imgs", imgs, (size_t)N * 6 * h->H * h->W * sizeof(float));
+        a.out("pose_out", pose_out, (size_t)N * 6 * sizeof(float));
+        a.out("tape", tape, (size_t)pn_tape_layout(pn, N, tl) * sizeof(float));
+        if (int rc = check_overlap(h, "tcsfm_posenet_forward_train", a)) return rc;
+    }
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     const long long hw = (long long)h->H * h->W;
@@ -129,6 +137,14 @@ int tcsfm_posenet_backward(tcsfm_posenet *pn, int N, const float *tape, const fl
     if (((uintptr_t)tape & 15) != 0) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_backward: tape must be 16-byte aligned");
     if (!d_pose) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_backward: d_pose is NULL");
     if (!d_imgs) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_backward: d_imgs is NULL");
+    {
+        PnTapeLayer tl[7];
+        ArgRanges a;
+        a.in("tape", tape, (size_t)pn_tape_layout(pn, N, tl) * sizeof(float));
+        a.in("d_pose", d_pose, (size_t)N * 6 * sizeof(float));
+        a.out("d_imgs", d_imgs, (size_t)N * 6 * h->H * h->W * sizeof(float));
+        if (int rc = check_overlap(h, "tcsfm_posenet_backward", a)) return rc;
+    }
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     if (int rc = pnb_prepare(pn)) return rc;
@@ -151,6 +167,23 @@ int tcsfm_posenet_param_backward(tcsfm_posenet *pn, int N, const float *imgs, co
     }
     req.hw = head_w_g; req.hb = head_b_g;
     if (req.w[0] && !imgs) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_param_backward: imgs is NULL (conv1's weight gradient reads the images)");
+    {
+        PnTapeLayer tl[7];
+        ArgRanges a;
+        const size_t img_b = (size_t)N * 6 * h->H * h->W * sizeof(float);
+        if (req.w[0]) a.in("imgs", imgs, img_b);
+        a.in("tape", tape, (size_t)pn_tape_layout(pn, N, tl) * sizeof(float));
+        a.in("d_pose", d_pose, (size_t)N * 6 * sizeof(float));
+        a.out("d_imgs", d_imgs, img_b);
+        for (int l = 0; l < 7; l++) {
+            const PnLayer &L = pn->L[l];
+            a.out("conv_w_g", req.w[l], (size_t)L.cout * L.cin * L.ks * L.ks * sizeof(float), l);
+            a.out("conv_b_g", req.b[l], L.cout * sizeof(float), l); a.out("gn_w_g", req.g[l], L.cout * sizeof(float), l);
+            a.out("gn_b_g", req.be[l], L.cout * sizeof(float), l);
+        }
+        a.out("head_w_g", head_w_g, 6 * 256 * sizeof(float)); a.out("head_b_g", head_b_g, 6 * sizeof(float));
+        if (int rc = check_overlap(h, "tcsfm_posenet_param_backward", a)) return rc;
+    }
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     if (int rc = pnb_prepare(pn)) return rc;

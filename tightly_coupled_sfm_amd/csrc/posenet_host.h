@@ -280,6 +280,12 @@ int tcsfm_posenet_forward(tcsfm_posenet *pn, int N, const float *imgs, float *po
     tcsfm_ctx *h = pn->h;
     if (!pn->loaded) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_forward: no weights loaded");
     if (N < 1 || N > pn->max_images || !imgs || !pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_forward: bad argument");
+    {
+        ArgRanges a;
+        a.in("imgs", imgs, (size_t)N * 6 * h->H * h->W * sizeof(float));
+        a.out("pose_out", pose_out, (size_t)N * 6 * sizeof(float));
+        if (int rc = check_overlap(h, "tcsfm_posenet_forward", a)) return rc;
+    }
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     const long long hw = (long long)h->H * h->W;
@@ -348,6 +354,14 @@ int tcsfm_solve_pose_iteratively(tcsfm_handle h, tcsfm_posenet *pn, int num_iter
     const int N = 2 * B * S;
     if (num_iter < 1 || B < 1 || S < 1 || N > pn->max_images || N > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_solve_pose_iteratively: sizes out of range");
     if (!tgt || !srcs || !depth_t || !depth_s || !K || !poses_out) return fail(h, TCSFM_E_ARG, "tcsfm_solve_pose_iteratively: NULL argument");
+    {
+        const size_t hw_b = (size_t)h->H * h->W * sizeof(float);
+        ArgRanges a;
+        a.in("tgt", tgt, (size_t)B * 3 * hw_b); a.in("srcs", srcs, (size_t)S * B * 3 * hw_b); a.in("depth_t", depth_t, (size_t)B * hw_b);
+        a.in("depth_s", depth_s, (size_t)S * B * hw_b); a.in("K", K, (size_t)B * 9 * sizeof(float));
+        a.out("poses_out", poses_out, (size_t)N * 6 * sizeof(float)); a.out("stacked_out", stacked_out, (size_t)N * num_iter * 6 * sizeof(float));
+        if (int rc = check_overlap(h, "tcsfm_solve_pose_iteratively", a)) return rc;
+    }
     if (int rc_q = drain_queued(h)) return rc_q;
     DeviceGuard dev_guard(h->device);
     if (int rc_ = pending_error(h)) return rc_;

@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "../../include/tcsfm.h"
+#include "arg_overlap.h"
 #include "kernels.h"
 #include "dense_kernel.h"
 #include "joint_kernel.h"
@@ -258,6 +259,12 @@ int fail(tcsfm_ctx *h, int code, const char *msg) {
     return code;
 }
 
+// a call's arrays against the overlap contract of include/tcsfm.h: TCSFM_E_ARG with "<entry>: <out> overlaps <other>", or TCSFM_OK
+int check_overlap(tcsfm_ctx *h, const char *entry, const ArgRanges &a) {
+    std::string msg;
+    return a.refused(entry, msg) ? fail(h, TCSFM_E_ARG, msg.c_str()) : TCSFM_OK;
+}
+
 // The device-side pinhole guards (init_pair, k_ground) raise a host-mapped status word; it is reported -- as the documented
 // TCSFM_E_INTRINSICS -- by the next call on the handle or by tcsfm_synchronize, without a device synchronisation of its own.
 static bool k_known(const tcsfm_ctx *h, const float *K, int n) {
@@ -312,10 +319,12 @@ void apply_window_rule(const tcsfm_ctx *h, const tcsfm_opts *o, int win_B, int w
     }
 }
 
-// The array arguments of one call.  With opts.host_ptrs in() copies a host array to the device and out() hands out a device buffer
+// The array arguments of one call.  With opts.host_ptrs in() stages a host array on the device and out() hands out a device buffer
 // that finish() copies back to its host pointer; with device pointers both pass the pointer through.  The device buffers are the
 // handle's staging slots (grown on demand), taken in order of registration -- a null argument takes its slot too, so an argument's
-// slot does not depend on which optional arguments a call passes.  The first error sticks in rc: later steps do nothing.  Holds the
+// slot does not depend on which optional arguments a call passes.  Every array is registered under its argument's name with its
+// extent: ready() applies the overlap contract of include/tcsfm.h (arg_overlap.h) -- a forbidden overlap refuses the call before
+// anything is enqueued -- and only then sends the staged inputs up.  The first error sticks in rc: later steps do nothing.  Holds the
 // handle's device for the call and starts with the pending device-side error check.
 struct Staging {
     tcsfm_ctx *h;
@@ -324,9 +333,13 @@ struct Staging {
     int rc = TCSFM_OK;
     size_t slot = 0;
     struct Back { void *host; const void *dev; size_t bytes; };
-    std::vector<Back> back;
+    std::vector<Back> back, up;
+    ArgRanges args;
 
-    Staging(tcsfm_ctx *h_, const tcsfm_opts *o_) : h(h_), o(o_), dev_guard(h_->device) { rc = pending_error(h); }
+    Staging(tcsfm_ctx *h_, const tcsfm_opts *o_) : h(h_), o(o_), dev_guard(h_->device) {
+        rc = pending_error(h);
+        args.io_free = o->host_ptrs != 0;
+    }
 
     // the next slot's device buffer, at least `bytes` long (null after an error)
     void *scratch(size_t bytes) {
@@ -343,23 +356,38 @@ struct Staging {
         s.cap = bytes;
         return TCSFM_OK;
     }
-    int upload(void *dev, const void *host, size_t bytes) {
-        HIPCHK(h, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream));
-        return TCSFM_OK;
-    }
     template <typename T>
-    const T *in(const T *p, size_t count) {
+    const T *in(const char *name, const T *p, size_t count) {
+        args.in(name, p, count * sizeof(T));
         if (!o->host_ptrs || !p) { slot++; return p; }
         void *d = scratch(count * sizeof(T));
-        if (d) rc = upload(d, p, count * sizeof(T));
+        if (d) up.push_back({const_cast<T *>(p), d, count * sizeof(T)});
         return (const T *)d;
     }
     template <typename T>
-    T *out(T *p, size_t count) {
+    T *out(const char *name, T *p, size_t count) {
+        args.out(name, p, count * sizeof(T));
         if (!o->host_ptrs || !p) { slot++; return p; }
         void *d = scratch(count * sizeof(T));
         if (d) back.push_back({p, d, count * sizeof(T)});
         return (T *)d;
+    }
+    // an output that is written on the host in every mode (takes no slot)
+    void host_out(const char *name, const void *p, size_t bytes) { args.out(name, p, bytes); }
+    void bless(const char *out_name, const char *in_name) { args.bless(out_name, in_name); }
+    // every array is registered: the overlap contract on behalf of `entry` (null: the caller has applied it), then the staged inputs go up
+    int ready(const char *entry) {
+        if (rc) return rc;
+        std::string msg;
+        if (entry && args.refused(entry, msg)) return rc = fail(h, TCSFM_E_ARG, msg.c_str());
+        for (const Back &u : up)
+            if ((rc = upload(const_cast<void *>(u.dev), u.host, u.bytes))) return rc;
+        up.clear();
+        return TCSFM_OK;
+    }
+    int upload(void *dev, const void *host, size_t bytes) {
+        HIPCHK(h, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream));
+        return TCSFM_OK;
     }
     // the outputs' copies back, in registration order, then a synchronisation when `sync` and the call staged host arrays
     int finish(bool sync = true) {
@@ -865,7 +893,7 @@ struct DrefExport { double *scal, *g_pose; float *d_g_rho; const float *d_depth0
 template <int NS>
 int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, const float *d_src, const float *d_dt, const float *d_ds,
                   const float *d_K, const float *d_pose_in, float *d_pose_out, float *d_depth_out, float *d_stats, const WinOff *wo, const DrefExport *ex,
-                  const CoalTab *ct = nullptr, float *const *ct_pose = nullptr, float *const *ct_depth = nullptr) {
+                  const CoalTab *ct = nullptr, float *const *ct_pose = nullptr, float *const *ct_depth = nullptr, bool out_on_input = false) {
     using JL = JointLayout<NS>;
     constexpr int S = NS;
     // B: targets of the launch sequence.  Coalesced calls (ct): ncall queued calls of cB targets each run as ONE sequence over B = ncall cB
@@ -929,7 +957,11 @@ int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, 
     if (pc) I.pose_lin = h->pose_lin;            // buffer 0 of [2][N][12]: every pair's transform at the first linearisation
     // the pack also zeroes the batch counters and -- plain refinement with fixed source maps -- leaves the inputs in the caller's depth
     // output: its inverse slots (the source maps) are final, the forward slots are overwritten by the last back-substitution
-    const bool direct_out = !ex && !(o->free_source_depths != 0) && o->n_iters > 0 && (d_depth_out != nullptr || ct != nullptr);
+    // ... unless the caller's depth_out lies on depth_t or depth_s (out_on_input: honoured, include/tcsfm.h; refine_overlap finds it): output
+    // slot s B + b and input slot s B + b hold different maps and other workgroups of the pack are still reading, so such a call leaves
+    // depth_out alone until the final copy from the work buffer, as the modes without a direct output do (a merged sequence carries no
+    // such call: the queued form runs it at once)
+    const bool direct_out = !ex && !(o->free_source_depths != 0) && o->n_iters > 0 && (d_depth_out != nullptr || ct != nullptr) && !out_on_input;
     if ((rc = run_pack(h, &oo, N, d_tgt, d_src, d_dt, d_ds, &I, ct ? 0 : B, S, h->depth0, wo, ct, direct_out && !ct ? d_depth_out : nullptr, h->dref_norms, 2 * TC_MAX_COAL,
                        ct ? ct_depth : nullptr))) return rc;
     if (ex && ex->d_depth0)       // the prior's centre given explicitly (slots of the forward pairs (0, b): index b)
@@ -1436,9 +1468,10 @@ int tcsfm_disp_to_depth(tcsfm_handle h, const tcsfm_opts *o, int64_t n, const fl
     if (!o || !disp || n < 1) return fail(h, TCSFM_E_ARG, "tcsfm_disp_to_depth: bad argument");
     if (!(o->min_depth > 0 && o->max_depth > o->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
     Staging st(h, o);
-    const float *d_in = st.in(disp, (size_t)n);
-    float *d_s = st.out(scaled, (size_t)n), *d_d = st.out(depth, (size_t)n);
-    if (st.rc) return st.rc;
+    const float *d_in = st.in("disp", disp, (size_t)n);
+    float *d_s = st.out("scaled_disp", scaled, (size_t)n), *d_d = st.out("depth", depth, (size_t)n);
+    st.bless("scaled_disp", "disp"); st.bless("depth", "disp");      // k_disp_to_depth: a thread loads disp[i] before it stores element i
+    if (st.ready("tcsfm_disp_to_depth")) return st.rc;
     hipLaunchKernelGGL(k_disp_to_depth, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, d_in, d_s, d_d, (long long)n,
                        1.f / o->max_depth, 1.f / o->min_depth);
     HIPCHK(h, hipGetLastError());
@@ -1451,9 +1484,9 @@ int tcsfm_ssim(tcsfm_handle h, const tcsfm_opts *o, int planes, const float *x, 
     if (!o || !x || !y || !out || planes < 1) return fail(h, TCSFM_E_ARG, "tcsfm_ssim: bad argument");
     Staging st(h, o);
     size_t hw = (size_t)h->H * h->W, n = hw * planes;
-    const float *d_x = st.in(x, n), *d_y = st.in(y, n);
-    float *d_o = st.out(out, n);
-    if (st.rc) return st.rc;
+    const float *d_x = st.in("x", x, n), *d_y = st.in("y", y, n);
+    float *d_o = st.out("out", out, n);
+    if (st.ready("tcsfm_ssim")) return st.rc;
     hipLaunchKernelGGL(k_ssim, dim3((unsigned)((hw + 255) / 256), planes), dim3(256), 0, h->stream, d_x, d_y, d_o, h->H, h->W);
     HIPCHK(h, hipGetLastError());
     return st.finish();
@@ -1467,9 +1500,11 @@ int tcsfm_disp_to_depth_backward(tcsfm_handle h, const tcsfm_opts *o, int64_t n,
     if (!g_scaled && !g_depth) return fail(h, TCSFM_E_ARG, "tcsfm_disp_to_depth_backward: no cotangent given");
     if (!(o->min_depth > 0 && o->max_depth > o->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
     Staging st(h, o);
-    const float *d_in = st.in(disp, (size_t)n), *d_gs = st.in(g_scaled, (size_t)n), *d_gd = st.in(g_depth, (size_t)n);
-    float *d_out = st.out(g_disp, (size_t)n);
-    if (st.rc) return st.rc;
+    const float *d_in = st.in("disp", disp, (size_t)n), *d_gs = st.in("g_scaled", g_scaled, (size_t)n), *d_gd = st.in("g_depth", g_depth, (size_t)n);
+    float *d_out = st.out("g_disp", g_disp, (size_t)n);
+    // k_disp_to_depth_bwd: a thread loads its float4 (or tail element) of all three inputs before its one store to the same elements
+    st.bless("g_disp", "disp"); st.bless("g_disp", "g_scaled"); st.bless("g_disp", "g_depth");
+    if (st.ready("tcsfm_disp_to_depth_backward")) return st.rc;
     // float4 accesses need 16-byte alignment of every array in use: otherwise the scalar tail takes everything
     const bool aligned = (((uintptr_t)d_in | (uintptr_t)d_gs | (uintptr_t)d_gd | (uintptr_t)d_out) & 15) == 0;
     const long long n4 = aligned ? (long long)(n / 4) : 0, threads = n4 + ((long long)n - 4 * n4);
@@ -1489,10 +1524,10 @@ int tcsfm_ssim_backward(tcsfm_handle h, const tcsfm_opts *o, int planes, const f
     Staging st(h, o);
     const size_t hw = (size_t)h->H * h->W, n = hw * planes;
     SsimGradParams P;
-    P.x = st.in(x, n); P.y = st.in(y, n); P.g_out = st.in(g_out, n);
-    P.g_x = st.out(g_x, n); P.g_y = st.out(g_y, n);
+    P.x = st.in("x", x, n); P.y = st.in("y", y, n); P.g_out = st.in("g_out", g_out, n);
+    P.g_x = st.out("g_x", g_x, n); P.g_y = st.out("g_y", g_y, n);
     P.H = h->H; P.W = h->W;
-    if (st.rc) return st.rc;
+    if (st.ready("tcsfm_ssim_backward")) return st.rc;
     const dim3 grid((unsigned)((h->W + PG_TW - 1) / PG_TW), (unsigned)((h->H + PG_TH - 1) / PG_TH), (unsigned)planes);
     hipLaunchKernelGGL(k_ssim_bwd, grid, dim3(256), 0, h->stream, P);
     HIPCHK(h, hipGetLastError());
@@ -1510,10 +1545,10 @@ int tcsfm_warp(tcsfm_handle h, const tcsfm_opts *o, int N, const float *src, con
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     if (o->depth_is_disp) return fail(h, TCSFM_E_ARG, "tcsfm_warp takes depth maps (call tcsfm_disp_to_depth first)");
     size_t hw = (size_t)h->H * h->W;
-    const float *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
-    const float *d_pose = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
-    float *d_rec = st.out(img_rec, N * 3 * hw), *d_valid = st.out(valid, N * hw), *d_pd = st.out(proj_depth, N * hw), *d_cd = st.out(comp_depth, N * hw);
-    if (st.rc) return st.rc;
+    const float *d_src = st.in("src", src, N * 3 * hw), *d_dt = st.in("depth_t", depth_t, N * hw), *d_ds = st.in("depth_s", depth_s, N * hw);
+    const float *d_pose = st.in("pose", pose, (size_t)N * 6), *d_K = st.in("K", K, (size_t)N * 9);
+    float *d_rec = st.out("img_rec", img_rec, N * 3 * hw), *d_valid = st.out("valid", valid, N * hw), *d_pd = st.out("proj_depth", proj_depth, N * hw), *d_cd = st.out("comp_depth", comp_depth, N * hw);
+    if (st.ready("tcsfm_warp")) return st.rc;
     if ((rc = run_init(h, o, N, d_pose, nullptr, d_K, 0))) return rc;
     WarpParams P;
     P.src = d_src; P.depth_t = d_dt; P.depth_s = d_ds; P.pc = h->pconst;
@@ -1535,10 +1570,10 @@ int tcsfm_warp_posenet_input(tcsfm_handle h, const tcsfm_opts *o, int N, const f
     if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt = st.in(tgt, N * 3 * hw), *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
-    const float *d_pose = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
-    float *d_out = st.out(posenet_in, N * 6 * hw), *d_valid = st.out(valid, N * hw);
-    if (st.rc) return st.rc;
+    const float *d_tgt = st.in("tgt", tgt, N * 3 * hw), *d_src = st.in("src", src, N * 3 * hw), *d_dt = st.in("depth_t", depth_t, N * hw), *d_ds = st.in("depth_s", depth_s, N * hw);
+    const float *d_pose = st.in("pose", pose, (size_t)N * 6), *d_K = st.in("K", K, (size_t)N * 9);
+    float *d_out = st.out("posenet_in", posenet_in, N * 6 * hw), *d_valid = st.out("valid", valid, N * hw);
+    if (st.ready("tcsfm_warp_posenet_input")) return st.rc;
     if ((rc = run_init(h, o, N, d_pose, nullptr, d_K, 0))) return rc;
     WarpParams P;
     P.src = d_src; P.depth_t = d_dt; P.depth_s = d_ds; P.pc = h->pconst;
@@ -1600,11 +1635,11 @@ int tcsfm_warp_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const float 
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     if (o->depth_is_disp) return fail(h, TCSFM_E_ARG, "tcsfm_warp_backward takes depth maps (call tcsfm_disp_to_depth first)");
     const size_t hw = (size_t)h->H * h->W;
-    const float *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
-    const float *d_pose_in = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
-    const float *d_grec = st.in(g_rec, N * 3 * hw), *d_gpd = st.in(g_proj_depth, N * hw), *d_gcd = st.in(g_comp_depth, N * hw);
-    float *o_dt = st.out(d_depth_t, N * hw), *o_ds = st.out(d_depth_s, N * hw), *o_pose = st.out(d_pose, (size_t)N * 6);
-    if (st.rc) return st.rc;
+    const float *d_src = st.in("src", src, N * 3 * hw), *d_dt = st.in("depth_t", depth_t, N * hw), *d_ds = st.in("depth_s", depth_s, N * hw);
+    const float *d_pose_in = st.in("pose", pose, (size_t)N * 6), *d_K = st.in("K", K, (size_t)N * 9);
+    const float *d_grec = st.in("g_rec", g_rec, N * 3 * hw), *d_gpd = st.in("g_proj_depth", g_proj_depth, N * hw), *d_gcd = st.in("g_comp_depth", g_comp_depth, N * hw);
+    float *o_dt = st.out("d_depth_t", d_depth_t, N * hw), *o_ds = st.out("d_depth_s", d_depth_s, N * hw), *o_pose = st.out("d_pose", d_pose, (size_t)N * 6);
+    if (st.ready("tcsfm_warp_backward")) return st.rc;
     if ((rc = warp_backward_dev(h, o, N, d_src, d_dt, d_ds, d_pose_in, d_K, d_grec, d_gpd, d_gcd, o_dt, o_ds, o_pose, false))) return rc;
     return st.finish();
 }
@@ -1640,10 +1675,10 @@ int tcsfm_photometric_maps_backward(tcsfm_handle h, const tcsfm_opts *o, int N, 
     Staging st(h, o);
     if (st.rc) return st.rc;
     const size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt = st.in(tgt, N * 3 * hw), *d_rec = st.in(img_rec, N * 3 * hw), *d_pd = st.in(proj_depth, N * hw), *d_cd = st.in(comp_depth, N * hw);
-    const float *d_gdiff = st.in(g_diff, N * hw), *d_gweight = st.in(g_weight, N * hw);
-    float *o_grec = st.out(g_rec, N * 3 * hw), *o_gpd = st.out(g_proj_depth, N * hw), *o_gcd = st.out(g_comp_depth, N * hw);
-    if (st.rc) return st.rc;
+    const float *d_tgt = st.in("tgt", tgt, N * 3 * hw), *d_rec = st.in("img_rec", img_rec, N * 3 * hw), *d_pd = st.in("proj_depth", proj_depth, N * hw), *d_cd = st.in("comp_depth", comp_depth, N * hw);
+    const float *d_gdiff = st.in("g_diff", g_diff, N * hw), *d_gweight = st.in("g_weight", g_weight, N * hw);
+    float *o_grec = st.out("g_rec", g_rec, N * 3 * hw), *o_gpd = st.out("g_proj_depth", g_proj_depth, N * hw), *o_gcd = st.out("g_comp_depth", g_comp_depth, N * hw);
+    if (st.ready("tcsfm_photometric_maps_backward")) return st.rc;
     if ((rc = photo_maps_backward_dev(h, o, N, d_tgt, d_rec, d_pd, d_cd, d_gdiff, d_gweight, nullptr, o_grec, o_gpd, o_gcd))) return rc;
     return st.finish();
 }
@@ -1660,11 +1695,11 @@ int tcsfm_photometric_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     if (o->depth_is_disp) return fail(h, TCSFM_E_ARG, "tcsfm_photometric_backward takes depth maps (call tcsfm_disp_to_depth first)");
     const size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt = st.in(tgt, N * 3 * hw), *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
-    const float *d_pose_in = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
-    const float *d_gdiff = st.in(g_diff, N * hw), *d_gweight = st.in(g_weight, N * hw), *d_gimg = st.in(g_img_rec, N * 3 * hw);
-    float *o_dt = st.out(d_depth_t, N * hw), *o_ds = st.out(d_depth_s, N * hw), *o_pose = st.out(d_pose, (size_t)N * 6);
-    if (st.rc) return st.rc;
+    const float *d_tgt = st.in("tgt", tgt, N * 3 * hw), *d_src = st.in("src", src, N * 3 * hw), *d_dt = st.in("depth_t", depth_t, N * hw), *d_ds = st.in("depth_s", depth_s, N * hw);
+    const float *d_pose_in = st.in("pose", pose, (size_t)N * 6), *d_K = st.in("K", K, (size_t)N * 9);
+    const float *d_gdiff = st.in("g_diff", g_diff, N * hw), *d_gweight = st.in("g_weight", g_weight, N * hw), *d_gimg = st.in("g_img_rec", g_img_rec, N * 3 * hw);
+    float *o_dt = st.out("d_depth_t", d_depth_t, N * hw), *o_ds = st.out("d_depth_s", d_depth_s, N * hw), *o_pose = st.out("d_pose", d_pose, (size_t)N * 6);
+    if (st.ready("tcsfm_photometric_backward")) return st.rc;
     if (!o_dt && !o_ds && !o_pose) return st.finish();
     // the cotangents that reach the warp: g_rec = (assembly's, from g_diff) + g_img_rec; g_proj_depth, g_comp_depth from g_weight
     const float *w_grec = d_gimg, *w_gpd = nullptr, *w_gcd = nullptr;
@@ -1702,11 +1737,12 @@ int tcsfm_photometric(tcsfm_handle h, const tcsfm_opts *o, int N, const float *t
     if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt = st.in(tgt, N * 3 * hw), *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
-    const float *d_pose = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9);
+    const float *d_tgt = st.in("tgt", tgt, N * 3 * hw), *d_src = st.in("src", src, N * 3 * hw), *d_dt = st.in("depth_t", depth_t, N * hw), *d_ds = st.in("depth_s", depth_s, N * hw);
+    const float *d_pose = st.in("pose", pose, (size_t)N * 6), *d_K = st.in("K", K, (size_t)N * 9);
     float *outs[6] = {diff, valid, weight, auto_err, auto_mask, img_rec}, *d_out[6];
-    for (int i = 0; i < 6; i++) d_out[i] = st.out(outs[i], (i == 5 ? 3 : 1) * N * hw);
-    if (st.rc) return st.rc;
+    static const char *const out_names[6] = {"diff", "valid", "weight", "auto_err", "auto_mask", "img_rec"};
+    for (int i = 0; i < 6; i++) d_out[i] = st.out(out_names[i], outs[i], (i == 5 ? 3 : 1) * N * hw);
+    if (st.ready("tcsfm_photometric")) return st.rc;
     if ((rc = run_pack(h, o, N, d_tgt, d_src, d_dt, d_ds))) return rc;
     if ((rc = run_init(h, o, N, d_pose, nullptr, d_K, 0))) return rc;
     LinParams P = lin_params(h, o, 6);
@@ -1761,9 +1797,13 @@ int tcsfm_linearize(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt
     if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt = st.in(tgt, N * 3 * hw), *d_src = st.in(src, N * 3 * hw), *d_dt = st.in(depth_t, N * hw), *d_ds = st.in(depth_s, N * hw);
-    const float *d_pose = st.in(pose, (size_t)N * 6), *d_K = st.in(K, (size_t)N * 9), *d_ls = st.in(log_scale, (size_t)N);
-    if (st.rc) return st.rc;
+    const float *d_tgt = st.in("tgt", tgt, N * 3 * hw), *d_src = st.in("src", src, N * 3 * hw), *d_dt = st.in("depth_t", depth_t, N * hw), *d_ds = st.in("depth_s", depth_s, N * hw);
+    const float *d_pose = st.in("pose", pose, (size_t)N * 6), *d_K = st.in("K", K, (size_t)N * 9), *d_ls = st.in("log_scale", log_scale, (size_t)N);
+    {
+        const size_t np_ = (size_t)np_of(o);
+        st.host_out("Hmat", Hmat, N * np_ * np_ * sizeof(double)); st.host_out("g", g, N * np_ * sizeof(double)); st.host_out("stats", stats, (size_t)N * 4 * sizeof(double));
+    }
+    if (st.ready("tcsfm_linearize")) return st.rc;
     std::vector<double> host;
     if ((rc = eval_once(h, o, N, N, d_tgt, d_src, d_dt, d_ds, d_pose, d_ls, d_K, MODE_LIN, host))) return rc;
     unpack_lin_records(host, N, np_of(o), Hmat, g, stats);
@@ -1785,10 +1825,12 @@ int tcsfm_linearize_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, co
     if ((rc = check_intrinsics(h, o, K, B))) return rc;
     const size_t hw = (size_t)h->H * h->W;
     const int np = np_of(o);
-    const float *d_tgt = st.in(tgt, B * 3 * hw), *d_src = st.in(srcs, (size_t)B * S * 3 * hw), *d_dt = st.in(depth_t, B * hw);
-    const float *d_ds = st.in(depth_s, (size_t)B * S * hw), *d_K = st.in(K, (size_t)B * 9), *d_pose = st.in(pose, (size_t)N * 6);
-    const float *d_ls = st.in(log_scale, (size_t)N);
-    if (st.rc) return st.rc;
+    const float *d_tgt = st.in("tgt", tgt, B * 3 * hw), *d_src = st.in("srcs", srcs, (size_t)B * S * 3 * hw), *d_dt = st.in("depth_t", depth_t, B * hw);
+    const float *d_ds = st.in("depth_s", depth_s, (size_t)B * S * hw), *d_K = st.in("K", K, (size_t)B * 9), *d_pose = st.in("pose", pose, (size_t)N * 6);
+    const float *d_ls = st.in("log_scale", log_scale, (size_t)N);
+    st.host_out("Hmat", Hmat, (size_t)N * np * np * sizeof(double)); st.host_out("g", g, (size_t)N * np * sizeof(double));
+    st.host_out("stats", stats, (size_t)N * 4 * sizeof(double));
+    if (st.ready("tcsfm_linearize_window")) return st.rc;
     InitParams I = init_params(h, o, N, d_pose, np == 7 ? d_ls : nullptr, d_K, 0);
     I.K_mod = B;
     if ((rc = run_pack(h, o, N, d_tgt, d_src, d_dt, d_ds, &I, B, S))) return rc;
@@ -1818,15 +1860,45 @@ int tcsfm_loss_surface(tcsfm_handle h, const tcsfm_opts *o, const float *tgt, co
     if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, 1))) return rc;
     size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt = st.in(tgt, 3 * hw), *d_src = st.in(src, 3 * hw), *d_dt = st.in(depth_t, hw), *d_ds = st.in(depth_s, hw);
-    const float *d_pose = st.in(poses, (size_t)P * 6), *d_K = st.in(K, (size_t)9);
-    if (st.rc) return st.rc;
+    const float *d_tgt = st.in("tgt", tgt, 3 * hw), *d_src = st.in("src", src, 3 * hw), *d_dt = st.in("depth_t", depth_t, hw), *d_ds = st.in("depth_s", depth_s, hw);
+    const float *d_pose = st.in("poses", poses, (size_t)P * 6), *d_K = st.in("K", K, (size_t)9);
+    st.host_out("cost_out", cost_out, (size_t)P * sizeof(double));
+    if (st.ready("tcsfm_loss_surface")) return st.rc;
     std::vector<double> host;
     tcsfm_opts oo = *o;
     oo.refine = TCSFM_REFINE_POSE;
     if ((rc = eval_once(h, &oo, P, 1, d_tgt, d_src, d_dt, d_ds, d_pose, nullptr, d_K, MODE_COST, host))) return rc;
     const int rec = 6 * 6 + 6 + 4;
     for (int i = 0; i < P; i++) cost_out[i] = host[(size_t)i * rec + 42];
+    return TCSFM_OK;
+}
+
+// The overlap contract (include/tcsfm.h) for the refine family, pose and dense modes, applied by every public form on its own behalf
+// before anything else happens (a graph replay and a queued call never reach the bodies' own staging with the caller's pointers).
+// Honoured: pose_out at pose_in, and the dense depth_out anywhere over depth_t / depth_s -- *depth_on_input then says so (device pointers).  Arguments the
+// later validation refuses (NULL handle or options, sizes out of range) are left to it.
+static int refine_overlap(tcsfm_ctx *h, const char *entry, const tcsfm_opts *o, int N, int win_B, int win_S, const float *tgt, const float *src,
+                          const float *depth_t, const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in,
+                          float *pose_out, float *log_scale_out, float *stats_out, float *depth_out, bool dense, bool *depth_on_input = nullptr) {
+    if (depth_on_input) *depth_on_input = false;
+    if (!h || !o || N < 1 || N > h->max_pairs || o->n_iters < 0 || o->n_iters > 1000) return TCSFM_OK;
+    const size_t hw = (size_t)h->H * h->W * sizeof(float), nt = win_B ? win_B : N, ns = win_B ? (size_t)win_B * win_S : N;
+    const bool scale = !dense && o->refine == TCSFM_REFINE_POSE_SCALE;
+    ArgRanges a;
+    a.io_free = o->host_ptrs != 0;
+    a.in("tgt", tgt, nt * 3 * hw); a.in(win_B ? "srcs" : "src", src, ns * 3 * hw); a.in("depth_t", depth_t, nt * hw); a.in("depth_s", depth_s, ns * hw);
+    a.in("K", K, nt * 9 * sizeof(float)); a.in("pose_in", pose_in, (size_t)N * 6 * sizeof(float));
+    if (scale) a.in("log_scale_in", log_scale_in, (size_t)N * sizeof(float));
+    a.out("pose_out", pose_out, (size_t)N * 6 * sizeof(float));
+    if (scale) a.out("log_scale_out", log_scale_out, (size_t)N * sizeof(float));
+    if (dense) a.out("depth_out", depth_out, (size_t)N * hw);
+    a.out("stats_out", stats_out, (size_t)N * (o->n_iters + 1) * TCSFM_NSTAT * sizeof(float));
+    a.bless("pose_out", "pose_in");
+    if (dense) { a.bless_any("depth_out", "depth_t"); a.bless_any("depth_out", "depth_s"); }
+    std::string msg;
+    if (a.refused(entry, msg)) return fail(h, TCSFM_E_ARG, msg.c_str());
+    // (staged host arrays land in the library's own, disjoint device buffers: nothing to avoid there)
+    if (depth_on_input) *depth_on_input = dense && !a.io_free && (a.overlap("depth_out", "depth_t") || a.overlap("depth_out", "depth_s"));
     return TCSFM_OK;
 }
 
@@ -1850,13 +1922,13 @@ static int refine_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, in
     if (!ct && (rc = check_intrinsics(h, o, K, nimg_t))) return rc;
     const size_t hw = (size_t)h->H * h->W;
     const int np = np_of(o);
-    const float *d_tgt = st.in(tgt, nimg_t * 3 * hw), *d_src = st.in(src, nimg_s * 3 * hw), *d_dt = st.in(depth_t, nimg_t * hw);
-    const float *d_ds = st.in(depth_s, nimg_s * hw), *d_K = st.in(K, (size_t)nimg_t * 9), *d_pose_in = st.in(pose_in, (size_t)N * 6);
-    const float *d_ls_in = st.in(log_scale_in, (size_t)N);
+    const float *d_tgt = st.in("tgt", tgt, nimg_t * 3 * hw), *d_src = st.in("src", src, nimg_s * 3 * hw), *d_dt = st.in("depth_t", depth_t, nimg_t * hw);
+    const float *d_ds = st.in("depth_s", depth_s, nimg_s * hw), *d_K = st.in("K", K, (size_t)nimg_t * 9), *d_pose_in = st.in("pose_in", pose_in, (size_t)N * 6);
+    const float *d_ls_in = st.in("log_scale_in", log_scale_in, (size_t)N);
     const size_t nstats = (size_t)N * (o->n_iters + 1) * TCSFM_NSTAT;
-    float *d_pose_out = st.out(pose_out, (size_t)N * 6), *d_ls_out = st.out(np == 7 ? log_scale_out : nullptr, (size_t)N);
-    float *d_stats = st.out(stats_out, nstats);
-    if (st.rc) return st.rc;
+    float *d_pose_out = st.out("pose_out", pose_out, (size_t)N * 6), *d_ls_out = st.out("log_scale_out", np == 7 ? log_scale_out : nullptr, (size_t)N);
+    float *d_stats = st.out("stats_out", stats_out, nstats);
+    if (st.ready(nullptr)) return st.rc;
     if (d_stats) HIPCHK(h, hipMemsetAsync(d_stats, 0, nstats * sizeof(float), h->stream));
     // per-pixel min over the sources: the forward pairs also evaluate the other sources' residuals (k_linearize<SEL>)
     const int n_sel = (win_B && win_S > 1 && o->argmin) ? win_B * win_S : 0;
@@ -2014,6 +2086,7 @@ int tcsfm_refine(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, c
                  const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in, float *pose_out,
                  float *log_scale_out, float *stats_out) {
     if (int rc_q = drain_queued(h)) return rc_q;
+    if (int rc_a = refine_overlap(h, "tcsfm_refine", o, N, 0, 0, tgt, src, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out, nullptr, false)) return rc_a;
     return refine_impl(h, o, N, 0, 0, tgt, src, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out);
 }
 
@@ -2023,6 +2096,7 @@ int tcsfm_refine_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const
     if (int rc_q = drain_queued(h)) return rc_q;
     if (!h) return TCSFM_E_ARG;
     if (B < 1 || S < 1 || (long long)2 * B * S > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_window: need 1 <= 2*B*S <= max_pairs");
+    if (int rc_a = refine_overlap(h, "tcsfm_refine_window", o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out, nullptr, false)) return rc_a;
     return refine_impl(h, o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out);
 }
 
@@ -2041,9 +2115,9 @@ int tcsfm_scale_recovery(tcsfm_handle h, const tcsfm_opts *o, int N, const float
         HIPCHK(h, hipMalloc((void **)&h->scale_keys, (size_t)h->max_pairs * hw * sizeof(unsigned)));
         HIPCHK(h, hipMalloc((void **)&h->scale_hist, 260 * sizeof(unsigned)));
     }
-    const float *d_depth = st.in(depth, N * hw), *d_K = st.in(K, (size_t)N * 9);
-    float *d_scale = st.out(scale_out, (size_t)1), *d_med = st.out(median_out, (size_t)1), *d_h = st.out(height_out, N * hw), *d_m = st.out(mask_out, N * hw);
-    if (st.rc) return st.rc;
+    const float *d_depth = st.in("depth", depth, N * hw), *d_K = st.in("K", K, (size_t)N * 9);
+    float *d_scale = st.out("scale_out", scale_out, (size_t)1), *d_med = st.out("median_out", median_out, (size_t)1), *d_h = st.out("height_out", height_out, N * hw), *d_m = st.out("mask_out", mask_out, N * hw);
+    if (st.ready("tcsfm_scale_recovery")) return st.rc;
     HIPCHK(h, hipMemsetAsync(h->scale_hist, 0, 260 * sizeof(unsigned), h->stream));
     GroundParams G;
     G.depth = d_depth; G.K = d_K; G.height = d_h; G.mask = d_m; G.keys = h->scale_keys; G.H = h->H; G.W = h->W; G.err = h->err_dev;
@@ -2070,10 +2144,11 @@ int tcsfm_smooth_loss(tcsfm_handle h, const tcsfm_opts *o, int N, const float *d
     Staging st(h, o);
     const size_t hw = (size_t)h->H * h->W;
     const int nb = (int)((hw + 255) / 256);
-    const float *d_disp = st.in(disp, N * hw), *d_img = st.in(img, N * 3 * hw);
+    const float *d_disp = st.in("disp", disp, N * hw), *d_img = st.in("img", img, N * 3 * hw);
     // scratch: N means (double) + N * nb * 2 partial sums, carved from the next staging slot
     float *scratch = (float *)st.scratch(((size_t)N * 2 + (size_t)N * nb * 2) * sizeof(float));
-    if (st.rc) return st.rc;
+    st.host_out("loss_out", loss_out, sizeof(double));
+    if (st.ready("tcsfm_smooth_loss")) return st.rc;
     double *mean = reinterpret_cast<double *>(scratch);
     float *partial = scratch + (size_t)N * 2;
     hipLaunchKernelGGL(k_smooth_mean, dim3(N), dim3(1024), 0, h->stream, d_disp, (int)hw, mean);
@@ -2098,12 +2173,12 @@ int tcsfm_smooth_loss_device(tcsfm_handle h, const tcsfm_opts *o, int N, const f
     Staging st(h, o);
     const size_t hw = (size_t)h->H * h->W;
     const int nb = (int)((hw + 255) / 256);
-    const float *d_disp = st.in(disp, N * hw), *d_img = st.in(img, N * 3 * hw);
-    float *d_loss = st.out(loss_out, (size_t)1);
-    double *d_stats = st.out(stats_out, (size_t)N * 3);
+    const float *d_disp = st.in("disp", disp, N * hw), *d_img = st.in("img", img, N * 3 * hw);
+    float *d_loss = st.out("loss_out", loss_out, (size_t)1);
+    double *d_stats = st.out("stats_out", stats_out, (size_t)N * 3);
     // scratch as in tcsfm_smooth_loss: N means (double) + N * nb * 2 partial sums
     float *scratch = (float *)st.scratch(((size_t)N * 2 + (size_t)N * nb * 2) * sizeof(float));
-    if (st.rc) return st.rc;
+    if (st.ready("tcsfm_smooth_loss_device")) return st.rc;
     double *mean = reinterpret_cast<double *>(scratch);
     float *partial = scratch + (size_t)N * 2;
     hipLaunchKernelGGL(k_smooth_mean, dim3(N), dim3(1024), 0, h->stream, d_disp, (int)hw, mean);
@@ -2124,10 +2199,10 @@ int tcsfm_smooth_loss_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const
     Staging st(h, o);
     const size_t hw = (size_t)h->H * h->W;
     SmoothGradParams P;
-    P.disp = st.in(disp, N * hw); P.img = st.in(img, N * 3 * hw); P.stats = st.in(stats, (size_t)N * 3); P.g_loss = st.in(g_loss, (size_t)1);
-    P.g_disp = st.out(g_disp, N * hw);
+    P.disp = st.in("disp", disp, N * hw); P.img = st.in("img", img, N * 3 * hw); P.stats = st.in("stats", stats, (size_t)N * 3); P.g_loss = st.in("g_loss", g_loss, (size_t)1);
+    P.g_disp = st.out("g_disp", g_disp, N * hw);
     P.H = h->H; P.W = h->W; P.N = N;
-    if (st.rc) return st.rc;
+    if (st.ready("tcsfm_smooth_loss_backward")) return st.rc;
     hipLaunchKernelGGL(k_smooth_bwd, dim3((unsigned)((hw + 255) / 256), N), dim3(256), 0, h->stream, P);
     HIPCHK(h, hipGetLastError());
     return st.finish();
@@ -2155,8 +2230,8 @@ static WindowLossParams window_loss_params(tcsfm_handle h, const tcsfm_opts *o, 
                                            const float *inv_diff, const float *inv_valid, const float *inv_weight, const float *inv_auto_mask) {
     const size_t n = (size_t)S * B * h->H * h->W;
     WindowLossParams P;
-    P.f_diff = st.in(fwd_diff, n); P.f_valid = st.in(fwd_valid, n); P.f_weight = st.in(fwd_weight, n); P.f_ame = st.in(fwd_auto_err, n);
-    P.i_diff = st.in(inv_diff, n); P.i_valid = st.in(inv_valid, n); P.i_weight = st.in(inv_weight, n); P.i_am = st.in(inv_auto_mask, n);
+    P.f_diff = st.in("fwd_diff", fwd_diff, n); P.f_valid = st.in("fwd_valid", fwd_valid, n); P.f_weight = st.in("fwd_weight", fwd_weight, n); P.f_ame = st.in("fwd_auto_err", fwd_auto_err, n);
+    P.i_diff = st.in("inv_diff", inv_diff, n); P.i_valid = st.in("inv_valid", inv_valid, n); P.i_weight = st.in("inv_weight", inv_weight, n); P.i_am = st.in("inv_auto_mask", inv_auto_mask, n);
     P.B = B; P.S = S; P.hw = h->H * h->W; P.argmin = argmin ? 1 : 0; P.automask = o->automask ? 1 : 0; P.inverse = inverse ? 1 : 0;
     P.w = (double)o->w_dc;
     return P;
@@ -2172,11 +2247,11 @@ int tcsfm_window_loss(tcsfm_handle h, const tcsfm_opts *o, int B, int S, int arg
     Staging st(h, o);
     WindowLossParams P = window_loss_params(h, o, st, B, S, argmin, inverse, fwd_diff, fwd_valid, fwd_weight, fwd_auto_err, inv_diff, inv_valid,
                                             inv_weight, inv_auto_mask);
-    float *d_loss = st.out(loss_out, (size_t)1);
-    double *d_stats = st.out(stats_out, (size_t)WL_NSTAT);
+    float *d_loss = st.out("loss_out", loss_out, (size_t)1);
+    double *d_stats = st.out("stats_out", stats_out, (size_t)WL_NSTAT);
     const int nu = (P.hw >> 2) + (P.hw & 3), per = 256 * WL_UNITS, nbx = (nu + per - 1) / per;      // the grid: a function of the shape only
     double *partial = (double *)st.scratch((size_t)nbx * B * WL_NSUM * sizeof(double));
-    if (st.rc) return st.rc;
+    if (st.ready("tcsfm_window_loss")) return st.rc;
     hipLaunchKernelGGL(k_window_loss, dim3(nbx, B), dim3(256), 0, h->stream, P, partial);
     hipLaunchKernelGGL(k_window_loss_final, dim3(1), dim3(256), 0, h->stream, (const double *)partial, nbx * B, P, d_stats, d_loss);
     HIPCHK(h, hipGetLastError());
@@ -2197,9 +2272,9 @@ int tcsfm_window_loss_backward(tcsfm_handle h, const tcsfm_opts *o, int B, int S
     G.in = window_loss_params(h, o, st, B, S, argmin, inverse, fwd_diff, fwd_valid, fwd_weight, fwd_auto_err, inv_diff, inv_valid, inv_weight,
                               inv_auto_mask);
     const size_t n = (size_t)S * B * G.in.hw;
-    G.stats = st.in(stats, (size_t)WL_NSTAT); G.g_loss = st.in(g_loss, (size_t)1);
-    G.g_f_diff = st.out(g_fwd_diff, n); G.g_f_weight = st.out(g_fwd_weight, n); G.g_i_diff = st.out(g_inv_diff, n); G.g_i_weight = st.out(g_inv_weight, n);
-    if (st.rc) return st.rc;
+    G.stats = st.in("stats", stats, (size_t)WL_NSTAT); G.g_loss = st.in("g_loss", g_loss, (size_t)1);
+    G.g_f_diff = st.out("g_fwd_diff", g_fwd_diff, n); G.g_f_weight = st.out("g_fwd_weight", g_fwd_weight, n); G.g_i_diff = st.out("g_inv_diff", g_inv_diff, n); G.g_i_weight = st.out("g_inv_weight", g_inv_weight, n);
+    if (st.ready("tcsfm_window_loss_backward")) return st.rc;
     const int nu = (G.in.hw >> 2) + (G.in.hw & 3);
     hipLaunchKernelGGL(k_window_loss_bwd, dim3((nu + 255) / 256, B), dim3(256), 0, h->stream, G);
     HIPCHK(h, hipGetLastError());
@@ -2210,7 +2285,7 @@ int tcsfm_window_loss_backward(tcsfm_handle h, const tcsfm_opts *o, int B, int S
 static int dense_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int win_S, const float *tgt, const float *src,
                       const float *depth_t, const float *depth_s, const float *K, const float *pose_in, float *pose_out,
                       float *depth_out, float *stats_out, const WinOff *wo, const CoalTab *ct = nullptr, float *const *ct_pose = nullptr,
-                      float *const *ct_depth = nullptr) {
+                      float *const *ct_depth = nullptr, bool depth_on_input = false) {
     int rc = check_common(h, o, N);
     if (rc) return rc;
     if (ct) {        // coalesced dense calls (flush_pending): per-pair Gauss-Newton form only, every array argument comes from the table
@@ -2243,14 +2318,14 @@ static int dense_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int
     if (ct && ref_mode && (o->host_ptrs || o->n_iters < 1 || stats_out)) return fail(h, TCSFM_E_ARG, "internal: merged reference-loss calls take device pointers and no statistics");
     const bool lm = o->solver == TCSFM_SOLVER_LM;
     if ((n_sel && (rc = ensure_sel_maps(h))) || (lm && (rc = ensure_dense_lm(h))) || (rc = ensure_dense_rec(h))) return rc;
-    const float *d_tgt = st.in(tgt, nimg_t * 3 * hw), *d_src = st.in(src, nimg_s * 3 * hw), *d_dt = st.in(depth_t, nimg_t * hw);
-    const float *d_ds = st.in(depth_s, nimg_s * hw), *d_K = st.in(K, (size_t)nimg_t * 9), *d_pose_in = st.in(pose_in, (size_t)N * 6);
+    const float *d_tgt = st.in("tgt", tgt, nimg_t * 3 * hw), *d_src = st.in("src", src, nimg_s * 3 * hw), *d_dt = st.in("depth_t", depth_t, nimg_t * hw);
+    const float *d_ds = st.in("depth_s", depth_s, nimg_s * hw), *d_K = st.in("K", K, (size_t)nimg_t * 9), *d_pose_in = st.in("pose_in", pose_in, (size_t)N * 6);
     const size_t nstats = (size_t)N * (o->n_iters + 1) * TCSFM_NSTAT;
-    float *d_pose_out = st.out(pose_out, (size_t)N * 6), *d_depth_out = st.out(depth_out, N * hw), *d_stats = st.out(stats_out, nstats);
-    if (st.rc) return st.rc;
+    float *d_pose_out = st.out("pose_out", pose_out, (size_t)N * 6), *d_depth_out = st.out("depth_out", depth_out, N * hw), *d_stats = st.out("stats_out", stats_out, nstats);
+    if (st.ready(nullptr)) return st.rc;
     if (d_stats) HIPCHK(h, hipMemsetAsync(d_stats, 0, nstats * sizeof(float), h->stream));
     if (ref_mode) {
-        if ((rc = dense_ref_runs[win_S - 1](h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth)))
+        if ((rc = dense_ref_runs[win_S - 1](h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth, depth_on_input)))
             return rc;
     } else if (win_B && o->dense_joint && win_S >= 2 && win_S <= JMAXS_OWN) {   // one depth map per target, 6S x 6S reduced system (joint_kernel.h)
         // (the library's own joint mode stays at S <= JMAXS_OWN = 3: wider windows there keep the per-pair depth copies below)
@@ -2364,10 +2439,10 @@ static int dense_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int
 
 static int dense_impl(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int win_S, const float *tgt, const float *src,
                       const float *depth_t, const float *depth_s, const float *K, const float *pose_in, float *pose_out,
-                      float *depth_out, float *stats_out, const WinOff *wo = nullptr) {
+                      float *depth_out, float *stats_out, const WinOff *wo = nullptr, bool depth_on_input = false) {
     const void *ptrs[10] = {tgt, src, depth_t, depth_s, K, pose_in, nullptr, pose_out, depth_out, stats_out};
     return replay_or_run(h, o, 1, N, win_B, win_S, ptrs, K, wo != nullptr, [&]() {
-        return dense_body(h, o, N, win_B, win_S, tgt, src, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out, wo);
+        return dense_body(h, o, N, win_B, win_S, tgt, src, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out, wo, nullptr, nullptr, nullptr, depth_on_input);
     });
 }
 
@@ -2375,7 +2450,9 @@ int tcsfm_refine_dense(tcsfm_handle h, const tcsfm_opts *o, int N, const float *
                        const float *depth_s, const float *K, const float *pose_in, float *pose_out, float *depth_out,
                        float *stats_out) {
     if (int rc_q = drain_queued(h)) return rc_q;
-    return dense_impl(h, o, N, 0, 0, tgt, src, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out);
+    bool on_input = false;
+    if (int rc_a = refine_overlap(h, "tcsfm_refine_dense", o, N, 0, 0, tgt, src, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr, stats_out, depth_out, true, &on_input)) return rc_a;
+    return dense_impl(h, o, N, 0, 0, tgt, src, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out, nullptr, on_input);
 }
 
 int tcsfm_refine_dense_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
@@ -2384,7 +2461,9 @@ int tcsfm_refine_dense_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S,
     if (int rc_q = drain_queued(h)) return rc_q;
     if (!h) return TCSFM_E_ARG;
     if (B < 1 || S < 1 || (long long)2 * B * S > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window: need 1 <= 2*B*S <= max_pairs");
-    return dense_impl(h, o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out);
+    bool on_input = false;
+    if (int rc_a = refine_overlap(h, "tcsfm_refine_dense_window", o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr, stats_out, depth_out, true, &on_input)) return rc_a;
+    return dense_impl(h, o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out, nullptr, on_input);
 }
 
 // ---- coalesced calls: queued B-window calls of one shape as ONE launch sequence (include/tcsfm.h)
@@ -2484,14 +2563,24 @@ int tcsfm_coalesce_counts(tcsfm_handle h, int *batches, int *calls) {
     return TCSFM_OK;
 }
 
+static int refine_window_queued(tcsfm_handle h, const char *entry, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
+                                const float *depth_t, const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in,
+                                float *pose_out, float *log_scale_out);
+
 int tcsfm_refine_window_queued(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs, const float *depth_t,
                                const float *depth_s, const float *K, const float *pose_in, float *pose_out) {
-    return tcsfm_refine_window_scale_queued(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr);
+    return refine_window_queued(h, "tcsfm_refine_window_queued", o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr);
 }
 
 int tcsfm_refine_window_scale_queued(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs, const float *depth_t,
                                      const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in, float *pose_out,
                                      float *log_scale_out) {
+    return refine_window_queued(h, "tcsfm_refine_window_scale_queued", o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out);
+}
+
+static int refine_window_queued(tcsfm_handle h, const char *entry, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
+                                const float *depth_t, const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in,
+                                float *pose_out, float *log_scale_out) {
     if (!h) return TCSFM_E_ARG;
     if (B < 1 || S < 1 || (long long)2 * B * S > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_window_queued: need 1 <= 2*B*S <= max_pairs");
     int rc = check_common(h, o, 2 * B * S);
@@ -2499,6 +2588,7 @@ int tcsfm_refine_window_scale_queued(tcsfm_handle h, const tcsfm_opts *o, int B,
     if (!tgt || !srcs || !depth_t || !depth_s || !K || !pose_in || !pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_refine_window_queued: NULL argument");
     if (o->host_ptrs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_window_queued: device pointers only");
     if (o->refine != TCSFM_REFINE_POSE_SCALE) { log_scale_in = nullptr; log_scale_out = nullptr; }
+    if ((rc = refine_overlap(h, entry, o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, nullptr, nullptr, false))) return rc;
     // the REFERENCE rule couples the windows of a call through its batch normalisers: such calls are never merged with others
     // (a profile session does not stop the merging: the merged launches are bracketed like any other -- bench.py's roofline.timed_mode)
     const bool mergeable = h->coal_max > 1 && o->window_rule == TCSFM_WINDOW_PAIR && !h->trace_bits && !h->trace_decide;
@@ -2529,7 +2619,11 @@ int tcsfm_refine_dense_window_queued(tcsfm_handle h, const tcsfm_opts *o, int B,
     const bool merge_ref = plain && o->window_rule == TCSFM_WINDOW_REFERENCE && S <= JMAXS && o->free_source_depths == 0 && o->prior_init >= 0.f && o->w_smooth >= 0.f &&
                            o->w_pose_consist == 0.f && (o->depth_param == TCSFM_DEPTH_FULL || (o->depth_param == TCSFM_DEPTH_QUARTER && h->H % 4 == 0 && h->W % 4 == 0)) &&
                            o->min_depth > 0 && o->max_depth > o->min_depth;
-    const bool mergeable = merge_ref || (plain && S == 1 && o->window_rule == TCSFM_WINDOW_PAIR && o->w_dc == 0.f);
+    // a call whose depth_out lies on its own depth inputs is honoured by the path that writes depth_out last: it is not merged
+    bool depth_on_input = false;
+    if ((rc = refine_overlap(h, "tcsfm_refine_dense_window_queued", o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr, nullptr,
+                             depth_out, true, &depth_on_input))) return rc;
+    const bool mergeable = !depth_on_input && (merge_ref || (plain && S == 1 && o->window_rule == TCSFM_WINDOW_PAIR && o->w_dc == 0.f));
     DeviceGuard dev_guard(h->device);
     if (!mergeable) {
         if ((rc = flush_pending(h))) return rc;
@@ -2548,7 +2642,7 @@ int tcsfm_refine_dense_window_queued(tcsfm_handle h, const tcsfm_opts *o, int B,
 
 static int linearize_dense_window_impl(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
                                        const float *depth_t, const float *depth_s, const float *K, const float *pose, const float *depth0,
-                                       double *scal_out, double *g_pose_out, float *g_rho_out, float *g_rho_src_out) {
+                                       double *scal_out, double *g_pose_out, float *g_rho_out, float *g_rho_src_out, const char *entry) {
     if (int rc_q = drain_queued(h)) return rc_q;
     if (!h) return TCSFM_E_ARG;
     if (B < 1 || S < 1 || S > JMAXS || (long long)2 * B * S > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_linearize_dense_window: need 1 <= S <= 4 and 2*B*S <= max_pairs");
@@ -2561,28 +2655,29 @@ static int linearize_dense_window_impl(tcsfm_handle h, const tcsfm_opts *o, int 
     if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, B))) return rc;
     const size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt = st.in(tgt, (size_t)B * 3 * hw), *d_src = st.in(srcs, (size_t)S * B * 3 * hw), *d_dt = st.in(depth_t, (size_t)B * hw);
-    const float *d_ds = st.in(depth_s, (size_t)S * B * hw), *d_K = st.in(K, (size_t)B * 9), *d_pose = st.in(pose, (size_t)N * 6);
-    const float *d_d0 = st.in(depth0, (size_t)B * hw);
-    float *d_g = st.out(g_rho_out, (size_t)B * hw), *d_gs = st.out(g_rho_src_out, (size_t)S * B * hw);
-    if (st.rc) return st.rc;
+    const float *d_tgt = st.in("tgt", tgt, (size_t)B * 3 * hw), *d_src = st.in("srcs", srcs, (size_t)S * B * 3 * hw), *d_dt = st.in("depth_t", depth_t, (size_t)B * hw);
+    const float *d_ds = st.in("depth_s", depth_s, (size_t)S * B * hw), *d_K = st.in("K", K, (size_t)B * 9), *d_pose = st.in("pose", pose, (size_t)N * 6);
+    const float *d_d0 = st.in("depth0", depth0, (size_t)B * hw);
+    float *d_g = st.out("g_rho_out", g_rho_out, (size_t)B * hw), *d_gs = st.out("g_rho_src_out", g_rho_src_out, (size_t)S * B * hw);
+    st.host_out("scal_out", scal_out, 8 * sizeof(double)); st.host_out("g_pose_out", g_pose_out, (size_t)N * 6 * sizeof(double));
+    if (st.ready(entry)) return st.rc;
     tcsfm_opts oo = *o;
     oo.n_iters = 1; oo.solver = TCSFM_SOLVER_GN;
     DrefExport ex{scal_out, g_pose_out, d_g, d_d0, d_gs};
-    if ((rc = dense_ref_runs[S - 1](h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex, nullptr, nullptr, nullptr))) return rc;
+    if ((rc = dense_ref_runs[S - 1](h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex, nullptr, nullptr, nullptr, false))) return rc;
     return st.finish();
 }
 
 int tcsfm_linearize_dense_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
                                  const float *depth_t, const float *depth_s, const float *K, const float *pose, const float *depth0,
                                  double *scal_out, double *g_pose_out, float *g_rho_out) {
-    return linearize_dense_window_impl(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose, depth0, scal_out, g_pose_out, g_rho_out, nullptr);
+    return linearize_dense_window_impl(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose, depth0, scal_out, g_pose_out, g_rho_out, nullptr, "tcsfm_linearize_dense_window");
 }
 int tcsfm_linearize_dense_window_sources(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
                                          const float *depth_t, const float *depth_s, const float *K, const float *pose, const float *depth0,
                                          double *scal_out, double *g_pose_out, float *g_rho_out, float *g_rho_src_out) {
     if (!g_rho_src_out) return h ? fail(h, TCSFM_E_ARG, "tcsfm_linearize_dense_window_sources: NULL argument") : TCSFM_E_ARG;
-    return linearize_dense_window_impl(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose, depth0, scal_out, g_pose_out, g_rho_out, g_rho_src_out);
+    return linearize_dense_window_impl(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose, depth0, scal_out, g_pose_out, g_rho_out, g_rho_src_out, "tcsfm_linearize_dense_window_sources");
 }
 
 // ---- lane self-probe.  MEASURED HAZARD (round 4): how well the streams of a process run side by side depends on the order
@@ -2748,6 +2843,8 @@ int tcsfm_refine_window_async(tcsfm_handle h, int lane, const tcsfm_opts *o, int
     tcsfm_ctx *c = lane_of(h, lane);
     if (!c) return h ? fail(h, TCSFM_E_ARG, "tcsfm_refine_window_async: no such lane (tcsfm_set_lanes)") : TCSFM_E_ARG;
     if (o && o->host_ptrs == 1) return fail(h, TCSFM_E_ARG, "tcsfm_refine_window_async: host_ptrs must be 0 (device) or 2 (pinned host, asynchronous)");
+    if (B >= 1 && S >= 1 && (long long)2 * B * S <= h->max_pairs)
+        if (int rc_a = refine_overlap(h, "tcsfm_refine_window_async", o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out, nullptr, false)) return rc_a;
     if (c == h || h->lanes_serial) return tcsfm_refine_window(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out);
     DeviceGuard dev_guard(h->device);
     // the lane starts behind everything queued on the parent's stream so far (the producers of the caller's device buffers) ...
@@ -2768,6 +2865,8 @@ int tcsfm_refine_dense_window_async(tcsfm_handle h, int lane, const tcsfm_opts *
     tcsfm_ctx *c = lane_of(h, lane);
     if (!c) return h ? fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window_async: no such lane (tcsfm_set_lanes)") : TCSFM_E_ARG;
     if (o && o->host_ptrs == 1) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window_async: host_ptrs must be 0 (device) or 2 (pinned host, asynchronous)");
+    if (B >= 1 && S >= 1 && (long long)2 * B * S <= h->max_pairs)
+        if (int rc_a = refine_overlap(h, "tcsfm_refine_dense_window_async", o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr, stats_out, depth_out, true)) return rc_a;
     if (c == h || h->lanes_serial) return tcsfm_refine_dense_window(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out);
     DeviceGuard dev_guard(h->device);
     HIPCHK(h, hipEventRecord(c->in_ev, h->stream));
@@ -2785,7 +2884,7 @@ int tcsfm_refine_dense_window_async(tcsfm_handle h, int lane, const tcsfm_opts *
 // poses of every window come from the coupled PoseNet loop (train_mono.py:64-80) on the window's lane instead of from the caller.
 static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, const float *frames, const float *depths, const float *K,
                          const float *pose_init, tcsfm_posenet *pn, int num_iter, float *pose_init_out, float *pose_out,
-                         float *log_scale_out, int ring, int windows_per_call, int target_pos, float *dense_depth_out = nullptr) {
+                         float *log_scale_out, int ring, int windows_per_call, int target_pos, const char *entry, float *dense_depth_out = nullptr) {
     if (int rc_q = drain_queued(h)) return rc_q;
     if (!h) return TCSFM_E_ARG;
     if (!o_in) return fail(h, TCSFM_E_ARG, "opts is NULL");
@@ -2794,6 +2893,20 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     if (!frames || !depths || !K || (!pose_init && !pn) || !pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: NULL input");
     if (windows_per_call < 0) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: windows_per_call < 0");
     if (target_pos < -1 || target_pos > S || S > TC_MAX_SRC_OFF) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: target_pos must be -1 or 0..S, S at most 8");
+    {   // The overlap contract (include/tcsfm.h).  Host arrays that are streamed: frames and depths are still going up while results come
+        // back, so only the pose pair is honoured -- pose_init is on the device, and the copy stream drained, before the first window is
+        // issued (small_ev below), and pose_out is written after the last one has finished.
+        const size_t hw_b = (size_t)h->H * h->W * sizeof(float), np6 = (size_t)(T - S) * N * 6 * sizeof(float);
+        ArgRanges a;
+        a.in("frames", frames, (size_t)T * 3 * hw_b); a.in("depths", depths, (size_t)T * hw_b); a.in("K", K, 9 * sizeof(float));
+        a.in("pose_init", pose_init, np6);
+        a.out("pose_init_out", pose_init_out, np6); a.out("pose_out", pose_out, np6);
+        if (o_in->refine == TCSFM_REFINE_POSE_SCALE && !dense_depth_out) a.out("log_scale_out", log_scale_out, (size_t)(T - S) * N * sizeof(float));
+        a.out("depth_out", dense_depth_out, (size_t)(T - S) * N * hw_b);
+        a.bless("pose_out", "pose_init");
+        std::string msg;
+        if (a.refused(entry, msg)) return fail(h, TCSFM_E_ARG, msg.c_str());
+    }
     // position of the target inside a window's S + 1 consecutive frames: the reference's loaders take the middle one
     // (data/kitti_loader.py:271-273: target_idx = int(len / 2), the sources are the others in order)
     const int tp = target_pos < 0 ? (S + 1) / 2 : target_pos;
@@ -3025,20 +3138,20 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
 int tcsfm_refine_sequence(tcsfm_handle h, const tcsfm_opts *o, int T, int S, const float *frames, const float *depths, const float *K,
                           const float *pose_init, float *pose_out, float *log_scale_out, int ring, int windows_per_call, int target_pos) {
     if (h && !pose_init) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: NULL input");
-    return sequence_impl(h, o, T, S, frames, depths, K, pose_init, nullptr, 0, nullptr, pose_out, log_scale_out, ring, windows_per_call, target_pos);
+    return sequence_impl(h, o, T, S, frames, depths, K, pose_init, nullptr, 0, nullptr, pose_out, log_scale_out, ring, windows_per_call, target_pos, "tcsfm_refine_sequence");
 }
 
 int tcsfm_odometry_sequence(tcsfm_handle h, tcsfm_posenet *pn, int num_iter, const tcsfm_opts *o, int T, int S, const float *frames,
                             const float *depths, const float *K, float *pose_init_out, float *pose_out, float *log_scale_out, int ring,
                             int windows_per_call, int target_pos) {
     if (h && !pn) return fail(h, TCSFM_E_ARG, "tcsfm_odometry_sequence: NULL PoseNet");
-    return sequence_impl(h, o, T, S, frames, depths, K, nullptr, pn, num_iter, pose_init_out, pose_out, log_scale_out, ring, windows_per_call, target_pos);
+    return sequence_impl(h, o, T, S, frames, depths, K, nullptr, pn, num_iter, pose_init_out, pose_out, log_scale_out, ring, windows_per_call, target_pos, "tcsfm_odometry_sequence");
 }
 
 int tcsfm_refine_dense_sequence(tcsfm_handle h, const tcsfm_opts *o, int T, int S, const float *frames, const float *depths, const float *K,
                                 const float *pose_init, float *pose_out, float *depth_out, int ring, int windows_per_call, int target_pos) {
     if (h && (!pose_init || !depth_out)) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_sequence: NULL input");
-    return sequence_impl(h, o, T, S, frames, depths, K, pose_init, nullptr, 0, nullptr, pose_out, nullptr, ring, windows_per_call, target_pos, depth_out);
+    return sequence_impl(h, o, T, S, frames, depths, K, pose_init, nullptr, 0, nullptr, pose_out, nullptr, ring, windows_per_call, target_pos, "tcsfm_refine_dense_sequence", depth_out);
 }
 
 int tcsfm_lane_wait(tcsfm_handle h, int lane) {
