@@ -3,6 +3,7 @@
 refinement with the drop-in DepthOptimizer, trajectory composition (validate.compute_trajectory) and odometry errors.
 
     python examples/run_sequence.py [--frames 40] [--sources 2]          (needs an MI355X)
+    python examples/run_sequence.py --frames-only CHECKPOINT              frames in, poses out: see frames_only() below
 
 The two "networks" are stand-ins with the reference models' call conventions: the depth net returns the scene's true
 disparity for whatever frame it is shown, the pose net returns a noisy version of the true relative pose (PoseNet-quality
@@ -47,8 +48,37 @@ class PoseNet(torch.nn.Module):
         return out if out is not None else torch.zeros(x.shape[0], 6, device=x.device)
 
 
+def frames_only(args):
+    """--frames-only: the library's own depth network and PoseNet from a reference checkpoint (a file with 'depth_state_dict' and
+    'pose_state_dict', or a run directory), attached to the engine, and ONE call per sequence that takes the frames alone --
+    PoseNetHIP.odometry_sequence(frames, None, K): depth network, coupled PoseNet loop and refinement all run inside it."""
+    from tightly_coupled_sfm_amd.depthnet import DepthNetHIP
+    from tightly_coupled_sfm_amd.engine import Engine, default_opts
+    from tightly_coupled_sfm_amd.posenet import PoseNetHIP, read_pose_state_dict
+    S = args.sources
+    eng = Engine(H, W, 2 * S * 8, lanes=2)
+    depth_net = DepthNetHIP(eng, 8).load_checkpoint(args.frames_only)
+    pose_net = PoseNetHIP(eng, 2 * S * 8, read_pose_state_dict(args.frames_only))
+    eng.attach_depthnet(depth_net)
+    pose = np.array([0.002, -0.001, 0.033, 0.001, -0.003, 0.001])
+    first = synth.make_pair(H, W, seed=500, pose_gt=pose)
+    frames = torch.as_tensor(np.stack([first["tgt"]] + [synth.make_pair(H, W, seed=500 + i, pose_gt=pose)["src"] for i in range(args.frames - 1)])
+                             .astype(np.float32)).pin_memory()
+    opts = default_opts(n_iters=args.gn_iters, min_depth=0.06, max_depth=2.67)
+    t0 = time.perf_counter()
+    init, refined = pose_net.odometry_sequence(frames, None, first["K"], opts, sources=S, iterations=4, target_pos=-1)
+    dt = time.perf_counter() - t0
+    print(f"{args.frames} frames -> {refined.shape[0]} windows of {2 * S} directed pairs in {dt * 1e3:.1f} ms (first call: allocations included)")
+    with np.printoptions(precision=4, suppress=True):
+        print("PoseNet poses of window 0:\n", init[0].numpy())
+        print("refined poses of window 0:\n", refined[0].numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--frames-only", metavar="CHECKPOINT", default=None,
+                    help="load the depth network and the PoseNet from this reference checkpoint and run the sequence from the frames alone "
+                         "(Engine.attach_depthnet + PoseNetHIP.odometry_sequence with depths=None)")
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--sources", type=int, default=1, choices=(1, 2))
     ap.add_argument("--gn-iters", type=int, default=8)
@@ -56,6 +86,8 @@ def main():
                     help="S = 2: minimise the reference's own compute_optimization_loss (default, as the mirror does) or every directed pair's "
                          "own cost (converges in about half the iterations: DESIGN.md section 2)")
     args = ap.parse_args()
+    if args.frames_only:
+        return frames_only(args)
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).cuda()
     rng = np.random.default_rng(0)
     options = {"diff_img_argmin": True, "automasking": True, "mode": "scaled", "l_depth_consist": True, "l_depth_consist_weight": 0.15,

@@ -155,6 +155,7 @@ enum { TCSFM_STAT_COST = 0, TCSFM_STAT_COST_PHOTO = 1, TCSFM_STAT_NMASK = 2, TCS
  *   4. opts.host_ptrs != 0.  The library stages the arrays: inputs go up before the first launch, outputs come back after the last,
  *      so an output may overlap an INPUT of the call in any way.  Two outputs sharing memory are refused in every mode.  The sequence
  *      calls always take host pointers but STREAM them (frames go up while results come back): only item 1 applies to them.
+ *      (A NULL `depths` of a sequence call -- the attached depth network's case -- takes part in nothing, as every NULL argument does.)
  *   5. Overlap between the arguments of two DIFFERENT calls (queued calls waiting for their flush, calls on different lanes) is
  *      outside this contract: the caller's buffers must stay valid and unchanged until the calls that use them have completed.
  * The honoured pairs, entry by entry (`=`: same base address, `~`: any overlap; device pointers):
@@ -769,13 +770,17 @@ int tcsfm_refine_dense_window_queued(tcsfm_handle h, const tcsfm_opts *o, int B,
  * role of the reference's config['minibatch'] (run_sequential_optimization.py:186 hands optimize_window a DataLoader batch of that
  * many windows), results depend on it exactly as the reference's loss depends on the minibatch, and are bit-identical to
  * tcsfm_refine_window calls over the same groups of windows; windows_per_call = 1 gives the per-window loss.
+ * depths == NULL: every frame's depth comes from the depth network attached with tcsfm_sequence_depthnet (below); with nothing
+ * attached a NULL depths is refused like any other NULL input.
  * pose_out may sit on pose_init; no other output may overlap another array of the call ("overlapping arguments"). */
 int tcsfm_refine_sequence(tcsfm_handle h, const tcsfm_opts *o, int T, int S, const float *frames, const float *depths, const float *K,
                           const float *pose_init, float *pose_out, float *log_scale_out, int ring, int windows_per_call, int target_pos);
 /* The same loop with the reference's pose initialisation inside it: for every window the coupled PoseNet loop of
  * train_mono.py:64-80 (tcsfm_solve_pose_iteratively, `num_iter` network evaluations: config['iterations'], 4 in the reference's
  * scripts) produces the initial poses on the window's lane, then the window is refined -- what optimize_window does per window
- * (optimizer.py:136-297) minus the depth network, whose per-frame output is the `depths` argument (depths, not disparities).
+ * (optimizer.py:136-297).  The depth network's per-frame output is the `depths` argument (depths, not disparities) -- or, with
+ * depths == NULL and a network attached (tcsfm_sequence_depthnet below), is computed inside the call: frames in, poses out, the
+ * first pass of optimizer.py:142-160 included.
  * `pn`: a loaded PoseNet of this handle with max_images >= 2*S; the lanes run copies of it that share its weights.
  * pose_init_out [T-S, 2*S, 6] (or NULL) receives the PoseNet poses, pose_out the refined ones.  Bit-identical to one
  * tcsfm_solve_pose_iteratively + tcsfm_refine_window per CALL's windows (windows_per_call of them as one batch; the PoseNet's
@@ -785,9 +790,22 @@ int tcsfm_odometry_sequence(tcsfm_handle h, tcsfm_posenet *pn, int num_iter, con
                             int windows_per_call, int target_pos);
 /* The dense mode (tcsfm_refine_dense_window: pose + per-pixel inverse depth with the Schur complement, BASELINE config 5) over a
  * sequence, same streaming and batching: depth_out [T-S, 2*S, H, W] (host) receives every directed pair's refined depth map.
- * Bit-identical to one tcsfm_refine_dense_window call per window. */
+ * Bit-identical to one tcsfm_refine_dense_window call per window.  depths == NULL: as for tcsfm_refine_sequence. */
 int tcsfm_refine_dense_sequence(tcsfm_handle h, const tcsfm_opts *o, int T, int S, const float *frames, const float *depths, const float *K,
                                 const float *pose_init, float *pose_out, float *depth_out, int ring, int windows_per_call, int target_pos);
+/* Attaches a depth network to the handle's sequence calls (dn = NULL detaches): while one is attached, the three calls above accept
+ * depths == NULL and compute every frame's depth on the device, once per frame, as the frame's chunk lands in the ring:
+ * disp_to_depth(net(frame), o->min_depth, o->max_depth)[1], as optimizer.py:146-158 does -- the bits of tcsfm_depthnet_forward with
+ * flip = 0 followed by tcsfm_disp_to_depth (the network's last kernel writes the depth; no disparity plane exists), so a frames-only
+ * call returns the bits of the same call on depths computed that way and passed in.  The depths never cross PCIe: a quarter fewer
+ * bytes go up per frame.  The stage runs on the call's pack stream, on a copy of the network that shares `dn`'s weights (a later
+ * tcsfm_depthnet_load / _load_device of `dn` is seen by it) and owns its activations -- allocated here, for dn's max_images images, and
+ * freed with `dn`; chunks of more frames run in groups.
+ *   dn must be a loaded depth network of this handle (TCSFM_E_ARG otherwise; tcsfm_last_error says so).
+ *   A non-NULL depths is used as given, whatever is attached.  depths == NULL with opts.depth_is_disp is refused (the stage produces
+ *   depths), and needs 0 < o->min_depth < o->max_depth.
+ *   tcsfm_depthnet_destroy of the attached network detaches it. */
+int tcsfm_sequence_depthnet(tcsfm_handle h, tcsfm_depthnet *dn);
 int tcsfm_lane_wait(tcsfm_handle h, int lane);
 int tcsfm_lane_synchronize(tcsfm_handle h, int lane);
 int tcsfm_lane_event(tcsfm_handle h, int lane, void **event_out);

@@ -1,7 +1,8 @@
 // Host side of the depth network (models/depth_w_access.py, num_scales = 1): ResNet18 encoder + U-Net decoder -- the topology, the work
 // split, the forward walks, the tapes of the training forward, the backward walks and the tcsfm_depthnet_* entry points.
 // Part of tcsfm_api.hip, the library's only translation unit: included after the context helpers (tcsfm_ctx, fail, HIPCHK, DeviceGuard,
-// drain_queued) and the kernels' headers.  include/tcsfm.h declares the entry points, so they have C linkage here.
+// drain_queued) and the kernels' headers, and before the sequence driver, whose depth stage is dn_sequence_depths.  include/tcsfm.h
+// declares the entry points, so they have C linkage here.
 #pragma once
 
 namespace {
@@ -64,6 +65,12 @@ struct tcsfm_depthnet {
     float *part = nullptr, *bpart = nullptr, *hpart = nullptr;   // weight / bias / head partials of one image group
     float *gA = nullptr, *gB = nullptr, *gC = nullptr, *gD = nullptr, *gV = nullptr;   // data-gradient scratch
     std::vector<float **> train_bufs() { return {&tbuf, &part, &bpart, &hpart, &gA, &gB, &gC, &gD, &gV}; }
+    // tcsfm_sequence_depthnet: the sequence calls' depth stage runs on `seq_clone` -- this network's weights (owns_weights = false: the
+    // device pointers of L[].w4 / bias, pw, pb, which a reload fills in place), its own activations, and its forward launches on
+    // `stream` (the handle's seq_pack) instead of the handle's stream -- so it needs neither this instance nor the handle's stream
+    bool owns_weights = true;
+    hipStream_t stream = nullptr;       // forward launches go here when set (dn_stream)
+    tcsfm_depthnet *seq_clone = nullptr;
 };
 
 namespace {
@@ -115,11 +122,45 @@ void dn_train_free(tcsfm_depthnet *dn) {
     for (float **p : dn->train_bufs()) { if (*p) (void)hipFree(*p); *p = nullptr; }
 }
 
+hipError_t dn_alloc_scratch(tcsfm_depthnet *dn) {
+    const size_t N = (size_t)dn->max_images, hw = (size_t)dn->h->H * dn->h->W;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipMalloc((void **)&dn->skip[k], N * (hw >> (2 * (k + 1))) * DN_SKIP_C[k] * sizeof(float));
+    float **enc[] = {&dn->pool, &dn->t1, &dn->t2, &dn->ds};
+    for (float **p : enc) if (e == hipSuccess) e = hipMalloc((void **)p, N * hw * 4 * sizeof(float));       // (H/4)(W/4) x 64 = H W x 4
+    if (e == hipSuccess) e = hipMalloc((void **)&dn->u, N * hw * 32 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&dn->x, N * hw * 32 * sizeof(float));
+    return e;
+}
+
 void dn_free(tcsfm_depthnet *dn) {
-    for (DnLayer &l : dn->L) { if (l.w4) (void)hipFree(l.w4); if (l.bias) (void)hipFree(l.bias); l.w4 = nullptr; l.bias = nullptr; }
-    dn_train_free(dn);
-    float *bufs[] = {dn->pw, dn->pb, dn->skip[0], dn->skip[1], dn->skip[2], dn->skip[3], dn->skip[4], dn->pool, dn->t1, dn->t2, dn->ds, dn->u, dn->x};
+    if (dn->seq_clone) { dn_free(dn->seq_clone); delete dn->seq_clone; dn->seq_clone = nullptr; }
+    if (dn->owns_weights) {
+        for (DnLayer &l : dn->L) { if (l.w4) (void)hipFree(l.w4); if (l.bias) (void)hipFree(l.bias); l.w4 = nullptr; l.bias = nullptr; }
+        dn_train_free(dn);
+        if (dn->pw) (void)hipFree(dn->pw);
+        if (dn->pb) (void)hipFree(dn->pb);
+    }
+    float *bufs[] = {dn->skip[0], dn->skip[1], dn->skip[2], dn->skip[3], dn->skip[4], dn->pool, dn->t1, dn->t2, dn->ds, dn->u, dn->x};
     for (float *p : bufs) if (p) (void)hipFree(p);
+}
+
+// forward launches of an instance: the handle's stream, or the sequence calls' stage stream for the clone they run
+hipStream_t dn_stream(const tcsfm_depthnet *dn) { return dn->stream ? dn->stream : dn->h->stream; }
+
+// the instance the sequence calls run `dn`'s network on (pn_for_lane's pattern): geometry, work split and weight pointers of `dn`, its
+// own skips and scratch, no training state.  The caller binds its `stream` per call.
+tcsfm_depthnet *dn_sequence_clone(tcsfm_depthnet *dn) {
+    if (dn->seq_clone) return dn->seq_clone;
+    tcsfm_depthnet *q = new tcsfm_depthnet(*dn);
+    q->owns_weights = false; q->seq_clone = nullptr; q->train_loaded = 0;
+    for (DnLayer &l : q->L) { l.wt4 = nullptr; l.raw = l.gw = l.gb = nullptr; }
+    for (float **p : q->train_bufs()) *p = nullptr;
+    q->hacc = nullptr;
+    for (int k = 0; k < 5; k++) q->skip[k] = nullptr;
+    q->pool = q->t1 = q->t2 = q->ds = q->u = q->x = nullptr;
+    if (dn_alloc_scratch(q) != hipSuccess) { dn_free(q); delete q; return nullptr; }
+    return dn->seq_clone = q;
 }
 
 // ---- the split kernels' dispatch: k_dn_conv (pixels = oh ow, blocks = coutp / 16) and k_dnb_dgrad (pixels = lane grid, blocks = cin / 16)
@@ -155,7 +196,7 @@ void dn_conv(tcsfm_depthnet *dn, int li, int N, const float *in, const float *re
     P.in = in; P.w4 = l.w4; P.bias = l.bias; P.res = res; P.out = out; P.aux = aux;
     P.cin = l.cin; P.cout = l.cout; P.coutp = l.coutp; P.ih = l.ih; P.iw = l.iw; P.oh = l.oh; P.ow = l.ow;
     P.stride = l.stride; P.pad = l.pad; P.up = l.up; P.reflect = l.reflect; P.epi = l.epi;
-    dn_launch_split<DnConvKernel>(l.ks, l.sp, l.oh * l.ow, l.coutp / 16, N, P, dn->h->stream);
+    dn_launch_split<DnConvKernel>(l.ks, l.sp, l.oh * l.ow, l.coutp / 16, N, P, dn_stream(dn));
 }
 
 // ---- tapes of the training forward.  A tape of N images is a list of entries, each [N][per-image size] (entry-major), so a group of
@@ -204,7 +245,11 @@ DnTape dn_tape_layout(const tcsfm_depthnet *dn, int dec, int N, float *base) {
 
 // ---- forward walks.  Where each launch's output goes: the instance's scratch (inference) or a tape's entries (training).
 struct DnEncDst { float *conv1, *pool, *t1[DN_BLOCKS], *out[DN_BLOCKS]; };
-struct DnDecDst { float *aux[DN_UPS], *u[DN_UPS], *x[DN_UPS], *feat, *disp; };
+struct DnDecDst {
+    float *aux[DN_UPS], *u[DN_UPS], *x[DN_UPS], *feat, *disp;
+    int as_depth = 0;                   // the head stores disp_to_depth's depth (of min_disp, max_disp) into `disp` instead: k_dn_predict<true>
+    float min_disp = 0.f, max_disp = 0.f;
+};
 
 // a stage's first block leaves its output in t2 (its input is the pooled map or a skip), the second one in the stage's skip
 DnEncDst dn_enc_scratch(const tcsfm_depthnet *dn, float *const sk[5]) {
@@ -233,9 +278,9 @@ int dn_encode(tcsfm_depthnet *dn, int N, const float *imgs, int flip, const DnEn
     const DnLayer &c1 = dn->L[0];
     DnConv1Params P1;
     P1.img = imgs; P1.w4 = c1.w4; P1.bias = c1.bias; P1.out = d.conv1; P1.ih = h->H; P1.iw = h->W; P1.oh = c1.oh; P1.ow = c1.ow; P1.flip = flip ? 1 : 0;
-    hipLaunchKernelGGL(k_dn_conv1<2>, dim3((c1.oh * c1.ow + 127) / 128, 1, N), dim3(256), 0, h->stream, P1);
+    hipLaunchKernelGGL(k_dn_conv1<2>, dim3((c1.oh * c1.ow + 127) / 128, 1, N), dim3(256), 0, dn_stream(dn), P1);
     const int ph = c1.oh / 2, pw = c1.ow / 2;
-    hipLaunchKernelGGL(k_dn_maxpool, dim3(dn_blocks((long long)N * ph * pw * 16)), dim3(256), 0, h->stream, (const float *)d.conv1, d.pool, N, 64, c1.oh,
+    hipLaunchKernelGGL(k_dn_maxpool, dim3(dn_blocks((long long)N * ph * pw * 16)), dim3(256), 0, dn_stream(dn), (const float *)d.conv1, d.pool, N, 64, c1.oh,
                        c1.ow, ph, pw);
     const float *x = d.pool;
     for (int j = 0; j < DN_BLOCKS; j++) {
@@ -259,8 +304,13 @@ int dn_decode(tcsfm_depthnet *dn, int N, const float *const sk[5], const DnDecDs
         x = d.x[i];
     }
     dn_conv(dn, dn->feat(), N, x, nullptr, d.feat);                                              // feature_convs.0: 32 -> 8, ELU
-    hipLaunchKernelGGL(k_dn_predict, dim3(dn_blocks((long long)N * h->H * h->W)), dim3(256), 0, h->stream, (const float *)d.feat, (const float *)dn->pw,
-                       (const float *)dn->pb, d.disp, N, h->H, h->W);
+    const dim3 head_grid(dn_blocks((long long)N * h->H * h->W));
+    if (d.as_depth)
+        hipLaunchKernelGGL(k_dn_predict<true>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->pw, (const float *)dn->pb,
+                           d.disp, N, h->H, h->W, d.min_disp, d.max_disp);
+    else
+        hipLaunchKernelGGL(k_dn_predict<false>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->pw, (const float *)dn->pb,
+                           d.disp, N, h->H, h->W, 0.f, 0.f);
     HIPCHK(h, hipGetLastError());
     return TCSFM_OK;
 }
@@ -595,6 +645,9 @@ int dn_encode_backward(tcsfm_depthnet *dn, int N, const DnTape &t, int i0, const
 void tcsfm_depthnet_destroy(tcsfm_depthnet *dn) {
     if (!dn) return;
     DeviceGuard dev_guard(dn->h->device);
+    // an attached network (tcsfm_sequence_depthnet) is detached: a sequence call synchronises its stage stream before it returns, so the
+    // clone has no work in flight here
+    if (dn->h->seq_dn == dn) dn->h->seq_dn = nullptr;
     dn_free(dn);
     delete dn;
 }
@@ -614,14 +667,9 @@ int tcsfm_depthnet_create(tcsfm_handle h, int max_images, tcsfm_depthnet **out) 
         if (e == hipSuccess) e = hipMalloc((void **)&l.w4, l.w4_count() * sizeof(dn_f4));
         if (e == hipSuccess) e = hipMalloc((void **)&l.bias, l.coutp * sizeof(float));
     }
-    const size_t N = (size_t)max_images, hw = (size_t)h->H * h->W;
     if (e == hipSuccess) e = hipMalloc((void **)&dn->pw, DN_HEAD_W * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&dn->pb, sizeof(float));
-    for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipMalloc((void **)&dn->skip[k], N * (hw >> (2 * (k + 1))) * DN_SKIP_C[k] * sizeof(float));
-    float **enc[] = {&dn->pool, &dn->t1, &dn->t2, &dn->ds};
-    for (float **p : enc) if (e == hipSuccess) e = hipMalloc((void **)p, N * hw * 4 * sizeof(float));       // (H/4)(W/4) x 64 = H W x 4
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->u, N * hw * 32 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->x, N * hw * 32 * sizeof(float));
+    if (e == hipSuccess) e = dn_alloc_scratch(dn);
     if (e != hipSuccess) { tcsfm_depthnet_destroy(dn); return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_depthnet_create: allocation failed"); }
     *out = dn;
     return TCSFM_OK;
@@ -734,6 +782,36 @@ int tcsfm_depthnet_forward(tcsfm_depthnet *dn, int N, const float *imgs, int fli
     if (int rc = dn_encode(dn, N, imgs, flip, dn_enc_scratch(dn, dn->skip))) return rc;
     return dn_decode(dn, N, dn->skip, dn_dec_scratch(dn, disp_out));
 }
+
+int tcsfm_sequence_depthnet(tcsfm_handle h, tcsfm_depthnet *dn) {
+    if (!h) return TCSFM_E_ARG;
+    if (int rc_q = drain_queued(h)) return rc_q;
+    if (!dn) { h->seq_dn = nullptr; return TCSFM_OK; }
+    if (dn->h != h || !dn->loaded) return fail(h, TCSFM_E_ARG, "tcsfm_sequence_depthnet: needs a loaded depth network of this handle (or NULL to detach)");
+    DeviceGuard dev_guard(h->device);
+    if (!dn_sequence_clone(dn)) return fail(h, TCSFM_E_NOMEM, "tcsfm_sequence_depthnet: no memory for the stage's activations");
+    h->seq_dn = dn;
+    return TCSFM_OK;
+}
+
+namespace {
+// The depth stage of a sequence call (sequence_impl): disp_to_depth(net(imgs), 1 / min_disp, 1 / max_disp)[1] of the n raw frames at
+// `imgs` into the planes at `depth`, on `stream`, by the attached network's clone -- groups of max_images images, the same bits per
+// image by the network's contract (its work split depends on H x W only).  The head writes the depth: no disparity plane exists.
+int dn_sequence_depths(tcsfm_depthnet *dn, hipStream_t stream, int n, const float *imgs, float *depth, float min_disp, float max_disp) {
+    tcsfm_depthnet *q = dn->seq_clone;
+    const size_t hw = (size_t)q->h->H * q->h->W;
+    q->stream = stream;
+    for (int i0 = 0; i0 < n; i0 += q->max_images) {
+        const int g = std::min(n - i0, q->max_images);
+        if (int rc = dn_encode(q, g, imgs + (size_t)i0 * 3 * hw, 0, dn_enc_scratch(q, q->skip))) return rc;
+        DnDecDst d = dn_dec_scratch(q, depth + (size_t)i0 * hw);
+        d.as_depth = 1; d.min_disp = min_disp; d.max_disp = max_disp;
+        if (int rc = dn_decode(q, g, q->skip, d)) return rc;
+    }
+    return TCSFM_OK;
+}
+}  // namespace
 
 int tcsfm_debug_depthnet_split(tcsfm_depthnet *dn, int layer, int *ks, int *oh, int *ow, int *nb, int *pb, int *kw) {
     if (!dn) return TCSFM_E_ARG;

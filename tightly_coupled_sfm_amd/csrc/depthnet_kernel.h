@@ -286,7 +286,12 @@ __global__ __launch_bounds__(256) void k_dn_maxpool(const float *in, float *out,
 // ---------------------------------------------------------------------------------------------------------------
 // predict_disps.0: reflect-padded 3x3 convolution 8 -> 1 (+ bias), sigmoid -> disparity [N][1][H][W]; one thread per pixel,
 // the 72 weights are wave-uniform.  Fixed summation order: taps row-major, channels ascending.
-__global__ __launch_bounds__(256) void k_dn_predict(const float *in, const float *w, const float *bias, float *disp, int N, int H, int W) {
+// DEPTH (the sequence calls' depth stage, depthnet_host.h dn_decode): the thread stores disp_to_depth's depth of its disparity instead
+// -- kernels.h disp_depth, the expression of k_disp_to_depth, on the value k_dn_predict<false> would have stored: the bits of
+// tcsfm_depthnet_forward followed by tcsfm_disp_to_depth, with no disparity plane and no second launch.
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void k_dn_predict(const float *in, const float *w, const float *bias, float *out, int N, int H, int W,
+                                                    float min_disp, float max_disp) {
     const long long total = (long long)N * H * W;
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
@@ -310,7 +315,8 @@ __global__ __launch_bounds__(256) void k_dn_predict(const float *in, const float
         }
     }
     s += bias[0];
-    disp[e] = 1.f / (1.f + expf(-s));
+    const float disp = 1.f / (1.f + expf(-s));
+    out[e] = DEPTH ? disp_depth(disp, min_disp, max_disp) : disp;
 }
 
 }  // namespace tc

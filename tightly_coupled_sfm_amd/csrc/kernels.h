@@ -626,6 +626,12 @@ __global__ __launch_bounds__(256) void k_pack_coal(PackParams P, CoalTab T) { pa
 // the frame's H2D copy: planar rgb + depth -> the bordered (rgb, depth) float4 image the warp gathers from + the (converted)
 // depth plane.  k_pack_cached then forms, per window call, only what is pair-specific: tgtpack = (target rgb, auto_err of THIS
 // (target, source) pair) and the pair's slots -- 16 B/pixel/pair written instead of 36.  Same values, bit for bit, as k_pack.
+// disp_to_depth (utils/learning_helpers.py:77-86): scaled = min_disp + (max_disp - min_disp) disp, depth = 1 / scaled.  ONE definition
+// for k_disp_to_depth, k_frame_pack and the depth network's depth-writing head (depthnet_kernel.h k_dn_predict<true>), so that the
+// multiply-add is contracted -- one expression: fused -- the same way in all three and their depths agree bit for bit.
+__device__ __forceinline__ float disp_scaled(float disp, float min_disp, float max_disp) { return min_disp + (max_disp - min_disp) * disp; }
+__device__ __forceinline__ float disp_depth(float disp, float min_disp, float max_disp) { return 1.f / disp_scaled(disp, min_disp, max_disp); }
+
 struct FramePackParams {
     const float *img, *depth;     // [F][3][H][W], [F][1][H][W] planar (ring slots)
     float4 *fpack;                // [F][H+2][W+2]
@@ -640,7 +646,7 @@ __global__ __launch_bounds__(256) void k_frame_pack(FramePackParams P) {
     const int v = idx / P.W, u = idx - v * P.W;
     const float *s = P.img + (size_t)f * 3 * hw;
     float d = P.depth[(size_t)f * hw + idx];
-    if (P.depth_is_disp) d = 1.f / (P.min_disp + (P.max_disp - P.min_disp) * d);       // disp_to_depth, learning_helpers.py:77-86
+    if (P.depth_is_disp) d = disp_depth(d, P.min_disp, P.max_disp);
     const int WB = P.W + 2;
     float4 *sp = P.fpack + (size_t)f * (P.H + 2) * WB;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -764,7 +770,7 @@ __global__ __launch_bounds__(256) void k_ssim(const float *x, const float *y, fl
 __global__ void k_disp_to_depth(const float *disp, float *scaled, float *depth, long long n, float min_disp, float max_disp) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float s = min_disp + (max_disp - min_disp) * disp[i];
+    float s = disp_scaled(disp[i], min_disp, max_disp);
     if (scaled) scaled[i] = s;
     if (depth) depth[i] = 1.f / s;
 }

@@ -170,6 +170,8 @@ struct tcsfm_ctx {
     hipStream_t seq_copy = nullptr;
     std::vector<hipEvent_t> seq_copied, seq_done, seq_raw;      // per chunk: frames usable by the lanes / per call: done / per chunk: raw frames landed
     hipStream_t seq_pack = nullptr;    // k_frame_pack runs here, behind the chunk's copy (event), beside the next chunk's copy
+    tcsfm_depthnet *seq_dn = nullptr;  // tcsfm_sequence_depthnet: the network whose clone computes the ring's depths on seq_pack when a sequence
+                                       // call gets depths == NULL (not owned; tcsfm_depthnet_destroy detaches it)
     struct KOk { const float *p; int n; };
     KOk K_ok[4] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}};   // device intrinsics pointers (and counts) that already passed the pinhole check
     int K_ok_next = 0;
@@ -2879,6 +2881,7 @@ int tcsfm_refine_dense_window_async(tcsfm_handle h, int lane, const tcsfm_opts *
 }
 
 #include "posenet_host.h"
+#include "depthnet_host.h"
 
 // The reference's sequential driver (run_sequential_optimization.py:186-247) as ONE call: see include/tcsfm.h.  With `pn` the initial
 // poses of every window come from the coupled PoseNet loop (train_mono.py:64-80) on the window's lane instead of from the caller.
@@ -2890,7 +2893,12 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     if (!o_in) return fail(h, TCSFM_E_ARG, "opts is NULL");
     const int N = 2 * S, L = h->lanes_serial ? 1 : (int)h->lanes.size() + 1;
     if (S < 1 || T <= S || N > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: need S >= 1, T > S and 2*S <= max_pairs");
-    if (!frames || !depths || !K || (!pose_init && !pn) || !pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: NULL input");
+    // depths == NULL: the attached depth network (tcsfm_sequence_depthnet) computes every frame's depth on the device as its chunk lands
+    const bool gen = !depths && h->seq_dn;
+    if (!frames || (!depths && !gen) || !K || (!pose_init && !pn) || !pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: NULL input");
+    if (gen && o_in->depth_is_disp)
+        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": depths == NULL (the attached depth network produces depths) cannot go with opts.depth_is_disp").c_str());
+    if (gen && !(o_in->min_depth > 0 && o_in->max_depth > o_in->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
     if (windows_per_call < 0) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: windows_per_call < 0");
     if (target_pos < -1 || target_pos > S || S > TC_MAX_SRC_OFF) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: target_pos must be -1 or 0..S, S at most 8");
     {   // The overlap contract (include/tcsfm.h).  Host arrays that are streamed: frames and depths are still going up while results come
@@ -2994,8 +3002,9 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     const size_t n_done = (size_t)2 * R + 2;               // a call's event is re-recorded long after its slots were recycled
     const size_t ND = n_done - 1;
     while (h->seq_copied.size() < (size_t)R) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_copied.push_back(e); }
-    while (use_cache && h->seq_raw.size() < (size_t)R) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_raw.push_back(e); }
-    if (use_cache && !h->seq_pack) HIPCHK(h, hipStreamCreateWithFlags(&h->seq_pack, hipStreamNonBlocking));
+    const bool staged = use_cache || gen;                  // the chunk has a producer stage on seq_pack: the depth network and / or k_frame_pack
+    while (staged && h->seq_raw.size() < (size_t)R) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_raw.push_back(e); }
+    if (staged && !h->seq_pack) HIPCHK(h, hipStreamCreateWithFlags(&h->seq_pack, hipStreamNonBlocking));
     while (h->seq_done.size() < n_done) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_done.push_back(e); }
     // Poses live on the device per CALL in the stacked order of the window form (forward pairs (s, b), then inverse pairs); the
     // caller's arrays are per window.  at(): offset (in pairs) of pair j of window w inside the staging arrays.
@@ -3021,6 +3030,11 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     hipEvent_t small_ev = h->seq_done[n_done - 1];
     HIPCHK(h, hipEventRecord(small_ev, cs));
     HIPCHK(h, hipEventSynchronize(small_ev));              // Kh / stage are host temporaries (pageable): gone from here on
+    const float gen_min_disp = gen ? 1.f / o.max_depth : 0.f, gen_max_disp = gen ? 1.f / o.min_depth : 0.f;      // tcsfm_disp_to_depth's arguments
+    if (gen) {             // the network's weights may still be being written on the handle's stream (tcsfm_depthnet_load_device is asynchronous)
+        HIPCHK(h, hipEventRecord(small_ev, h->stream));    // (small_ev is free again: the host has just waited for it)
+        HIPCHK(h, hipStreamWaitEvent(h->seq_pack, small_ev, 0));
+    }
     std::vector<tcsfm_ctx *> lane(L);
     std::vector<tcsfm_posenet *> net(L, nullptr);
     std::vector<hipStream_t> ls(L);
@@ -3050,18 +3064,34 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
             for (long long r = last; r >= 0 && r > last - L; r--)     // -- the latest of those calls on every lane (a lane's stream is in order)
                 HIPCHK(h, hipStreamWaitEvent(cs, h->seq_done[r % ND], 0));
             HIPCHK(h, hipMemcpyAsync(h->seq_img + (size_t)slot * 3 * hw, frames + (size_t)nxt * 3 * hw, (size_t)nf * 3 * hw * sizeof(float), hipMemcpyHostToDevice, cs));
-            HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)slot * hw, depths + (size_t)nxt * hw, (size_t)nf * hw * sizeof(float), hipMemcpyHostToDevice, cs));
+            if (!gen) HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)slot * hw, depths + (size_t)nxt * hw, (size_t)nf * hw * sizeof(float), hipMemcpyHostToDevice, cs));
             // mirror of the first M slots behind the ring (the frames of a call never wrap).  The frames cross PCIe ONCE: raw mirrors are
             // device-to-device copies, and with the pack cache only the PoseNet reads raw frames -- otherwise the mirror exists as packs only
             const int nm = slot < M ? (nf < M - slot ? nf : M - slot) : 0;
             if (nm > 0 && (!use_cache || pn)) {
                 HIPCHK(h, hipMemcpyAsync(h->seq_img + (size_t)(R + slot) * 3 * hw, h->seq_img + (size_t)slot * 3 * hw, (size_t)nm * 3 * hw * sizeof(float), hipMemcpyDeviceToDevice, cs));
-                HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)(R + slot) * hw, h->seq_depth + (size_t)slot * hw, (size_t)nm * hw * sizeof(float), hipMemcpyDeviceToDevice, cs));
+                if (!gen) HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)(R + slot) * hw, h->seq_depth + (size_t)slot * hw, (size_t)nm * hw * sizeof(float), hipMemcpyDeviceToDevice, cs));
             }
-            if (use_cache) {      // pack the frames that just landed (and their mirrors), once -- on the PACK stream, so that the next chunk's
-                                  // copy does not queue behind the kernel (a sequence with S = 1 is PCIe-bound: the copy stream is its critical path)
+            if (staged) {         // the chunk's producer stage runs on the PACK stream, behind the raw frames (seq_raw), so that the next chunk's
+                                  // copy does not queue behind its kernels (a sequence with S = 1 is PCIe-bound: the copy stream is its critical path)
                 HIPCHK(h, hipEventRecord(h->seq_raw[slot / C], cs));
                 HIPCHK(h, hipStreamWaitEvent(h->seq_pack, h->seq_raw[slot / C], 0));
+            }
+            if (gen) {
+                // Depths of the frames that just landed, once per frame, by the attached network's clone on the pack stream -- neither the
+                // copy stream nor a lane's, so lane 0's windows on h->stream do not hold it up -- then the depth planes' mirror.
+                // Slot recycling needs no new event.  The stage WRITES seq_depth[slot ..] (+ mirror) and READS seq_img[slot ..]; it starts
+                // behind seq_raw, i.e. behind this chunk's copy, and that copy waited (above: slot_reader -> seq_done) for every call that
+                // read the slots' previous frames and depths -- so the stage's writes come after those reads.  The NEXT copy into these
+                // slots waits for the calls that read THIS chunk (slot_reader again: every frame is read by an issued call before its slot
+                // is reused, nxt + C - 1 - R < c0), and each of those calls waited for seq_copied, which this stream records after the
+                // stage: so the next copy also comes after the stage's reads of seq_img and its activations are free for the next chunk
+                // (one stream, in order).
+                if ((rc = dn_sequence_depths(h->seq_dn, h->seq_pack, nf, h->seq_img + (size_t)slot * 3 * hw, h->seq_depth + (size_t)slot * hw, gen_min_disp, gen_max_disp))) break;
+                if (nm > 0 && (!use_cache || pn))
+                    HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)(R + slot) * hw, h->seq_depth + (size_t)slot * hw, (size_t)nm * hw * sizeof(float), hipMemcpyDeviceToDevice, h->seq_pack));
+            }
+            if (use_cache) {      // pack the frames that just landed (and their mirrors), once
                 FramePackParams Fp;
                 Fp.H = h->H; Fp.W = h->W; Fp.depth_is_disp = o.depth_is_disp;
                 Fp.min_disp = o.depth_is_disp ? 1.f / o.max_depth : 0.f; Fp.max_disp = o.depth_is_disp ? 1.f / o.min_depth : 0.f;
@@ -3072,12 +3102,11 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
                 };
                 pack(slot, slot, nf);
                 if (nm > 0) pack(slot, R + slot, nm);
-                HIPCHK(h, hipEventRecord(h->seq_copied[slot / C], h->seq_pack));
-            } else {
-                HIPCHK(h, hipEventRecord(h->seq_copied[slot / C], cs));
             }
+            HIPCHK(h, hipEventRecord(h->seq_copied[slot / C], staged ? h->seq_pack : cs));
             nxt += nf;
         }
+        if (rc) break;
         const int l = (int)(ci % L), s0 = c0 % R;
         for (int k = c0 / C; k <= (c0 + nbw - 1 + S) / C; k++) HIPCHK(h, hipStreamWaitEvent(ls[l], h->seq_copied[(k * C % R) / C], 0));
         tcsfm_ctx *c = lane[l];
@@ -3314,7 +3343,6 @@ int tcsfm_profile_kernel_busy(tcsfm_handle h, double *ms_busy, int64_t *launches
     return TCSFM_OK;
 }
 
-#include "depthnet_host.h"
 #include "posenet_wgrad_host.h"
 #include "posenet_grad_host.h"
 #include "optim_host.h"

@@ -188,6 +188,7 @@ class Engine:
             raise RuntimeError(f"tcsfm_create failed ({rc}): {self.lib.tcsfm_last_error(None).decode()}")
         self._h = h
         self._nets = {}         # the native networks living on this handle: id -> (destroy function, pointer), see _adopt
+        self._seq_depthnet = None   # attach_depthnet: the DepthNetHIP behind depths=None of the sequence calls
         self.lanes = 1
         self.lanes_serial = False
         self.use_torch_stream()
@@ -872,18 +873,39 @@ class Engine:
         self._call(self.lib.tcsfm_refine_dense_window_async(self._h, int(lane), C.byref(opts), B, S, self._p(tgt), self._p(srcs), self._p(depth_t),
                                                             self._p(depth_s), self._p(K), self._p(pose), self._p(pose_out), self._p(depth_out), None))
 
-    def refine_sequence(self, frames: torch.Tensor, depths: torch.Tensor, K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
+    def attach_depthnet(self, net):
+        """tcsfm_sequence_depthnet: `net` (a loaded DepthNetHIP of this engine; None detaches) computes the depths of refine_sequence,
+        refine_dense_sequence and PoseNetHIP.odometry_sequence calls that pass depths=None -- on the device, frame by frame as the
+        frames land, the bits of Engine.disp_to_depth(net.forward(frames), opts.min_depth, opts.max_depth)[1].  The engine keeps a
+        reference to `net` while it is attached."""
+        if net is not None and (getattr(net, "eng", None) is not self or not getattr(net, "_dn", None)):
+            raise ValueError("attach_depthnet: needs a DepthNetHIP of this engine (or None)")
+        self._call(self.lib.tcsfm_sequence_depthnet(self._h, None if net is None else net._dn))
+        self._seq_depthnet = net
+
+    def _seq_depths(self, depths, T):
+        """the `depths` argument of a sequence call: a checked CPU tensor, or None where an attached depth network stands in"""
+        if depths is None:
+            net = getattr(self, "_seq_depthnet", None)
+            if net is None or not getattr(net, "_dn", None):
+                raise ValueError("depths=None needs a depth network: call Engine.attach_depthnet(DepthNetHIP) first")
+            return None
+        return self._cpu(depths, (T, 1, self.H, self.W), "depths")
+
+    def refine_sequence(self, frames: torch.Tensor, depths: Optional[torch.Tensor], K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
                         ring: int = 0, log_scale: bool = False, windows_per_call: int = 0, target_pos: int = 0):
         """tcsfm_refine_sequence: the whole window loop of a sequence inside the library (frames [T,3,H,W] / depths [T,1,H,W] CPU
         tensors -- pinned for asynchronous copies --, K [3,3], init_poses [T-S, 2S, 6]) -> refined poses [T-S, 2S, 6] (CPU tensor;
         with log_scale=True also the log depth scales [T-S, 2S]); calls of `windows_per_call` windows (0 = default 8, capped by max_pairs / 2S) run on
         the engine's lanes.  Window w = frames w .. w+S; its target is frame w + target_pos (0: the first; -1: the middle one, (S+1)//2, as
-        the reference's loaders choose it), its sources the others in order"""
+        the reference's loaders choose it), its sources the others in order.  depths=None: the depth network of attach_depthnet
+        computes them inside the call"""
+        T, S = int(frames.shape[0]), int(sources)
+        depths = self._seq_depths(depths, T)
         self._bind()
         o = opts or default_opts()
         cpu = lambda a, shape, name: self._cpu(a, shape, name)
-        T, S = int(frames.shape[0]), int(sources)
-        frames = cpu(frames, (T, 3, self.H, self.W), "frames"); depths = cpu(depths, (T, 1, self.H, self.W), "depths")
+        frames = cpu(frames, (T, 3, self.H, self.W), "frames")
         Kc = cpu(torch.as_tensor(np.asarray(K, dtype=np.float32)), (3, 3), "K")
         p0 = cpu(torch.as_tensor(np.asarray(init_poses, dtype=np.float32)), (T - S, 2 * S, 6), "init_poses")
         out = torch.empty_like(p0)
@@ -893,16 +915,17 @@ class Engine:
                                                   int(windows_per_call), int(target_pos)))
         return (out, ls) if log_scale else out
 
-    def refine_dense_sequence(self, frames: torch.Tensor, depths: torch.Tensor, K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
+    def refine_dense_sequence(self, frames: torch.Tensor, depths: Optional[torch.Tensor], K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
                               ring: int = 0, windows_per_call: int = 0, target_pos: int = 0, out_depths: Optional[torch.Tensor] = None):
         """tcsfm_refine_dense_sequence: the dense mode (pose + per-pixel inverse depth) over a sequence, arguments as refine_sequence
         -> (poses [T-S, 2S, 6], refined depth maps [T-S, 2S, 1, H, W]) as CPU tensors.
         out_depths: a caller-owned (pinned) CPU tensor of that shape to receive the depth maps; a caller that runs sequence after
         sequence should pass one -- pinning a fresh 70 MB result buffer costs ten times the refinement of a 120-frame sequence."""
+        T, S = int(frames.shape[0]), int(sources)
+        depths = self._seq_depths(depths, T)
         self._bind()
         o = opts or default_opts()
-        T, S = int(frames.shape[0]), int(sources)
-        frames = self._cpu(frames, (T, 3, self.H, self.W), "frames"); depths = self._cpu(depths, (T, 1, self.H, self.W), "depths")
+        frames = self._cpu(frames, (T, 3, self.H, self.W), "frames")
         Kc = self._cpu(torch.as_tensor(np.asarray(K, dtype=np.float32)), (3, 3), "K")
         p0 = self._cpu(torch.as_tensor(np.asarray(init_poses, dtype=np.float32)), (T - S, 2 * S, 6), "init_poses")
         out = torch.empty_like(p0)
@@ -912,7 +935,7 @@ class Engine:
             dout = out_depths
             if dout.is_cuda or dout.dtype != torch.float32 or not dout.is_contiguous() or tuple(dout.shape) != (T - S, 2 * S, 1, self.H, self.W):
                 raise TypeError("out_depths must be a contiguous float32 CPU tensor [T-S, 2S, 1, H, W]")
-        hp = lambda t: C.c_void_p(t.data_ptr())
+        hp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         self._call(self.lib.tcsfm_refine_dense_sequence(self._h, C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(p0), hp(out), hp(dout), int(ring),
                                                         int(windows_per_call), int(target_pos)))
         return out, dout

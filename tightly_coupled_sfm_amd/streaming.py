@@ -60,9 +60,10 @@ class SequenceRefiner:
 
     def run_native(self, frames, depths, K, init_poses, ring: int = 0) -> torch.Tensor:
         """The same loop inside the library (tcsfm_refine_sequence: four-frame copies, events and lanes driven from C++) -> refined
-        poses [T-S, 2*S, 6] as a CPU tensor; bit-identical to run()"""
+        poses [T-S, 2*S, 6] as a CPU tensor; bit-identical to run().  depths=None: the depth network attached to the engine
+        (self.eng.attach_depthnet) computes them inside the call"""
         pin = lambda a: a if (isinstance(a, torch.Tensor) and not a.is_cuda) else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32)
-        return self.eng.refine_sequence(pin(frames), pin(depths), K, init_poses, self.opts, sources=self.S, ring=ring)
+        return self.eng.refine_sequence(pin(frames), None if depths is None else pin(depths), K, init_poses, self.opts, sources=self.S, ring=ring)
 
     def run(self, frames, depths, K, init_poses) -> torch.Tensor:
         """-> refined poses [T-S, 2*S, 6] (GPU tensor, complete on return)"""
