@@ -4,6 +4,7 @@ refinement with the drop-in DepthOptimizer, trajectory composition (validate.com
 
     python examples/run_sequence.py [--frames 40] [--sources 2]          (needs an MI355X)
     python examples/run_sequence.py --frames-only CHECKPOINT              frames in, poses out: see frames_only() below
+    python examples/run_sequence.py --frames-only CHECKPOINT --u8-frames  ... from the camera's bytes: interleaved 8-bit RGB [T,H,W,3]
 
 The two "networks" are stand-ins with the reference models' call conventions: the depth net returns the scene's true
 disparity for whatever frame it is shown, the pose net returns a noisy version of the true relative pose (PoseNet-quality
@@ -64,6 +65,10 @@ def frames_only(args):
     first = synth.make_pair(H, W, seed=500, pose_gt=pose)
     frames = torch.as_tensor(np.stack([first["tgt"]] + [synth.make_pair(H, W, seed=500 + i, pose_gt=pose)["src"] for i in range(args.frames - 1)])
                              .astype(np.float32)).pin_memory()
+    if args.u8_frames:      # what a camera or a decoder delivers: interleaved 8-bit RGB.  The bytes go up as they are (a quarter of the
+        # float frames' PCIe traffic and pinned memory) and the library makes u8 / 255 on the device -- ArrayToTensor's values, bit for bit
+        frames = torch.from_numpy(np.ascontiguousarray(np.round(frames.numpy() * 255).astype(np.uint8).transpose(0, 2, 3, 1))).pin_memory()
+        print(f"frames: uint8 {list(frames.shape)} (HWC), {frames.numel() / 1e6:.1f} MB pinned")
     opts = default_opts(n_iters=args.gn_iters, min_depth=0.06, max_depth=2.67)
     t0 = time.perf_counter()
     init, refined = pose_net.odometry_sequence(frames, None, first["K"], opts, sources=S, iterations=4, target_pos=-1)
@@ -79,6 +84,9 @@ def main():
     ap.add_argument("--frames-only", metavar="CHECKPOINT", default=None,
                     help="load the depth network and the PoseNet from this reference checkpoint and run the sequence from the frames alone "
                          "(Engine.attach_depthnet + PoseNetHIP.odometry_sequence with depths=None)")
+    ap.add_argument("--u8-frames", action="store_true",
+                    help="with --frames-only: quantise the synthetic frames to interleaved 8-bit RGB [T,H,W,3] and feed the bytes "
+                         "(the library converts them on the device: tcsfm_sequence_frame_format)")
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--sources", type=int, default=1, choices=(1, 2))
     ap.add_argument("--gn-iters", type=int, default=8)
@@ -88,6 +96,8 @@ def main():
     args = ap.parse_args()
     if args.frames_only:
         return frames_only(args)
+    if args.u8_frames:
+        ap.error("--u8-frames goes with --frames-only (the per-window loop below holds its frames on the device: Engine.frames_from_u8 is for that)")
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).cuda()
     rng = np.random.default_rng(0)
     options = {"diff_img_argmin": True, "automasking": True, "mode": "scaled", "l_depth_consist": True, "l_depth_consist_weight": 0.15,

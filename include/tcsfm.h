@@ -174,7 +174,10 @@ enum { TCSFM_STAT_COST = 0, TCSFM_STAT_COST_PHOTO = 1, TCSFM_STAT_NMASK = 2, TCS
  *   tcsfm_refine_dense_sequence: pose_out = pose_init
  * (end of the honoured pairs; tcsfm_odometry_sequence takes no initial poses.)  The parameter tables of the networks and of the
  * optimiser (skips_out[5], d_skips[5], grads[], conv_w_g[7] ..., params[]) contribute one range per non-NULL element; the optimiser's
- * parameters are outputs of every step (two tensors of one optimiser must not share memory, a gradient must not lie on a parameter). */
+ * parameters are outputs of every step (two tensors of one optimiser must not share memory, a gradient must not lie on a parameter).
+ * tcsfm_frames_from_u8 declares its two arrays `const void *src` / `void *dst` (bytes in, floats out) and enforces its one rule itself:
+ * dst overlapping src in any way is refused with "tcsfm_frames_from_u8: dst overlaps src"; nothing about it is honoured.  While a U8
+ * format is set (tcsfm_sequence_frame_format) the `frames` range of a sequence call is T*3*H*W bytes, not floats. */
 
 /* ---- lifetime ------------------------------------------------------------------------------- */
 
@@ -806,6 +809,25 @@ int tcsfm_refine_dense_sequence(tcsfm_handle h, const tcsfm_opts *o, int T, int 
  *   depths), and needs 0 < o->min_depth < o->max_depth.
  *   tcsfm_depthnet_destroy of the attached network detaches it. */
 int tcsfm_sequence_depthnet(tcsfm_handle h, tcsfm_depthnet *dn);
+/* 8-bit camera frames.  Cameras, decoders and image files deliver interleaved 8-bit RGB; the reference turns it into floats on the host
+ * (utils/custom_transforms.py:62-76 ArrayToTensor: transpose to C x H x W, .float() / 255).  tcsfm_sequence_frame_format sets how the
+ * three sequence calls above read their `frames` argument -- a sticky setting of the handle, like tcsfm_sequence_depthnet; a new handle
+ * is TCSFM_FRAMES_F32_CHW.  While a U8 format is set, `frames` is read as `const uint8_t *` in that layout (the prototypes stay as they
+ * are: cast the pointer); the overlap check takes it as T*3*H*W BYTES.  The bytes cross PCIe as they are (a quarter of the float
+ * frames' bytes: 7 instead of 16 B/pixel with depths given, 3 instead of 12 B/pixel with a depth network attached) into a device byte
+ * ring, and a kernel on the call's pack stream writes the float ring before anything else reads it -- the pack cache, the PoseNet loop,
+ * the depth-network stage and the dense mode are unchanged.  Each byte b becomes float32(b / 255), correctly rounded (a true fp32
+ * division, the value torch.from_numpy(im).float() / 255 computes): a U8 call returns the bits of the float call on u8 / 255.
+ *   An unknown format: TCSFM_E_ARG, tcsfm_last_error says so, the setting is unchanged.  A NULL handle: TCSFM_E_ARG.
+ * tcsfm_frames_from_u8 is the same kernel as an operator, for callers of the window entries, who hold device pointers: N >= 1 frames of
+ * `format` (TCSFM_FRAMES_U8_CHW or TCSFM_FRAMES_U8_HWC; TCSFM_FRAMES_F32_CHW is refused) at DEVICE pointer src (N*3*H*W bytes, any
+ * address) -> planar float32 [N,3,H,W] at DEVICE pointer dst (aligned for float), on the handle's stream (asynchronous).  o->host_ptrs must be 0: a host
+ * caller has the sequence calls.  dst overlapping src is refused ("overlapping arguments"). */
+#define TCSFM_FRAMES_F32_CHW 0   /* default: [T,3,H,W] float32 in [0,1]                                  */
+#define TCSFM_FRAMES_U8_CHW  1   /* [T,3,H,W] uint8                                                       */
+#define TCSFM_FRAMES_U8_HWC  2   /* [T,H,W,3] uint8, interleaved RGB as cameras deliver it                */
+int tcsfm_sequence_frame_format(tcsfm_handle h, int format);
+int tcsfm_frames_from_u8(tcsfm_handle h, const tcsfm_opts *o, int format, int N, const void *src, void *dst);
 int tcsfm_lane_wait(tcsfm_handle h, int lane);
 int tcsfm_lane_synchronize(tcsfm_handle h, int lane);
 int tcsfm_lane_event(tcsfm_handle h, int lane, void **event_out);

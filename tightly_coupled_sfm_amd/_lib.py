@@ -98,6 +98,7 @@ REFINE_POSE, REFINE_POSE_SCALE = 0, 1
 WINDOW_PAIR, WINDOW_REFERENCE = 0, 1
 DEPTH_FULL, DEPTH_QUARTER = 0, 1
 OPTIM_ADAM, OPTIM_SGD = 0, 1
+FRAMES_F32_CHW, FRAMES_U8_CHW, FRAMES_U8_HWC = 0, 1, 2     # tcsfm_sequence_frame_format / tcsfm_frames_from_u8
 STAT_POSE = 4
 NSTAT = 10        # cost, cost_photo, n_mask, lambda, pose[6]  (include/tcsfm.h TCSFM_STAT_*)
 
@@ -187,6 +188,8 @@ _SIGNATURES = {
     "tcsfm_odometry_sequence": (C.c_int, [_P, _P, C.c_int, C.POINTER(Opts), C.c_int, C.c_int] + [_P] * 6 + [C.c_int, C.c_int, C.c_int]),
     "tcsfm_refine_dense_sequence": (C.c_int, [_P, C.POINTER(Opts), C.c_int, C.c_int] + [_P] * 6 + [C.c_int, C.c_int, C.c_int]),
     "tcsfm_sequence_depthnet": (C.c_int, [_P, _P]),
+    "tcsfm_sequence_frame_format": (C.c_int, [_P, C.c_int]),
+    "tcsfm_frames_from_u8": (C.c_int, [_P, C.POINTER(Opts), C.c_int, C.c_int, _P, _P]),
     "tcsfm_lane_wait": (C.c_int, [_P, C.c_int]),
     "tcsfm_lane_synchronize": (C.c_int, [_P, C.c_int]),
     "tcsfm_lane_event": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),

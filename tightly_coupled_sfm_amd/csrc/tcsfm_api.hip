@@ -27,6 +27,7 @@
 #include "loss_grad_kernel.h"
 #include "window_loss_kernel.h"
 #include "optim_kernel.h"
+#include "frames_u8_kernel.h"
 
 using namespace tc;
 
@@ -172,6 +173,9 @@ struct tcsfm_ctx {
     hipStream_t seq_pack = nullptr;    // k_frame_pack runs here, behind the chunk's copy (event), beside the next chunk's copy
     tcsfm_depthnet *seq_dn = nullptr;  // tcsfm_sequence_depthnet: the network whose clone computes the ring's depths on seq_pack when a sequence
                                        // call gets depths == NULL (not owned; tcsfm_depthnet_destroy detaches it)
+    int seq_fmt = TCSFM_FRAMES_F32_CHW;  // tcsfm_sequence_frame_format: how the sequence calls read their `frames` argument
+    uint8_t *seq_u8 = nullptr;         // U8 formats: device ring of the frames' BYTES ([seq_u8_slots][3 H W], no mirror slots); k_frames_u8 turns a
+    int seq_u8_slots = 0;              // chunk into the floats of seq_img on seq_pack
     struct KOk { const float *p; int n; };
     KOk K_ok[4] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}};   // device intrinsics pointers (and counts) that already passed the pinhole check
     int K_ok_next = 0;
@@ -1422,7 +1426,7 @@ void tcsfm_destroy(tcsfm_handle h) {
     void *ptrs[] = {h->stamp_buf, h->tgtpack, h->srcpack, h->depth_work, h->partials, h->blockrec, h->tickets, h->state, h->pconst, h->lin_out,
                     h->jrec, h->jrec_acc, h->jblockrec, h->jdepth_acc, h->jstate, h->jdelta, h->jpart, h->jtick, h->dref_norms, h->dref_ext, h->dref_export, h->qres_rho, h->qres_rec, h->pose_lin, h->dref_smooth, h->jrec_src, h->jstate_src, h->jdelta_src, h->dref_ext_src, h->qres_rho_src, h->qres_rec_src,
                     h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept, h->dbg_stamps, h->wgrad_rec, h->wgrad_fix, h->wgrad_gmax, h->pgrad_fwd, h->pgrad_cot,
-                    h->seq_fpack, h->seq_fdepth, h->pair_idx, h->seq_img, h->seq_depth, h->seq_pose_in, h->seq_pose_out, h->seq_ls_out, h->seq_K, h->seq_dense, h->seq_dense_tmp};
+                    h->seq_fpack, h->seq_fdepth, h->pair_idx, h->seq_img, h->seq_depth, h->seq_pose_in, h->seq_pose_out, h->seq_ls_out, h->seq_K, h->seq_dense, h->seq_dense_tmp, h->seq_u8};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &s : h->stage)
@@ -2895,6 +2899,9 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     if (S < 1 || T <= S || N > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: need S >= 1, T > S and 2*S <= max_pairs");
     // depths == NULL: the attached depth network (tcsfm_sequence_depthnet) computes every frame's depth on the device as its chunk lands
     const bool gen = !depths && h->seq_dn;
+    // tcsfm_sequence_frame_format: `frames` points at bytes; they go up as they are and k_frames_u8 makes the ring's floats on the device
+    const bool u8 = h->seq_fmt != TCSFM_FRAMES_F32_CHW;
+    const uint8_t *frames_u8 = (const uint8_t *)frames;
     if (!frames || (!depths && !gen) || !K || (!pose_init && !pn) || !pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: NULL input");
     if (gen && o_in->depth_is_disp)
         return fail(h, TCSFM_E_ARG, (std::string(entry) + ": depths == NULL (the attached depth network produces depths) cannot go with opts.depth_is_disp").c_str());
@@ -2906,7 +2913,8 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
         // issued (small_ev below), and pose_out is written after the last one has finished.
         const size_t hw_b = (size_t)h->H * h->W * sizeof(float), np6 = (size_t)(T - S) * N * 6 * sizeof(float);
         ArgRanges a;
-        a.in("frames", frames, (size_t)T * 3 * hw_b); a.in("depths", depths, (size_t)T * hw_b); a.in("K", K, 9 * sizeof(float));
+        a.in("frames", frames, u8 ? (size_t)T * 3 * h->H * h->W : (size_t)T * 3 * hw_b);      // (a U8 format: T*3*H*W bytes, not floats)
+        a.in("depths", depths, (size_t)T * hw_b); a.in("K", K, 9 * sizeof(float));
         a.in("pose_init", pose_init, np6);
         a.out("pose_init_out", pose_init_out, np6); a.out("pose_out", pose_out, np6);
         if (o_in->refine == TCSFM_REFINE_POSE_SCALE && !dense_depth_out) a.out("log_scale_out", log_scale_out, (size_t)(T - S) * N * sizeof(float));
@@ -2961,6 +2969,12 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
         if (h->seq_fdepth) { HIPCHK(h, hipFree(h->seq_fdepth)); h->seq_fdepth = nullptr; }
         h->seq_slots = R + M;
     }
+    if (u8 && h->seq_u8_slots < R) {                        // the byte ring: R slots, no mirror (the kernel writes the float mirror slots itself)
+        if (h->seq_u8) HIPCHK(h, hipFree(h->seq_u8));
+        h->seq_u8 = nullptr; h->seq_u8_slots = 0;
+        HIPCHK(h, hipMalloc((void **)&h->seq_u8, (size_t)R * 3 * hw));
+        h->seq_u8_slots = R;
+    }
     const bool use_cache = dense_depth_out == nullptr;      // (the dense modes rewrite per-pair depth planes: they keep the per-pair pack)
     if (use_cache && !h->seq_fpack) {
         HIPCHK(h, hipMalloc((void **)&h->seq_fpack, (size_t)h->seq_slots * (h->H + 2) * (h->W + 2) * sizeof(float4)));
@@ -3002,7 +3016,7 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     const size_t n_done = (size_t)2 * R + 2;               // a call's event is re-recorded long after its slots were recycled
     const size_t ND = n_done - 1;
     while (h->seq_copied.size() < (size_t)R) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_copied.push_back(e); }
-    const bool staged = use_cache || gen;                  // the chunk has a producer stage on seq_pack: the depth network and / or k_frame_pack
+    const bool staged = use_cache || gen || u8;            // the chunk has a producer stage on seq_pack: k_frames_u8, the depth network and / or k_frame_pack
     while (staged && h->seq_raw.size() < (size_t)R) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_raw.push_back(e); }
     if (staged && !h->seq_pack) HIPCHK(h, hipStreamCreateWithFlags(&h->seq_pack, hipStreamNonBlocking));
     while (h->seq_done.size() < n_done) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_done.push_back(e); }
@@ -3063,19 +3077,32 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
             for (int k = 0; k < nf; k++) { if (slot_reader[slot + k] > last) last = slot_reader[slot + k]; slot_reader[slot + k] = -1; }
             for (long long r = last; r >= 0 && r > last - L; r--)     // -- the latest of those calls on every lane (a lane's stream is in order)
                 HIPCHK(h, hipStreamWaitEvent(cs, h->seq_done[r % ND], 0));
-            HIPCHK(h, hipMemcpyAsync(h->seq_img + (size_t)slot * 3 * hw, frames + (size_t)nxt * 3 * hw, (size_t)nf * 3 * hw * sizeof(float), hipMemcpyHostToDevice, cs));
+            if (u8) HIPCHK(h, hipMemcpyAsync(h->seq_u8 + (size_t)slot * 3 * hw, frames_u8 + (size_t)nxt * 3 * hw, (size_t)nf * 3 * hw, hipMemcpyHostToDevice, cs));
+            else HIPCHK(h, hipMemcpyAsync(h->seq_img + (size_t)slot * 3 * hw, frames + (size_t)nxt * 3 * hw, (size_t)nf * 3 * hw * sizeof(float), hipMemcpyHostToDevice, cs));
             if (!gen) HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)slot * hw, depths + (size_t)nxt * hw, (size_t)nf * hw * sizeof(float), hipMemcpyHostToDevice, cs));
             // mirror of the first M slots behind the ring (the frames of a call never wrap).  The frames cross PCIe ONCE: raw mirrors are
             // device-to-device copies, and with the pack cache only the PoseNet reads raw frames -- otherwise the mirror exists as packs only
             const int nm = slot < M ? (nf < M - slot ? nf : M - slot) : 0;
             if (nm > 0 && (!use_cache || pn)) {
-                HIPCHK(h, hipMemcpyAsync(h->seq_img + (size_t)(R + slot) * 3 * hw, h->seq_img + (size_t)slot * 3 * hw, (size_t)nm * 3 * hw * sizeof(float), hipMemcpyDeviceToDevice, cs));
+                // (a U8 format: the floats do not exist yet -- k_frames_u8 below writes the raw mirror slots with the ring's)
+                if (!u8) HIPCHK(h, hipMemcpyAsync(h->seq_img + (size_t)(R + slot) * 3 * hw, h->seq_img + (size_t)slot * 3 * hw, (size_t)nm * 3 * hw * sizeof(float), hipMemcpyDeviceToDevice, cs));
                 if (!gen) HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)(R + slot) * hw, h->seq_depth + (size_t)slot * hw, (size_t)nm * hw * sizeof(float), hipMemcpyDeviceToDevice, cs));
             }
             if (staged) {         // the chunk's producer stage runs on the PACK stream, behind the raw frames (seq_raw), so that the next chunk's
                                   // copy does not queue behind its kernels (a sequence with S = 1 is PCIe-bound: the copy stream is its critical path)
                 HIPCHK(h, hipEventRecord(h->seq_raw[slot / C], cs));
                 HIPCHK(h, hipStreamWaitEvent(h->seq_pack, h->seq_raw[slot / C], 0));
+            }
+            if (u8) {
+                // The chunk's bytes -> the ring's floats (and the raw mirror slots, where somebody reads them), ONE launch, first on the pack
+                // stream: the depth network and k_frame_pack below read its output in stream order.  Recycling, as for the depth stage below:
+                // the kernel's WRITES to seq_img[slot ..] (+ mirror) come after the reads of the slots' previous frames -- this chunk's copy
+                // waited for those calls' seq_done events (slot_reader above), and the kernel waits for that copy (seq_raw).  The NEXT copy
+                // into the same seq_u8 slots waits for the calls that read THIS chunk, those calls waited for seq_copied, and seq_copied is
+                // recorded on this stream after the kernel: so a byte slot is never overwritten while the kernel may still read it.
+                float *mirror = nm > 0 && (!use_cache || pn) ? h->seq_img + (size_t)(R + slot) * 3 * hw : nullptr;
+                HIPCHK(h, launch_frames_u8(h->seq_pack, h->seq_fmt == TCSFM_FRAMES_U8_HWC, nf, h->seq_u8 + (size_t)slot * 3 * hw, h->seq_img + (size_t)slot * 3 * hw,
+                                           mirror, mirror ? nm : 0, hw));
             }
             if (gen) {
                 // Depths of the frames that just landed, once per frame, by the attached network's clone on the pack stream -- neither the
@@ -3181,6 +3208,35 @@ int tcsfm_refine_dense_sequence(tcsfm_handle h, const tcsfm_opts *o, int T, int 
                                 const float *pose_init, float *pose_out, float *depth_out, int ring, int windows_per_call, int target_pos) {
     if (h && (!pose_init || !depth_out)) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_sequence: NULL input");
     return sequence_impl(h, o, T, S, frames, depths, K, pose_init, nullptr, 0, nullptr, pose_out, nullptr, ring, windows_per_call, target_pos, "tcsfm_refine_dense_sequence", depth_out);
+}
+
+int tcsfm_sequence_frame_format(tcsfm_handle h, int format) {
+    if (!h) return TCSFM_E_ARG;
+    if (format != TCSFM_FRAMES_F32_CHW && format != TCSFM_FRAMES_U8_CHW && format != TCSFM_FRAMES_U8_HWC)
+        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_frame_format: format must be TCSFM_FRAMES_F32_CHW, TCSFM_FRAMES_U8_CHW or TCSFM_FRAMES_U8_HWC");
+    h->seq_fmt = format;
+    return TCSFM_OK;
+}
+
+int tcsfm_frames_from_u8(tcsfm_handle h, const tcsfm_opts *o, int format, int N, const void *src, void *dst) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    if (!h) return TCSFM_E_ARG;
+    if (!o || !src || !dst) return fail(h, TCSFM_E_ARG, "tcsfm_frames_from_u8: NULL argument");
+    if (format != TCSFM_FRAMES_U8_CHW && format != TCSFM_FRAMES_U8_HWC)
+        return fail(h, TCSFM_E_ARG, "tcsfm_frames_from_u8: format must be TCSFM_FRAMES_U8_CHW or TCSFM_FRAMES_U8_HWC (float frames need no conversion)");
+    if (N < 1) return fail(h, TCSFM_E_ARG, "tcsfm_frames_from_u8: N must be at least 1");
+    if (o->host_ptrs != 0)
+        return fail(h, TCSFM_E_ARG, "tcsfm_frames_from_u8: host_ptrs must be 0 (device pointers); host frames go through the sequence calls (tcsfm_sequence_frame_format)");
+    if (((uintptr_t)dst & 3) != 0) return fail(h, TCSFM_E_ARG, "tcsfm_frames_from_u8: dst must be aligned for float");
+    const size_t hw = (size_t)h->H * h->W;
+    ArgRanges a;
+    a.in("src", src, (size_t)N * 3 * hw); a.out("dst", dst, (size_t)N * 3 * hw * sizeof(float));
+    std::string msg;
+    if (a.refused("tcsfm_frames_from_u8", msg)) return fail(h, TCSFM_E_ARG, msg.c_str());
+    DeviceGuard dev_guard(h->device);
+    if (int rc_ = pending_error(h)) return rc_;
+    HIPCHK(h, launch_frames_u8(h->stream, format == TCSFM_FRAMES_U8_HWC, N, (const uint8_t *)src, (float *)dst, nullptr, 0, hw));
+    return TCSFM_OK;
 }
 
 int tcsfm_lane_wait(tcsfm_handle h, int lane) {

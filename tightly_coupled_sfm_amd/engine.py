@@ -8,6 +8,7 @@ reference's 6-vectors ``[tx,ty,tz,rx,ry,rz]`` (models/stn.py:143-158).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional
 
@@ -29,6 +30,24 @@ def _chk(t: torch.Tensor, shape, name: str) -> torch.Tensor:
         # same wording as the reference's check_sizes (models/stn.py:24-30)
         raise AssertionError("wrong size for {}, expected {}, got  {}".format(name, "x".join(map(str, shape)), list(t.shape)))
     return t.contiguous()
+
+
+def frame_format(frames: torch.Tensor, H: int, W: int) -> int:
+    """How a sequence call reads the CPU tensor `frames` (tcsfm_sequence_frame_format): _lib.FRAMES_F32_CHW for float32 (its shape is
+    checked where it always was), FRAMES_U8_CHW for uint8 [T,3,H,W], FRAMES_U8_HWC for uint8 [T,H,W,3] -- H, W >= 4, so the two cannot
+    be confused.  Anything else is a TypeError.  Pure: touches neither the library nor the GPU."""
+    if not isinstance(frames, torch.Tensor) or frames.device.type != "cpu":
+        raise TypeError("frames must be a CPU tensor (pinned for asynchronous copies): float32 [T,3,H,W], or uint8 [T,3,H,W] / [T,H,W,3]")
+    if frames.dtype == torch.float32:
+        return _lib.FRAMES_F32_CHW
+    if frames.dtype != torch.uint8:
+        raise TypeError(f"frames must be float32 or uint8 (got {frames.dtype})")
+    shape = tuple(frames.shape)
+    if len(shape) == 4 and shape[1:] == (3, H, W):
+        return _lib.FRAMES_U8_CHW
+    if len(shape) == 4 and shape[1:] == (H, W, 3):
+        return _lib.FRAMES_U8_HWC
+    raise TypeError(f"uint8 frames must be [T,3,{H},{W}] or [T,{H},{W},3] (got {list(shape)})")
 
 
 def _copy_opts(o: Opts) -> Opts:
@@ -892,9 +911,49 @@ class Engine:
             return None
         return self._cpu(depths, (T, 1, self.H, self.W), "depths")
 
+    def _seq_frames(self, frames, T):
+        """the `frames` argument of a sequence call, checked before anything touches the GPU -> (contiguous CPU tensor, frame format)"""
+        frames = torch.as_tensor(frames)
+        fmt = frame_format(frames, self.H, self.W)
+        if fmt == _lib.FRAMES_F32_CHW:
+            return self._cpu(frames, (T, 3, self.H, self.W), "frames"), fmt
+        return frames.contiguous(), fmt
+
+    @contextlib.contextmanager
+    def _frame_format(self, fmt):
+        """the handle reads `frames` as `fmt` for the one call inside the block, and as float32 again afterwards, whatever happens"""
+        if fmt == _lib.FRAMES_F32_CHW:
+            yield
+            return
+        self._call(self.lib.tcsfm_sequence_frame_format(self._h, int(fmt)))
+        try:
+            yield
+        finally:
+            self.lib.tcsfm_sequence_frame_format(self._h, _lib.FRAMES_F32_CHW)
+
+    def frames_from_u8(self, u8: torch.Tensor) -> torch.Tensor:
+        """tcsfm_frames_from_u8: uint8 CUDA frames [N,3,H,W] or [N,H,W,3] (interleaved RGB) -> float32 [N,3,H,W], the correctly rounded
+        u8 / 255 of the reference's ArrayToTensor, for callers of the window entries; on the engine's stream"""
+        if not isinstance(u8, torch.Tensor) or not u8.is_cuda or u8.dtype != torch.uint8:
+            raise TypeError("frames_from_u8 takes a uint8 CUDA tensor")
+        shape = tuple(u8.shape)
+        if len(shape) == 4 and shape[1:] == (3, self.H, self.W):
+            fmt = _lib.FRAMES_U8_CHW
+        elif len(shape) == 4 and shape[1:] == (self.H, self.W, 3):
+            fmt = _lib.FRAMES_U8_HWC
+        else:
+            raise TypeError(f"uint8 frames must be [N,3,{self.H},{self.W}] or [N,{self.H},{self.W},3] (got {list(shape)})")
+        self._bind()
+        u8 = u8.contiguous()
+        out = torch.empty((shape[0], 3, self.H, self.W), dtype=torch.float32, device=u8.device)
+        o = default_opts()
+        self._call(self.lib.tcsfm_frames_from_u8(self._h, C.byref(o), fmt, int(shape[0]), self._p(u8), self._p(out)))
+        return out
+
     def refine_sequence(self, frames: torch.Tensor, depths: Optional[torch.Tensor], K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
                         ring: int = 0, log_scale: bool = False, windows_per_call: int = 0, target_pos: int = 0):
-        """tcsfm_refine_sequence: the whole window loop of a sequence inside the library (frames [T,3,H,W] / depths [T,1,H,W] CPU
+        """tcsfm_refine_sequence: the whole window loop of a sequence inside the library (frames [T,3,H,W] float32 -- or the camera's
+        bytes, uint8 [T,3,H,W] / [T,H,W,3], converted to u8 / 255 on the device -- / depths [T,1,H,W] CPU
         tensors -- pinned for asynchronous copies --, K [3,3], init_poses [T-S, 2S, 6]) -> refined poses [T-S, 2S, 6] (CPU tensor;
         with log_scale=True also the log depth scales [T-S, 2S]); calls of `windows_per_call` windows (0 = default 8, capped by max_pairs / 2S) run on
         the engine's lanes.  Window w = frames w .. w+S; its target is frame w + target_pos (0: the first; -1: the middle one, (S+1)//2, as
@@ -902,17 +961,18 @@ class Engine:
         computes them inside the call"""
         T, S = int(frames.shape[0]), int(sources)
         depths = self._seq_depths(depths, T)
+        frames, fmt = self._seq_frames(frames, T)
         self._bind()
         o = opts or default_opts()
         cpu = lambda a, shape, name: self._cpu(a, shape, name)
-        frames = cpu(frames, (T, 3, self.H, self.W), "frames")
         Kc = cpu(torch.as_tensor(np.asarray(K, dtype=np.float32)), (3, 3), "K")
         p0 = cpu(torch.as_tensor(np.asarray(init_poses, dtype=np.float32)), (T - S, 2 * S, 6), "init_poses")
         out = torch.empty_like(p0)
         ls = torch.zeros((T - S, 2 * S), dtype=torch.float32) if log_scale else None
         hp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._call(self.lib.tcsfm_refine_sequence(self._h, C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(p0), hp(out), hp(ls), int(ring),
-                                                  int(windows_per_call), int(target_pos)))
+        with self._frame_format(fmt):
+            self._call(self.lib.tcsfm_refine_sequence(self._h, C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(p0), hp(out), hp(ls), int(ring),
+                                                      int(windows_per_call), int(target_pos)))
         return (out, ls) if log_scale else out
 
     def refine_dense_sequence(self, frames: torch.Tensor, depths: Optional[torch.Tensor], K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
@@ -923,9 +983,9 @@ class Engine:
         sequence should pass one -- pinning a fresh 70 MB result buffer costs ten times the refinement of a 120-frame sequence."""
         T, S = int(frames.shape[0]), int(sources)
         depths = self._seq_depths(depths, T)
+        frames, fmt = self._seq_frames(frames, T)
         self._bind()
         o = opts or default_opts()
-        frames = self._cpu(frames, (T, 3, self.H, self.W), "frames")
         Kc = self._cpu(torch.as_tensor(np.asarray(K, dtype=np.float32)), (3, 3), "K")
         p0 = self._cpu(torch.as_tensor(np.asarray(init_poses, dtype=np.float32)), (T - S, 2 * S, 6), "init_poses")
         out = torch.empty_like(p0)
@@ -936,8 +996,9 @@ class Engine:
             if dout.is_cuda or dout.dtype != torch.float32 or not dout.is_contiguous() or tuple(dout.shape) != (T - S, 2 * S, 1, self.H, self.W):
                 raise TypeError("out_depths must be a contiguous float32 CPU tensor [T-S, 2S, 1, H, W]")
         hp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._call(self.lib.tcsfm_refine_dense_sequence(self._h, C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(p0), hp(out), hp(dout), int(ring),
-                                                        int(windows_per_call), int(target_pos)))
+        with self._frame_format(fmt):
+            self._call(self.lib.tcsfm_refine_dense_sequence(self._h, C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(p0), hp(out), hp(dout), int(ring),
+                                                            int(windows_per_call), int(target_pos)))
         return out, dout
 
     @staticmethod

@@ -266,22 +266,23 @@ class PoseNetHIP:
 
     def odometry_sequence(self, frames, depths, K, opts=None, sources: int = 1, iterations: int = 4, ring: int = 0, windows_per_call: int = 0,
                           target_pos: int = 0):
-        """tcsfm_odometry_sequence: for every window of a sequence (frames [T,3,H,W] / depths [T,1,H,W] CPU tensors, pinned for
+        """tcsfm_odometry_sequence: for every window of a sequence (frames [T,3,H,W] float32, or uint8 [T,3,H,W] / [T,H,W,3] / depths [T,1,H,W] CPU tensors, pinned for
         asynchronous copies; K [3,3]) the coupled PoseNet loop gives the initial poses and the engine refines them, windows
         running on the engine's lanes -> (initial poses, refined poses), each [T-S, 2S, 6] CPU tensors.  depths=None: the depth
         network of Engine.attach_depthnet computes them inside the call (frames in, poses out)"""
         e = self.eng
         T, S = int(frames.shape[0]), int(sources)
         depths = e._seq_depths(depths, T)
+        frames, fmt = e._seq_frames(frames, T)
         e._bind()
         from .engine import default_opts
         o = opts or default_opts()
-        frames = e._cpu(frames, (T, 3, e.H, e.W), "frames")
         Kc = e._cpu(torch.as_tensor(np.asarray(K, dtype=np.float32)), (3, 3), "K")
         init = torch.empty((T - S, 2 * S, 6), dtype=torch.float32); out = torch.empty_like(init)
         hp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        e._call(self.lib.tcsfm_odometry_sequence(e._h, self._pn, int(iterations), C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(init), hp(out),
-                                                 None, int(ring), int(windows_per_call), int(target_pos)))
+        with e._frame_format(fmt):
+            e._call(self.lib.tcsfm_odometry_sequence(e._h, self._pn, int(iterations), C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(init), hp(out),
+                                                     None, int(ring), int(windows_per_call), int(target_pos)))
         return init, out
 
     def solve_pose_iteratively(self, num_iter: int, tgt, srcs, depth_t, depth_s, K):
