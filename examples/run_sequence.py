@@ -5,6 +5,7 @@ refinement with the drop-in DepthOptimizer, trajectory composition (validate.com
     python examples/run_sequence.py [--frames 40] [--sources 2]          (needs an MI355X)
     python examples/run_sequence.py --frames-only CHECKPOINT              frames in, poses out: see frames_only() below
     python examples/run_sequence.py --frames-only CHECKPOINT --u8-frames  ... from the camera's bytes: interleaved 8-bit RGB [T,H,W,3]
+    python examples/run_sequence.py --frames-only CHECKPOINT --camera-size 376x1241   ... from camera-size bytes [T,376,1241,3]: resized on the device
 
 The two "networks" are stand-ins with the reference models' call conventions: the depth net returns the scene's true
 disparity for whatever frame it is shown, the pose net returns a noisy version of the true relative pose (PoseNet-quality
@@ -69,9 +70,22 @@ def frames_only(args):
         # float frames' PCIe traffic and pinned memory) and the library makes u8 / 255 on the device -- ArrayToTensor's values, bit for bit
         frames = torch.from_numpy(np.ascontiguousarray(np.round(frames.numpy() * 255).astype(np.uint8).transpose(0, 2, 3, 1))).pin_memory()
         print(f"frames: uint8 {list(frames.shape)} (HWC), {frames.numel() / 1e6:.1f} MB pinned")
+    source_size, K = None, first["K"]
+    if args.camera_size:    # what the camera really delivers: frames of ITS size (KITTI: 1241 x 376).  The reference's loaders shrink every frame
+        # with Pillow's Lanczos filter on the host and scale K (data/scannet_test_loader.py:157-170); here the camera's bytes go up as they
+        # are, the library makes the H x W frames on the device -- Pillow's bytes exactly -- and Engine.scale_intrinsics makes K
+        h, w = (int(v) for v in args.camera_size.lower().split("x"))
+        big = torch.nn.functional.interpolate(frames.float() if frames.dtype != torch.uint8 else frames.permute(0, 3, 1, 2).float() / 255,
+                                              size=(h, w), mode="bilinear", align_corners=False)       # a stand-in camera: the scene enlarged
+        frames = (big * 255).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().pin_memory()
+        source_size = (h, w)
+        K_camera = np.asarray(first["K"], dtype=np.float64) * np.array([[w / W], [h / H], [1.0]])       # the camera's own intrinsics
+        K = eng.scale_intrinsics(K_camera, source_size)
+        print(f"frames: uint8 {list(frames.shape)} at the camera's size, {frames.numel() / 1e6:.1f} MB pinned; K scaled to {W}x{H}:\n{K}")
     opts = default_opts(n_iters=args.gn_iters, min_depth=0.06, max_depth=2.67)
     t0 = time.perf_counter()
-    init, refined = pose_net.odometry_sequence(frames, None, first["K"], opts, sources=S, iterations=4, target_pos=-1)
+    init, refined = pose_net.odometry_sequence(frames, None, K, opts, sources=S, iterations=4, target_pos=-1,
+                                               **({} if source_size is None else {"source_size": source_size}))
     dt = time.perf_counter() - t0
     print(f"{args.frames} frames -> {refined.shape[0]} windows of {2 * S} directed pairs in {dt * 1e3:.1f} ms (first call: allocations included)")
     with np.printoptions(precision=4, suppress=True):
@@ -87,6 +101,9 @@ def main():
     ap.add_argument("--u8-frames", action="store_true",
                     help="with --frames-only: quantise the synthetic frames to interleaved 8-bit RGB [T,H,W,3] and feed the bytes "
                          "(the library converts them on the device: tcsfm_sequence_frame_format)")
+    ap.add_argument("--camera-size", metavar="HxW", default="",
+                    help="with --frames-only: feed interleaved 8-bit frames of this size (e.g. 376x1241, a KITTI camera) and let the library "
+                         "resize them on the device with Pillow's Lanczos bytes (source_size=: tcsfm_sequence_frame_source)")
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--sources", type=int, default=1, choices=(1, 2))
     ap.add_argument("--gn-iters", type=int, default=8)
@@ -96,6 +113,8 @@ def main():
     args = ap.parse_args()
     if args.frames_only:
         return frames_only(args)
+    if args.camera_size:
+        ap.error("--camera-size goes with --frames-only (for frames held on the device: Engine.resize_u8)")
     if args.u8_frames:
         ap.error("--u8-frames goes with --frames-only (the per-window loop below holds its frames on the device: Engine.frames_from_u8 is for that)")
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).cuda()

@@ -177,7 +177,9 @@ enum { TCSFM_STAT_COST = 0, TCSFM_STAT_COST_PHOTO = 1, TCSFM_STAT_NMASK = 2, TCS
  * parameters are outputs of every step (two tensors of one optimiser must not share memory, a gradient must not lie on a parameter).
  * tcsfm_frames_from_u8 declares its two arrays `const void *src` / `void *dst` (bytes in, floats out) and enforces its one rule itself:
  * dst overlapping src in any way is refused with "tcsfm_frames_from_u8: dst overlaps src"; nothing about it is honoured.  While a U8
- * format is set (tcsfm_sequence_frame_format) the `frames` range of a sequence call is T*3*H*W bytes, not floats. */
+ * format is set (tcsfm_sequence_frame_format) the `frames` range of a sequence call is T*3*H*W bytes, not floats -- T*3*src_h*src_w
+ * bytes with a frame source set (tcsfm_sequence_frame_source).  tcsfm_resize_u8 is declared and behaves like tcsfm_frames_from_u8:
+ * "tcsfm_resize_u8: dst overlaps src". */
 
 /* ---- lifetime ------------------------------------------------------------------------------- */
 
@@ -828,6 +830,28 @@ int tcsfm_sequence_depthnet(tcsfm_handle h, tcsfm_depthnet *dn);
 #define TCSFM_FRAMES_U8_HWC  2   /* [T,H,W,3] uint8, interleaved RGB as cameras deliver it                */
 int tcsfm_sequence_frame_format(tcsfm_handle h, int format);
 int tcsfm_frames_from_u8(tcsfm_handle h, const tcsfm_opts *o, int format, int N, const void *src, void *dst);
+/* Camera-size frames.  No camera delivers the H x W the solver and the networks work at; the reference shrinks every frame on the host
+ * with Pillow, Image.resize((W, H), Image.ANTIALIAS) -- Lanczos, support 3 (data/scannet_test_loader.py:157-170 inside the run-time
+ * loader, data/create_kitti_odometry_data.py:56-65, data/create_kitti_eigen_data.py:30-35) -- and scales the intrinsics.  Pillow's 8-bit
+ * resize is integer arithmetic (22-bit fixed-point coefficients, int32 sums, a clip to a byte after each of its two passes), and
+ * k_resize_u8 (csrc/resize_u8_kernel.h) returns ITS BYTES EXACTLY.
+ * tcsfm_sequence_frame_source is a sticky setting of the handle, like tcsfm_sequence_frame_format; (0, 0) means none and is the default.
+ * While it is set AND a U8 format is set, the three sequence calls read `frames` as [T,src_h,src_w,3] (TCSFM_FRAMES_U8_HWC) or
+ * [T,3,src_h,src_w] (TCSFM_FRAMES_U8_CHW) bytes; the overlap check takes it as T*3*src_h*src_w bytes.  The bytes cross PCIe at source
+ * size into the byte ring, and the chunk's first launch on the pack stream is k_resize_u8 in k_frames_u8's place: it writes the float
+ * ring and its mirror slots with float32(b / 255) of Pillow's bytes, so the call returns the bits of the same call on frames resized by
+ * Pillow on the host.  Everything behind it is unchanged.  K keeps its meaning: the intrinsics of the H x W images
+ * (tcsfm_scale_intrinsics makes them from the camera's).
+ *   Refusals (TCSFM_E_ARG, tcsfm_last_error says why, the setting is unchanged): a negative size; exactly one of the two zero; a source
+ *   beyond the kernel's tile -- more than 8 times H or W along that axis, or a side above 32768.  Upscaling is allowed, as Pillow allows
+ *   it.  A NULL handle: TCSFM_E_ARG.  A sequence call with a source set and TCSFM_FRAMES_F32_CHW: TCSFM_E_ARG.
+ * tcsfm_resize_u8 is the same kernel as an operator, on the handle's stream (asynchronous): N >= 1 frames of `format`
+ * (TCSFM_FRAMES_U8_HWC or TCSFM_FRAMES_U8_CHW) and size src_h x src_w at DEVICE pointer src (any address) -> H x W frames at DEVICE
+ * pointer dst: dst_format == format gives Pillow's bytes in the source's layout, dst_format == TCSFM_FRAMES_F32_CHW the planar
+ * float32 [N,3,H,W] of b / 255 (dst aligned for float).  o->host_ptrs must be 0.  The same size limits.  dst overlapping src in any way
+ * is refused ("tcsfm_resize_u8: dst overlaps src"); nothing about it is honoured. */
+int tcsfm_sequence_frame_source(tcsfm_handle h, int src_h, int src_w);
+int tcsfm_resize_u8(tcsfm_handle h, const tcsfm_opts *o, int format, int N, int src_h, int src_w, const void *src, int dst_format, void *dst);
 int tcsfm_lane_wait(tcsfm_handle h, int lane);
 int tcsfm_lane_synchronize(tcsfm_handle h, int lane);
 int tcsfm_lane_event(tcsfm_handle h, int lane, void **event_out);
@@ -892,6 +916,20 @@ void tcsfm_se3_exp(const double xi[6], double T[12]);            /* xi = [rho, p
 void tcsfm_se3_log(const double T[12], double xi[6]);
 void tcsfm_se3_mul(const double A[12], const double B[12], double C[12]);
 void tcsfm_se3_inv(const double A[12], double B[12]);
+
+
+/* ---- camera-size frames, host (no GPU needed): the resize's coefficient table and the loaders' intrinsics scaling ------------------
+ * tcsfm_resize_coeffs: Pillow's 8-bit Lanczos table of one axis, input length `in` -> output length `out` (both >= 1), in double:
+ *     scale = in / out;  fs = max(scale, 1);  support = 3 fs;  *ksize_out = (int)ceil(support) * 2 + 1
+ *     output xx:  center = (xx + 0.5) scale;  xmin = max((int)(center - support + 0.5), 0);  n = min((int)(center + support + 0.5), in) - xmin
+ *                 w[x] = lanczos((x + xmin - center + 0.5) / fs), divided by their sum, times 1 << 22, rounded half away from zero
+ *   bounds[out][2] = {xmin, n}, kk[out][ksize] (zero beyond n).  With bounds or kk NULL only *ksize_out is written: call twice.
+ * tcsfm_scale_intrinsics: K_src, K_out are 9 floats each (row-major 3x3; declared void like tcsfm_frames_from_u8's arrays).  Row 0 is
+ *   (float)((double)K * ((double)W / src_w)), row 1 (float)((double)K * ((double)H / src_h)) -- the loaders' K[0] *= zoom_x;
+ *   K[1] *= zoom_y -- and row 2 is copied.  K_out may be K_src.
+ * Both return TCSFM_OK, or TCSFM_E_ARG for a NULL pointer or a size below 1. */
+int tcsfm_resize_coeffs(int in, int out, int *ksize_out, int *bounds, int *kk);
+int tcsfm_scale_intrinsics(int src_h, int src_w, int H, int W, const void *K_src, void *K_out);
 
 #ifdef __cplusplus
 }

@@ -190,6 +190,8 @@ _SIGNATURES = {
     "tcsfm_sequence_depthnet": (C.c_int, [_P, _P]),
     "tcsfm_sequence_frame_format": (C.c_int, [_P, C.c_int]),
     "tcsfm_frames_from_u8": (C.c_int, [_P, C.POINTER(Opts), C.c_int, C.c_int, _P, _P]),
+    "tcsfm_sequence_frame_source": (C.c_int, [_P, C.c_int, C.c_int]),
+    "tcsfm_resize_u8": (C.c_int, [_P, C.POINTER(Opts), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "tcsfm_lane_wait": (C.c_int, [_P, C.c_int]),
     "tcsfm_lane_synchronize": (C.c_int, [_P, C.c_int]),
     "tcsfm_lane_event": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
@@ -206,6 +208,8 @@ _SIGNATURES = {
     "tcsfm_se3_log": (None, [_P, _P]),
     "tcsfm_se3_mul": (None, [_P, _P, _P]),
     "tcsfm_se3_inv": (None, [_P, _P]),
+    "tcsfm_resize_coeffs": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P]),
+    "tcsfm_scale_intrinsics": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

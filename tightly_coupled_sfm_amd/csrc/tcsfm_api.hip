@@ -28,6 +28,7 @@
 #include "window_loss_kernel.h"
 #include "optim_kernel.h"
 #include "frames_u8_kernel.h"
+#include "resize_u8_kernel.h"
 
 using namespace tc;
 
@@ -174,8 +175,10 @@ struct tcsfm_ctx {
     tcsfm_depthnet *seq_dn = nullptr;  // tcsfm_sequence_depthnet: the network whose clone computes the ring's depths on seq_pack when a sequence
                                        // call gets depths == NULL (not owned; tcsfm_depthnet_destroy detaches it)
     int seq_fmt = TCSFM_FRAMES_F32_CHW;  // tcsfm_sequence_frame_format: how the sequence calls read their `frames` argument
-    uint8_t *seq_u8 = nullptr;         // U8 formats: device ring of the frames' BYTES ([seq_u8_slots][3 H W], no mirror slots); k_frames_u8 turns a
-    int seq_u8_slots = 0;              // chunk into the floats of seq_img on seq_pack
+    uint8_t *seq_u8 = nullptr;         // U8 formats: device ring of the frames' BYTES (R slots of 3 H W -- or, with a frame source set, of
+    size_t seq_u8_bytes = 0;           // 3 src_h src_w -- bytes, no mirror slots); k_frames_u8 / k_resize_u8 turns a chunk into the floats of seq_img on seq_pack
+    int seq_src_h = 0, seq_src_w = 0;  // tcsfm_sequence_frame_source: the camera's frame size (0, 0: none -- frames arrive at H x W)
+    std::vector<ResizeTable> resize_tabs;      // coefficient tables of the source sizes seen so far, on the device (resize_table())
     struct KOk { const float *p; int n; };
     KOk K_ok[4] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}};   // device intrinsics pointers (and counts) that already passed the pinhole check
     int K_ok_next = 0;
@@ -1429,6 +1432,8 @@ void tcsfm_destroy(tcsfm_handle h) {
                     h->seq_fpack, h->seq_fdepth, h->pair_idx, h->seq_img, h->seq_depth, h->seq_pose_in, h->seq_pose_out, h->seq_ls_out, h->seq_K, h->seq_dense, h->seq_dense_tmp, h->seq_u8};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    for (auto &t : h->resize_tabs)
+        if (t.dev) (void)hipFree(t.dev);
     for (auto &s : h->stage)
         if (s.p) (void)hipFree(s.p);
     for (auto &e : h->ev_pool) (void)hipEventDestroy(e);
@@ -2887,6 +2892,25 @@ int tcsfm_refine_dense_window_async(tcsfm_handle h, int lane, const tcsfm_opts *
 #include "posenet_host.h"
 #include "depthnet_host.h"
 
+// The device copy of the resize tables for (src_h, src_w) -> the handle's (H, W): built on the host once per source size and kept for the
+// handle's life (a handful of ints per output row and column).  NULL: h->err says why (the caller returns TCSFM_E_HIP / TCSFM_E_ARG).
+static const ResizeTable *resize_table(tcsfm_handle h, int src_h, int src_w) {
+    for (const auto &t : h->resize_tabs)
+        if (t.sh == src_h && t.sw == src_w) return &t;
+    ResizeTable T;
+    T.sh = src_h; T.sw = src_w; T.H = h->H; T.W = h->W;
+    std::vector<int> blob;
+    if (!resize_build_table(T, blob)) { h->err = "resize: the source size is beyond the kernel's tile (resize_u8_kernel.h)"; return nullptr; }
+    if (hipError_t e = hipMalloc((void **)&T.dev, blob.size() * sizeof(int))) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return nullptr; }
+    if (hipError_t e = hipMemcpy(T.dev, blob.data(), blob.size() * sizeof(int), hipMemcpyHostToDevice)) {      // (synchronous: blob is a temporary)
+        h->err = std::string("hipMemcpy: ") + hipGetErrorString(e);
+        (void)hipFree(T.dev);
+        return nullptr;
+    }
+    h->resize_tabs.push_back(T);
+    return &h->resize_tabs.back();
+}
+
 // The reference's sequential driver (run_sequential_optimization.py:186-247) as ONE call: see include/tcsfm.h.  With `pn` the initial
 // poses of every window come from the coupled PoseNet loop (train_mono.py:64-80) on the window's lane instead of from the caller.
 static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, const float *frames, const float *depths, const float *K,
@@ -2902,6 +2926,11 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     // tcsfm_sequence_frame_format: `frames` points at bytes; they go up as they are and k_frames_u8 makes the ring's floats on the device
     const bool u8 = h->seq_fmt != TCSFM_FRAMES_F32_CHW;
     const uint8_t *frames_u8 = (const uint8_t *)frames;
+    // tcsfm_sequence_frame_source: the bytes are camera-size frames; k_resize_u8 takes k_frames_u8's place and writes Pillow's H x W frames
+    const bool resize = h->seq_src_h > 0;
+    if (resize && !u8)
+        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": a frame source size (tcsfm_sequence_frame_source) needs a U8 frame format, not TCSFM_FRAMES_F32_CHW").c_str());
+    const size_t frame_bytes = resize ? (size_t)3 * h->seq_src_h * h->seq_src_w : (size_t)3 * h->H * h->W;      // of one frame of a U8 format
     if (!frames || (!depths && !gen) || !K || (!pose_init && !pn) || !pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: NULL input");
     if (gen && o_in->depth_is_disp)
         return fail(h, TCSFM_E_ARG, (std::string(entry) + ": depths == NULL (the attached depth network produces depths) cannot go with opts.depth_is_disp").c_str());
@@ -2913,7 +2942,7 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
         // issued (small_ev below), and pose_out is written after the last one has finished.
         const size_t hw_b = (size_t)h->H * h->W * sizeof(float), np6 = (size_t)(T - S) * N * 6 * sizeof(float);
         ArgRanges a;
-        a.in("frames", frames, u8 ? (size_t)T * 3 * h->H * h->W : (size_t)T * 3 * hw_b);      // (a U8 format: T*3*H*W bytes, not floats)
+        a.in("frames", frames, u8 ? (size_t)T * frame_bytes : (size_t)T * 3 * hw_b);      // (a U8 format: T*3*H*W -- T*3*src_h*src_w -- bytes, not floats)
         a.in("depths", depths, (size_t)T * hw_b); a.in("K", K, 9 * sizeof(float));
         a.in("pose_init", pose_init, np6);
         a.out("pose_init_out", pose_init_out, np6); a.out("pose_out", pose_out, np6);
@@ -2969,12 +2998,14 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
         if (h->seq_fdepth) { HIPCHK(h, hipFree(h->seq_fdepth)); h->seq_fdepth = nullptr; }
         h->seq_slots = R + M;
     }
-    if (u8 && h->seq_u8_slots < R) {                        // the byte ring: R slots, no mirror (the kernel writes the float mirror slots itself)
+    if (u8 && h->seq_u8_bytes < (size_t)R * frame_bytes) {  // the byte ring: R slots, no mirror (the kernel writes the float mirror slots itself)
         if (h->seq_u8) HIPCHK(h, hipFree(h->seq_u8));
-        h->seq_u8 = nullptr; h->seq_u8_slots = 0;
-        HIPCHK(h, hipMalloc((void **)&h->seq_u8, (size_t)R * 3 * hw));
-        h->seq_u8_slots = R;
+        h->seq_u8 = nullptr; h->seq_u8_bytes = 0;
+        HIPCHK(h, hipMalloc((void **)&h->seq_u8, (size_t)R * frame_bytes));
+        h->seq_u8_bytes = (size_t)R * frame_bytes;
     }
+    const ResizeTable *rtab = nullptr;
+    if (resize && !(rtab = resize_table(h, h->seq_src_h, h->seq_src_w))) return TCSFM_E_HIP;
     const bool use_cache = dense_depth_out == nullptr;      // (the dense modes rewrite per-pair depth planes: they keep the per-pair pack)
     if (use_cache && !h->seq_fpack) {
         HIPCHK(h, hipMalloc((void **)&h->seq_fpack, (size_t)h->seq_slots * (h->H + 2) * (h->W + 2) * sizeof(float4)));
@@ -3077,7 +3108,7 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
             for (int k = 0; k < nf; k++) { if (slot_reader[slot + k] > last) last = slot_reader[slot + k]; slot_reader[slot + k] = -1; }
             for (long long r = last; r >= 0 && r > last - L; r--)     // -- the latest of those calls on every lane (a lane's stream is in order)
                 HIPCHK(h, hipStreamWaitEvent(cs, h->seq_done[r % ND], 0));
-            if (u8) HIPCHK(h, hipMemcpyAsync(h->seq_u8 + (size_t)slot * 3 * hw, frames_u8 + (size_t)nxt * 3 * hw, (size_t)nf * 3 * hw, hipMemcpyHostToDevice, cs));
+            if (u8) HIPCHK(h, hipMemcpyAsync(h->seq_u8 + (size_t)slot * frame_bytes, frames_u8 + (size_t)nxt * frame_bytes, (size_t)nf * frame_bytes, hipMemcpyHostToDevice, cs));
             else HIPCHK(h, hipMemcpyAsync(h->seq_img + (size_t)slot * 3 * hw, frames + (size_t)nxt * 3 * hw, (size_t)nf * 3 * hw * sizeof(float), hipMemcpyHostToDevice, cs));
             if (!gen) HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)slot * hw, depths + (size_t)nxt * hw, (size_t)nf * hw * sizeof(float), hipMemcpyHostToDevice, cs));
             // mirror of the first M slots behind the ring (the frames of a call never wrap).  The frames cross PCIe ONCE: raw mirrors are
@@ -3100,9 +3131,13 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
                 // waited for those calls' seq_done events (slot_reader above), and the kernel waits for that copy (seq_raw).  The NEXT copy
                 // into the same seq_u8 slots waits for the calls that read THIS chunk, those calls waited for seq_copied, and seq_copied is
                 // recorded on this stream after the kernel: so a byte slot is never overwritten while the kernel may still read it.
+                // With a frame source set the slots are 3 src_h src_w bytes and the launch is k_resize_u8: the same reads (this chunk's
+                // byte slots), the same writes (seq_img[slot ..] + mirror), the same place in the stream -- the argument holds as it stands.
                 float *mirror = nm > 0 && (!use_cache || pn) ? h->seq_img + (size_t)(R + slot) * 3 * hw : nullptr;
-                HIPCHK(h, launch_frames_u8(h->seq_pack, h->seq_fmt == TCSFM_FRAMES_U8_HWC, nf, h->seq_u8 + (size_t)slot * 3 * hw, h->seq_img + (size_t)slot * 3 * hw,
-                                           mirror, mirror ? nm : 0, hw));
+                const bool hwc = h->seq_fmt == TCSFM_FRAMES_U8_HWC;
+                if (resize) HIPCHK(h, launch_resize_u8(h->seq_pack, *rtab, hwc, true, nf, h->seq_u8 + (size_t)slot * frame_bytes, h->seq_img + (size_t)slot * 3 * hw,
+                                                       mirror, mirror ? nm : 0));
+                else HIPCHK(h, launch_frames_u8(h->seq_pack, hwc, nf, h->seq_u8 + (size_t)slot * 3 * hw, h->seq_img + (size_t)slot * 3 * hw, mirror, mirror ? nm : 0, hw));
             }
             if (gen) {
                 // Depths of the frames that just landed, once per frame, by the attached network's clone on the pack stream -- neither the
@@ -3236,6 +3271,56 @@ int tcsfm_frames_from_u8(tcsfm_handle h, const tcsfm_opts *o, int format, int N,
     DeviceGuard dev_guard(h->device);
     if (int rc_ = pending_error(h)) return rc_;
     HIPCHK(h, launch_frames_u8(h->stream, format == TCSFM_FRAMES_U8_HWC, N, (const uint8_t *)src, (float *)dst, nullptr, 0, hw));
+    return TCSFM_OK;
+}
+
+int tcsfm_sequence_frame_source(tcsfm_handle h, int src_h, int src_w) {
+    if (!h) return TCSFM_E_ARG;
+    if (src_h == 0 && src_w == 0) { h->seq_src_h = h->seq_src_w = 0; return TCSFM_OK; }
+    if (src_h <= 0 || src_w <= 0)
+        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_frame_source: src_h and src_w must both be positive, or both 0 (no source size)");
+    if (const char *why = resize_refusal(src_h, src_w, h->H, h->W)) return fail(h, TCSFM_E_ARG, (std::string("tcsfm_sequence_frame_source: ") + why).c_str());
+    h->seq_src_h = src_h; h->seq_src_w = src_w;
+    return TCSFM_OK;
+}
+
+int tcsfm_resize_u8(tcsfm_handle h, const tcsfm_opts *o, int format, int N, int src_h, int src_w, const void *src, int dst_format, void *dst) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    if (!h) return TCSFM_E_ARG;
+    if (!o || !src || !dst) return fail(h, TCSFM_E_ARG, "tcsfm_resize_u8: NULL argument");
+    if (format != TCSFM_FRAMES_U8_CHW && format != TCSFM_FRAMES_U8_HWC)
+        return fail(h, TCSFM_E_ARG, "tcsfm_resize_u8: format must be TCSFM_FRAMES_U8_CHW or TCSFM_FRAMES_U8_HWC");
+    if (dst_format != format && dst_format != TCSFM_FRAMES_F32_CHW)
+        return fail(h, TCSFM_E_ARG, "tcsfm_resize_u8: dst_format must be the source's format (bytes) or TCSFM_FRAMES_F32_CHW");
+    if (N < 1) return fail(h, TCSFM_E_ARG, "tcsfm_resize_u8: N must be at least 1");
+    if (o->host_ptrs != 0)
+        return fail(h, TCSFM_E_ARG, "tcsfm_resize_u8: host_ptrs must be 0 (device pointers); host frames go through the sequence calls (tcsfm_sequence_frame_source)");
+    if (src_h <= 0 || src_w <= 0) return fail(h, TCSFM_E_ARG, "tcsfm_resize_u8: src_h and src_w must be positive");
+    if (const char *why = resize_refusal(src_h, src_w, h->H, h->W)) return fail(h, TCSFM_E_ARG, (std::string("tcsfm_resize_u8: ") + why).c_str());
+    const bool f32 = dst_format == TCSFM_FRAMES_F32_CHW;
+    if (f32 && ((uintptr_t)dst & 3) != 0) return fail(h, TCSFM_E_ARG, "tcsfm_resize_u8: a float dst must be aligned for float");
+    const size_t hw = (size_t)h->H * h->W;
+    ArgRanges a;
+    a.in("src", src, (size_t)N * 3 * src_h * src_w); a.out("dst", dst, (size_t)N * 3 * hw * (f32 ? sizeof(float) : 1));
+    std::string msg;
+    if (a.refused("tcsfm_resize_u8", msg)) return fail(h, TCSFM_E_ARG, msg.c_str());
+    DeviceGuard dev_guard(h->device);
+    if (int rc_ = pending_error(h)) return rc_;
+    const ResizeTable *T = resize_table(h, src_h, src_w);
+    if (!T) return TCSFM_E_HIP;
+    HIPCHK(h, launch_resize_u8(h->stream, *T, format == TCSFM_FRAMES_U8_HWC, f32, N, (const uint8_t *)src, dst, nullptr, 0));
+    return TCSFM_OK;
+}
+
+int tcsfm_resize_coeffs(int in, int out, int *ksize_out, int *bounds, int *kk) {
+    if (in < 1 || out < 1 || !ksize_out) return TCSFM_E_ARG;
+    *ksize_out = tc::resize_coeffs(in, out, bounds, kk);
+    return TCSFM_OK;
+}
+
+int tcsfm_scale_intrinsics(int src_h, int src_w, int H, int W, const void *K_src, void *K_out) {
+    if (src_h < 1 || src_w < 1 || H < 1 || W < 1 || !K_src || !K_out) return TCSFM_E_ARG;
+    tc::scale_intrinsics(src_h, src_w, H, W, (const float *)K_src, (float *)K_out);
     return TCSFM_OK;
 }
 

@@ -50,6 +50,26 @@ def frame_format(frames: torch.Tensor, H: int, W: int) -> int:
     raise TypeError(f"uint8 frames must be [T,3,{H},{W}] or [T,{H},{W},3] (got {list(shape)})")
 
 
+def source_frame_format(frames: torch.Tensor, source_size) -> int:
+    """frame_format for camera-size frames (tcsfm_sequence_frame_source): `frames` must be a uint8 CPU tensor [T,h,w,3] (FRAMES_U8_HWC) or
+    [T,3,h,w] (FRAMES_U8_CHW) with (h, w) = source_size -- given explicitly, never guessed from the tensor.  (A 3 x 3 source fits both:
+    it is read as interleaved.)  Pure."""
+    try:
+        h, w = (int(v) for v in source_size)
+    except (TypeError, ValueError):
+        raise TypeError("source_size must be a pair (h, w)") from None
+    if h <= 0 or w <= 0:
+        raise ValueError(f"source_size must be positive (got {(h, w)})")
+    if not isinstance(frames, torch.Tensor) or frames.device.type != "cpu" or frames.dtype != torch.uint8:
+        raise TypeError("with source_size, frames must be a uint8 CPU tensor [T,h,w,3] or [T,3,h,w] (float frames are already at the engine's size)")
+    shape = tuple(frames.shape)
+    if len(shape) == 4 and shape[1:] == (h, w, 3):
+        return _lib.FRAMES_U8_HWC
+    if len(shape) == 4 and shape[1:] == (3, h, w):
+        return _lib.FRAMES_U8_CHW
+    raise TypeError(f"uint8 frames of source_size {(h, w)} must be [T,{h},{w},3] or [T,3,{h},{w}] (got {list(shape)})")
+
+
 def _copy_opts(o: Opts) -> Opts:
     c = Opts()
     C.memmove(C.byref(c), C.byref(o), C.sizeof(Opts))
@@ -911,9 +931,12 @@ class Engine:
             return None
         return self._cpu(depths, (T, 1, self.H, self.W), "depths")
 
-    def _seq_frames(self, frames, T):
-        """the `frames` argument of a sequence call, checked before anything touches the GPU -> (contiguous CPU tensor, frame format)"""
+    def _seq_frames(self, frames, T, source_size=None):
+        """the `frames` argument of a sequence call, checked before anything touches the GPU -> (contiguous CPU tensor, frame format).
+        source_size=(h, w): camera-size bytes, [T,h,w,3] or [T,3,h,w] (tcsfm_sequence_frame_source)"""
         frames = torch.as_tensor(frames)
+        if source_size is not None:
+            return frames.contiguous(), source_frame_format(frames, source_size)
         fmt = frame_format(frames, self.H, self.W)
         if fmt == _lib.FRAMES_F32_CHW:
             return self._cpu(frames, (T, 3, self.H, self.W), "frames"), fmt
@@ -930,6 +953,54 @@ class Engine:
             yield
         finally:
             self.lib.tcsfm_sequence_frame_format(self._h, _lib.FRAMES_F32_CHW)
+
+    @contextlib.contextmanager
+    def _frame_source(self, source_size):
+        """the handle reads `frames` at the camera's size for the one call inside the block, and at H x W again afterwards"""
+        if source_size is None:
+            yield
+            return
+        h, w = (int(v) for v in source_size)
+        self._call(self.lib.tcsfm_sequence_frame_source(self._h, h, w))
+        try:
+            yield
+        finally:
+            self.lib.tcsfm_sequence_frame_source(self._h, 0, 0)
+
+    def resize_u8(self, frames_u8: torch.Tensor, source_layout: str = "hwc", out: str = "f32") -> torch.Tensor:
+        """tcsfm_resize_u8: uint8 CUDA frames at the camera's size, [N,h,w,3] (source_layout "hwc") or [N,3,h,w] ("chw"), -> the engine's
+        H x W with the bytes of Pillow's Image.resize((W, H), Image.LANCZOS): out="u8" in the source's layout, out="f32" as float32
+        [N,3,H,W] = bytes / 255 (what the window entries read); on the engine's stream"""
+        if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
+            raise TypeError("resize_u8 takes a uint8 CUDA tensor [N,h,w,3] or [N,3,h,w]")
+        if source_layout not in ("hwc", "chw") or out not in ("f32", "u8"):
+            raise ValueError("source_layout must be 'hwc' or 'chw', out 'f32' or 'u8'")
+        shape = tuple(frames_u8.shape)
+        hwc = source_layout == "hwc"
+        if shape[3 if hwc else 1] != 3:
+            raise TypeError(f"{source_layout} frames must be {'[N,h,w,3]' if hwc else '[N,3,h,w]'} (got {list(shape)})")
+        n, (h, w) = shape[0], (shape[1:3] if hwc else shape[2:4])
+        fmt = _lib.FRAMES_U8_HWC if hwc else _lib.FRAMES_U8_CHW
+        self._bind()
+        src = frames_u8.contiguous()
+        if out == "f32":
+            dst, dfmt = torch.empty((n, 3, self.H, self.W), dtype=torch.float32, device=src.device), _lib.FRAMES_F32_CHW
+        else:
+            dst, dfmt = torch.empty((n, self.H, self.W, 3) if hwc else (n, 3, self.H, self.W), dtype=torch.uint8, device=src.device), fmt
+        o = default_opts()
+        self._call(self.lib.tcsfm_resize_u8(self._h, C.byref(o), fmt, int(n), int(h), int(w), self._p(src), dfmt, self._p(dst)))
+        return dst
+
+    def scale_intrinsics(self, K, source_size) -> np.ndarray:
+        """tcsfm_scale_intrinsics: the camera's K [3,3] at source_size=(h, w) -> float32 K of the engine's H x W frames, as the reference's
+        loaders scale it (K[0] *= W / w; K[1] *= H / h in double).  Host only."""
+        h, w = (int(v) for v in source_size)
+        Ks = np.ascontiguousarray(np.asarray(K, dtype=np.float32).reshape(3, 3))
+        out = np.empty((3, 3), dtype=np.float32)
+        rc = _lib.load().tcsfm_scale_intrinsics(h, w, int(self.H), int(self.W), Ks.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise ValueError(f"scale_intrinsics: source_size {(h, w)} must be positive")
+        return out
 
     def frames_from_u8(self, u8: torch.Tensor) -> torch.Tensor:
         """tcsfm_frames_from_u8: uint8 CUDA frames [N,3,H,W] or [N,H,W,3] (interleaved RGB) -> float32 [N,3,H,W], the correctly rounded
@@ -951,17 +1022,19 @@ class Engine:
         return out
 
     def refine_sequence(self, frames: torch.Tensor, depths: Optional[torch.Tensor], K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
-                        ring: int = 0, log_scale: bool = False, windows_per_call: int = 0, target_pos: int = 0):
+                        ring: int = 0, log_scale: bool = False, windows_per_call: int = 0, target_pos: int = 0, source_size=None):
         """tcsfm_refine_sequence: the whole window loop of a sequence inside the library (frames [T,3,H,W] float32 -- or the camera's
         bytes, uint8 [T,3,H,W] / [T,H,W,3], converted to u8 / 255 on the device -- / depths [T,1,H,W] CPU
         tensors -- pinned for asynchronous copies --, K [3,3], init_poses [T-S, 2S, 6]) -> refined poses [T-S, 2S, 6] (CPU tensor;
         with log_scale=True also the log depth scales [T-S, 2S]); calls of `windows_per_call` windows (0 = default 8, capped by max_pairs / 2S) run on
         the engine's lanes.  Window w = frames w .. w+S; its target is frame w + target_pos (0: the first; -1: the middle one, (S+1)//2, as
         the reference's loaders choose it), its sources the others in order.  depths=None: the depth network of attach_depthnet
-        computes them inside the call"""
+        computes them inside the call.  source_size=(h, w): `frames` are the camera's bytes at ITS size, uint8 [T,h,w,3] or [T,3,h,w]; the
+        library resizes them to H x W on the device with Pillow's Lanczos bytes (tcsfm_sequence_frame_source); K is the H x W frames'
+        (Engine.scale_intrinsics)"""
         T, S = int(frames.shape[0]), int(sources)
         depths = self._seq_depths(depths, T)
-        frames, fmt = self._seq_frames(frames, T)
+        frames, fmt = self._seq_frames(frames, T, source_size)
         self._bind()
         o = opts or default_opts()
         cpu = lambda a, shape, name: self._cpu(a, shape, name)
@@ -970,20 +1043,22 @@ class Engine:
         out = torch.empty_like(p0)
         ls = torch.zeros((T - S, 2 * S), dtype=torch.float32) if log_scale else None
         hp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with self._frame_format(fmt):
+        with self._frame_format(fmt), self._frame_source(source_size):
             self._call(self.lib.tcsfm_refine_sequence(self._h, C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(p0), hp(out), hp(ls), int(ring),
                                                       int(windows_per_call), int(target_pos)))
         return (out, ls) if log_scale else out
 
     def refine_dense_sequence(self, frames: torch.Tensor, depths: Optional[torch.Tensor], K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
-                              ring: int = 0, windows_per_call: int = 0, target_pos: int = 0, out_depths: Optional[torch.Tensor] = None):
+                              ring: int = 0, windows_per_call: int = 0, target_pos: int = 0, out_depths: Optional[torch.Tensor] = None,
+                              source_size=None):
         """tcsfm_refine_dense_sequence: the dense mode (pose + per-pixel inverse depth) over a sequence, arguments as refine_sequence
         -> (poses [T-S, 2S, 6], refined depth maps [T-S, 2S, 1, H, W]) as CPU tensors.
         out_depths: a caller-owned (pinned) CPU tensor of that shape to receive the depth maps; a caller that runs sequence after
-        sequence should pass one -- pinning a fresh 70 MB result buffer costs ten times the refinement of a 120-frame sequence."""
+        sequence should pass one -- pinning a fresh 70 MB result buffer costs ten times the refinement of a 120-frame sequence.
+        source_size=(h, w): camera-size bytes, as for refine_sequence."""
         T, S = int(frames.shape[0]), int(sources)
         depths = self._seq_depths(depths, T)
-        frames, fmt = self._seq_frames(frames, T)
+        frames, fmt = self._seq_frames(frames, T, source_size)
         self._bind()
         o = opts or default_opts()
         Kc = self._cpu(torch.as_tensor(np.asarray(K, dtype=np.float32)), (3, 3), "K")
@@ -996,7 +1071,7 @@ class Engine:
             if dout.is_cuda or dout.dtype != torch.float32 or not dout.is_contiguous() or tuple(dout.shape) != (T - S, 2 * S, 1, self.H, self.W):
                 raise TypeError("out_depths must be a contiguous float32 CPU tensor [T-S, 2S, 1, H, W]")
         hp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with self._frame_format(fmt):
+        with self._frame_format(fmt), self._frame_source(source_size):
             self._call(self.lib.tcsfm_refine_dense_sequence(self._h, C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(p0), hp(out), hp(dout), int(ring),
                                                             int(windows_per_call), int(target_pos)))
         return out, dout

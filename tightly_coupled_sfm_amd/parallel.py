@@ -72,16 +72,21 @@ def sequence_block(n_windows: int, rank: int, world: int, windows_per_call: int 
     return min(lo_c * wpc, n_windows), min(hi_c * wpc, n_windows)
 
 
+def _source_kw(source_size):
+    """source_size=(h, w) of the sequence entry points (camera-size bytes: Engine.refine_sequence), passed on only when it is given"""
+    return {} if source_size is None else {"source_size": source_size}
+
+
 def refine_sequence_sharded(engine, frames: torch.Tensor, depths: torch.Tensor, K, init_poses: torch.Tensor, opts=None, sources: int = 1,
                             windows_per_call: int = 8, target_pos: int = 0, group=None, gather_device: Optional[torch.device] = None,
-                            refine_fn: Optional[Callable[..., torch.Tensor]] = None) -> torch.Tensor:
+                            refine_fn: Optional[Callable[..., torch.Tensor]] = None, source_size=None) -> torch.Tensor:
     """The window loop of ONE sequence over all ranks of `group` (run_sequential_optimization.py:186-247 on N GPUs).
 
     frames [T,3,H,W], depths [T,1,H,W] (CPU, pinned for asynchronous uploads), K [3,3], init_poses [T-S, 2S, 6]; every rank
     passes the same arguments (or at least its own block of them: only rows lo .. hi+S of frames / depths and lo .. hi of
     init_poses are read).  -> refined poses [T-S, 2S, 6] on every rank (CPU tensor).
     gather_device: where the collective runs -- the GPU for RCCL (default when the backend is nccl), the CPU for gloo.
-    refine_fn: stand-in for engine.refine_sequence (CPU tests)."""
+    refine_fn: stand-in for engine.refine_sequence (CPU tests).  source_size=(h, w): frames are camera-size bytes (Engine.refine_sequence)."""
     T, S = int(frames.shape[0]), int(sources)
     n_win = T - S
     if dist.is_available() and dist.is_initialized():
@@ -92,7 +97,7 @@ def refine_sequence_sharded(engine, frames: torch.Tensor, depths: torch.Tensor, 
     if hi > lo:
         run = refine_fn or engine.refine_sequence
         local = run(frames[lo:hi + S], depths[lo:hi + S], K, init_poses[lo:hi], opts, sources=S, windows_per_call=windows_per_call,
-                    target_pos=target_pos)
+                    target_pos=target_pos, **_source_kw(source_size))
         local = torch.as_tensor(local).reshape(hi - lo, 2 * S * 6)
     else:
         local = torch.zeros((0, 2 * S * 6), dtype=torch.float32)
@@ -121,7 +126,8 @@ def _gather_window_blocks(local: torch.Tensor, n_win: int, width: int, windows_p
 
 def odometry_sequence_sharded(net, frames: torch.Tensor, depths: torch.Tensor, K, opts=None, sources: int = 1, iterations: int = 4,
                               windows_per_call: int = 8, target_pos: int = 0, group=None, gather_device: Optional[torch.device] = None,
-                              run_fn: Optional[Callable[..., Tuple[torch.Tensor, torch.Tensor]]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                              run_fn: Optional[Callable[..., Tuple[torch.Tensor, torch.Tensor]]] = None,
+                              source_size=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """tcsfm_odometry_sequence (PoseNet loop + refinement per window, run_sequential_optimization.py:186-247 with
     train_mono.py:64-80 inside) over all ranks of `group`: blocks of whole calls + S overlap frames per rank, as
     refine_sequence_sharded; ONE all_gather carries initial and refined poses together.
@@ -138,7 +144,7 @@ def odometry_sequence_sharded(net, frames: torch.Tensor, depths: torch.Tensor, K
     if hi > lo:
         run = run_fn or net.odometry_sequence
         init, out = run(frames[lo:hi + S], depths[lo:hi + S], K, opts, sources=S, iterations=iterations, windows_per_call=windows_per_call,
-                        target_pos=target_pos)
+                        target_pos=target_pos, **_source_kw(source_size))
         local = torch.cat([torch.as_tensor(init).reshape(hi - lo, 2 * S * 6), torch.as_tensor(out).reshape(hi - lo, 2 * S * 6)], 1)
     else:
         local = torch.zeros((0, 4 * S * 6), dtype=torch.float32)
@@ -148,7 +154,8 @@ def odometry_sequence_sharded(net, frames: torch.Tensor, depths: torch.Tensor, K
 
 def refine_dense_sequence_sharded(engine, frames: torch.Tensor, depths: torch.Tensor, K, init_poses: torch.Tensor, opts=None, sources: int = 1,
                                   windows_per_call: int = 8, target_pos: int = 0, gather_depths: bool = False, group=None,
-                                  gather_device: Optional[torch.device] = None, refine_fn: Optional[Callable[..., Tuple[torch.Tensor, torch.Tensor]]] = None):
+                                  gather_device: Optional[torch.device] = None, refine_fn: Optional[Callable[..., Tuple[torch.Tensor, torch.Tensor]]] = None,
+                                  source_size=None):
     """tcsfm_refine_dense_sequence (the reference's sequential driver with `optimize_depth_pred`: optimizer.py:289-297 returns `depths_opt`,
     run_sequential_optimization.py:195-216 reads `disp_opt`) over all ranks of `group`: blocks of whole calls + S overlap frames per rank as
     refine_sequence_sharded.  Arguments as there.
@@ -168,11 +175,11 @@ def refine_dense_sequence_sharded(engine, frames: torch.Tensor, depths: torch.Te
     else:
         world, rank = 1, 0
     lo, hi = sequence_block(n_win, rank, world, windows_per_call)
-    Hh, Ww = int(frames.shape[2]), int(frames.shape[3])
+    Hh, Ww = (int(frames.shape[2]), int(frames.shape[3])) if source_size is None else (int(depths.shape[2]), int(depths.shape[3]))      # (the maps' size)
     if hi > lo:
         run = refine_fn or engine.refine_dense_sequence
         local_p, local_d = run(frames[lo:hi + S], depths[lo:hi + S], K, init_poses[lo:hi], opts, sources=S, windows_per_call=windows_per_call,
-                               target_pos=target_pos)
+                               target_pos=target_pos, **_source_kw(source_size))
         local_p = torch.as_tensor(local_p).reshape(hi - lo, 2 * S * 6)
         local_d = torch.as_tensor(local_d).reshape(hi - lo, 2 * S, 1, Hh, Ww)
     else:

@@ -58,17 +58,19 @@ class SequenceRefiner:
             self.ring_depth[slot].copy_(depth, non_blocking=True)
             self.copied[slot].record(self.copy_stream)
 
-    def run_native(self, frames, depths, K, init_poses, ring: int = 0) -> torch.Tensor:
+    def run_native(self, frames, depths, K, init_poses, ring: int = 0, source_size=None) -> torch.Tensor:
         """The same loop inside the library (tcsfm_refine_sequence: four-frame copies, events and lanes driven from C++) -> refined
         poses [T-S, 2*S, 6] as a CPU tensor; bit-identical to run().  depths=None: the depth network attached to the engine
         (self.eng.attach_depthnet) computes them inside the call.  frames: float32 [T,3,H,W], or the camera's bytes -- uint8 [T,3,H,W] or
-        [T,H,W,3] -- which the library converts on the device (Engine.refine_sequence)"""
+        [T,H,W,3] -- which the library converts on the device (Engine.refine_sequence); with source_size=(h, w) the
+        bytes are at the camera's size, [T,h,w,3] or [T,3,h,w], and the library resizes them too"""
         pin = lambda a: a if (isinstance(a, torch.Tensor) and not a.is_cuda) else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32)
         if isinstance(frames, torch.Tensor) and frames.is_cuda:
             raise TypeError("frames must be a CPU tensor (the library stages the sequence itself)")
         if isinstance(frames, np.ndarray) and frames.dtype == np.uint8:
             frames = torch.from_numpy(np.ascontiguousarray(frames))
-        return self.eng.refine_sequence(pin(frames), None if depths is None else pin(depths), K, init_poses, self.opts, sources=self.S, ring=ring)
+        return self.eng.refine_sequence(pin(frames), None if depths is None else pin(depths), K, init_poses, self.opts, sources=self.S, ring=ring,
+                                        **({} if source_size is None else {"source_size": source_size}))
 
     def run(self, frames, depths, K, init_poses) -> torch.Tensor:
         """-> refined poses [T-S, 2*S, 6] (GPU tensor, complete on return)"""
