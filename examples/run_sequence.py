@@ -85,12 +85,23 @@ def frames_only(args):
     opts = default_opts(n_iters=args.gn_iters, min_depth=0.06, max_depth=2.67)
     t0 = time.perf_counter()
     init, refined = pose_net.odometry_sequence(frames, None, K, opts, sources=S, iterations=4, target_pos=-1,
-                                               **({} if source_size is None else {"source_size": source_size}))
+                                               **({} if source_size is None else {"source_size": source_size}),
+                                               **({} if args.cam_height is None else {"cam_height": args.cam_height / DEPTH_UNIT}))
     dt = time.perf_counter() - t0
     print(f"{args.frames} frames -> {refined.shape[0]} windows of {2 * S} directed pairs in {dt * 1e3:.1f} ms (first call: allocations included)")
     with np.printoptions(precision=4, suppress=True):
         print("PoseNet poses of window 0:\n", init[0].numpy())
         print("refined poses of window 0:\n", refined[0].numpy())
+        if args.cam_height is not None:     # metres: the DNet ground-plane scale of every window's target frame, computed inside the call from
+            # the ring's own depth planes (run_sequential_optimization.py:224-227: 30 * scale_factor * t)
+            from tightly_coupled_sfm_amd.streaming import metric_poses
+            sc = eng.sequence_scales()
+            metric = metric_poses(refined, sc["scale"], S, target_pos=-1, depth_unit=DEPTH_UNIT)
+            print(f"per-frame scales (ground pixels {sc['count'].tolist()[:6]} ...):\n", sc["scale"].numpy()[:6], "...")
+            print("refined poses of window 0, translations in metres:\n", metric[0].numpy())
+
+
+DEPTH_UNIT = 30.0       # the reference's depth unit in metres (run_sequential_optimization.py:224)
 
 
 def main():
@@ -104,6 +115,9 @@ def main():
     ap.add_argument("--camera-size", metavar="HxW", default="",
                     help="with --frames-only: feed interleaved 8-bit frames of this size (e.g. 376x1241, a KITTI camera) and let the library "
                          "resize them on the device with Pillow's Lanczos bytes (source_size=: tcsfm_sequence_frame_source)")
+    ap.add_argument("--cam-height", type=float, default=None, metavar="METRES",
+                    help="with --frames-only: the camera's height above the ground (KITTI: 1.65); every frame's DNet scale is computed inside "
+                         "the call (cam_height=: tcsfm_sequence_scale) and the translations are printed in metres (streaming.metric_poses)")
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--sources", type=int, default=1, choices=(1, 2))
     ap.add_argument("--gn-iters", type=int, default=8)
@@ -113,6 +127,8 @@ def main():
     args = ap.parse_args()
     if args.frames_only:
         return frames_only(args)
+    if args.cam_height is not None:
+        ap.error("--cam-height goes with --frames-only (the per-window loop below gets its scale from DepthOptimizer)")
     if args.camera_size:
         ap.error("--camera-size goes with --frames-only (for frames held on the device: Engine.resize_u8)")
     if args.u8_frames:

@@ -461,6 +461,19 @@ int tcsfm_linearize_dense_window_sources(tcsfm_handle h, const tcsfm_opts *o, in
  * scale_out [1]; optional: median_out [1], height_out / mask_out [N,1,H,W]. */
 int tcsfm_scale_recovery(tcsfm_handle h, const tcsfm_opts *o, int N, const float *depth, const float *K, float real_cam_height,
                          int pad_to_batch, float *scale_out, float *median_out, float *height_out, float *mask_out);
+/* operator: per-item scales of N depth maps, device pointers, on the handle's stream (asynchronous).  Item n's scale_out[n] and
+ * median_out[n] are, bit for bit, what tcsfm_scale_recovery(h, o, 1, depth_n, K_n, real_cam_height, 0, ...) returns for that item
+ * alone; count_out[n] is its number of ground pixels, and an item without any gets the quiet NaN in both.  Two launches per call,
+ * whatever N: k_ground and k_median_frames (csrc/frame_scale_kernel.h: one workgroup per item runs the whole radix select), against
+ * nine launches and a memset per tcsfm_scale_recovery call.  The arrays are declared void like tcsfm_scale_intrinsics': depth is
+ * float [N,H*W], K float [N,9], scale_out / median_out float [N], count_out int32 [N].
+ *   Refused with TCSFM_E_ARG (tcsfm_last_error says why; nothing is launched, the outputs keep their contents): a NULL depth, K or
+ *   scale_out; N < 1 or N > max_pairs; H < 5 or W < 5 ("image too small", as tcsfm_scale_recovery); o->host_ptrs != 0 (a host caller
+ *   has the sequence calls: tcsfm_sequence_scale); an output overlapping depth, K or another output ("overlapping arguments").
+ *   The intrinsics are checked as tcsfm_scale_recovery checks them. */
+int tcsfm_scale_recovery_frames(tcsfm_handle h, const tcsfm_opts *o, int N,
+        const void *depth /* float [N,H*W] */, const void *K /* float [N,9] */, float real_cam_height,
+        void *scale_out /* float [N] */, void *median_out /* float [N] or NULL */, int *count_out /* [N] or NULL */);
 
 /* ---- PoseNet and the coupled pose loop ----------------------------------------
  * The reference's PoseNet (models/pose_models.py:88-147: seven weight-standardised stride-2 convolutions + GroupNorm(16) + ReLU,
@@ -852,6 +865,29 @@ int tcsfm_frames_from_u8(tcsfm_handle h, const tcsfm_opts *o, int format, int N,
  * is refused ("tcsfm_resize_u8: dst overlaps src"); nothing about it is honoured. */
 int tcsfm_sequence_frame_source(tcsfm_handle h, int src_h, int src_w);
 int tcsfm_resize_u8(tcsfm_handle h, const tcsfm_opts *o, int format, int N, int src_h, int src_w, const void *src, int dst_format, void *dst);
+/* Metric scale.  The poses of the three sequence calls are in the depth network's unit; the reference's sequential driver turns a
+ * window's translations into metres with the DNet ground-plane scale of the window's TARGET depth (optimizer.py:254-256;
+ * run_sequential_optimization.py:224-227: 30 * scale_factor * t).  tcsfm_sequence_scale is a sticky setting of the handle, like
+ * tcsfm_sequence_frame_format: real_cam_height > 0 switches the stage on, 0 (the default) off.  While it is on, every frame of a
+ * sequence call gets scale = real_cam_height / (exact lower median of its ground pixels' camera heights) -- tcsfm_scale_recovery_frames
+ * on the ring's own depth planes, on the call's pack stream, once per chunk of frames (two launches: k_ground, k_median_frames): behind
+ * the depth-network stage when depths == NULL, behind the chunk's copy when depths are given.  The depths never leave the device for it.
+ * The scale is PER FRAME: it does not depend on the lanes, on windows_per_call or on the ring.  It is the scale of the depths the windows
+ * START from: the reference's scale_factor_init, and -- with frozen networks and TCSFM_REFINE_POSE, which leave the depths alone -- also
+ * its scale_factor; a caller with TCSFM_REFINE_POSE_SCALE divides frame f's scale by exp(log_scale) of the pair whose depth it scaled.
+ * Everything else of the call is unchanged: pose_out, pose_init_out, log_scale_out and depth_out are the bits of the call with the
+ * stage off.  The prototypes of the sequence calls stay as they are: the results are fetched afterwards.
+ *   tcsfm_sequence_scale   refuses a negative, NaN or infinite height (TCSFM_E_ARG, the setting is unchanged).  A NULL handle: TCSFM_E_ARG.
+ *   A sequence call with the stage on is refused (TCSFM_E_ARG, tcsfm_last_error says why) with opts.depth_is_disp -- the stage needs
+ *   depths -- and with H < 5 or W < 5.
+ *   tcsfm_sequence_scales  results of the LAST sequence call that ran with the stage on: HOST arrays of T entries by frame index
+ *                          (scale_out float [T]; median_out float [T] or NULL; count_out int32 [T] or NULL: ground pixels; a frame
+ *                          without any has NaN scale and median).  The handle keeps them until the next sequence call; a call that
+ *                          fails, or runs with the stage off, leaves none.  T must be that call's T: otherwise, or with nothing kept,
+ *                          TCSFM_E_ARG.  Window w's factor is depth unit (30) * scale[w + tp], tp the target's position as above. */
+int tcsfm_sequence_scale(tcsfm_handle h, float real_cam_height);
+int tcsfm_sequence_scales(tcsfm_handle h, int T, void *scale_out /* float [T] */, void *median_out /* float [T] or NULL */,
+        int *count_out /* [T] or NULL */);
 int tcsfm_lane_wait(tcsfm_handle h, int lane);
 int tcsfm_lane_synchronize(tcsfm_handle h, int lane);
 int tcsfm_lane_event(tcsfm_handle h, int lane, void **event_out);

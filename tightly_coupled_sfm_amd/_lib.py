@@ -192,6 +192,9 @@ _SIGNATURES = {
     "tcsfm_frames_from_u8": (C.c_int, [_P, C.POINTER(Opts), C.c_int, C.c_int, _P, _P]),
     "tcsfm_sequence_frame_source": (C.c_int, [_P, C.c_int, C.c_int]),
     "tcsfm_resize_u8": (C.c_int, [_P, C.POINTER(Opts), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "tcsfm_scale_recovery_frames": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, C.c_float, _P, _P, _P]),
+    "tcsfm_sequence_scale": (C.c_int, [_P, C.c_float]),
+    "tcsfm_sequence_scales": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "tcsfm_lane_wait": (C.c_int, [_P, C.c_int]),
     "tcsfm_lane_synchronize": (C.c_int, [_P, C.c_int]),
     "tcsfm_lane_event": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),

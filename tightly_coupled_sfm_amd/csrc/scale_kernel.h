@@ -16,6 +16,7 @@ struct GroundParams {
     unsigned *keys;       // [N][H*W] float bits of the height where masked, 0xFFFFFFFF elsewhere
     int H, W;
     int *err;             // host-mapped status word: set to 1 when an image's intrinsics are not pinhole (or null)
+    int k_stride = 9;     // floats between the intrinsics of consecutive images; 0: one K for all of them (the sequence calls' scale stage)
 };
 
 __device__ __forceinline__ void bp(const float *depth, int W, float ifx, float icx, float ify, float icy, int v, int u, float *p) {
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(256) void k_ground(GroundParams P) {
     const int n = blockIdx.y, hw = P.H * P.W, H = P.H, W = P.W;
     if (idx >= hw) return;
     int v = idx / W, u = idx - v * W;
-    const float *K = P.K + n * 9, *depth = P.depth + (size_t)n * hw;
+    const float *K = P.K + n * P.k_stride, *depth = P.depth + (size_t)n * hw;
     if (K[1] != 0.f || K[3] != 0.f || K[6] != 0.f || K[7] != 0.f || K[8] != 1.f || K[0] == 0.f || K[4] == 0.f) {
         // device-side guard of the pinhole contract (the host validates a given device buffer only once): no ground anywhere ->
         // the median and the scale come out NaN, and the status word turns the next call / synchronize into TCSFM_E_INTRINSICS

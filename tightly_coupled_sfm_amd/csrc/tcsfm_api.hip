@@ -17,6 +17,7 @@
 #include "joint_kernel.h"
 #include "dense_ref_kernel.h"
 #include "scale_kernel.h"
+#include "frame_scale_kernel.h"
 #include "posenet_kernel.h"
 #include "depthnet_kernel.h"
 #include "depthnet_grad_kernel.h"
@@ -179,6 +180,14 @@ struct tcsfm_ctx {
     size_t seq_u8_bytes = 0;           // 3 src_h src_w -- bytes, no mirror slots); k_frames_u8 / k_resize_u8 turns a chunk into the floats of seq_img on seq_pack
     int seq_src_h = 0, seq_src_w = 0;  // tcsfm_sequence_frame_source: the camera's frame size (0, 0: none -- frames arrive at H x W)
     std::vector<ResizeTable> resize_tabs;      // coefficient tables of the source sizes seen so far, on the device (resize_table())
+    // tcsfm_sequence_scale: the sequence calls' per-frame scale stage (k_ground + k_median_frames on seq_pack, once per chunk)
+    float seq_cam_height = 0.f;        // > 0: the stage is on
+    unsigned *seq_scale_keys = nullptr;  // key planes of ONE chunk (not scale_keys: the operators on the handle's stream own that)
+    size_t seq_scale_keys_frames = 0;
+    float *seq_scale_dev = nullptr;    // results by ABSOLUTE frame index: [cap] scales | [cap] medians | [cap] counts (int32)
+    size_t seq_scale_cap = 0;
+    std::vector<float> seq_scale_res;  // the last call's results on the host, same layout with cap = seq_scale_T (counts as bit patterns)
+    int seq_scale_T = 0;               // 0: nothing kept
     struct KOk { const float *p; int n; };
     KOk K_ok[4] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}};   // device intrinsics pointers (and counts) that already passed the pinhole check
     int K_ok_next = 0;
@@ -1429,7 +1438,8 @@ void tcsfm_destroy(tcsfm_handle h) {
     void *ptrs[] = {h->stamp_buf, h->tgtpack, h->srcpack, h->depth_work, h->partials, h->blockrec, h->tickets, h->state, h->pconst, h->lin_out,
                     h->jrec, h->jrec_acc, h->jblockrec, h->jdepth_acc, h->jstate, h->jdelta, h->jpart, h->jtick, h->dref_norms, h->dref_ext, h->dref_export, h->qres_rho, h->qres_rec, h->pose_lin, h->dref_smooth, h->jrec_src, h->jstate_src, h->jdelta_src, h->dref_ext_src, h->qres_rho_src, h->qres_rec_src,
                     h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept, h->dbg_stamps, h->wgrad_rec, h->wgrad_fix, h->wgrad_gmax, h->pgrad_fwd, h->pgrad_cot,
-                    h->seq_fpack, h->seq_fdepth, h->pair_idx, h->seq_img, h->seq_depth, h->seq_pose_in, h->seq_pose_out, h->seq_ls_out, h->seq_K, h->seq_dense, h->seq_dense_tmp, h->seq_u8};
+                    h->seq_fpack, h->seq_fdepth, h->pair_idx, h->seq_img, h->seq_depth, h->seq_pose_in, h->seq_pose_out, h->seq_ls_out, h->seq_K, h->seq_dense, h->seq_dense_tmp, h->seq_u8,
+                    h->seq_scale_keys, h->seq_scale_dev};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &t : h->resize_tabs)
@@ -2144,6 +2154,48 @@ int tcsfm_scale_recovery(tcsfm_handle h, const tcsfm_opts *o, int N, const float
     }
     HIPCHK(h, hipGetLastError());
     return st.finish();
+}
+
+// k_ground + k_median_frames over `n` depth planes on `stream`: two launches, one workgroup of the second per plane.
+// TCSFM_MEDIAN_LDS_KEYS (measurement and test hook, read at every call): the masked keys a workgroup keeps in LDS after its first
+// pass, 0 .. kMedianLdsKeys (the default); a frame with more reads its plane in every round.  The results do not depend on it.
+static void launch_frame_scales(tcsfm_ctx *h, hipStream_t stream, int n, const float *depth, const float *K, int k_stride, unsigned *keys,
+                                float real_cam_height, float *scale, float *median, int *count) {
+    const size_t hw = (size_t)h->H * h->W;
+    GroundParams G;
+    G.depth = depth; G.K = K; G.height = nullptr; G.mask = nullptr; G.keys = keys; G.H = h->H; G.W = h->W; G.err = h->err_dev; G.k_stride = k_stride;
+    hipLaunchKernelGGL(k_ground, dim3((unsigned)((hw + 255) / 256), n), dim3(256), 0, stream, G);
+    const char *lds_env = getenv("TCSFM_MEDIAN_LDS_KEYS");
+    const int lds_keys = lds_env ? atoi(lds_env) : kMedianLdsKeys;
+    hipLaunchKernelGGL(k_median_frames, dim3(n), dim3(kMedianThreads), 0, stream, (const unsigned *)keys, (int)hw, lds_keys, real_cam_height, scale, median, count);
+}
+
+int tcsfm_scale_recovery_frames(tcsfm_handle h, const tcsfm_opts *o, int N, const void *depth, const void *K, float real_cam_height,
+                                void *scale_out, void *median_out, int *count_out) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    int rc = check_common(h, o, N);
+    if (rc) return rc;
+    if (!depth || !K || !scale_out) return fail(h, TCSFM_E_ARG, "tcsfm_scale_recovery_frames: NULL argument");
+    if (h->H < 5 || h->W < 5) return fail(h, TCSFM_E_ARG, "tcsfm_scale_recovery_frames: image too small");
+    if (o->host_ptrs != 0)
+        return fail(h, TCSFM_E_ARG, "tcsfm_scale_recovery_frames: host_ptrs must be 0 (device pointers); a host caller has the sequence calls (tcsfm_sequence_scale)");
+    const size_t hw = (size_t)h->H * h->W;
+    ArgRanges a;
+    a.in("depth", depth, (size_t)N * hw * sizeof(float)); a.in("K", K, (size_t)N * 9 * sizeof(float));
+    a.out("scale_out", scale_out, (size_t)N * sizeof(float)); a.out("median_out", median_out, (size_t)N * sizeof(float));
+    a.out("count_out", count_out, (size_t)N * sizeof(int));
+    if ((rc = check_overlap(h, "tcsfm_scale_recovery_frames", a))) return rc;
+    DeviceGuard dev_guard(h->device);
+    if ((rc = pending_error(h))) return rc;
+    if ((rc = check_intrinsics(h, o, (const float *)K, N))) return rc;
+    if (!h->scale_keys) {
+        HIPCHK(h, hipMalloc((void **)&h->scale_keys, (size_t)h->max_pairs * hw * sizeof(unsigned)));
+        HIPCHK(h, hipMalloc((void **)&h->scale_hist, 260 * sizeof(unsigned)));
+    }
+    launch_frame_scales(h, h->stream, N, (const float *)depth, (const float *)K, 9, h->scale_keys, real_cam_height, (float *)scale_out,
+                        (float *)median_out, count_out);
+    HIPCHK(h, hipGetLastError());
+    return TCSFM_OK;
 }
 
 int tcsfm_smooth_loss(tcsfm_handle h, const tcsfm_opts *o, int N, const float *disp, const float *img, double *loss_out) {
@@ -2918,6 +2970,7 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
                          float *log_scale_out, int ring, int windows_per_call, int target_pos, const char *entry, float *dense_depth_out = nullptr) {
     if (int rc_q = drain_queued(h)) return rc_q;
     if (!h) return TCSFM_E_ARG;
+    h->seq_scale_T = 0;                                    // tcsfm_sequence_scales: only a call that succeeds with the stage on leaves results
     if (!o_in) return fail(h, TCSFM_E_ARG, "opts is NULL");
     const int N = 2 * S, L = h->lanes_serial ? 1 : (int)h->lanes.size() + 1;
     if (S < 1 || T <= S || N > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: need S >= 1, T > S and 2*S <= max_pairs");
@@ -2935,6 +2988,12 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     if (gen && o_in->depth_is_disp)
         return fail(h, TCSFM_E_ARG, (std::string(entry) + ": depths == NULL (the attached depth network produces depths) cannot go with opts.depth_is_disp").c_str());
     if (gen && !(o_in->min_depth > 0 && o_in->max_depth > o_in->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
+    // tcsfm_sequence_scale: every frame's DNet scale from the ring's depth plane, on the pack stream
+    const bool scale_on = h->seq_cam_height > 0.f;
+    if (scale_on && o_in->depth_is_disp)
+        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": the scale stage (tcsfm_sequence_scale) needs depths, not disparities (opts.depth_is_disp)").c_str());
+    if (scale_on && (h->H < 5 || h->W < 5))
+        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": the scale stage (tcsfm_sequence_scale): image too small").c_str());
     if (windows_per_call < 0) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: windows_per_call < 0");
     if (target_pos < -1 || target_pos > S || S > TC_MAX_SRC_OFF) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: target_pos must be -1 or 0..S, S at most 8");
     {   // The overlap contract (include/tcsfm.h).  Host arrays that are streamed: frames and depths are still going up while results come
@@ -3039,6 +3098,18 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
         HIPCHK(h, hipMalloc(&h->seq_K, (size_t)WB * 9 * sizeof(float)));
         h->seq_K_n = WB;
     }
+    if (scale_on && h->seq_scale_keys_frames < (size_t)C) {      // key planes of one chunk; results of every frame of the sequence
+        if (h->seq_scale_keys) HIPCHK(h, hipFree(h->seq_scale_keys));
+        h->seq_scale_keys = nullptr; h->seq_scale_keys_frames = 0;
+        HIPCHK(h, hipMalloc((void **)&h->seq_scale_keys, (size_t)C * hw * sizeof(unsigned)));
+        h->seq_scale_keys_frames = (size_t)C;
+    }
+    if (scale_on && h->seq_scale_cap < (size_t)T) {
+        if (h->seq_scale_dev) HIPCHK(h, hipFree(h->seq_scale_dev));
+        h->seq_scale_dev = nullptr; h->seq_scale_cap = 0;
+        HIPCHK(h, hipMalloc((void **)&h->seq_scale_dev, (size_t)3 * T * sizeof(float)));
+        h->seq_scale_cap = (size_t)T;
+    }
     if (!h->seq_copy) {   // high priority: a hardware queue outside the pool the normal-priority streams share (a copy stream that lands in
         int lo = 0, hi = 0;   // a lane's queue parks its slot-recycling waits in front of that lane's kernels), and copies go first anyway
         HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
@@ -3047,7 +3118,7 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     const size_t n_done = (size_t)2 * R + 2;               // a call's event is re-recorded long after its slots were recycled
     const size_t ND = n_done - 1;
     while (h->seq_copied.size() < (size_t)R) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_copied.push_back(e); }
-    const bool staged = use_cache || gen || u8;            // the chunk has a producer stage on seq_pack: k_frames_u8, the depth network and / or k_frame_pack
+    const bool staged = use_cache || gen || u8 || scale_on;      // the chunk has a stage on seq_pack: k_frames_u8, the depth network, the scale stage and / or k_frame_pack
     while (staged && h->seq_raw.size() < (size_t)R) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_raw.push_back(e); }
     if (staged && !h->seq_pack) HIPCHK(h, hipStreamCreateWithFlags(&h->seq_pack, hipStreamNonBlocking));
     while (h->seq_done.size() < n_done) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_done.push_back(e); }
@@ -3153,6 +3224,18 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
                 if (nm > 0 && (!use_cache || pn))
                     HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)(R + slot) * hw, h->seq_depth + (size_t)slot * hw, (size_t)nm * hw * sizeof(float), hipMemcpyDeviceToDevice, h->seq_pack));
             }
+            if (scale_on) {
+                // Scales of the frames that just landed: k_ground + k_median_frames, two launches per chunk, behind the depth stage in
+                // stream order -- or, with depths given, behind the chunk's copy (seq_raw).  The stage READS seq_depth[slot .. slot + nf)
+                // only (never a mirror slot) and WRITES its own key planes (one chunk's; the next chunk's stage follows on this stream)
+                // and the results, which are indexed by the ABSOLUTE frame: nothing about them is recycled.  It precedes this chunk's
+                // seq_copied record, so the recycling argument above covers it as it stands: the next copy into these slots waits for
+                // the calls that read this chunk, and those waited for seq_copied -- hence for these reads.
+                float *res = h->seq_scale_dev;
+                const size_t cap = h->seq_scale_cap;
+                launch_frame_scales(h, h->seq_pack, nf, h->seq_depth + (size_t)slot * hw, h->seq_K, 0, h->seq_scale_keys, h->seq_cam_height,
+                                    res + nxt, res + cap + nxt, (int *)(res + 2 * cap) + nxt);
+            }
             if (use_cache) {      // pack the frames that just landed (and their mirrors), once
                 FramePackParams Fp;
                 Fp.H = h->H; Fp.W = h->W; Fp.depth_is_disp = o.depth_is_disp;
@@ -3223,6 +3306,12 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     if ((rc = fetch(pose_out, h->seq_pose_out, 6))) return rc;
     if (pose_init_out && (rc = fetch(pose_init_out, h->seq_pose_in, 6))) return rc;
     if (log_scale_out && np == 7 && !dense && (rc = fetch(log_scale_out, h->seq_ls_out, 1))) return rc;
+    if (scale_on) {       // the frames' scales: one copy, after the pack stream's final synchronisation above; kept for tcsfm_sequence_scales
+        h->seq_scale_res.resize((size_t)3 * T);
+        for (int a_ = 0; a_ < 3; a_++)
+            HIPCHK(h, hipMemcpy(h->seq_scale_res.data() + (size_t)a_ * T, h->seq_scale_dev + (size_t)a_ * h->seq_scale_cap, (size_t)T * sizeof(float), hipMemcpyDeviceToHost));
+        h->seq_scale_T = T;
+    }
     return TCSFM_OK;
 }
 
@@ -3250,6 +3339,27 @@ int tcsfm_sequence_frame_format(tcsfm_handle h, int format) {
     if (format != TCSFM_FRAMES_F32_CHW && format != TCSFM_FRAMES_U8_CHW && format != TCSFM_FRAMES_U8_HWC)
         return fail(h, TCSFM_E_ARG, "tcsfm_sequence_frame_format: format must be TCSFM_FRAMES_F32_CHW, TCSFM_FRAMES_U8_CHW or TCSFM_FRAMES_U8_HWC");
     h->seq_fmt = format;
+    return TCSFM_OK;
+}
+
+int tcsfm_sequence_scale(tcsfm_handle h, float real_cam_height) {
+    if (!h) return TCSFM_E_ARG;
+    if (!(real_cam_height >= 0.f) || std::isinf(real_cam_height))
+        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_scale: real_cam_height must be finite and > 0 (stage on) or 0 (off)");
+    h->seq_cam_height = real_cam_height;
+    return TCSFM_OK;
+}
+
+int tcsfm_sequence_scales(tcsfm_handle h, int T, void *scale_out, void *median_out, int *count_out) {
+    if (!h) return TCSFM_E_ARG;
+    if (!scale_out) return fail(h, TCSFM_E_ARG, "tcsfm_sequence_scales: NULL argument");
+    if (h->seq_scale_T == 0)
+        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_scales: nothing kept (the last sequence call failed or ran with the stage off: tcsfm_sequence_scale)");
+    if (T != h->seq_scale_T) return fail(h, TCSFM_E_ARG, "tcsfm_sequence_scales: T differs from the T of the last sequence call");
+    const float *r = h->seq_scale_res.data();
+    memcpy(scale_out, r, (size_t)T * sizeof(float));
+    if (median_out) memcpy(median_out, r + T, (size_t)T * sizeof(float));
+    if (count_out) memcpy(count_out, r + 2 * (size_t)T, (size_t)T * sizeof(int));
     return TCSFM_OK;
 }
 

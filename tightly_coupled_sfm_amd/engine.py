@@ -19,6 +19,19 @@ from . import _lib
 from ._lib import Opts, default_opts  # noqa: F401
 
 
+def check_cam_height(cam_height) -> Optional[float]:
+    """the `cam_height` keyword of the sequence methods (tcsfm_sequence_scale): None (the stage stays off) or a positive finite number,
+    checked before anything touches the GPU -> float or None"""
+    if cam_height is None:
+        return None
+    if isinstance(cam_height, bool) or not isinstance(cam_height, (int, float, np.integer, np.floating)):
+        raise TypeError(f"cam_height must be a number or None (got {type(cam_height).__name__})")
+    v = float(cam_height)
+    if not (v > 0.0 and np.isfinite(v)):
+        raise ValueError(f"cam_height must be positive and finite (got {v})")
+    return v
+
+
 def _chk(t: torch.Tensor, shape, name: str) -> torch.Tensor:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
@@ -831,6 +844,23 @@ class Engine:
                                                  int(pad_to_batch), self._p(scale), self._p(med), self._p(hm), self._p(mm)))
         return (scale, med, hm, mm) if maps else scale
 
+    def scale_recovery_frames(self, depth, intrinsics, real_cam_height: float):
+        """tcsfm_scale_recovery_frames: depth [N,1,H,W], K [N,3,3] or [3,3] (one camera for all) -> (scale [N], median [N], count [N]
+        int32) as CUDA tensors: item n's scale and median are the bits of scale_recovery(depth[n:n+1], K[n:n+1], h), count its ground
+        pixels; two launches whatever N, on the engine's stream"""
+        self._bind()
+        N = depth.shape[0]
+        depth = _chk(depth, (N, 1, self.H, self.W), "depth")
+        if isinstance(intrinsics, torch.Tensor) and tuple(intrinsics.shape) == (3, 3):
+            intrinsics = intrinsics[None].expand(N, 3, 3).contiguous()
+        K = _chk(intrinsics, (N, 3, 3), "intrinsics")
+        scale = torch.empty(N, device=depth.device, dtype=torch.float32); med = torch.empty_like(scale)
+        count = torch.empty(N, device=depth.device, dtype=torch.int32)
+        o = default_opts()
+        self._call(self.lib.tcsfm_scale_recovery_frames(self._h, C.byref(o), N, self._p(depth), self._p(K), float(real_cam_height),
+                                                        self._p(scale), self._p(med), self._p(count)))
+        return scale, med, count
+
     # -- lanes: several refinements in flight (include/tcsfm.h "lanes") -----------------------------------------
     def set_lanes(self, n: int):
         _lib.warn_if_queues_late(int(n))
@@ -967,6 +997,30 @@ class Engine:
         finally:
             self.lib.tcsfm_sequence_frame_source(self._h, 0, 0)
 
+    @contextlib.contextmanager
+    def _cam_height(self, cam_height, T):
+        """the scale stage (tcsfm_sequence_scale) is on, at this camera height, for the one call inside the block, and off again afterwards"""
+        self._seq_scale_T = 0
+        if cam_height is None:
+            yield
+            return
+        self._call(self.lib.tcsfm_sequence_scale(self._h, float(cam_height)))
+        try:
+            yield
+            self._seq_scale_T = int(T)
+        finally:
+            self.lib.tcsfm_sequence_scale(self._h, 0.0)
+
+    def sequence_scales(self, T: Optional[int] = None):
+        """tcsfm_sequence_scales: the per-frame scales of the last sequence call that ran with cam_height= -> dict(scale [T] float32,
+        median [T] float32, count [T] int32) of CPU tensors, by frame index; a frame without ground pixels has NaN scale and median.
+        Window w's metric factor is depth_unit * scale[w + tp] (streaming.metric_poses).  Raises when that call kept nothing."""
+        T = int(getattr(self, "_seq_scale_T", 0) if T is None else T)
+        scale = torch.empty(max(T, 1), dtype=torch.float32); med = torch.empty_like(scale); count = torch.empty(max(T, 1), dtype=torch.int32)
+        hp = lambda t: C.c_void_p(t.data_ptr())
+        self._call(self.lib.tcsfm_sequence_scales(self._h, T, hp(scale), hp(med), hp(count)))
+        return dict(scale=scale[:T], median=med[:T], count=count[:T])
+
     def resize_u8(self, frames_u8: torch.Tensor, source_layout: str = "hwc", out: str = "f32") -> torch.Tensor:
         """tcsfm_resize_u8: uint8 CUDA frames at the camera's size, [N,h,w,3] (source_layout "hwc") or [N,3,h,w] ("chw"), -> the engine's
         H x W with the bytes of Pillow's Image.resize((W, H), Image.LANCZOS): out="u8" in the source's layout, out="f32" as float32
@@ -1022,7 +1076,7 @@ class Engine:
         return out
 
     def refine_sequence(self, frames: torch.Tensor, depths: Optional[torch.Tensor], K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
-                        ring: int = 0, log_scale: bool = False, windows_per_call: int = 0, target_pos: int = 0, source_size=None):
+                        ring: int = 0, log_scale: bool = False, windows_per_call: int = 0, target_pos: int = 0, source_size=None, cam_height=None):
         """tcsfm_refine_sequence: the whole window loop of a sequence inside the library (frames [T,3,H,W] float32 -- or the camera's
         bytes, uint8 [T,3,H,W] / [T,H,W,3], converted to u8 / 255 on the device -- / depths [T,1,H,W] CPU
         tensors -- pinned for asynchronous copies --, K [3,3], init_poses [T-S, 2S, 6]) -> refined poses [T-S, 2S, 6] (CPU tensor;
@@ -1031,7 +1085,10 @@ class Engine:
         the reference's loaders choose it), its sources the others in order.  depths=None: the depth network of attach_depthnet
         computes them inside the call.  source_size=(h, w): `frames` are the camera's bytes at ITS size, uint8 [T,h,w,3] or [T,3,h,w]; the
         library resizes them to H x W on the device with Pillow's Lanczos bytes (tcsfm_sequence_frame_source); K is the H x W frames'
-        (Engine.scale_intrinsics)"""
+        (Engine.scale_intrinsics).  cam_height=h (metres / depth unit; None: off): every frame's DNet ground-plane scale is computed from
+        the ring's own depth plane inside the call (tcsfm_sequence_scale); fetch them with Engine.sequence_scales().  The return values
+        are unchanged."""
+        cam_height = check_cam_height(cam_height)
         T, S = int(frames.shape[0]), int(sources)
         depths = self._seq_depths(depths, T)
         frames, fmt = self._seq_frames(frames, T, source_size)
@@ -1043,19 +1100,20 @@ class Engine:
         out = torch.empty_like(p0)
         ls = torch.zeros((T - S, 2 * S), dtype=torch.float32) if log_scale else None
         hp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with self._frame_format(fmt), self._frame_source(source_size):
+        with self._frame_format(fmt), self._frame_source(source_size), self._cam_height(cam_height, T):
             self._call(self.lib.tcsfm_refine_sequence(self._h, C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(p0), hp(out), hp(ls), int(ring),
                                                       int(windows_per_call), int(target_pos)))
         return (out, ls) if log_scale else out
 
     def refine_dense_sequence(self, frames: torch.Tensor, depths: Optional[torch.Tensor], K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
                               ring: int = 0, windows_per_call: int = 0, target_pos: int = 0, out_depths: Optional[torch.Tensor] = None,
-                              source_size=None):
+                              source_size=None, cam_height=None):
         """tcsfm_refine_dense_sequence: the dense mode (pose + per-pixel inverse depth) over a sequence, arguments as refine_sequence
         -> (poses [T-S, 2S, 6], refined depth maps [T-S, 2S, 1, H, W]) as CPU tensors.
         out_depths: a caller-owned (pinned) CPU tensor of that shape to receive the depth maps; a caller that runs sequence after
         sequence should pass one -- pinning a fresh 70 MB result buffer costs ten times the refinement of a 120-frame sequence.
-        source_size=(h, w): camera-size bytes, as for refine_sequence."""
+        source_size=(h, w): camera-size bytes, as for refine_sequence.  cam_height: per-frame scales, as for refine_sequence."""
+        cam_height = check_cam_height(cam_height)
         T, S = int(frames.shape[0]), int(sources)
         depths = self._seq_depths(depths, T)
         frames, fmt = self._seq_frames(frames, T, source_size)
@@ -1071,7 +1129,7 @@ class Engine:
             if dout.is_cuda or dout.dtype != torch.float32 or not dout.is_contiguous() or tuple(dout.shape) != (T - S, 2 * S, 1, self.H, self.W):
                 raise TypeError("out_depths must be a contiguous float32 CPU tensor [T-S, 2S, 1, H, W]")
         hp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with self._frame_format(fmt), self._frame_source(source_size):
+        with self._frame_format(fmt), self._frame_source(source_size), self._cam_height(cam_height, T):
             self._call(self.lib.tcsfm_refine_dense_sequence(self._h, C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(p0), hp(out), hp(dout), int(ring),
                                                             int(windows_per_call), int(target_pos)))
         return out, dout

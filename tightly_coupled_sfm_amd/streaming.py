@@ -17,7 +17,27 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from .engine import Engine, Opts, default_opts
+from .engine import Engine, Opts, check_cam_height, default_opts
+
+
+def metric_poses(poses, scale, sources: int, target_pos: int = 0, depth_unit: float = 30.0):
+    """The sequence calls' poses in metres (run_sequential_optimization.py:224-227: 30 * scale_factor * t): poses [T-S, 2S, 6]
+    (translation first), scale [T] per frame (Engine.sequence_scales()['scale']); the translation of every pair of window w is
+    multiplied by depth_unit * scale[w + tp], the scale of the window's TARGET frame -- tp = target_pos as in include/tcsfm.h
+    (-1: the middle frame, (S+1)//2).  Host arithmetic in float32; returns a new array of the input's kind (torch or NumPy)."""
+    S = int(sources)
+    if target_pos < -1 or target_pos > S:
+        raise ValueError("target_pos must be -1 or 0..S")
+    tp = (S + 1) // 2 if target_pos < 0 else int(target_pos)
+    is_torch = isinstance(poses, torch.Tensor)
+    p = (poses.detach().cpu().numpy() if is_torch else np.asarray(poses)).astype(np.float32, copy=True)
+    sc = (scale.detach().cpu().numpy() if isinstance(scale, torch.Tensor) else np.asarray(scale)).astype(np.float32)
+    nwin = p.shape[0]
+    if p.ndim != 3 or p.shape[1:] != (2 * S, 6) or sc.shape != (nwin + S,):
+        raise ValueError(f"poses must be [T-S, {2 * S}, 6] and scale [T] (got {list(p.shape)} and {list(sc.shape)})")
+    factor = np.float32(depth_unit) * sc[tp:tp + nwin]
+    p[:, :, :3] *= factor[:, None, None]
+    return torch.from_numpy(p) if is_torch else p
 
 
 class SequenceRefiner:
@@ -58,19 +78,22 @@ class SequenceRefiner:
             self.ring_depth[slot].copy_(depth, non_blocking=True)
             self.copied[slot].record(self.copy_stream)
 
-    def run_native(self, frames, depths, K, init_poses, ring: int = 0, source_size=None) -> torch.Tensor:
+    def run_native(self, frames, depths, K, init_poses, ring: int = 0, source_size=None, cam_height=None) -> torch.Tensor:
         """The same loop inside the library (tcsfm_refine_sequence: four-frame copies, events and lanes driven from C++) -> refined
         poses [T-S, 2*S, 6] as a CPU tensor; bit-identical to run().  depths=None: the depth network attached to the engine
         (self.eng.attach_depthnet) computes them inside the call.  frames: float32 [T,3,H,W], or the camera's bytes -- uint8 [T,3,H,W] or
         [T,H,W,3] -- which the library converts on the device (Engine.refine_sequence); with source_size=(h, w) the
-        bytes are at the camera's size, [T,h,w,3] or [T,3,h,w], and the library resizes them too"""
+        bytes are at the camera's size, [T,h,w,3] or [T,3,h,w], and the library resizes them too.  cam_height=h: the frames' DNet scales
+        are computed inside the call (self.eng.sequence_scales(); metric_poses applies them)"""
+        cam_height = check_cam_height(cam_height)
         pin = lambda a: a if (isinstance(a, torch.Tensor) and not a.is_cuda) else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32)
         if isinstance(frames, torch.Tensor) and frames.is_cuda:
             raise TypeError("frames must be a CPU tensor (the library stages the sequence itself)")
         if isinstance(frames, np.ndarray) and frames.dtype == np.uint8:
             frames = torch.from_numpy(np.ascontiguousarray(frames))
         return self.eng.refine_sequence(pin(frames), None if depths is None else pin(depths), K, init_poses, self.opts, sources=self.S, ring=ring,
-                                        **({} if source_size is None else {"source_size": source_size}))
+                                        **({} if source_size is None else {"source_size": source_size}),
+                                        **({} if cam_height is None else {"cam_height": cam_height}))
 
     def run(self, frames, depths, K, init_poses) -> torch.Tensor:
         """-> refined poses [T-S, 2*S, 6] (GPU tensor, complete on return)"""
