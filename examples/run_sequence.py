@@ -86,7 +86,8 @@ def frames_only(args):
     t0 = time.perf_counter()
     init, refined = pose_net.odometry_sequence(frames, None, K, opts, sources=S, iterations=4, target_pos=-1,
                                                **({} if source_size is None else {"source_size": source_size}),
-                                               **({} if args.cam_height is None else {"cam_height": args.cam_height / DEPTH_UNIT}))
+                                               **({} if args.cam_height is None else {"cam_height": args.cam_height / DEPTH_UNIT}),
+                                               **({"disparity": "post"} if args.save_disps else {}))
     dt = time.perf_counter() - t0
     print(f"{args.frames} frames -> {refined.shape[0]} windows of {2 * S} directed pairs in {dt * 1e3:.1f} ms (first call: allocations included)")
     with np.printoptions(precision=4, suppress=True):
@@ -99,6 +100,11 @@ def frames_only(args):
             metric = metric_poses(refined, sc["scale"], S, target_pos=-1, depth_unit=DEPTH_UNIT)
             print(f"per-frame scales (ground pixels {sc['count'].tolist()[:6]} ...):\n", sc["scale"].numpy()[:6], "...")
             print("refined poses of window 0, translations in metres:\n", metric[0].numpy())
+    if args.save_disps:     # the structure: every frame's flip-post-processed disparity (helpers.get_disp_for_eigen), kept on the device inside
+        # the call and fetched once -- float64 [T,H,W], np.concatenate of the driver's pred_disps: what evaluate_depth_eigen.py loads
+        disps = eng.sequence_disparities()
+        np.save(args.save_disps, disps)
+        print(f"disparities: float64 {list(disps.shape)}, {disps.min():.4f} .. {disps.max():.4f} -> {args.save_disps}")
 
 
 DEPTH_UNIT = 30.0       # the reference's depth unit in metres (run_sequential_optimization.py:224)
@@ -118,6 +124,9 @@ def main():
     ap.add_argument("--cam-height", type=float, default=None, metavar="METRES",
                     help="with --frames-only: the camera's height above the ground (KITTI: 1.65); every frame's DNet scale is computed inside "
                          "the call (cam_height=: tcsfm_sequence_scale) and the translations are printed in metres (streaming.metric_poses)")
+    ap.add_argument("--save-disps", metavar="FILE", default="",
+                    help="with --frames-only: keep every frame's flip-post-processed disparity inside the call (disparity=\"post\": "
+                         "tcsfm_sequence_disparity) and write them as the .npy file paper_plots_and_data/evaluate_depth_eigen.py loads")
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--sources", type=int, default=1, choices=(1, 2))
     ap.add_argument("--gn-iters", type=int, default=8)
@@ -129,6 +138,8 @@ def main():
         return frames_only(args)
     if args.cam_height is not None:
         ap.error("--cam-height goes with --frames-only (the per-window loop below gets its scale from DepthOptimizer)")
+    if args.save_disps:
+        ap.error("--save-disps goes with --frames-only (the per-window loop below has helpers.get_disp_for_eigen)")
     if args.camera_size:
         ap.error("--camera-size goes with --frames-only (for frames held on the device: Engine.resize_u8)")
     if args.u8_frames:

@@ -179,7 +179,9 @@ enum { TCSFM_STAT_COST = 0, TCSFM_STAT_COST_PHOTO = 1, TCSFM_STAT_NMASK = 2, TCS
  * dst overlapping src in any way is refused with "tcsfm_frames_from_u8: dst overlaps src"; nothing about it is honoured.  While a U8
  * format is set (tcsfm_sequence_frame_format) the `frames` range of a sequence call is T*3*H*W bytes, not floats -- T*3*src_h*src_w
  * bytes with a frame source set (tcsfm_sequence_frame_source).  tcsfm_resize_u8 is declared and behaves like tcsfm_frames_from_u8:
- * "tcsfm_resize_u8: dst overlaps src". */
+ * "tcsfm_resize_u8: dst overlaps src".  tcsfm_disp_post_process and tcsfm_depthnet_disp_for_eigen are declared the same way (float32 in,
+ * float64 out) and honour nothing either: "tcsfm_disp_post_process: out overlaps l_disp" (or r_disp_mirrored),
+ * "tcsfm_depthnet_disp_for_eigen: out overlaps imgs". */
 
 /* ---- lifetime ------------------------------------------------------------------------------- */
 
@@ -888,6 +890,53 @@ int tcsfm_resize_u8(tcsfm_handle h, const tcsfm_opts *o, int format, int N, int 
 int tcsfm_sequence_scale(tcsfm_handle h, float real_cam_height);
 int tcsfm_sequence_scales(tcsfm_handle h, int T, void *scale_out /* float [T] */, void *median_out /* float [T] or NULL */,
         int *count_out /* [T] or NULL */);
+/* Structure.  The reference's sequential driver also keeps every window's disparity (run_sequential_optimization.py:215-220, 257-267:
+ * optimized_results['disp_opt'], the input of paper_plots_and_data/evaluate_depth_eigen.py) -- helpers.get_disp_for_eigen
+ * (optimization_experiments/helpers.py:35-49): the network on the frame and on its mirror image, disp_to_depth's scaled_disp of both,
+ * the second un-flipped, the two blended by batch_post_process_disparity (utils/learning_helpers.py:115-123).  tcsfm_sequence_disparity
+ * is a sticky setting of the handle, like tcsfm_sequence_scale; TCSFM_SEQ_DISP_OFF is the default.  While a mode is on, each of the three
+ * sequence calls, run with depths == NULL and a network attached (tcsfm_sequence_depthnet), keeps every frame's disparity in a device
+ * store of the handle, indexed by the frame number (T*H*W floats or doubles, grown when a call needs more, freed with the handle):
+ *   TCSFM_SEQ_DISP_PLAIN  the depth stage's head stores the scaled disparity next to the depth: one more store, no more launches.  The
+ *                         bits of tcsfm_depthnet_forward with flip = 0 followed by tcsfm_disp_to_depth's scaled_disp.
+ *   TCSFM_SEQ_DISP_POST   a second pass of the network over the mirrored frame and the blend kernel follow the first pass, per group
+ *                         of the network's max_images frames, on the call's pack stream before the chunk is handed to the lanes.
+ *                         float64, the bits of tcsfm_depthnet_disp_for_eigen on the frame alone: they do not depend on the lanes, on
+ *                         windows_per_call, on the ring or on the chunking.
+ * Everything else of the call is unchanged: pose_out, pose_init_out, log_scale_out, depth_out and tcsfm_sequence_scales' results are the
+ * bits of the call with the stage off.  The prototypes of the sequence calls stay as they are: the planes are fetched afterwards.
+ *   tcsfm_sequence_disparity    an unknown mode: TCSFM_E_ARG, the setting is unchanged.  A NULL handle: TCSFM_E_ARG.
+ *   A sequence call with the stage on is refused (TCSFM_E_ARG, tcsfm_last_error says why) with depths != NULL -- the stage keeps the
+ *   network's own output --, with no network attached, and with min_depth / max_depth out of order.
+ *   tcsfm_sequence_disparities  planes first .. first + count - 1 of the LAST sequence call that ran with the stage on, copied to the
+ *                               HOST array `out` [count,H,W] -- float32 (PLAIN) or float64 (POST); *mode_out (or NULL) says which --
+ *                               synchronously.  T must be that call's T, 0 <= first, count >= 1, first + count <= T: otherwise, or
+ *                               with nothing kept, TCSFM_E_ARG.  A call that fails, or runs with the stage off, leaves nothing.
+ * The operators, for callers who hold device pointers (asynchronous, on the handle's stream; o->host_ptrs must be 0; the array
+ * parameters are declared void like tcsfm_frames_from_u8's: float32 in, float64 out, aligned for their types):
+ *   tcsfm_disp_post_process        the blend alone.  l_disp [N,H,W] float32: scaled disparity of the frames; r_disp_mirrored [N,H,W]
+ *                                  float32: of the mirrored frames, STILL mirrored (the kernel reads it reversed); out [N,H,W] float64:
+ *                                      r = r_disp_mirrored[n][y][W-1-x];  m = float32(0.5 * (l + r))
+ *                                      out = ((r_mask[x] * l + l_mask[x] * r) + ((1.0 - l_mask[x]) - r_mask[x]) * m)
+ *                                  in float64, every operation rounded on its own, r_mask[x] = l_mask[W-1-x]: NumPy's evaluation of
+ *                                  the reference's line on float32 planes, bit for bit.
+ *   tcsfm_depthnet_disp_for_eigen  get_disp_for_eigen of N >= 1 device-resident frames imgs [N,3,H,W] float32 -> out [N,H,W] float64,
+ *                                  in groups of the instance's max_images (o->min_depth, o->max_depth: disp_to_depth's); the planes of
+ *                                  one group are the instance's own scratch.  The sequence stage's code path.
+ *   out overlapping an input is refused ("overlapping arguments").
+ * tcsfm_flip_ramp (host, no GPU needed): l_mask_out [W] doubles, W >= 2 (TCSFM_E_ARG otherwise):
+ *     lin[i] = i * (1.0 / (W - 1)), lin[W-1] = 1.0 -- np.linspace(0, 1, W) --;  l_mask[i] = 1.0 - min(max(20.0 * (lin[i] - 0.05), 0.0), 1.0) */
+#define TCSFM_SEQ_DISP_OFF   0
+#define TCSFM_SEQ_DISP_PLAIN 1   /* scaled_disp of every frame, float32: disp_to_depth(net(frame))[0]              */
+#define TCSFM_SEQ_DISP_POST  2   /* get_disp_for_eigen of every frame, float64: straight + mirrored pass, blended */
+int tcsfm_sequence_disparity(tcsfm_handle h, int mode);
+int tcsfm_sequence_disparities(tcsfm_handle h, int T, int first, int count, void *out /* HOST [count,H,W], float32 (PLAIN) or float64 (POST) */,
+                               int *mode_out /* or NULL */);
+int tcsfm_disp_post_process(tcsfm_handle h, const tcsfm_opts *o, int N, const void *l_disp /* float32 [N,H,W] */,
+                            const void *r_disp_mirrored /* float32 [N,H,W] */, void *out /* float64 [N,H,W] */);
+int tcsfm_depthnet_disp_for_eigen(tcsfm_depthnet *dn, const tcsfm_opts *o, int N, const void *imgs /* float32 [N,3,H,W] */,
+                                  void *out /* float64 [N,H,W] */);
+int tcsfm_flip_ramp(int W, void *l_mask_out /* double [W] */);
 int tcsfm_lane_wait(tcsfm_handle h, int lane);
 int tcsfm_lane_synchronize(tcsfm_handle h, int lane);
 int tcsfm_lane_event(tcsfm_handle h, int lane, void **event_out);

@@ -99,6 +99,7 @@ WINDOW_PAIR, WINDOW_REFERENCE = 0, 1
 DEPTH_FULL, DEPTH_QUARTER = 0, 1
 OPTIM_ADAM, OPTIM_SGD = 0, 1
 FRAMES_F32_CHW, FRAMES_U8_CHW, FRAMES_U8_HWC = 0, 1, 2     # tcsfm_sequence_frame_format / tcsfm_frames_from_u8
+SEQ_DISP_OFF, SEQ_DISP_PLAIN, SEQ_DISP_POST = 0, 1, 2      # tcsfm_sequence_disparity
 STAT_POSE = 4
 NSTAT = 10        # cost, cost_photo, n_mask, lambda, pose[6]  (include/tcsfm.h TCSFM_STAT_*)
 
@@ -195,6 +196,11 @@ _SIGNATURES = {
     "tcsfm_scale_recovery_frames": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, C.c_float, _P, _P, _P]),
     "tcsfm_sequence_scale": (C.c_int, [_P, C.c_float]),
     "tcsfm_sequence_scales": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "tcsfm_sequence_disparity": (C.c_int, [_P, C.c_int]),
+    "tcsfm_sequence_disparities": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
+    "tcsfm_disp_post_process": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P]),
+    "tcsfm_depthnet_disp_for_eigen": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P]),
+    "tcsfm_flip_ramp": (C.c_int, [C.c_int, _P]),
     "tcsfm_lane_wait": (C.c_int, [_P, C.c_int]),
     "tcsfm_lane_synchronize": (C.c_int, [_P, C.c_int]),
     "tcsfm_lane_event": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),

@@ -58,6 +58,9 @@ struct tcsfm_depthnet {
     float *skip[5] = {};                // tcsfm_depthnet_forward's own skips, NHWC
     float *pool = nullptr, *t1 = nullptr, *t2 = nullptr, *ds = nullptr;   // encoder scratch, N * H * W * 4 floats each
     float *u = nullptr, *x = nullptr;   // decoder scratch, N * H * W * 32 floats each
+    // tcsfm_depthnet_disp_for_eigen / the sequence calls' disparity stage: scaled-disparity planes of ONE group of max_images images,
+    // the straight pass's and the mirrored pass's (still mirrored); allocated on first use (dn_post_scratch), owned by the instance
+    float *post_l = nullptr, *post_r = nullptr;
     // training state (allocated by the first tcsfm_depthnet_load_device)
     int train_loaded = 0;
     float *tbuf = nullptr;              // one allocation: the layers' raw / gw / gb regions and the head's gradient accumulator
@@ -141,7 +144,7 @@ void dn_free(tcsfm_depthnet *dn) {
         if (dn->pw) (void)hipFree(dn->pw);
         if (dn->pb) (void)hipFree(dn->pb);
     }
-    float *bufs[] = {dn->skip[0], dn->skip[1], dn->skip[2], dn->skip[3], dn->skip[4], dn->pool, dn->t1, dn->t2, dn->ds, dn->u, dn->x};
+    float *bufs[] = {dn->skip[0], dn->skip[1], dn->skip[2], dn->skip[3], dn->skip[4], dn->pool, dn->t1, dn->t2, dn->ds, dn->u, dn->x, dn->post_l, dn->post_r};
     for (float *p : bufs) if (p) (void)hipFree(p);
 }
 
@@ -158,7 +161,7 @@ tcsfm_depthnet *dn_sequence_clone(tcsfm_depthnet *dn) {
     for (float **p : q->train_bufs()) *p = nullptr;
     q->hacc = nullptr;
     for (int k = 0; k < 5; k++) q->skip[k] = nullptr;
-    q->pool = q->t1 = q->t2 = q->ds = q->u = q->x = nullptr;
+    q->pool = q->t1 = q->t2 = q->ds = q->u = q->x = q->post_l = q->post_r = nullptr;
     if (dn_alloc_scratch(q) != hipSuccess) { dn_free(q); delete q; return nullptr; }
     return dn->seq_clone = q;
 }
@@ -249,6 +252,9 @@ struct DnDecDst {
     float *aux[DN_UPS], *u[DN_UPS], *x[DN_UPS], *feat, *disp;
     int as_depth = 0;                   // the head stores disp_to_depth's depth (of min_disp, max_disp) into `disp` instead: k_dn_predict<true>
     float min_disp = 0.f, max_disp = 0.f;
+    // disp_post_kernel.h k_dn_head: with as_depth, ALSO disp_to_depth's scaled disparity into `scaled`; scaled_only: that alone, into `disp`
+    float *scaled = nullptr;
+    int scaled_only = 0;
 };
 
 // a stage's first block leaves its output in t2 (its input is the pooled map or a skip), the second one in the stage's skip
@@ -305,7 +311,13 @@ int dn_decode(tcsfm_depthnet *dn, int N, const float *const sk[5], const DnDecDs
     }
     dn_conv(dn, dn->feat(), N, x, nullptr, d.feat);                                              // feature_convs.0: 32 -> 8, ELU
     const dim3 head_grid(dn_blocks((long long)N * h->H * h->W));
-    if (d.as_depth)
+    if (d.scaled_only)
+        hipLaunchKernelGGL(k_dn_head<DN_HEAD_SCALED>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->pw, (const float *)dn->pb,
+                           d.disp, (float *)nullptr, N, h->H, h->W, d.min_disp, d.max_disp);
+    else if (d.as_depth && d.scaled)
+        hipLaunchKernelGGL(k_dn_head<DN_HEAD_DEPTH_SCALED>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->pw, (const float *)dn->pb,
+                           d.disp, d.scaled, N, h->H, h->W, d.min_disp, d.max_disp);
+    else if (d.as_depth)
         hipLaunchKernelGGL(k_dn_predict<true>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->pw, (const float *)dn->pb,
                            d.disp, N, h->H, h->W, d.min_disp, d.max_disp);
     else
@@ -795,23 +807,90 @@ int tcsfm_sequence_depthnet(tcsfm_handle h, tcsfm_depthnet *dn) {
 }
 
 namespace {
+// the two scaled-disparity planes of one group (tcsfm_depthnet::post_l / post_r), allocated on first use
+int dn_post_scratch(tcsfm_depthnet *dn, const char *fn) {
+    if (dn->post_l && dn->post_r) return TCSFM_OK;
+    const size_t bytes = (size_t)dn->max_images * dn->h->H * dn->h->W * sizeof(float);
+    hipError_t e = dn->post_l ? hipSuccess : hipMalloc((void **)&dn->post_l, bytes);
+    if (e == hipSuccess && !dn->post_r) e = hipMalloc((void **)&dn->post_r, bytes);
+    if (e != hipSuccess) return fail(dn->h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, (std::string(fn) + ": no memory for the disparity planes").c_str());
+    return TCSFM_OK;
+}
+
+// helpers.get_disp_for_eigen of ONE group of g <= max_images images on `dn`'s stream: the straight pass (its head stores the scaled
+// disparity into post_l -- and, with `depth`, disp_to_depth's depth there: the sequence calls' depth stage), the pass on the mirrored
+// images (scaled disparity into post_r, still mirrored), then k_disp_post into `out` [g,H,W] float64.  `ramp`: flip_ramp_device(h).
+// The code path of tcsfm_depthnet_disp_for_eigen and of the sequence calls' TCSFM_SEQ_DISP_POST stage alike.
+int dn_group_disp_for_eigen(tcsfm_depthnet *dn, int g, const float *imgs, float *depth, float min_disp, float max_disp, const double *ramp, double *out) {
+    tcsfm_ctx *h = dn->h;
+    if (int rc = dn_encode(dn, g, imgs, 0, dn_enc_scratch(dn, dn->skip))) return rc;
+    DnDecDst d = dn_dec_scratch(dn, depth ? depth : dn->post_l);
+    d.min_disp = min_disp; d.max_disp = max_disp;
+    if (depth) { d.as_depth = 1; d.scaled = dn->post_l; } else d.scaled_only = 1;
+    if (int rc = dn_decode(dn, g, dn->skip, d)) return rc;
+    if (int rc = dn_encode(dn, g, imgs, 1, dn_enc_scratch(dn, dn->skip))) return rc;
+    DnDecDst m = dn_dec_scratch(dn, dn->post_r);
+    m.min_disp = min_disp; m.max_disp = max_disp; m.scaled_only = 1;
+    if (int rc = dn_decode(dn, g, dn->skip, m)) return rc;
+    HIPCHK(h, launch_disp_post(dn_stream(dn), g, h->H, h->W, dn->post_l, dn->post_r, ramp, out));
+    return TCSFM_OK;
+}
+
 // The depth stage of a sequence call (sequence_impl): disp_to_depth(net(imgs), 1 / min_disp, 1 / max_disp)[1] of the n raw frames at
 // `imgs` into the planes at `depth`, on `stream`, by the attached network's clone -- groups of max_images images, the same bits per
-// image by the network's contract (its work split depends on H x W only).  The head writes the depth: no disparity plane exists.
-int dn_sequence_depths(tcsfm_depthnet *dn, hipStream_t stream, int n, const float *imgs, float *depth, float min_disp, float max_disp) {
+// image by the network's contract (its work split depends on H x W only).  The head writes the depth: with the disparity stage off
+// (disp_mode = TCSFM_SEQ_DISP_OFF) no disparity plane exists.  TCSFM_SEQ_DISP_PLAIN: the same head launch also stores the scaled
+// disparity into the float planes at `disp_store`.  TCSFM_SEQ_DISP_POST: get_disp_for_eigen of every frame into the float64 planes at
+// `disp_store` (dn_group_disp_for_eigen: a second, mirrored pass and the blend per group; `ramp` and the clone's planes are the caller's
+// to have ready).  The depths are the same bits in all three modes: one expression on one value.
+int dn_sequence_depths(tcsfm_depthnet *dn, hipStream_t stream, int n, const float *imgs, float *depth, float min_disp, float max_disp,
+                       int disp_mode = TCSFM_SEQ_DISP_OFF, void *disp_store = nullptr, const double *ramp = nullptr) {
     tcsfm_depthnet *q = dn->seq_clone;
     const size_t hw = (size_t)q->h->H * q->h->W;
     q->stream = stream;
     for (int i0 = 0; i0 < n; i0 += q->max_images) {
         const int g = std::min(n - i0, q->max_images);
+        if (disp_mode == TCSFM_SEQ_DISP_POST) {
+            if (int rc = dn_group_disp_for_eigen(q, g, imgs + (size_t)i0 * 3 * hw, depth + (size_t)i0 * hw, min_disp, max_disp, ramp,
+                                                 (double *)disp_store + (size_t)i0 * hw)) return rc;
+            continue;
+        }
         if (int rc = dn_encode(q, g, imgs + (size_t)i0 * 3 * hw, 0, dn_enc_scratch(q, q->skip))) return rc;
         DnDecDst d = dn_dec_scratch(q, depth + (size_t)i0 * hw);
         d.as_depth = 1; d.min_disp = min_disp; d.max_disp = max_disp;
+        if (disp_mode == TCSFM_SEQ_DISP_PLAIN) d.scaled = (float *)disp_store + (size_t)i0 * hw;
         if (int rc = dn_decode(q, g, q->skip, d)) return rc;
     }
     return TCSFM_OK;
 }
 }  // namespace
+
+int tcsfm_depthnet_disp_for_eigen(tcsfm_depthnet *dn, const tcsfm_opts *o, int N, const void *imgs, void *out) {
+    if (!dn) return TCSFM_E_ARG;
+    tcsfm_ctx *h = dn->h;
+    const char *fn = "tcsfm_depthnet_disp_for_eigen";
+    if (!dn->loaded) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_disp_for_eigen: no weights loaded");
+    if (!o || !imgs || !out || N < 1) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_disp_for_eigen: bad argument");
+    if (o->host_ptrs != 0) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_disp_for_eigen: host_ptrs must be 0 (device pointers); a host caller has the sequence calls (tcsfm_sequence_disparity)");
+    if (!(o->min_depth > 0 && o->max_depth > o->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
+    if (((uintptr_t)imgs & 3) != 0 || ((uintptr_t)out & 7) != 0) return fail(h, TCSFM_E_ARG, "tcsfm_depthnet_disp_for_eigen: imgs must be aligned for float, out for double");
+    const size_t hw = (size_t)h->H * h->W;
+    {
+        ArgRanges a;
+        a.in("imgs", imgs, (size_t)N * 3 * hw * sizeof(float));
+        a.out("out", out, (size_t)N * hw * sizeof(double));
+        if (int rc = check_overlap(h, fn, a)) return rc;
+    }
+    if (int rc_q = drain_queued(h)) return rc_q;
+    DeviceGuard dev_guard(h->device);
+    if (int rc = dn_post_scratch(dn, fn)) return rc;
+    const double *ramp = flip_ramp_device(h);
+    if (!ramp) return TCSFM_E_HIP;
+    for (int i0 = 0; i0 < N; i0 += dn->max_images)
+        if (int rc = dn_group_disp_for_eigen(dn, std::min(N - i0, dn->max_images), (const float *)imgs + (size_t)i0 * 3 * hw, nullptr, 1.f / o->max_depth,
+                                             1.f / o->min_depth, ramp, (double *)out + (size_t)i0 * hw)) return rc;
+    return TCSFM_OK;
+}
 
 int tcsfm_debug_depthnet_split(tcsfm_depthnet *dn, int layer, int *ks, int *oh, int *ow, int *nb, int *pb, int *kw) {
     if (!dn) return TCSFM_E_ARG;

@@ -289,12 +289,8 @@ __global__ __launch_bounds__(256) void k_dn_maxpool(const float *in, float *out,
 // DEPTH (the sequence calls' depth stage, depthnet_host.h dn_decode): the thread stores disp_to_depth's depth of its disparity instead
 // -- kernels.h disp_depth, the expression of k_disp_to_depth, on the value k_dn_predict<false> would have stored: the bits of
 // tcsfm_depthnet_forward followed by tcsfm_disp_to_depth, with no disparity plane and no second launch.
-template <bool DEPTH>
-__global__ __launch_bounds__(256) void k_dn_predict(const float *in, const float *w, const float *bias, float *out, int N, int H, int W,
-                                                    float min_disp, float max_disp) {
-    const long long total = (long long)N * H * W;
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
+// dn_head_disp: the sigmoid disparity of pixel e, shared with the heads of disp_post_kernel.h (k_dn_head), which store other functions of it.
+__device__ __forceinline__ float dn_head_disp(const float *in, const float *w, const float *bias, long long e, int H, int W) {
     const int x = (int)(e % W), y = (int)((e / W) % H), n = (int)(e / ((long long)W * H));
     const float *src = in + (size_t)n * H * W * 8;
     float s = 0.f;
@@ -315,7 +311,16 @@ __global__ __launch_bounds__(256) void k_dn_predict(const float *in, const float
         }
     }
     s += bias[0];
-    const float disp = 1.f / (1.f + expf(-s));
+    return 1.f / (1.f + expf(-s));
+}
+
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void k_dn_predict(const float *in, const float *w, const float *bias, float *out, int N, int H, int W,
+                                                    float min_disp, float max_disp) {
+    const long long total = (long long)N * H * W;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const float disp = dn_head_disp(in, w, bias, e, H, W);
     out[e] = DEPTH ? disp_depth(disp, min_disp, max_disp) : disp;
 }
 

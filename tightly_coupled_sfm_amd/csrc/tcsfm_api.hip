@@ -30,6 +30,7 @@
 #include "optim_kernel.h"
 #include "frames_u8_kernel.h"
 #include "resize_u8_kernel.h"
+#include "disp_post_kernel.h"
 
 using namespace tc;
 
@@ -188,6 +189,12 @@ struct tcsfm_ctx {
     size_t seq_scale_cap = 0;
     std::vector<float> seq_scale_res;  // the last call's results on the host, same layout with cap = seq_scale_T (counts as bit patterns)
     int seq_scale_T = 0;               // 0: nothing kept
+    // tcsfm_sequence_disparity: the sequence calls' disparity stage (the depth stage's head / a second, mirrored pass + k_disp_post on seq_pack)
+    int seq_disp_mode = TCSFM_SEQ_DISP_OFF;
+    void *seq_disp_dev = nullptr;      // every frame's plane by ABSOLUTE frame index: [T][H][W] float32 (PLAIN) or float64 (POST)
+    size_t seq_disp_bytes = 0;
+    int seq_disp_T = 0, seq_disp_kept = TCSFM_SEQ_DISP_OFF;      // the last call's T (0: nothing kept) and mode, for tcsfm_sequence_disparities
+    double *flip_ramp = nullptr;       // l_mask [W] of the flip post-processing on the device (flip_ramp_device), built on first use
     struct KOk { const float *p; int n; };
     KOk K_ok[4] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}};   // device intrinsics pointers (and counts) that already passed the pinhole check
     int K_ok_next = 0;
@@ -1439,7 +1446,7 @@ void tcsfm_destroy(tcsfm_handle h) {
                     h->jrec, h->jrec_acc, h->jblockrec, h->jdepth_acc, h->jstate, h->jdelta, h->jpart, h->jtick, h->dref_norms, h->dref_ext, h->dref_export, h->qres_rho, h->qres_rec, h->pose_lin, h->dref_smooth, h->jrec_src, h->jstate_src, h->jdelta_src, h->dref_ext_src, h->qres_rho_src, h->qres_rec_src,
                     h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept, h->dbg_stamps, h->wgrad_rec, h->wgrad_fix, h->wgrad_gmax, h->pgrad_fwd, h->pgrad_cot,
                     h->seq_fpack, h->seq_fdepth, h->pair_idx, h->seq_img, h->seq_depth, h->seq_pose_in, h->seq_pose_out, h->seq_ls_out, h->seq_K, h->seq_dense, h->seq_dense_tmp, h->seq_u8,
-                    h->seq_scale_keys, h->seq_scale_dev};
+                    h->seq_scale_keys, h->seq_scale_dev, h->seq_disp_dev, h->flip_ramp};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &t : h->resize_tabs)
@@ -2941,6 +2948,32 @@ int tcsfm_refine_dense_window_async(tcsfm_handle h, int lane, const tcsfm_opts *
     return TCSFM_OK;
 }
 
+// The flip post-processing's ramp table (flip_ramp.h) for the handle's W on the device: built on the host on first use,
+// kept for the handle's life.  NULL: h->err says why.
+static const double *flip_ramp_device(tcsfm_handle h) {
+    if (h->flip_ramp) return h->flip_ramp;
+    std::vector<double> ramp((size_t)h->W);
+    flip_ramp(h->W, ramp.data());
+    double *dev = nullptr;
+    if (hipError_t e = hipMalloc((void **)&dev, ramp.size() * sizeof(double))) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return nullptr; }
+    if (hipError_t e = hipMemcpy(dev, ramp.data(), ramp.size() * sizeof(double), hipMemcpyHostToDevice)) {      // (synchronous: ramp is a temporary)
+        h->err = std::string("hipMemcpy: ") + hipGetErrorString(e);
+        (void)hipFree(dev);
+        return nullptr;
+    }
+    return h->flip_ramp = dev;
+}
+
+// k_disp_post over n planes: the vector form where the row pairs are aligned (W even, 8-byte l / rf, 16-byte out), else the scalar one
+static hipError_t launch_disp_post(hipStream_t s, int n, int H, int W, const float *l, const float *rf, const double *ramp, double *out) {
+    const long long rows = (long long)n * H, threads = rows * ((W + 1) / 2);
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    const bool vec = W % 2 == 0 && (((uintptr_t)l | (uintptr_t)rf) & 7) == 0 && ((uintptr_t)out & 15) == 0;
+    if (vec) hipLaunchKernelGGL(k_disp_post<true>, grid, dim3(256), 0, s, l, rf, ramp, out, rows, W);
+    else hipLaunchKernelGGL(k_disp_post<false>, grid, dim3(256), 0, s, l, rf, ramp, out, rows, W);
+    return hipGetLastError();
+}
+
 #include "posenet_host.h"
 #include "depthnet_host.h"
 
@@ -2971,6 +3004,7 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     if (int rc_q = drain_queued(h)) return rc_q;
     if (!h) return TCSFM_E_ARG;
     h->seq_scale_T = 0;                                    // tcsfm_sequence_scales: only a call that succeeds with the stage on leaves results
+    h->seq_disp_T = 0;                                     // tcsfm_sequence_disparities: the same rule
     if (!o_in) return fail(h, TCSFM_E_ARG, "opts is NULL");
     const int N = 2 * S, L = h->lanes_serial ? 1 : (int)h->lanes.size() + 1;
     if (S < 1 || T <= S || N > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: need S >= 1, T > S and 2*S <= max_pairs");
@@ -2984,6 +3018,12 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
     if (resize && !u8)
         return fail(h, TCSFM_E_ARG, (std::string(entry) + ": a frame source size (tcsfm_sequence_frame_source) needs a U8 frame format, not TCSFM_FRAMES_F32_CHW").c_str());
     const size_t frame_bytes = resize ? (size_t)3 * h->seq_src_h * h->seq_src_w : (size_t)3 * h->H * h->W;      // of one frame of a U8 format
+    // tcsfm_sequence_disparity: every frame's disparity kept on the device; the stage needs the attached network's own output
+    const int disp_mode = h->seq_disp_mode;
+    if (disp_mode != TCSFM_SEQ_DISP_OFF && depths)
+        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": the disparity stage (tcsfm_sequence_disparity) needs depths == NULL: it keeps the attached depth network's own output").c_str());
+    if (disp_mode != TCSFM_SEQ_DISP_OFF && !h->seq_dn)
+        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": the disparity stage (tcsfm_sequence_disparity) needs an attached depth network (tcsfm_sequence_depthnet)").c_str());
     if (!frames || (!depths && !gen) || !K || (!pose_init && !pn) || !pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: NULL input");
     if (gen && o_in->depth_is_disp)
         return fail(h, TCSFM_E_ARG, (std::string(entry) + ": depths == NULL (the attached depth network produces depths) cannot go with opts.depth_is_disp").c_str());
@@ -3110,6 +3150,20 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
         HIPCHK(h, hipMalloc((void **)&h->seq_scale_dev, (size_t)3 * T * sizeof(float)));
         h->seq_scale_cap = (size_t)T;
     }
+    const double *disp_ramp = nullptr;
+    if (disp_mode != TCSFM_SEQ_DISP_OFF) {                  // every frame's plane, by absolute frame index; grown when a call needs more
+        const size_t need = (size_t)T * hw * (disp_mode == TCSFM_SEQ_DISP_POST ? sizeof(double) : sizeof(float));
+        if (h->seq_disp_bytes < need) {
+            if (h->seq_disp_dev) HIPCHK(h, hipFree(h->seq_disp_dev));
+            h->seq_disp_dev = nullptr; h->seq_disp_bytes = 0;
+            HIPCHK(h, hipMalloc(&h->seq_disp_dev, need));
+            h->seq_disp_bytes = need;
+        }
+        if (disp_mode == TCSFM_SEQ_DISP_POST) {             // the clone's two planes of one group and the ramp
+            if (int rc_ = dn_post_scratch(h->seq_dn->seq_clone, entry)) return rc_;
+            if (!(disp_ramp = flip_ramp_device(h))) return TCSFM_E_HIP;
+        }
+    }
     if (!h->seq_copy) {   // high priority: a hardware queue outside the pool the normal-priority streams share (a copy stream that lands in
         int lo = 0, hi = 0;   // a lane's queue parks its slot-recycling waits in front of that lane's kernels), and copies go first anyway
         HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
@@ -3220,7 +3274,14 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
                 // is reused, nxt + C - 1 - R < c0), and each of those calls waited for seq_copied, which this stream records after the
                 // stage: so the next copy also comes after the stage's reads of seq_img and its activations are free for the next chunk
                 // (one stream, in order).
-                if ((rc = dn_sequence_depths(h->seq_dn, h->seq_pack, nf, h->seq_img + (size_t)slot * 3 * hw, h->seq_depth + (size_t)slot * hw, gen_min_disp, gen_max_disp))) break;
+                // The disparity stage (tcsfm_sequence_disparity) is part of the same stage, in the same group loop, on this stream and
+                // before the chunk's seq_copied record: PLAIN adds a store to the head's launch; POST reads seq_img[slot ..] a second
+                // time (the mirrored pass) and writes the clone's own planes and the store, which is indexed by the ABSOLUTE frame and
+                // never recycled.  Its reads of seq_img precede seq_copied like the first pass's, so the argument covers them as it stands.
+                void *disp_at = disp_mode == TCSFM_SEQ_DISP_OFF ? nullptr
+                                : (char *)h->seq_disp_dev + (size_t)nxt * hw * (disp_mode == TCSFM_SEQ_DISP_POST ? sizeof(double) : sizeof(float));
+                if ((rc = dn_sequence_depths(h->seq_dn, h->seq_pack, nf, h->seq_img + (size_t)slot * 3 * hw, h->seq_depth + (size_t)slot * hw, gen_min_disp, gen_max_disp,
+                                             disp_mode, disp_at, disp_ramp))) break;
                 if (nm > 0 && (!use_cache || pn))
                     HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)(R + slot) * hw, h->seq_depth + (size_t)slot * hw, (size_t)nm * hw * sizeof(float), hipMemcpyDeviceToDevice, h->seq_pack));
             }
@@ -3312,6 +3373,7 @@ static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, c
             HIPCHK(h, hipMemcpy(h->seq_scale_res.data() + (size_t)a_ * T, h->seq_scale_dev + (size_t)a_ * h->seq_scale_cap, (size_t)T * sizeof(float), hipMemcpyDeviceToHost));
         h->seq_scale_T = T;
     }
+    if (disp_mode != TCSFM_SEQ_DISP_OFF) { h->seq_disp_T = T; h->seq_disp_kept = disp_mode; }      // (the pack stream was synchronised above)
     return TCSFM_OK;
 }
 
@@ -3360,6 +3422,57 @@ int tcsfm_sequence_scales(tcsfm_handle h, int T, void *scale_out, void *median_o
     memcpy(scale_out, r, (size_t)T * sizeof(float));
     if (median_out) memcpy(median_out, r + T, (size_t)T * sizeof(float));
     if (count_out) memcpy(count_out, r + 2 * (size_t)T, (size_t)T * sizeof(int));
+    return TCSFM_OK;
+}
+
+int tcsfm_sequence_disparity(tcsfm_handle h, int mode) {
+    if (!h) return TCSFM_E_ARG;
+    if (mode != TCSFM_SEQ_DISP_OFF && mode != TCSFM_SEQ_DISP_PLAIN && mode != TCSFM_SEQ_DISP_POST)
+        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_disparity: mode must be TCSFM_SEQ_DISP_OFF, TCSFM_SEQ_DISP_PLAIN or TCSFM_SEQ_DISP_POST");
+    h->seq_disp_mode = mode;
+    return TCSFM_OK;
+}
+
+int tcsfm_sequence_disparities(tcsfm_handle h, int T, int first, int count, void *out, int *mode_out) {
+    if (!h) return TCSFM_E_ARG;
+    if (!out) return fail(h, TCSFM_E_ARG, "tcsfm_sequence_disparities: NULL argument");
+    if (h->seq_disp_T == 0)
+        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_disparities: nothing kept (the last sequence call failed or ran with the stage off: tcsfm_sequence_disparity)");
+    if (T != h->seq_disp_T) return fail(h, TCSFM_E_ARG, "tcsfm_sequence_disparities: T differs from the T of the last sequence call");
+    if (first < 0 || count < 1 || first > T - count) return fail(h, TCSFM_E_ARG, "tcsfm_sequence_disparities: need 0 <= first, count >= 1 and first + count <= T");
+    const size_t plane = (size_t)h->H * h->W * (h->seq_disp_kept == TCSFM_SEQ_DISP_POST ? sizeof(double) : sizeof(float));
+    DeviceGuard dev_guard(h->device);
+    HIPCHK(h, hipMemcpy(out, (const char *)h->seq_disp_dev + (size_t)first * plane, (size_t)count * plane, hipMemcpyDeviceToHost));
+    if (mode_out) *mode_out = h->seq_disp_kept;
+    return TCSFM_OK;
+}
+
+int tcsfm_disp_post_process(tcsfm_handle h, const tcsfm_opts *o, int N, const void *l_disp, const void *r_disp_mirrored, void *out) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    if (!h) return TCSFM_E_ARG;
+    if (!o || !l_disp || !r_disp_mirrored || !out) return fail(h, TCSFM_E_ARG, "tcsfm_disp_post_process: NULL argument");
+    if (N < 1) return fail(h, TCSFM_E_ARG, "tcsfm_disp_post_process: N must be at least 1");
+    if (o->host_ptrs != 0)
+        return fail(h, TCSFM_E_ARG, "tcsfm_disp_post_process: host_ptrs must be 0 (device pointers); a host caller has the sequence calls (tcsfm_sequence_disparity)");
+    if (h->W < 2) return fail(h, TCSFM_E_ARG, "tcsfm_disp_post_process: the ramp needs W >= 2");
+    if ((((uintptr_t)l_disp | (uintptr_t)r_disp_mirrored) & 3) != 0 || ((uintptr_t)out & 7) != 0)
+        return fail(h, TCSFM_E_ARG, "tcsfm_disp_post_process: the inputs must be aligned for float, out for double");
+    const size_t hw = (size_t)h->H * h->W;
+    ArgRanges a;
+    a.in("l_disp", l_disp, (size_t)N * hw * sizeof(float)); a.in("r_disp_mirrored", r_disp_mirrored, (size_t)N * hw * sizeof(float));
+    a.out("out", out, (size_t)N * hw * sizeof(double));
+    if (int rc = check_overlap(h, "tcsfm_disp_post_process", a)) return rc;
+    DeviceGuard dev_guard(h->device);
+    if (int rc_ = pending_error(h)) return rc_;
+    const double *ramp = flip_ramp_device(h);
+    if (!ramp) return TCSFM_E_HIP;
+    HIPCHK(h, launch_disp_post(h->stream, N, h->H, h->W, (const float *)l_disp, (const float *)r_disp_mirrored, ramp, (double *)out));
+    return TCSFM_OK;
+}
+
+int tcsfm_flip_ramp(int W, void *l_mask_out) {
+    if (W < 2 || !l_mask_out) return TCSFM_E_ARG;
+    tc::flip_ramp(W, (double *)l_mask_out);
     return TCSFM_OK;
 }
 

@@ -152,6 +152,20 @@ class DepthNetHIP:
             e._call(self.lib.tcsfm_depthnet_forward(self._dn, i1 - i0, e._p(imgs[i0:i1]), int(bool(flip)), e._p(disp[i0:i1])))
         return disp
 
+    def disp_for_eigen(self, imgs: torch.Tensor, min_depth: Optional[float] = None, max_depth: Optional[float] = None) -> torch.Tensor:
+        """tcsfm_depthnet_disp_for_eigen: helpers.get_disp_for_eigen on the device -- the network on the frames and on their mirror
+        images, disp_to_depth's scaled_disp of both (min_depth / max_depth: default_opts' when None), the second un-flipped, blended by
+        batch_post_process_disparity in float64 with NumPy's bits: imgs [N,3,H,W] float32 CUDA -> float64 [N,H,W]"""
+        from .engine import default_opts
+        e = self.eng
+        e._bind()
+        N = int(imgs.shape[0])
+        imgs = _chk(imgs, (N, 3, e.H, e.W), "imgs")
+        o = default_opts(**{k: float(v) for k, v in (("min_depth", min_depth), ("max_depth", max_depth)) if v is not None})
+        out = torch.empty((N, e.H, e.W), device=imgs.device, dtype=torch.float64)
+        e._call(self.lib.tcsfm_depthnet_disp_for_eigen(self._dn, C.byref(o), N, e._p(imgs), e._p(out)))
+        return out
+
     @staticmethod
     def _to_nhwc(s: torch.Tensor) -> torch.Tensor:
         """[N,C,h,w] -> the NHWC buffer: the tensor behind a view this class returned, else an NHWC-contiguous copy"""

@@ -32,6 +32,19 @@ def check_cam_height(cam_height) -> Optional[float]:
     return v
 
 
+DISPARITY_MODES = {None: _lib.SEQ_DISP_OFF, "plain": _lib.SEQ_DISP_PLAIN, "post": _lib.SEQ_DISP_POST}
+
+
+def check_disparity(disparity) -> int:
+    """the `disparity` keyword of the sequence methods (tcsfm_sequence_disparity): None (the stage stays off), "plain" or "post" -> the
+    mode, checked before anything touches the GPU"""
+    if disparity is not None and not isinstance(disparity, str):
+        raise TypeError(f"disparity must be None, 'plain' or 'post' (got {type(disparity).__name__})")
+    if disparity not in DISPARITY_MODES:
+        raise ValueError(f"disparity must be None, 'plain' or 'post' (got {disparity!r})")
+    return DISPARITY_MODES[disparity]
+
+
 def _chk(t: torch.Tensor, shape, name: str) -> torch.Tensor:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
@@ -1011,6 +1024,56 @@ class Engine:
         finally:
             self.lib.tcsfm_sequence_scale(self._h, 0.0)
 
+    @contextlib.contextmanager
+    def _disparity(self, mode, T):
+        """the disparity stage (tcsfm_sequence_disparity) is on, in this mode, for the one call inside the block, and off again afterwards"""
+        self._seq_disp = None
+        if mode == _lib.SEQ_DISP_OFF:
+            yield
+            return
+        self._call(self.lib.tcsfm_sequence_disparity(self._h, int(mode)))
+        try:
+            yield
+            self._seq_disp = (int(T), int(mode))
+        finally:
+            self.lib.tcsfm_sequence_disparity(self._h, _lib.SEQ_DISP_OFF)
+
+    def sequence_disparities(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """tcsfm_sequence_disparities: frames first .. first + count - 1 (count=None: to the last) of the disparities the last sequence
+        call kept with disparity= -> NumPy [count,H,W]: float32 for "plain" (disp_to_depth's scaled_disp of the network's output),
+        float64 for "post" (helpers.get_disp_for_eigen of every frame: np.concatenate of the driver's pred_disps).  Raises when that call
+        kept nothing."""
+        T, mode = getattr(self, "_seq_disp", None) or (0, _lib.SEQ_DISP_POST)
+        first = int(first)
+        count = max(T - first, 1) if count is None else int(count)
+        out = np.empty((max(count, 1), self.H, self.W), dtype=np.float64 if mode == _lib.SEQ_DISP_POST else np.float32)
+        got = C.c_int(0)
+        self._call(self.lib.tcsfm_sequence_disparities(self._h, T, first, count, out.ctypes.data_as(C.c_void_p), C.byref(got)))
+        assert got.value == mode
+        return out
+
+    def flip_ramp(self, W: Optional[int] = None) -> np.ndarray:
+        """tcsfm_flip_ramp: l_mask of batch_post_process_disparity for width W (default: the engine's), float64 [W] with the bits of
+        1.0 - np.clip(20 * (np.linspace(0, 1, W) - 0.05), 0, 1).  Host only."""
+        W = int(self.W if W is None else W)
+        out = np.empty(max(W, 1), dtype=np.float64)
+        if _lib.load().tcsfm_flip_ramp(W, out.ctypes.data_as(C.c_void_p)) != 0:
+            raise ValueError(f"flip_ramp: W must be at least 2 (got {W})")
+        return out
+
+    def disp_post_process(self, l_disp: torch.Tensor, r_disp_mirrored: torch.Tensor) -> torch.Tensor:
+        """tcsfm_disp_post_process: batch_post_process_disparity on the device.  l_disp [N,H,W] (or [N,1,H,W]) float32 CUDA: the frames'
+        scaled disparity; r_disp_mirrored: the mirrored frames', STILL mirrored (the kernel un-flips it) -> float64 [N,H,W], NumPy's bits
+        of the reference's expression; on the engine's stream"""
+        N = int(l_disp.shape[0])
+        l = _chk(l_disp.reshape(N, self.H, self.W), (N, self.H, self.W), "l_disp")
+        r = _chk(r_disp_mirrored.reshape(N, self.H, self.W), (N, self.H, self.W), "r_disp_mirrored")
+        self._bind()
+        out = torch.empty((N, self.H, self.W), dtype=torch.float64, device=l.device)
+        o = default_opts()
+        self._call(self.lib.tcsfm_disp_post_process(self._h, C.byref(o), N, self._p(l), self._p(r), self._p(out)))
+        return out
+
     def sequence_scales(self, T: Optional[int] = None):
         """tcsfm_sequence_scales: the per-frame scales of the last sequence call that ran with cam_height= -> dict(scale [T] float32,
         median [T] float32, count [T] int32) of CPU tensors, by frame index; a frame without ground pixels has NaN scale and median.
@@ -1076,7 +1139,8 @@ class Engine:
         return out
 
     def refine_sequence(self, frames: torch.Tensor, depths: Optional[torch.Tensor], K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
-                        ring: int = 0, log_scale: bool = False, windows_per_call: int = 0, target_pos: int = 0, source_size=None, cam_height=None):
+                        ring: int = 0, log_scale: bool = False, windows_per_call: int = 0, target_pos: int = 0, source_size=None, cam_height=None,
+                        disparity=None):
         """tcsfm_refine_sequence: the whole window loop of a sequence inside the library (frames [T,3,H,W] float32 -- or the camera's
         bytes, uint8 [T,3,H,W] / [T,H,W,3], converted to u8 / 255 on the device -- / depths [T,1,H,W] CPU
         tensors -- pinned for asynchronous copies --, K [3,3], init_poses [T-S, 2S, 6]) -> refined poses [T-S, 2S, 6] (CPU tensor;
@@ -1086,9 +1150,11 @@ class Engine:
         computes them inside the call.  source_size=(h, w): `frames` are the camera's bytes at ITS size, uint8 [T,h,w,3] or [T,3,h,w]; the
         library resizes them to H x W on the device with Pillow's Lanczos bytes (tcsfm_sequence_frame_source); K is the H x W frames'
         (Engine.scale_intrinsics).  cam_height=h (metres / depth unit; None: off): every frame's DNet ground-plane scale is computed from
-        the ring's own depth plane inside the call (tcsfm_sequence_scale); fetch them with Engine.sequence_scales().  The return values
-        are unchanged."""
+        the ring's own depth plane inside the call (tcsfm_sequence_scale); fetch them with Engine.sequence_scales().  disparity="plain" /
+        "post" (depths=None only): every frame's scaled disparity / flip-post-processed disparity (helpers.get_disp_for_eigen) is kept on
+        the device inside the call (tcsfm_sequence_disparity); fetch them with Engine.sequence_disparities().  The return values are unchanged."""
         cam_height = check_cam_height(cam_height)
+        disp_mode = check_disparity(disparity)
         T, S = int(frames.shape[0]), int(sources)
         depths = self._seq_depths(depths, T)
         frames, fmt = self._seq_frames(frames, T, source_size)
@@ -1100,20 +1166,22 @@ class Engine:
         out = torch.empty_like(p0)
         ls = torch.zeros((T - S, 2 * S), dtype=torch.float32) if log_scale else None
         hp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with self._frame_format(fmt), self._frame_source(source_size), self._cam_height(cam_height, T):
+        with self._frame_format(fmt), self._frame_source(source_size), self._cam_height(cam_height, T), self._disparity(disp_mode, T):
             self._call(self.lib.tcsfm_refine_sequence(self._h, C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(p0), hp(out), hp(ls), int(ring),
                                                       int(windows_per_call), int(target_pos)))
         return (out, ls) if log_scale else out
 
     def refine_dense_sequence(self, frames: torch.Tensor, depths: Optional[torch.Tensor], K, init_poses, opts: Optional[Opts] = None, sources: int = 1,
                               ring: int = 0, windows_per_call: int = 0, target_pos: int = 0, out_depths: Optional[torch.Tensor] = None,
-                              source_size=None, cam_height=None):
+                              source_size=None, cam_height=None, disparity=None):
         """tcsfm_refine_dense_sequence: the dense mode (pose + per-pixel inverse depth) over a sequence, arguments as refine_sequence
         -> (poses [T-S, 2S, 6], refined depth maps [T-S, 2S, 1, H, W]) as CPU tensors.
         out_depths: a caller-owned (pinned) CPU tensor of that shape to receive the depth maps; a caller that runs sequence after
         sequence should pass one -- pinning a fresh 70 MB result buffer costs ten times the refinement of a 120-frame sequence.
-        source_size=(h, w): camera-size bytes, as for refine_sequence.  cam_height: per-frame scales, as for refine_sequence."""
+        source_size=(h, w): camera-size bytes, as for refine_sequence.  cam_height: per-frame scales, as for refine_sequence.
+        disparity: the frames' disparities, as for refine_sequence."""
         cam_height = check_cam_height(cam_height)
+        disp_mode = check_disparity(disparity)
         T, S = int(frames.shape[0]), int(sources)
         depths = self._seq_depths(depths, T)
         frames, fmt = self._seq_frames(frames, T, source_size)
@@ -1129,7 +1197,7 @@ class Engine:
             if dout.is_cuda or dout.dtype != torch.float32 or not dout.is_contiguous() or tuple(dout.shape) != (T - S, 2 * S, 1, self.H, self.W):
                 raise TypeError("out_depths must be a contiguous float32 CPU tensor [T-S, 2S, 1, H, W]")
         hp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with self._frame_format(fmt), self._frame_source(source_size), self._cam_height(cam_height, T):
+        with self._frame_format(fmt), self._frame_source(source_size), self._cam_height(cam_height, T), self._disparity(disp_mode, T):
             self._call(self.lib.tcsfm_refine_dense_sequence(self._h, C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(p0), hp(out), hp(dout), int(ring),
                                                             int(windows_per_call), int(target_pos)))
         return out, dout

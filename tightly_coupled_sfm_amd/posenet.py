@@ -265,15 +265,18 @@ class PoseNetHIP:
         return raw.permute(0, 3, 1, 2), scsh
 
     def odometry_sequence(self, frames, depths, K, opts=None, sources: int = 1, iterations: int = 4, ring: int = 0, windows_per_call: int = 0,
-                          target_pos: int = 0, source_size=None, cam_height=None):
+                          target_pos: int = 0, source_size=None, cam_height=None, disparity=None):
         """tcsfm_odometry_sequence: for every window of a sequence (frames [T,3,H,W] float32, or uint8 [T,3,H,W] / [T,H,W,3] / depths [T,1,H,W] CPU tensors, pinned for
         asynchronous copies; K [3,3]) the coupled PoseNet loop gives the initial poses and the engine refines them, windows
         running on the engine's lanes -> (initial poses, refined poses), each [T-S, 2S, 6] CPU tensors.  depths=None: the depth
         network of Engine.attach_depthnet computes them inside the call (frames in, poses out).  source_size=(h, w): `frames` are
         camera-size bytes, uint8 [T,h,w,3] or [T,3,h,w], resized on the device (Engine.refine_sequence).  cam_height=h: every frame's
-        DNet scale from the ring's own depth plane (tcsfm_sequence_scale); fetch them with Engine.sequence_scales()"""
-        from .engine import check_cam_height
+        DNet scale from the ring's own depth plane (tcsfm_sequence_scale); fetch them with Engine.sequence_scales().  disparity="plain" /
+        "post" (depths=None only): every frame's disparity is kept inside the call (tcsfm_sequence_disparity); fetch them with
+        Engine.sequence_disparities()"""
+        from .engine import check_cam_height, check_disparity
         cam_height = check_cam_height(cam_height)
+        disp_mode = check_disparity(disparity)
         e = self.eng
         T, S = int(frames.shape[0]), int(sources)
         depths = e._seq_depths(depths, T)
@@ -284,7 +287,7 @@ class PoseNetHIP:
         Kc = e._cpu(torch.as_tensor(np.asarray(K, dtype=np.float32)), (3, 3), "K")
         init = torch.empty((T - S, 2 * S, 6), dtype=torch.float32); out = torch.empty_like(init)
         hp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with e._frame_format(fmt), e._frame_source(source_size), e._cam_height(cam_height, T):
+        with e._frame_format(fmt), e._frame_source(source_size), e._cam_height(cam_height, T), e._disparity(disp_mode, T):
             e._call(self.lib.tcsfm_odometry_sequence(e._h, self._pn, int(iterations), C.byref(o), T, S, hp(frames), hp(depths), hp(Kc), hp(init), hp(out),
                                                      None, int(ring), int(windows_per_call), int(target_pos)))
         return init, out

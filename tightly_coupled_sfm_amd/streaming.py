@@ -17,7 +17,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from .engine import Engine, Opts, check_cam_height, default_opts
+from .engine import Engine, Opts, check_cam_height, check_disparity, default_opts
 
 
 def metric_poses(poses, scale, sources: int, target_pos: int = 0, depth_unit: float = 30.0):
@@ -78,14 +78,16 @@ class SequenceRefiner:
             self.ring_depth[slot].copy_(depth, non_blocking=True)
             self.copied[slot].record(self.copy_stream)
 
-    def run_native(self, frames, depths, K, init_poses, ring: int = 0, source_size=None, cam_height=None) -> torch.Tensor:
+    def run_native(self, frames, depths, K, init_poses, ring: int = 0, source_size=None, cam_height=None, disparity=None) -> torch.Tensor:
         """The same loop inside the library (tcsfm_refine_sequence: four-frame copies, events and lanes driven from C++) -> refined
         poses [T-S, 2*S, 6] as a CPU tensor; bit-identical to run().  depths=None: the depth network attached to the engine
         (self.eng.attach_depthnet) computes them inside the call.  frames: float32 [T,3,H,W], or the camera's bytes -- uint8 [T,3,H,W] or
         [T,H,W,3] -- which the library converts on the device (Engine.refine_sequence); with source_size=(h, w) the
         bytes are at the camera's size, [T,h,w,3] or [T,3,h,w], and the library resizes them too.  cam_height=h: the frames' DNet scales
-        are computed inside the call (self.eng.sequence_scales(); metric_poses applies them)"""
+        are computed inside the call (self.eng.sequence_scales(); metric_poses applies them).  disparity="plain" / "post" (depths=None
+        only): the frames' disparities are kept inside the call (self.eng.sequence_disparities())"""
         cam_height = check_cam_height(cam_height)
+        check_disparity(disparity)
         pin = lambda a: a if (isinstance(a, torch.Tensor) and not a.is_cuda) else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32)
         if isinstance(frames, torch.Tensor) and frames.is_cuda:
             raise TypeError("frames must be a CPU tensor (the library stages the sequence itself)")
@@ -93,7 +95,8 @@ class SequenceRefiner:
             frames = torch.from_numpy(np.ascontiguousarray(frames))
         return self.eng.refine_sequence(pin(frames), None if depths is None else pin(depths), K, init_poses, self.opts, sources=self.S, ring=ring,
                                         **({} if source_size is None else {"source_size": source_size}),
-                                        **({} if cam_height is None else {"cam_height": cam_height}))
+                                        **({} if cam_height is None else {"cam_height": cam_height}),
+                                        **({} if disparity is None else {"disparity": disparity}))
 
     def run(self, frames, depths, K, init_poses) -> torch.Tensor:
         """-> refined poses [T-S, 2*S, 6] (GPU tensor, complete on return)"""
