@@ -2012,7 +2012,29 @@ void orc_refine_dense_joint(int H, int W, int B, int S, const real *tgt, const r
  * sampled-depth terms and e dW/d. terms are gradient-only, as in every other mode.  Inverse pairs: 6 x 6 pose systems under the
  * window REFERENCE rule (linearize_masked with the batch normaliser), their depth is not an unknown.
  */
-typedef struct { double *Dq, *Bq, *Hs, *gs; } dref_src_sys;   /* [SB][n], [SB][n][6], [SB][36] (reduced), [SB][6] (reduced) */
+typedef struct { double *Dq, *Bq, *Hs, *gs; } dref_src_sys;
+/* Optional side outputs of linearize_dense_ref / dref_source_depth_gradient (orc_linearize_dense_ref_forced): beside every gradient entry the
+ * sum over its contributions of |contribution| -- what an entry-by-entry accuracy check measures an error against (the dense counterpart of
+ * lin_t.gabs).  A contribution is one term as the loss is written: per source, per colour channel, per tap of the 3 x 3 SSIM window (its
+ * x and y parts apart: they are summed apart), per scattered bilinear tap, the weight term, the depth-consistency term, every window tap of
+ * the prior, every edge of the smoothness term and its per-image constant.  The inverse pairs' pose rows take linearize_masked's gabs (per
+ * pixel).  ntap / ntap_s: how many scattered taps landed on a pixel.  Nothing here feeds back into the gradients: their bits do not change. */
+typedef struct {
+    double *g_rho_abs, *g_xi_abs, *g_rho_s_abs;   /* [B][n], [2SB][6], [SB][n] or NULL */
+    double *ntap, *ntap_s;                        /* [B][n], [SB][n] or NULL */
+    double *mask;                                 /* [2SB][n]: the masks the sums ran under (the forward pairs' selection, the inverse pairs' own) */
+    double L_dc_inv;                              /* the inverse pairs' share of L_dc */
+} dref_abs;
+static __thread dref_abs *g_dref_abs = NULL;
+/* Planted faults (tests of the JUDGE, tests/test_dense_linearize_exact_inputs_cpu.py: a check is shown to catch a kernel that forgets a halo tap or
+ * a scatter path by making this restatement forget it): forward pair `pair` skips tap `tap` (0..8, row-major) of the SSIM window centred on
+ * `pixel` in all three channels; an inverse pair's scattered tap t of pixel i is dropped where scatter_drop[(m n + i)] has bit t set.
+ * Off (pair < 0, scatter_drop NULL) unless orc_dref_plant_fault switched it on; it switches off again with (-1, 0, 0, NULL). */
+static __thread int g_fault_pair = -1, g_fault_pixel = 0, g_fault_tap = 0;
+static __thread const unsigned char *g_fault_scatter = NULL;
+void orc_dref_plant_fault(int pair, int pixel, int tap, const unsigned char *scatter_drop) {
+    g_fault_pair = pair; g_fault_pixel = pixel; g_fault_tap = tap; g_fault_scatter = scatter_drop;
+}   /* [SB][n], [SB][n][6], [SB][36] (reduced), [SB][6] (reduced) */
 /* Gradient of the same loss w.r.t. the SOURCE inverse-depth maps rho_s(m, q) = 1 / depth_s(m, q), m = (s, b) -- the leaves of the
  * reference's optimize_depth_pred that the engine holds fixed (optimizer.py:194-198: the quarter-resolution disparities of the target AND
  * of every source are optimised).  Their role mirrors the target map's:
@@ -2034,6 +2056,9 @@ static void dref_source_depth_gradient(int H, int W, int B, int S, const real *t
     const double eps = op->irls_eps;
     (void)ae;
     memset(g_rho_s, 0, sizeof(double) * (size_t)SB * n);
+    dref_abs *ab = (g_dref_abs && g_dref_abs->g_rho_s_abs) ? g_dref_abs : NULL;
+    double *adj_abs = ab ? (double *)malloc(sizeof(double) * n) : NULL;
+    if (ab) { memset(ab->g_rho_s_abs, 0, sizeof(double) * (size_t)SB * n); memset(ab->ntap_s, 0, sizeof(double) * (size_t)SB * n); }
     px_t *px = (px_t *)malloc(sizeof(px_t) * n);
     real *rec = (real *)malloc(sizeof(real) * 3 * n);
     double *adj = (double *)malloc(sizeof(double) * 2 * n), *Lam = (double *)calloc((size_t)3 * n, sizeof(double));
@@ -2042,6 +2067,7 @@ static void dref_source_depth_gradient(int H, int W, int B, int S, const real *t
         const real *ti = srcs + (size_t)m * 3 * n;      /* the inverse pair's target image = source image m */
         const real *ds = depth_s + (size_t)m * n;
         double *gr = g_rho_s + (size_t)m * n;
+        double *gra = ab ? ab->g_rho_s_abs + (size_t)m * n : NULL, *nts = ab ? ab->ntap_s + (size_t)m * n : NULL;
         /* ---- (ii) first: the forward pair m samples this map: adjoint of the bilinear sample (its sums join the local gradient below) ---- */
         cam_t c;
         cam_setup(&c, H, W, K + 9 * b, T + 12 * m, 0.0);
@@ -2071,7 +2097,10 @@ static void dref_source_depth_gradient(int H, int W, int B, int S, const real *t
                 const double w4[4] = {(1 - wx) * (1 - wy), wx * (1 - wy), (1 - wx) * wy, wx * wy};
                 for (int t = 0; t < 4; t++) {
                     const int xx = x0 + (t & 1), yy = y0 + (t >> 1);
-                    if (xx >= 0 && xx < W && yy >= 0 && yy < H) gr[yy * W + xx] -= (double)ds[yy * W + xx] * ds[yy * W + xx] * coef * w4[t];   /* d / d rho = -depth^2 d / d depth */
+                    if (xx >= 0 && xx < W && yy >= 0 && yy < H) {
+                        gr[yy * W + xx] -= (double)ds[yy * W + xx] * ds[yy * W + xx] * coef * w4[t];   /* d / d rho = -depth^2 d / d depth */
+                        if (ab) { gra[yy * W + xx] += fabs((double)ds[yy * W + xx] * ds[yy * W + xx] * coef * w4[t]); nts[yy * W + xx] += 1; }
+                    }
                 }
             }
         /* ---- (i) the inverse pair: per-pixel quantities with the inverse-depth column ---- */
@@ -2089,6 +2118,7 @@ static void dref_source_depth_gradient(int H, int W, int B, int S, const real *t
             for (int ch = 0; ch < 3; ch++) rec[ch * n + i] = px[i].rec[ch];
         memset(adj, 0, sizeof(double) * 2 * n);
         memset(Lam, 0, sizeof(double) * 3 * n);
+        if (ab) memset(adj_abs, 0, sizeof(double) * n);
         double gxi[6] = {0, 0, 0, 0, 0, 0}, Hxx[36], Sm[36], gsv[6] = {0, 0, 0, 0, 0, 0};
         memset(Hxx, 0, sizeof(Hxx)); memset(Sm, 0, sizeof(Sm));
         for (int v = 0; v < H; v++)
@@ -2109,6 +2139,7 @@ static void dref_source_depth_gradient(int H, int W, int B, int S, const real *t
                     const real sgn = (ar <= 1) ? forced_sign(r, (real)1e-6, i, 6 + 2 * ch) : (real)0;
                     adj[2 * i] += am * Wt * wl * sgn * P->gx[ch];
                     adj[2 * i + 1] += am * Wt * wl * sgn * P->gy[ch];
+                    if (ab) adj_abs[i] += fabs(am * Wt * wl * sgn * P->gx[ch] * P->a[6]) + fabs(am * Wt * wl * sgn * P->gy[ch] * P->b[6]);
                     if (ar <= 1) {
                         real w1 = wl * Wt / (ar > reps ? ar : reps);
                         lxx += w1 * P->gx[ch] * P->gx[ch]; lxy += w1 * P->gx[ch] * P->gy[ch]; lyy += w1 * P->gy[ch] * P->gy[ch];
@@ -2127,6 +2158,7 @@ static void dref_source_depth_gradient(int H, int W, int B, int S, const real *t
                                 const real cf = ws * (cA + cB * y[qi] + cC * xx[qi]);
                                 adj[2 * qi] += am * Wt * cf * px[qi].gx[ch];
                                 adj[2 * qi + 1] += am * Wt * cf * px[qi].gy[ch];
+                                if (ab) adj_abs[qi] += fabs(am * Wt * cf * px[qi].gx[ch] * px[qi].a[6]) + fabs(am * Wt * cf * px[qi].gy[ch] * px[qi].b[6]);
                                 Sx += px[qi].gx[ch]; Sy += px[qi].gy[ch];
                             }
                         const real ninth = (real)1 / 9;
@@ -2139,12 +2171,14 @@ static void dref_source_depth_gradient(int H, int W, int B, int S, const real *t
                 /* the pair's own weight: -M diff d dd / d theta */
                 for (int j = 0; j < 6; j++) gxi[j] -= a_i * am * e * kdd * (P->pd * P->zc[j] - P->cd * P->dpd[j]);
                 gr[i] -= a_i * am * e * kdd * (P->pd * P->zc[6] - P->cd * P->dpd[6]);
+                if (ab) gra[i] += fabs(a_i * am * e * kdd * (P->pd * P->zc[6] - P->cd * P->dpd[6]));
             }
         for (int i = 0; i < n; i++) {
             const px_t *P = &px[i];
             const double ax = a_i * adj[2 * i], ay = a_i * adj[2 * i + 1];
             for (int j = 0; j < 6; j++) gxi[j] += ax * P->a[j] + ay * P->b[j];
             gr[i] += ax * P->a[6] + ay * P->b[6];
+            if (ab) gra[i] += a_i * adj_abs[i];
             const double am = a_i * imask[(size_t)m * n + i];
             const double lxx = am * Lam[3 * i], lxy = am * Lam[3 * i + 1], lyy = am * Lam[3 * i + 2];
             /* depth consistency of the inverse pair (every pixel of the image) */
@@ -2154,6 +2188,7 @@ static void dref_source_depth_gradient(int H, int W, int B, int S, const real *t
             for (int j = 0; j < 7; j++) ddJ[j] = sg * 2.0 * (P->pd * P->zc[j] - P->cd * P->dpd[j]) / ((double)sum * sum);
             const double inf = bdc * fmin(1.0, dd / eps), k3 = P->dc_in ? bdc / fmax((double)dd, eps) : 0.0;
             gr[i] += inf * ddJ[6];
+            if (ab) gra[i] += fabs(inf * ddJ[6]);
             const double la6 = lxx * P->a[6] + lxy * P->b[6], lb6 = lxy * P->a[6] + lyy * P->b[6];
             double D = la6 * P->a[6] + lb6 * P->b[6] + k3 * ddJ[6] * ddJ[6], Bv[6];
             for (int j = 0; j < 6; j++) {
@@ -2179,7 +2214,7 @@ static void dref_source_depth_gradient(int H, int W, int B, int S, const real *t
             }
     }
     g_force_bits = NULL;
-    free(px); free(rec); free(adj); free(Lam);
+    free(px); free(rec); free(adj); free(Lam); free(adj_abs);
 }
 
 typedef struct {
@@ -2200,6 +2235,10 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
     memset(sc, 0, sizeof(*sc));
     memset(g_xi, 0, sizeof(double) * 12 * SB);
     memset(g_rho, 0, sizeof(double) * (size_t)B * n);
+    dref_abs *ab = g_dref_abs;      /* side outputs (see dref_abs): written only, never read back into a gradient */
+    double *ext_abs = ab ? (double *)calloc((size_t)B * n, sizeof(double)) : NULL;
+    if (ab) { memset(ab->g_rho_abs, 0, sizeof(double) * (size_t)B * n); memset(ab->g_xi_abs, 0, sizeof(double) * 12 * SB);
+              memset(ab->ntap, 0, sizeof(double) * (size_t)B * n); ab->L_dc_inv = 0; }
     /* ---------- inverse pairs: masks, the batch normaliser K_i ---------- */
     real *imask = (real *)malloc(sizeof(real) * (size_t)SB * n);
     double Ki = 0;
@@ -2235,6 +2274,7 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
         for (int j = 0; j < 6; j++) { g_xi[6 * pn + j] = L.g[j]; if (gi) gi[6 * m + j] = L.g[j]; }
         if (Hi) for (int j = 0; j < 36; j++) Hi[36 * m + j] = L.H[(j / 6) * 6 + (j % 6)];
         sc->L_inv += L.cost_photo; sc->L_dc += L.cost_dc;
+        if (ab) { for (int j = 0; j < 6; j++) ab->g_xi_abs[6 * pn + j] = L.gabs[j]; ab->L_dc_inv += L.cost_dc; }
         /* scatter: term(p) = a_i M W diff + b dd, W = 1 - dd, dd = clamp(|cd - pd| / (cd + pd)); pd = sample of the target depth */
         cam_t c;
         cam_setup(&c, H, W, K + 9 * b, T + 12 * pn, 0.0);
@@ -2258,7 +2298,11 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
                 const double w4[4] = {(1 - wx) * (1 - wy), wx * (1 - wy), (1 - wx) * wy, wx * wy};
                 for (int t = 0; t < 4; t++) {
                     const int xx = x0 + (t & 1), yy = y0 + (t >> 1);
-                    if (xx >= 0 && xx < W && yy >= 0 && yy < H) ext[(size_t)b * n + yy * W + xx] += coef * w4[t];
+                    if (g_fault_scatter && ((g_fault_scatter[(size_t)m * n + i] >> t) & 1)) continue;
+                    if (xx >= 0 && xx < W && yy >= 0 && yy < H) {
+                        ext[(size_t)b * n + yy * W + xx] += coef * w4[t];
+                        if (ab) { ext_abs[(size_t)b * n + yy * W + xx] += fabs(coef * w4[t]); ab->ntap[(size_t)b * n + yy * W + xx] += 1; }
+                    }
                 }
             }
         free(Eo); free(Mo);
@@ -2334,14 +2378,19 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
     for (size_t i = 0; i < (size_t)SB * n; i++) Kf += mask[i];
     sc->Kf = Kf;
     const double a_f = Kf > 0 ? (argmin ? 1.0 : 0.25) / Kf : 0.0;
+    if (ab) for (size_t i = 0; i < (size_t)SB * n; i++) { ab->mask[i] = mask[i]; ab->mask[(size_t)SB * n + i] = imask[i]; }
     /* ---------- forward group of every target ---------- */
     double *gx_adj = (double *)malloc(sizeof(double) * (size_t)n * 2 * S), *Lam = (double *)malloc(sizeof(double) * (size_t)n * 3 * S);
     double *own = (double *)malloc(sizeof(double) * n), *gxi = (double *)malloc(sizeof(double) * NP), *Hxx = (double *)malloc(sizeof(double) * (size_t)NP * NP);
     double *Sm = (double *)malloc(sizeof(double) * (size_t)NP * NP), *gs = (double *)malloc(sizeof(double) * NP);
     double *pri_g = (double *)malloc(sizeof(double) * n), *pri_D = (double *)malloc(sizeof(double) * n);
     real *sig = (real *)malloc(sizeof(real) * n), *sig0 = (real *)malloc(sizeof(real) * n);
+    double *adj_abs = ab ? (double *)malloc(sizeof(double) * (size_t)n * S) : NULL, *own_abs = ab ? (double *)malloc(sizeof(double) * n) : NULL;
+    double *pri_abs = ab ? (double *)malloc(sizeof(double) * n) : NULL, *gxi_abs = ab ? (double *)malloc(sizeof(double) * NP) : NULL;
     for (int b = 0; b < B; b++) {
         const real *tg = tgt + (size_t)b * 3 * n;
+        if (ab) { memset(adj_abs, 0, sizeof(double) * (size_t)n * S); memset(own_abs, 0, sizeof(double) * n); memset(pri_abs, 0, sizeof(double) * n);
+                  memset(gxi_abs, 0, sizeof(double) * NP); }
         memset(gx_adj, 0, sizeof(double) * (size_t)n * 2 * S); memset(Lam, 0, sizeof(double) * (size_t)n * 3 * S);
         memset(own, 0, sizeof(double) * n); memset(gxi, 0, sizeof(double) * NP); memset(Hxx, 0, sizeof(double) * (size_t)NP * NP);
         memset(Sm, 0, sizeof(double) * (size_t)NP * NP); memset(gs, 0, sizeof(double) * NP);
@@ -2364,6 +2413,11 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
                         real sgn = (ar <= 1) ? forced_sign(r, (real)1e-6, i, 6 + 2 * ch) : (real)0;
                         gx_adj[((size_t)s * n + i) * 2] += am * Wt * wl * sgn * P->gx[ch];
                         gx_adj[((size_t)s * n + i) * 2 + 1] += am * Wt * wl * sgn * P->gy[ch];
+                        if (ab) {
+                            const double tx_ = am * Wt * wl * sgn * P->gx[ch], ty_ = am * Wt * wl * sgn * P->gy[ch];
+                            adj_abs[(size_t)s * n + i] += fabs(tx_ * P->a[6]) + fabs(ty_ * P->b[6]);
+                            for (int j = 0; j < 6; j++) gxi_abs[6 * s + j] += fabs(tx_ * P->a[j]) + fabs(ty_ * P->b[j]);
+                        }
                         if (ar <= 1) {
                             real w1 = wl * Wt / (ar > reps ? ar : reps);
                             lxx += w1 * P->gx[ch] * P->gx[ch]; lxy += w1 * P->gx[ch] * P->gy[ch]; lyy += w1 * P->gy[ch] * P->gy[ch];
@@ -2379,8 +2433,15 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
                                 for (int du = -1; du <= 1; du++) {
                                     int qi = refl(v + dv, H) * W + refl(u + du, W);
                                     real cf = ws * (cA + cB * y[qi] + cC * xx[qi]);
+                                    if (g_fault_pair == m && g_fault_pixel == i && g_fault_tap == (dv + 1) * 3 + du + 1) cf = 0;
                                     gx_adj[((size_t)s * n + qi) * 2] += am * Wt * cf * px[m][qi].gx[ch];
                                     gx_adj[((size_t)s * n + qi) * 2 + 1] += am * Wt * cf * px[m][qi].gy[ch];
+                                    if (ab) {
+                                        const px_t *Q = &px[m][qi];
+                                        const double tx_ = am * Wt * cf * Q->gx[ch], ty_ = am * Wt * cf * Q->gy[ch];
+                                        adj_abs[(size_t)s * n + qi] += fabs(tx_ * Q->a[6]) + fabs(ty_ * Q->b[6]);
+                                        for (int j = 0; j < 6; j++) gxi_abs[6 * s + j] += fabs(tx_ * Q->a[j]) + fabs(ty_ * Q->b[j]);
+                                    }
                                     Sx += px[m][qi].gx[ch]; Sy += px[m][qi].gy[ch];
                                 }
                             const real ninth = (real)1 / 9;
@@ -2403,6 +2464,10 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
                 double kdd = sg * 2.0 / ((double)sum * sum), e = diff[(size_t)m * n + i];
                 for (int j = 0; j < 6; j++) gxi[6 * sx_ + j] -= am * e * kdd * (X->pd * X->zc[j] - X->cd * X->dpd[j]);
                 own[i] -= am * e * kdd * (X->pd * X->zc[6] - X->cd * X->dpd[6]);
+                if (ab) {
+                    own_abs[i] += fabs(am * e * kdd * (X->pd * X->zc[6] - X->cd * X->dpd[6]));
+                    for (int j = 0; j < 6; j++) gxi_abs[6 * sx_ + j] += fabs(am * e * kdd * (X->pd * X->zc[j] - X->cd * X->dpd[j]));
+                }
             }
         }
         g_force_bits = NULL;
@@ -2428,6 +2493,7 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
                         for (int du = -1; du <= 1; du++) {
                             int qi = refl(v + dv, H) * W + refl(u + du, W);
                             pri_g[qi] += wp * (cA + cB * sig[qi] + cC * sig0[qi]) / rd;          /* d sigma / d rho = 1 / r */
+                            if (ab) pri_abs[qi] += fabs(wp * (cA + cB * sig[qi] + cC * sig0[qi]) / rd);
                         }
                     pri_D[v * W + u] = wp / (rd * rd) * (1.0 / q.d2 + 1.0 / (9.0 * q.d1));
                 }
@@ -2458,22 +2524,26 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
                         Tb += ce * ad;
                         const double gl = ce * dd_ / den / m;                 /* = c_e s_e / m away from zero */
                         pri_g[i] += gl / rd; pri_g[j] -= gl / rd;
+                        if (ab) { pri_abs[i] += fabs(gl / rd); pri_abs[j] += fabs(gl / rd); }
                         const double dl = 2.0 * ce / (m * m * den) / (rd * rd);
                         pri_D[i] += dl; pri_D[j] += dl;
                     }
             for (int i = 0; i < n; i++) pri_g[i] -= Tb / (m * n) / rd;
+            if (ab) for (int i = 0; i < n; i++) pri_abs[i] += fabs(Tb / (m * n) / rd);
             sc->L_init += Tb;                                       /* (booked with the prior: both are terms on the map alone) */
         }
         /* assemble */
         for (int i = 0; i < n; i++) {
             const double dep = depth_t[(size_t)b * n + i];
             double gr = a_f * own[i] + pri_g[i] - dep * dep * ext[(size_t)b * n + i], D = pri_D[i], Bv[6 * JMAXS];
+            double gra = ab ? a_f * own_abs[i] + pri_abs[i] + dep * dep * ext_abs[(size_t)b * n + i] : 0.0;
             for (int s = 0; s < S; s++) {
                 const int m = s * B + b;
                 const px_t *P = &px[m][i];
                 const double ax = a_f * gx_adj[((size_t)s * n + i) * 2], ay = a_f * gx_adj[((size_t)s * n + i) * 2 + 1];
                 for (int j = 0; j < 6; j++) gxi[6 * s + j] += gx_adj[((size_t)s * n + i) * 2] * P->a[j] + gx_adj[((size_t)s * n + i) * 2 + 1] * P->b[j];
                 gr += ax * P->a[6] + ay * P->b[6];
+                if (ab) gra += a_f * adj_abs[(size_t)s * n + i];
                 const double am = a_f * mask[(size_t)m * n + i];
                 const double lxx = am * Lam[((size_t)s * n + i) * 3], lxy = am * Lam[((size_t)s * n + i) * 3 + 1], lyy = am * Lam[((size_t)s * n + i) * 3 + 2];
                 /* depth consistency of THIS forward pair (every pixel of the image) */
@@ -2486,6 +2556,7 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
                 sc->L_dc += bdc * dd;
                 const double inf = bdc * fmin(1.0, dd / eps), k3 = P->dc_in ? bdc / fmax((double)dd, eps) : 0.0;
                 gr += inf * ddJ[6];
+                if (ab) { gra += fabs(inf * ddJ[6]); for (int j = 0; j < 6; j++) ab->g_xi_abs[6 * m + j] += fabs(inf * ddJ[j]); }
                 const double la6 = lxx * P->a[6] + lxy * P->b[6], lb6 = lxy * P->a[6] + lyy * P->b[6];
                 D += la6 * P->a[6] + lb6 * P->b[6] + k3 * ddJ[6] * ddJ[6];
                 for (int j = 0; j < 6; j++) {
@@ -2498,6 +2569,7 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
             for (int s = 0; s < S; s++)
                 if (px[s * B + b][i].valid && !px[s * B + b][i].dc_in) D = 0;    /* sampled across the zero padding: the pixel keeps its depth */
             g_rho[(size_t)b * n + i] = gr;
+            if (ab) ab->g_rho_abs[(size_t)b * n + i] = gra;
             if (Dq) Dq[(size_t)b * n + i] = D;
             if (Bq) memcpy(Bq + ((size_t)b * n + i) * NP, Bv, sizeof(double) * NP);
             const double Dd = (1.0 + lambda_depth) * D;
@@ -2508,7 +2580,10 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
                 }
         }
         for (int s = 0; s < S; s++)
-            for (int j = 0; j < 6; j++) g_xi[6 * (s * B + b) + j] += a_f * gxi[6 * s + j];
+            for (int j = 0; j < 6; j++) {
+                g_xi[6 * (s * B + b) + j] += a_f * gxi[6 * s + j];
+                if (ab) ab->g_xi_abs[6 * (s * B + b) + j] += a_f * gxi_abs[6 * s + j];
+            }
         if (Hj && gj)
             for (int j = 0; j < NP; j++) {
                 gj[(size_t)b * NP + j] = g_xi[6 * ((j / 6) * B + b) + (j % 6)] + gs[j];
@@ -2525,6 +2600,7 @@ static void linearize_dense_ref(int H, int W, int B, int S, const real *tgt, con
     for (int m = 0; m < SB; m++) { free(px[m]); free(rec[m]); }
     free(px); free(rec); free(diff); free(valid); free(Wm); free(mask); free(margin); free(imask); free(ext);
     free(gx_adj); free(Lam); free(own); free(gxi); free(Hxx); free(Sm); free(gs); free(pri_g); free(pri_D); free(sig); free(sig0);
+    free(ext_abs); free(adj_abs); free(own_abs); free(pri_abs); free(gxi_abs);
 }
 
 static void dref_auto_err(int H, int W, int B, int S, const real *tgt, const real *srcs, const orc_opts *op, real *ae /* [2SB][n] */, const real **aep) {
@@ -2537,11 +2613,17 @@ static void dref_auto_err(int H, int W, int B, int S, const real *tgt, const rea
     }
 }
 
-/* one linearisation at given poses: the loss, its gradients, the Gauss-Newton blocks (tests: reference autograd pin, golden G13) */
-void orc_linearize_dense_ref(int H, int W, int B, int S, const real *tgt, const real *srcs, const real *depth_t, const real *depth_s, const real *depth0,
-                             const real *K, const orc_opts *op, int argmin, double w_init, double min_depth, double max_depth, double lambda_depth,
-                             const double *pose /* [2SB][6] */, double *scal /* [7]: loss, L_fwd, L_inv, L_dc, L_init, K_f, K_i */, double *g_xi, double *g_rho,
-                             double *Hj, double *gj, double *Dq, double *Bq, double *Hi, double *gi, double *g_rho_s /* [SB][n] or NULL */) {
+/* one linearisation at given poses: the loss, its gradients, the Gauss-Newton blocks (tests: reference autograd pin, golden G13).
+ * bits [2SB][n] or NULL: under the engine's decisions of this ONE linearisation (tcsfm_linearize_dense_window under tcsfm_debug_trace), as
+ * orc_refine_dense_ref replays an iterate -- the source maps' gradient included; the flip statistics book it as linearisation 0.
+ * g_rho_abs [B][n], g_xi_abs [2SB][6], g_rho_s_abs [SB][n] (with g_rho_s), ntap [B][n], ntap_s [SB][n] (with g_rho_s), mask_out [2SB][n]: see
+ * dref_abs; all or none.
+ * scal [8]: loss, L_fwd, L_inv, L_dc, L_init, K_f, K_i, the inverse pairs' share of L_dc. */
+void orc_linearize_dense_ref_forced(int H, int W, int B, int S, const real *tgt, const real *srcs, const real *depth_t, const real *depth_s, const real *depth0,
+                                    const real *K, const orc_opts *op, int argmin, double w_init, double min_depth, double max_depth, double lambda_depth,
+                                    const double *pose /* [2SB][6] */, const unsigned short *bits, double *scal, double *g_xi, double *g_rho,
+                                    double *Hj, double *gj, double *Dq, double *Bq, double *Hi, double *gi, double *g_rho_s /* [SB][n] or NULL */,
+                                    double *g_rho_abs, double *g_xi_abs, double *g_rho_s_abs, double *ntap, double *ntap_s, double *mask_out /* [2SB][n] */) {
     const int n = H * W, SB = S * B;
     real *ae = (real *)malloc(sizeof(real) * (size_t)2 * SB * n);
     const real **aep = (const real **)malloc(sizeof(real *) * 2 * SB);
@@ -2549,18 +2631,31 @@ void orc_linearize_dense_ref(int H, int W, int B, int S, const real *tgt, const 
     dref_auto_err(H, W, B, S, tgt, srcs, op, ae, aep);
     for (int m = 0; m < 2 * SB; m++) orc_pose_to_T(pose + 6 * m, T + 12 * m);
     dref_scal sc;
-    linearize_dense_ref(H, W, B, S, tgt, srcs, depth_t, depth_s, depth0, K, op, argmin, w_init, min_depth, max_depth, lambda_depth, T, aep, NULL, &sc,
+    dref_abs ab = {g_rho_abs, g_xi_abs, g_rho_s ? g_rho_s_abs : NULL, ntap, g_rho_s ? ntap_s : NULL, mask_out, 0.0};
+    g_dref_abs = g_rho_abs ? &ab : NULL;
+    g_lin_idx = bits ? 0 : -1;
+    linearize_dense_ref(H, W, B, S, tgt, srcs, depth_t, depth_s, depth0, K, op, argmin, w_init, min_depth, max_depth, lambda_depth, T, aep, bits, &sc,
                         g_xi, g_rho, Hj, gj, Dq, Bq, Hi, gi, g_rho_s, NULL);
+    g_lin_idx = -1;
+    g_dref_abs = NULL;
     if (op->w_pose_consist > 0) {      /* l_pose_consist (optimizer.py:95-96): value and the gradient w.r.t. every pair's left perturbation (pinned on golden G13 `full_pc`) */
         for (int m = 0; m < 2 * SB; m++) {
             double pc, pg[6], pH[36];
             pose_consist_term(T + 12 * m, T + 12 * (m < SB ? m + SB : m - SB), op->w_pose_consist / (6.0 * SB), op->irls_eps, &pc, pg, pH);
             sc.loss += pc;
-            for (int i = 0; i < 6; i++) g_xi[6 * m + i] += pg[i];
+            for (int i = 0; i < 6; i++) { g_xi[6 * m + i] += pg[i]; if (g_xi_abs) g_xi_abs[6 * m + i] += fabs(pg[i]); }
         }
     }
     scal[0] = sc.loss; scal[1] = sc.L_fwd; scal[2] = sc.L_inv; scal[3] = sc.L_dc; scal[4] = sc.L_init; scal[5] = sc.Kf; scal[6] = sc.Ki;
+    if (g_rho_abs) scal[7] = ab.L_dc_inv;
     free(ae); free(aep); free(T);
+}
+void orc_linearize_dense_ref(int H, int W, int B, int S, const real *tgt, const real *srcs, const real *depth_t, const real *depth_s, const real *depth0,
+                             const real *K, const orc_opts *op, int argmin, double w_init, double min_depth, double max_depth, double lambda_depth,
+                             const double *pose /* [2SB][6] */, double *scal /* [7]: loss, L_fwd, L_inv, L_dc, L_init, K_f, K_i */, double *g_xi, double *g_rho,
+                             double *Hj, double *gj, double *Dq, double *Bq, double *Hi, double *gi, double *g_rho_s /* [SB][n] or NULL */) {
+    orc_linearize_dense_ref_forced(H, W, B, S, tgt, srcs, depth_t, depth_s, depth0, K, op, argmin, w_init, min_depth, max_depth, lambda_depth, pose, NULL,
+                                   scal, g_xi, g_rho, Hj, gj, Dq, Bq, Hi, gi, g_rho_s, NULL, NULL, NULL, NULL, NULL, NULL);
 }
 
 /* Gauss-Newton on the reference loss: n_iters x { linearise ; joint step of every target's (poses, depth map) ; step of every

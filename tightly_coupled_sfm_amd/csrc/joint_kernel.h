@@ -211,7 +211,9 @@ __device__ __forceinline__ void dense_joint_body(const LinParams &P, const Joint
             tap4_lerp(S.t, val, gx, gy);
             const bool oob = S.g.oobx || S.g.ooby;
             float pd = c.es * val.w, cd = S.g.Z;
-            float Wt = 1.f - clamp01(fabsf(cd - pd) * frcp(cd + pd));
+            // pd == 0 (the sample lies in the zero padding as a whole): |cd - pd| / (cd + pd) is exactly 1 and the weight exactly 0, as the
+            // reference's division has it -- cd * rcp(cd) may be 1 - 2^-24, which left 6e-8 of a photometric term on pixels that carry none
+            float Wt = pd == 0.f ? 0.f : 1.f - clamp01(fabsf(cd - pd) * frcp(cd + pd));
             if (write) {
                 float Wuse = Wt;
                 if (REF && ref_w0) {            // the same thread stages the same position for every source: no barrier needed
