@@ -692,6 +692,7 @@ int tcsfm_lane_probe(tcsfm_handle h, int *serial, float *one_stream_ms, float *t
  * allocations checked (-1: guards are off), *n_damaged = how many have a damaged band.  The GPU test suite runs with the guards on. */
 int tcsfm_debug_check_guards(int *n_allocations, int *n_damaged);
 /* ... and its self-test: writes four bytes past the end of a scratch allocation of its own and says whether the bands caught it
+ * AND the check an entry runs over allocations it frees itself (tcsfm_debug_solve) counted that allocation and not an intact one
  * (*detected = 1 / 0; -1: guards are off) */
 int tcsfm_debug_guard_selftest(int *detected);
 /* Read-out of the PoseNet's most recent evaluation on `pn`, for layer-by-layer tests (layer = 1..7):
@@ -992,6 +993,43 @@ int tcsfm_debug_trace(tcsfm_handle h, uint16_t *bits, int64_t bits_capacity, int
 /* Diagnostic builds: 100 MHz wall-clock stamps of the phases of the last k_solve launch of pair 0 (zeros unless the
  * handle was created with TCSFM_DEBUG_STAMPS set in the environment). */
 int tcsfm_debug_stamps(tcsfm_handle h, long long out[8]);
+/* Test hook: ONE launch of a production pose solve kernel on records and optimiser state the caller gives (tests/test_gpu_solve_exact.py
+ * compares it with exact arithmetic).  Every array is HOST memory; the entry copies them into device allocations of its own (not the
+ * handle's scratch), launches on the handle's stream, synchronises once and copies every output array back WHOLE -- the caller fills them
+ * with a sentinel beforehand and sees what the kernel left alone.  variant: 0 k_solve, 1 k_solve_lean, 2 / 3 the pair role of
+ * k_solve_front without / with the pose-consistency code.  np (6 / 7), has_dc, the solver, the chart, the damping schedule, prior_scale
+ * and b_dc = w_dc / (H W) come from `opts` and the handle as in a refine call; mode: 0 iteration step, 1 final LM cost check, 2 export of
+ * the normal equations.  `state` and `pconst` hold the library's PairState / PairConst structs (sizes: tcsfm_debug_solve_layout).
+ * Anything that would index outside the given arrays or reach a branch the variant has compiled out is refused with TCSFM_E_ARG before
+ * anything is launched (tcsfm_last_error says what).  With TCSFM_DEBUG_GUARDS=1 the guard bands of the entry's own allocations are read back
+ * before they are freed: a launch that wrote outside them makes the call return TCSFM_E_HIP (tcsfm_debug_check_guards sees live
+ * allocations only). */
+typedef struct tcsfm_debug_solve_args {
+    int32_t variant, N, ngrp, mode, it;
+    int32_t n_alloc;              /* pairs every per-pair array below holds (>= N): pairs N .. n_alloc - 1 are never touched */
+    int32_t rule, grp_fwd, n_pairs;
+    int32_t norm_n, norm_Bt, norm_B;                      /* norms [norm_n][2] */
+    int32_t pc_np, pc_self0, pc_part0, pose_lin_pairs;    /* pose_lin [2][pose_lin_pairs][12] */
+    int32_t c_ncall, c_B, c_S, c_n0;
+    int32_t c_len[16];            /* pairs the per-call arrays hold */
+    double scale_fwd, scale_inv, w_pc, pc_eps;
+    const float *records;         /* [n_alloc][ngrp][nacc] */
+    const int32_t *norms;         /* or NULL: the counts are summed from the records */
+    void *state;                  /* [n_alloc] PairState, in and out */
+    void *pconst;                 /* [n_alloc] PairConst, in and out */
+    double *lin_out;              /* [n_alloc][np np + np + 4] or NULL */
+    double *delta_out;            /* [n_alloc][8] or NULL */
+    int32_t *accept_out, *trace_decide;   /* [n_alloc] or NULL */
+    float *pose_out;              /* [n_alloc][6] or NULL (NULL: no launch emits a pose) */
+    float *log_scale_out;         /* [n_alloc] or NULL */
+    float *c_pose_out[16];        /* c_ncall > 0: [c_len[i]][6] per call */
+    float *c_ls_out[16];          /*              [c_len[i]] per call, or NULL */
+    float *stats;                 /* [n_alloc][n_iters + 1][TCSFM_NSTAT] or NULL */
+    double *pose_lin;             /* in and out, or NULL */
+} tcsfm_debug_solve_args;
+int tcsfm_debug_solve(tcsfm_handle h, const tcsfm_opts *opts, tcsfm_debug_solve_args *args);
+/* sizeof(PairState), sizeof(PairConst) as the library was compiled (host, no GPU needed) */
+int tcsfm_debug_solve_layout(int *sizeof_pair_state, int *sizeof_pair_const);
 
 /* ---- SE(3) utilities, host, double (replace liegroups.SE3 at data/kitti_loader_stereo.py:129-147,
  *      validate.py:65-71; liegroups is an absent third-party dependency, version unpinned) ---------- */

@@ -1,0 +1,187 @@
+"""Host-only conditions of tests/solve_exact_inputs.py: every case is what its name claims, the struct mirrors have the library's sizes, the
+judge passes the clean float64 twin on every case and fails each planted fault of the twin on at least one."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import solve_exact_inputs as SX
+
+
+def _twin_with(fault):
+    return lambda c: SX.twin(c, fault)
+
+
+def test_struct_mirrors_have_the_librarys_sizes():
+    from tightly_coupled_sfm_amd import build, _lib
+    build.build()
+    ss, sc = _lib.debug_solve_layout()
+    assert (ss, sc) == (C.sizeof(_lib.PairState), C.sizeof(_lib.PairConst)) == (SX.STATE_DT.itemsize, SX.CONST_DT.itemsize)
+    for name, _ in _lib.PairState._fields_:
+        assert getattr(_lib.PairState, name).offset == SX.STATE_DT.fields[name][1], name
+    for name, _ in _lib.PairConst._fields_:
+        assert getattr(_lib.PairConst, name).offset == SX.CONST_DT.fields[name][1], name
+
+
+def test_args_struct_matches_the_header():
+    """tcsfm_debug_solve_args as the C compiler lays it out against the ctypes mirror"""
+    import os, subprocess, tempfile
+    from conftest import REPO
+    from tightly_coupled_sfm_amd import _lib
+    names = ["c_len", "scale_fwd", "records", "state", "lin_out", "trace_decide", "c_pose_out", "c_ls_out", "stats", "pose_lin"]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "tcsfm.h"\nint main(void){printf("%zu", sizeof(tcsfm_debug_solve_args));' + \
+          "".join(f'printf(" %zu", offsetof(tcsfm_debug_solve_args, {n}));' for n in names) + "return 0;}"
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "s.c"), "w").write(src)
+        subprocess.check_call(["gcc", "-std=c99", "-I" + os.path.join(REPO, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
+        got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
+    assert got == [C.sizeof(_lib.DebugSolveArgs)] + [getattr(_lib.DebugSolveArgs, n).offset for n in names]
+    assert _lib.DebugSolveArgs.c_pose_out.size == SX.TC_MAX_COAL * C.sizeof(C.c_void_p)
+
+
+def test_split_is_derived_from_the_live_accumulators():
+    assert [SX.split(0, n, d) for n in (6, 7) for d in (False, True)] == [(8, 32), (4, 32), (4, 32), (2, 32)]
+    assert [SX.split(2, n, d) for n in (6, 7) for d in (False, True)] == [(32, 16), (16, 16), (16, 16), (8, 16)]
+    assert SX.sweep_ngrp(0, 6, False) == [1, 2, 7, 8, 9, 240, 255, 256, 257, 515] and max(SX.sweep_ngrp(1, 6, False)) == 1027
+
+
+def test_sweep_records_are_distinct_enough():
+    """one record dropped, doubled or taken from the neighbouring pair moves every sum by more than 1000 times its bound"""
+    for c in SX.sweep_cases():
+        L = SX.layout(c.np)
+        live = SX.live_accs(c.np, c.has_dc)
+        v = c.rec[:c.N].astype(np.float64)
+        dead = [a for a in range(L.NACC) if a not in live]
+        assert np.all(np.isnan(c.rec[c.N:])) and np.all(np.isnan(c.rec[:c.N][:, :, dead])) and np.all(np.isfinite(v[:, :, live]))
+        bound = (c.ngrp + 4) * 2.0 ** -53 * np.abs(v).sum(axis=1, keepdims=True)
+        assert np.all(np.abs(v[:, :, live]) > 1000 * bound[:, :, live]), c.name
+        assert np.all(np.abs(v - np.roll(v, -1, axis=0))[:, :, live] > 1000 * bound[:, :, live]), c.name
+        cnt = v[:, :, L.S + 1]
+        assert np.all(cnt == np.round(cnt)) and np.all(cnt > 0)
+
+
+def test_cases_are_what_their_names_claim():
+    conds = []
+    for c in SX.all_cases():
+        ex = SX.exact(c)
+        e, S = ex[0], c.state[0]
+        for cl in c.claims:
+            key, val = (cl, None) if isinstance(cl, str) else cl
+            if key == "tie":
+                assert e.cost == SX.F(float(S["cost_cur"])) and not e.decide, c.name
+            elif key in ("accept", "reject"):
+                assert all(x.decide == (key == "accept") for x in ex), c.name
+            elif key == "lam_same":
+                assert e.lam_out == S["lam"], c.name
+            elif key == "lam_down":
+                assert e.lam_out == S["lam"] * c.lam_down > c.lam_min, c.name
+            elif key == "lam_clamped":
+                assert S["lam"] * c.lam_down < c.lam_min == e.lam_out, c.name
+            elif key == "bad_pivot":
+                assert not e.ok and min(float(e.Hs[i][i]) for i in range(c.np)) < 0 and all(x == 0 for x in e.d), c.name
+            elif key == "zero_step":
+                assert e.ok and all(x == 0 for x in e.d), c.name
+            elif key == "nmask0":
+                assert e.nmask == 0 and e.an == 0, c.name
+            elif key == "group0":
+                assert ex[0].an == 0 and ex[1].an == 0 and ex[2].an > 0, c.name
+            elif key == "gn_final":
+                assert all(x.final for x in ex), c.name
+            elif key == "scale_step":
+                assert e.d[6] != 0 and S["stry"] != S["s0"], c.name
+            elif key in ("cond", "cond_scaled", "cond_beyond"):
+                k = SX.cond_of(c, 0)
+                assert val / 3 <= k <= val * 300, (c.name, k)
+                if key == "cond_scaled":
+                    H = np.array([[float(x) for x in r] for r in e.Hs])
+                    assert H[3, 3] / H[0, 0] > 1e3, c.name
+                if c.judged:
+                    conds.append(k)
+                else:
+                    assert k > SX.COND_JUDGED_MAX
+            elif key == "branch":
+                t2 = sum(float(x) ** 2 for x in e.d[3:6])
+                assert (t2 < 0.09) == (val == "series"), (c.name, t2)
+            elif key == "step":
+                assert max(abs(float(a) - b) for a, b in zip(e.d, val)) < 1e-20, c.name
+            elif key == "sin":
+                assert c.state[0]["Ttry"][2] == val and (abs(1 - abs(val)) <= 1e-7), c.name
+            elif key == "pc":
+                assert SX.pc_on(c) and c.w_pc > 0
+                if "unsliced" in c.name:
+                    r = np.abs(e.pc_r)
+                    assert r.min() < c.pc_eps < r.max(), (c.name, r)
+            elif key == "sweep":
+                pass
+            else:
+                raise AssertionError(cl)
+    assert min(conds) < 30 and max(conds) >= 100 * SX.GOLDEN_COND_MAX and max(conds) <= SX.COND_JUDGED_MAX
+    # the steps either side of se3_exp's switch are neighbouring doubles
+    assert SX.X_LO * SX.X_LO < 0.09 <= SX.X_HI * SX.X_HI and SX.X_HI == np.nextafter(SX.X_LO, 1)
+    by = SX.by_name()
+    assert by["rule norms1 scale 1.0"].norms[1, 1] == 0 and SX.exact(by["rule norms1 scale 1.0"])[3].an == 0
+    assert by["coalesced n0 0 np7"].c_ls == (True, False)
+    assert by["extract sin 1 + ulp"].state[0]["Ttry"][2] > 1
+    assert {c.it & 1 for c in SX.pc_cases()} == {0, 1}
+
+
+def test_judge_passes_the_clean_twin():
+    for c in SX.all_cases():
+        fails, _ = SX.judge_case(c, SX.clean_twin)
+        assert not fails, fails[:3]
+        if SX.wants_m8_export(c):
+            assert not SX.check_m8_export(c, SX.twin)
+        if "sweep" in c.claims:
+            assert not SX.check_alone(c, SX.twin)
+    assert sum(SX.wants_m8_export(c) for c in SX.all_cases()) >= 40 and any(SX.wants_m8_export(c) and c.np == 7 for c in SX.all_cases())
+
+
+FAULTS = {
+    "drop_boundary": lambda c: "sweep" in c.claims and c.ngrp in (257, 129, 65, 513),
+    "neighbour": lambda c: "sweep" in c.claims and c.ngrp in (2, 240),
+    "dead_acc": lambda c: "sweep" in c.claims and not c.has_dc and c.ngrp == 2,
+    "rcp40": lambda c: c.name in ("sweep v0 np6 dc0 ngrp240", "cond 1e+00 np6"),
+    "undamped": lambda c: c.name.startswith("lm accept np") or c.name.startswith("lm reject"),
+    "no_clamp": lambda c: "lam_clamped" in c.claims,
+    "tie_accept": lambda c: "tie" in c.claims,
+    "m8_not_restored": lambda c: c.name.startswith("lm reject"),
+    "exp_right": lambda c: c.name.startswith("gn it"),
+    "pose_nonfinal": lambda c: c.name.startswith("gn it0") or c.name.startswith("lm accept np"),
+    "wrong_half": lambda c: c.name.startswith("pc v"),
+    "partner_off": lambda c: c.name.startswith("pc v"),
+}
+
+
+@pytest.mark.parametrize("fault", sorted(FAULTS))
+def test_judge_fails_every_planted_fault(fault):
+    cases = [c for c in SX.all_cases() if FAULTS[fault](c)]
+    assert cases
+    caught = [c.name for c in cases if SX.judge_case(c, _twin_with(fault))[0]]
+    assert caught, f"the judge passed the twin with fault {fault!r} on {[c.name for c in cases]}"
+    if fault in ("tie_accept", "wrong_half", "partner_off", "no_clamp", "exp_right", "m8_not_restored"):
+        assert caught == [c.name for c in cases], (fault, caught)          # (these are caught on EVERY case that reaches the branch)
+
+
+def test_refusal_cases_break_one_rule_each():
+    names = [n for n, _, _ in SX.refusal_cases()]
+    assert len(names) == len(set(names)) >= 18
+    assert len({w for _, _, w in SX.refusal_cases()}) >= 13
+
+
+def test_golden_condition_number_is_the_oracles(oracle64):
+    """GOLDEN_COND_MAX recomputed: the largest cond(H) of the float64 oracle over the golden pairs whose H can have full rank"""
+    from conftest import load_golden
+    from oracle.oracle import default_opts
+    worst = 0.0
+    for name in ("s8x16", "s24x40", "s48x160"):
+        g = load_golden(name)
+        for pose in g["poses"]:
+            for npar in (6, 7):
+                lin = oracle64.linearize(g["tgt"], g["src"], g["depth_t"], g["depth_s"], pose, g["K"], default_opts(nparam=npar))
+                if 3 * lin["n_mask"] < npar:          # (three residual rows per masked pixel: an empty or one-pixel mask)
+                    continue
+                H = lin["H"].copy()
+                if npar == 7:
+                    H[6, 6] += 2 * default_opts().prior_scale
+                worst = max(worst, float(np.linalg.cond(H)))
+    assert abs(worst / SX.GOLDEN_COND_MAX - 1) < 1e-3, worst

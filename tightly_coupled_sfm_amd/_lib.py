@@ -104,6 +104,33 @@ STAT_POSE = 4
 NSTAT = 10        # cost, cost_photo, n_mask, lambda, pose[6]  (include/tcsfm.h TCSFM_STAT_*)
 
 _P = C.c_void_p
+
+
+class PairState(C.Structure):
+    """mirror of struct PairState (csrc/kernels.h); its size is checked against tcsfm_debug_solve_layout"""
+    _fields_ = [("Tcur", C.c_double * 12), ("Ttry", C.c_double * 12), ("scur", C.c_double), ("stry", C.c_double), ("s0", C.c_double),
+                ("lam", C.c_double), ("cost_cur", C.c_double), ("M8", C.c_double * 64), ("K", C.c_double * 9),
+                ("have_cur", C.c_int32), ("pad", C.c_int32)]
+
+
+class PairConst(C.Structure):
+    """mirror of struct PairConst (csrc/kernels.h)"""
+    _fields_ = [("A", C.c_float * 9), ("kt", C.c_float * 3), ("R", C.c_float * 9), ("t", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("ki0", C.c_float), ("ki2", C.c_float), ("ki4", C.c_float), ("ki5", C.c_float),
+                ("es", C.c_float), ("img", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
+class DebugSolveArgs(C.Structure):
+    """mirror of struct tcsfm_debug_solve_args"""
+    _fields_ = [(k, C.c_int32) for k in ("variant", "N", "ngrp", "mode", "it", "n_alloc", "rule", "grp_fwd", "n_pairs", "norm_n", "norm_Bt", "norm_B",
+                                         "pc_np", "pc_self0", "pc_part0", "pose_lin_pairs", "c_ncall", "c_B", "c_S", "c_n0")] + \
+               [("c_len", C.c_int32 * 16)] + \
+               [(k, C.c_double) for k in ("scale_fwd", "scale_inv", "w_pc", "pc_eps")] + \
+               [(k, _P) for k in ("records", "norms", "state", "pconst", "lin_out", "delta_out", "accept_out", "trace_decide", "pose_out", "log_scale_out")] + \
+               [("c_pose_out", _P * 16), ("c_ls_out", _P * 16), ("stats", _P), ("pose_lin", _P)]
+
+
 _SIGNATURES = {
     "tcsfm_lane_probe": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "tcsfm_debug_check_guards": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -211,6 +238,8 @@ _SIGNATURES = {
     "tcsfm_profile_kernel_busy": (C.c_int, [_P, _P, _P]),
     "tcsfm_debug_stamps": (C.c_int, [_P, _P]),
     "tcsfm_debug_trace": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64]),
+    "tcsfm_debug_solve": (C.c_int, [_P, C.POINTER(Opts), C.POINTER(DebugSolveArgs)]),
+    "tcsfm_debug_solve_layout": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tcsfm_pose_to_matrix": (None, [_P, _P]),
     "tcsfm_matrix_to_pose": (None, [_P, _P]),
     "tcsfm_se3_exp": (None, [_P, _P]),
@@ -251,6 +280,13 @@ def check_guards():
     if rc != 0:
         raise RuntimeError(f"tcsfm_debug_check_guards failed ({rc})")
     return n.value, bad.value
+
+
+def debug_solve_layout():
+    """(sizeof(PairState), sizeof(PairConst)) as the library was compiled (tcsfm_debug_solve_layout; no GPU needed)"""
+    a, b = C.c_int(0), C.c_int(0)
+    load().tcsfm_debug_solve_layout(C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 def default_opts(**kw) -> Opts:

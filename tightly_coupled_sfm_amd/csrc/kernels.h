@@ -347,7 +347,7 @@ struct CoalTab {
     const float *ls[TC_MAX_COAL];       // per call: initial log depth-scales of its pairs (TCSFM_REFINE_POSE_SCALE), or null (0)
 };
 struct CoalIdx { int call, bl, s, inv, li; };      // li: the pair's index in ITS call's stacked order
-__device__ __forceinline__ CoalIdx coal_index(int ncall, int cB, int cS, int n) {
+__host__ __device__ __forceinline__ CoalIdx coal_index(int ncall, int cB, int cS, int n) {
     const int Bt = ncall * cB, SB = cS * Bt;
     CoalIdx r;
     r.inv = n >= SB;

@@ -359,6 +359,13 @@ class Engine:
         self._trace = None
         return b.cpu().numpy().view(np.uint16), d.cpu().numpy()
 
+    def debug_solve(self, opts, args) -> int:
+        """test hook (tcsfm_debug_solve): ONE launch of a production pose solve kernel on the host records and state of `args`
+        (_lib.DebugSolveArgs; numpy arrays behind its pointers, outputs filled in place).  -> the return code: 0, or TCSFM_E_ARG for a
+        refused launch (last_error() says why; nothing ran)"""
+        self._bind()
+        return int(self.lib.tcsfm_debug_solve(self._h, C.byref(opts), C.byref(args)))
+
     @property
     def dev(self) -> torch.device:
         return torch.device("cuda", self.device)
