@@ -87,7 +87,7 @@ def frames_only(args):
     init, refined = pose_net.odometry_sequence(frames, None, K, opts, sources=S, iterations=4, target_pos=-1,
                                                **({} if source_size is None else {"source_size": source_size}),
                                                **({} if args.cam_height is None else {"cam_height": args.cam_height / DEPTH_UNIT}),
-                                               **({"disparity": "post"} if args.save_disps else {}))
+                                               **({"disparity": "post"} if args.save_disps or args.gt_depths else {}))
     dt = time.perf_counter() - t0
     print(f"{args.frames} frames -> {refined.shape[0]} windows of {2 * S} directed pairs in {dt * 1e3:.1f} ms (first call: allocations included)")
     with np.printoptions(precision=4, suppress=True):
@@ -105,6 +105,12 @@ def frames_only(args):
         disps = eng.sequence_disparities()
         np.save(args.save_disps, disps)
         print(f"disparities: float64 {list(disps.shape)}, {disps.min():.4f} .. {disps.max():.4f} -> {args.save_disps}")
+    if args.gt_depths:      # the paper's depth table: evaluate_depth_eigen.py's loop on the device, over the planes the call kept -- no plane
+        # is fetched; the ground truth (one float32 plane per frame, sizes may differ) goes up in groups of one size
+        from tightly_coupled_sfm_amd import evaluate_depth_eigen as ev
+        gt_depths = ev.load_gt_depths(args.gt_depths)
+        n = min(len(gt_depths), args.frames)
+        print(ev.format_table(ev.evaluate(None, list(gt_depths[:n]), eng, benchmark="eigen", median_scaling=True)))
 
 
 DEPTH_UNIT = 30.0       # the reference's depth unit in metres (run_sequential_optimization.py:224)
@@ -127,6 +133,10 @@ def main():
     ap.add_argument("--save-disps", metavar="FILE", default="",
                     help="with --frames-only: keep every frame's flip-post-processed disparity inside the call (disparity=\"post\": "
                          "tcsfm_sequence_disparity) and write them as the .npy file paper_plots_and_data/evaluate_depth_eigen.py loads")
+    ap.add_argument("--gt-depths", metavar="FILE.npz", default="",
+                    help="with --frames-only: the reference's gt_depths.npz (loaded as paper_plots_and_data/evaluate_depth_eigen.py loads it); "
+                         "the disparities kept inside the call are evaluated against it on the device (tcsfm_sequence_depth_eval) and the "
+                         "script's table is printed")
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--sources", type=int, default=1, choices=(1, 2))
     ap.add_argument("--gn-iters", type=int, default=8)
@@ -140,6 +150,8 @@ def main():
         ap.error("--cam-height goes with --frames-only (the per-window loop below gets its scale from DepthOptimizer)")
     if args.save_disps:
         ap.error("--save-disps goes with --frames-only (the per-window loop below has helpers.get_disp_for_eigen)")
+    if args.gt_depths:
+        ap.error("--gt-depths goes with --frames-only (it evaluates the disparities a frames-only call keeps)")
     if args.camera_size:
         ap.error("--camera-size goes with --frames-only (for frames held on the device: Engine.resize_u8)")
     if args.u8_frames:

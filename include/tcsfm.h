@@ -181,7 +181,8 @@ enum { TCSFM_STAT_COST = 0, TCSFM_STAT_COST_PHOTO = 1, TCSFM_STAT_NMASK = 2, TCS
  * bytes with a frame source set (tcsfm_sequence_frame_source).  tcsfm_resize_u8 is declared and behaves like tcsfm_frames_from_u8:
  * "tcsfm_resize_u8: dst overlaps src".  tcsfm_disp_post_process and tcsfm_depthnet_disp_for_eigen are declared the same way (float32 in,
  * float64 out) and honour nothing either: "tcsfm_disp_post_process: out overlaps l_disp" (or r_disp_mirrored),
- * "tcsfm_depthnet_disp_for_eigen: out overlaps imgs". */
+ * "tcsfm_depthnet_disp_for_eigen: out overlaps imgs".  So are tcsfm_depth_eval ("tcsfm_depth_eval: metrics_out overlaps disp" or gt) and
+ * tcsfm_sequence_depth_eval, whose two arrays are the host's ("tcsfm_sequence_depth_eval: metrics_out overlaps gt"). */
 
 /* ---- lifetime ------------------------------------------------------------------------------- */
 
@@ -938,6 +939,51 @@ int tcsfm_disp_post_process(tcsfm_handle h, const tcsfm_opts *o, int N, const vo
 int tcsfm_depthnet_disp_for_eigen(tcsfm_depthnet *dn, const tcsfm_opts *o, int N, const void *imgs /* float32 [N,3,H,W] */,
                                   void *out /* float64 [N,H,W] */);
 int tcsfm_flip_ramp(int W, void *l_mask_out /* double [W] */);
+/* Evaluation.  What the reference does with those planes is paper_plots_and_data/evaluate_depth_eigen.py:133-177: resize each plane to
+ * the ground truth's size, depth_unit / disp, mask and crop, median scaling, clip, seven error metrics per frame.  One launch evaluates N
+ * frames, one workgroup per frame; no resized plane is written and, for the sequence form, no plane leaves the device.  Per frame
+ * TCSFM_NEVAL doubles: abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, ratio (1.0 with median scaling off), n_valid (masked pixels),
+ * n_median (masked pixels with gt < max_depth: the median's subset).  n_valid == 0: the seven metrics are NaN; n_median == 0 with
+ * scaling on: ratio and the metrics are NaN.  The arithmetic, float64 with every operation rounded on its own:
+ *   resize   bilinear, half-pixel centres, edges clamped: per axis scale = 1.0 / (n_dst / n_src), f = float32((d + 0.5) * scale - 0.5),
+ *            s = floor(f), f = float32(f - s), (s < 0: s = 0, f = 0), (s >= n_src - 1: s = n_src - 1, f = 0), weights float32(1 - f) and
+ *            f promoted to double, second tap min(s + 1, n_src - 1); the horizontal pass first.  This restates OpenCV's INTER_LINEAR; bit
+ *            equality with cv2.resize is not claimed, and the exact-2x shrink (where OpenCV averages areas) is not special-cased.  A
+ *            float32 plane is promoted first (exact).  Disparities must be positive and finite.
+ *   mask     TCSFM_EVAL_EIGEN: gt > min_depth && gt < max_depth (float32 compares) inside rows [int(0.40810811 gt_h), int(0.99189189 gt_h))
+ *            and columns [int(0.03594771 gt_w), int(0.96405229 gt_w)) (tcsfm_depth_eval_crop: y0, y1, x0, x1; host, no GPU);
+ *            TCSFM_EVAL_EIGEN_BENCHMARK: gt > 0, the whole plane.
+ *   scaling  ratio = float64(median(gt)) / median(pred) over the subset, np.median's: the middle element or the mean of the two middle
+ *            ones in the array's own type (float32 for gt); pred *= ratio.  Then np.clip(pred, 0, max_depth), pred < min_depth -> min_depth.
+ *   metrics  compute_errors on float64(gt); log(gt) is a float64 log (the reference's is a float32 one).  Sums in a fixed order: the
+ *            results are bit-reproducible and do not depend on lds_pairs.
+ * lds_pairs: how many masked pixels (each one (gt, pred) pair) the workgroup's list in LDS may hold (< 0: the default, its maximum); a
+ * frame with more scans its crop again in every pass, with the same results.
+ *   tcsfm_depth_eval           disp [N,H,W] (H, W the handle's) float32 (disp_is_f64 = 0) or float64, gt, metrics_out: DEVICE pointers;
+ *                              asynchronous on the handle's stream; o->host_ptrs must be 0.
+ *   tcsfm_sequence_depth_eval  planes first .. first + count - 1 of the store left by the LAST sequence call that ran with
+ *                              tcsfm_sequence_disparity on (PLAIN or POST) against HOST ground truth of ONE size (KITTI's sizes differ
+ *                              between drives: the caller groups frames by size); gt is staged in groups, the call returns synchronously.
+ *                              T, first, count: tcsfm_sequence_disparities' rules.
+ * Refused with TCSFM_E_ARG (tcsfm_last_error says why, nothing is launched, the outputs keep their contents): a NULL pointer, N < 1,
+ * gt_h or gt_w < 1, an unknown protocol, !(0 < min_depth < max_depth), a depth_unit that is not positive and finite, metrics_out
+ * overlapping an input ("overlapping arguments"); for the sequence form nothing kept, another T, a range outside [0, T). */
+#define TCSFM_EVAL_EIGEN 0
+#define TCSFM_EVAL_EIGEN_BENCHMARK 1
+#define TCSFM_NEVAL 10
+typedef struct tcsfm_depth_eval_opts {
+    int32_t protocol, median_scaling;
+    float min_depth, max_depth;
+    double depth_unit;
+    int32_t lds_pairs; /* <0: default */
+} tcsfm_depth_eval_opts;
+void tcsfm_depth_eval_default_opts(tcsfm_depth_eval_opts *e); /* EIGEN, 1, 1e-3, 80, 30.0, -1 */
+int tcsfm_depth_eval_crop(int protocol, int gt_h, int gt_w, int *crop_out /* 4 ints: y0, y1, x0, x1 */);
+int tcsfm_depth_eval(tcsfm_handle h, const tcsfm_opts *o, const tcsfm_depth_eval_opts *e, int N, int disp_is_f64,
+                     const void *disp /* DEVICE [N,H,W] */, int gt_h, int gt_w, const void *gt /* DEVICE float32 [N,gt_h,gt_w] */,
+                     void *metrics_out /* DEVICE double [N][TCSFM_NEVAL] */);
+int tcsfm_sequence_depth_eval(tcsfm_handle h, const tcsfm_depth_eval_opts *e, int T, int first, int count, int gt_h, int gt_w,
+                              const void *gt /* HOST float32 [count,gt_h,gt_w] */, void *metrics_out /* HOST double [count][TCSFM_NEVAL] */);
 int tcsfm_lane_wait(tcsfm_handle h, int lane);
 int tcsfm_lane_synchronize(tcsfm_handle h, int lane);
 int tcsfm_lane_event(tcsfm_handle h, int lane, void **event_out);

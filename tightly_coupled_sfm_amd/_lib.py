@@ -92,6 +92,14 @@ class Opts(C.Structure):
                 ("min_depth", C.c_float), ("max_depth", C.c_float), ("prior_scale", C.c_float), ("lambda_depth", C.c_float), ("prior_depth", C.c_float), ("window_rule", C.c_int32), ("dense_joint", C.c_int32), ("prior_init", C.c_float), ("depth_param", C.c_int32), ("w_pose_consist", C.c_float), ("w_smooth", C.c_float), ("free_source_depths", C.c_int32)]
 
 
+class DepthEvalOpts(C.Structure):
+    """mirror of struct tcsfm_depth_eval_opts"""
+    _fields_ = [("protocol", C.c_int32), ("median_scaling", C.c_int32), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("depth_unit", C.c_double), ("lds_pairs", C.c_int32)]
+
+
+EVAL_EIGEN, EVAL_EIGEN_BENCHMARK = 0, 1                      # tcsfm_depth_eval_opts.protocol
+NEVAL = 10        # abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, ratio, n_valid, n_median  (include/tcsfm.h TCSFM_NEVAL)
 SOLVER_GN, SOLVER_LM = 0, 1
 PARAM_SE3, PARAM_EULER = 0, 1
 REFINE_POSE, REFINE_POSE_SCALE = 0, 1
@@ -228,6 +236,10 @@ _SIGNATURES = {
     "tcsfm_disp_post_process": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P, _P]),
     "tcsfm_depthnet_disp_for_eigen": (C.c_int, [_P, C.POINTER(Opts), C.c_int, _P, _P]),
     "tcsfm_flip_ramp": (C.c_int, [C.c_int, _P]),
+    "tcsfm_depth_eval_default_opts": (None, [C.POINTER(DepthEvalOpts)]),
+    "tcsfm_depth_eval_crop": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "tcsfm_depth_eval": (C.c_int, [_P, C.POINTER(Opts), C.POINTER(DepthEvalOpts), C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    "tcsfm_sequence_depth_eval": (C.c_int, [_P, C.POINTER(DepthEvalOpts), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "tcsfm_lane_wait": (C.c_int, [_P, C.c_int]),
     "tcsfm_lane_synchronize": (C.c_int, [_P, C.c_int]),
     "tcsfm_lane_event": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
@@ -287,6 +299,27 @@ def debug_solve_layout():
     a, b = C.c_int(0), C.c_int(0)
     load().tcsfm_debug_solve_layout(C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+def depth_eval_opts(protocol="eigen", median_scaling=True, min_depth=1e-3, max_depth=80.0, depth_unit=30.0, lds_pairs=-1) -> DepthEvalOpts:
+    """tcsfm_depth_eval_default_opts with the given fields; protocol: "eigen", "eigen_benchmark" or the integer"""
+    e = DepthEvalOpts()
+    load().tcsfm_depth_eval_default_opts(C.byref(e))
+    names = {"eigen": EVAL_EIGEN, "eigen_benchmark": EVAL_EIGEN_BENCHMARK}
+    if isinstance(protocol, str) and protocol not in names:
+        raise ValueError(f"protocol must be 'eigen' or 'eigen_benchmark' (got {protocol!r})")
+    e.protocol = names[protocol] if isinstance(protocol, str) else int(protocol)
+    e.median_scaling, e.min_depth, e.max_depth = int(bool(median_scaling)), float(min_depth), float(max_depth)
+    e.depth_unit, e.lds_pairs = float(depth_unit), int(lds_pairs)
+    return e
+
+
+def depth_eval_crop(protocol, gt_h: int, gt_w: int):
+    """tcsfm_depth_eval_crop: (y0, y1, x0, x1) of the pixels the protocol looks at.  Host only."""
+    c = (C.c_int * 4)()
+    if load().tcsfm_depth_eval_crop(int(protocol), int(gt_h), int(gt_w), c) != 0:
+        raise ValueError(f"depth_eval_crop: unknown protocol {protocol} or a size below 1 ({gt_h} x {gt_w})")
+    return tuple(c)
 
 
 def default_opts(**kw) -> Opts:

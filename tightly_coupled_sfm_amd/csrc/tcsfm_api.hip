@@ -31,6 +31,7 @@
 #include "frames_u8_kernel.h"
 #include "resize_u8_kernel.h"
 #include "disp_post_kernel.h"
+#include "depth_eval_kernel.h"
 
 using namespace tc;
 
@@ -216,6 +217,11 @@ struct tcsfm_ctx {
     size_t seq_disp_bytes = 0;
     int seq_disp_T = 0, seq_disp_kept = TCSFM_SEQ_DISP_OFF;      // the last call's T (0: nothing kept) and mode, for tcsfm_sequence_disparities
     double *flip_ramp = nullptr;       // l_mask [W] of the flip post-processing on the device (flip_ramp_device), built on first use
+    // tcsfm_sequence_depth_eval: one group of staged ground truth and the call's metrics, grown when a call needs more
+    void *eval_gt_dev = nullptr;
+    size_t eval_gt_bytes = 0;
+    double *eval_out_dev = nullptr;
+    size_t eval_out_rows = 0;
     struct KOk { const float *p; int n; };
     KOk K_ok[4] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}};   // device intrinsics pointers (and counts) that already passed the pinhole check
     int K_ok_next = 0;
@@ -1470,7 +1476,7 @@ void tcsfm_destroy(tcsfm_handle h) {
                     h->jrec, h->jrec_acc, h->jblockrec, h->jdepth_acc, h->jstate, h->jdelta, h->jpart, h->jtick, h->dref_norms, h->dref_ext, h->dref_export, h->qres_rho, h->qres_rec, h->pose_lin, h->dref_smooth, h->jrec_src, h->jstate_src, h->jdelta_src, h->dref_ext_src, h->qres_rho_src, h->qres_rec_src,
                     h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept, h->dbg_stamps, h->wgrad_rec, h->wgrad_fix, h->wgrad_gmax, h->pgrad_fwd, h->pgrad_cot,
                     h->seq_fpack, h->seq_fdepth, h->pair_idx, h->seq_img, h->seq_depth, h->seq_pose_in, h->seq_pose_out, h->seq_ls_out, h->seq_K, h->seq_dense, h->seq_dense_tmp, h->seq_u8,
-                    h->seq_scale_keys, h->seq_scale_dev, h->seq_disp_dev, h->flip_ramp};
+                    h->seq_scale_keys, h->seq_scale_dev, h->seq_disp_dev, h->flip_ramp, h->eval_gt_dev, h->eval_out_dev};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &t : h->resize_tabs)
@@ -3867,6 +3873,7 @@ int tcsfm_profile_kernel_busy(tcsfm_handle h, double *ms_busy, int64_t *launches
 #include "posenet_wgrad_host.h"
 #include "posenet_grad_host.h"
 #include "optim_host.h"
+#include "depth_eval_host.h"
 
 void tcsfm_pose_to_matrix(const double pose[6], double T[12]) { tc::pose_to_T(pose, T); }
 void tcsfm_matrix_to_pose(const double T[12], double pose[6]) { tc::T_to_pose(T, pose); }

@@ -1059,6 +1059,40 @@ class Engine:
         assert got.value == mode
         return out
 
+    def depth_eval(self, disp: torch.Tensor, gt: torch.Tensor, protocol="eigen", median_scaling: bool = True, min_depth: float = 1e-3,
+                   max_depth: float = 80.0, depth_unit: float = 30.0, lds_pairs: int = -1) -> torch.Tensor:
+        """tcsfm_depth_eval: the per-frame evaluation of paper_plots_and_data/evaluate_depth_eigen.py on the device.  disp [N,H,W] (or
+        [N,1,H,W]) float32 or float64 CUDA: disparity planes at the engine's size; gt [N,gt_h,gt_w] float32 CUDA -> float64 [N,10]:
+        abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, ratio, n_valid, n_median per frame (include/tcsfm.h); on the engine's stream"""
+        if not isinstance(disp, torch.Tensor) or not disp.is_cuda or disp.dtype not in (torch.float32, torch.float64):
+            raise TypeError("disp must be a float32 or float64 CUDA tensor")
+        N = int(disp.shape[0])
+        d = disp.reshape(N, self.H, self.W).contiguous()
+        if gt.dim() != 3:
+            raise AssertionError("wrong size for gt, expected {}xgt_hxgt_w, got  {}".format(N, list(gt.shape)))
+        g = _chk(gt, (N, int(gt.shape[1]), int(gt.shape[2])), "gt")
+        self._bind()
+        out = torch.empty((N, _lib.NEVAL), dtype=torch.float64, device=d.device)
+        o, e = default_opts(), _lib.depth_eval_opts(protocol, median_scaling, min_depth, max_depth, depth_unit, lds_pairs)
+        self._call(self.lib.tcsfm_depth_eval(self._h, C.byref(o), C.byref(e), N, int(d.dtype == torch.float64), self._p(d), int(g.shape[1]),
+                                             int(g.shape[2]), self._p(g), self._p(out)))
+        return out
+
+    def sequence_depth_eval(self, gt: np.ndarray, first: int = 0, protocol="eigen", median_scaling: bool = True, min_depth: float = 1e-3,
+                            max_depth: float = 80.0, depth_unit: float = 30.0, lds_pairs: int = -1) -> np.ndarray:
+        """tcsfm_sequence_depth_eval: frames first .. first + len(gt) - 1 of the disparities the last sequence call kept with disparity=
+        ("plain" or "post"), evaluated on the device against gt, NumPy float32 [count,gt_h,gt_w] of ONE size -> NumPy float64 [count,10]
+        as depth_eval's.  The planes do not leave the device.  Raises when that call kept nothing."""
+        gt = np.ascontiguousarray(gt, dtype=np.float32)
+        if gt.ndim != 3 or gt.shape[0] < 1:
+            raise ValueError(f"gt must be [count,gt_h,gt_w] with count >= 1 (got {list(gt.shape)})")
+        T = (getattr(self, "_seq_disp", None) or (0, 0))[0]
+        out = np.empty((gt.shape[0], _lib.NEVAL), dtype=np.float64)
+        e = _lib.depth_eval_opts(protocol, median_scaling, min_depth, max_depth, depth_unit, lds_pairs)
+        self._call(self.lib.tcsfm_sequence_depth_eval(self._h, C.byref(e), T, int(first), int(gt.shape[0]), int(gt.shape[1]), int(gt.shape[2]),
+                                                      gt.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def flip_ramp(self, W: Optional[int] = None) -> np.ndarray:
         """tcsfm_flip_ramp: l_mask of batch_post_process_disparity for width W (default: the engine's), float64 [W] with the bits of
         1.0 - np.clip(20 * (np.linspace(0, 1, W) - 0.05), 0, 1).  Host only."""
