@@ -95,28 +95,21 @@ int tcsfm_sequence_depth_eval(tcsfm_handle h, const tcsfm_depth_eval_opts *e, in
     if (int rc_ = pending_error(h)) return rc_;
     // ground truth goes up in groups of at most 64 MB (a group of one frame when a plane is larger), the metrics come back once
     const size_t per_group = std::max<size_t>(1, std::min<size_t>((size_t)count, ((size_t)64 << 20) / gt_plane));
-    if (h->eval_gt_bytes < per_group * gt_plane) {
-        if (h->eval_gt_dev) { HIPCHK(h, hipStreamSynchronize(h->stream)); HIPCHK(h, hipFree(h->eval_gt_dev)); }
-        h->eval_gt_dev = nullptr; h->eval_gt_bytes = 0;
-        HIPCHK(h, hipMalloc(&h->eval_gt_dev, per_group * gt_plane));
-        h->eval_gt_bytes = per_group * gt_plane;
-    }
-    if (h->eval_out_rows < (size_t)count) {
-        if (h->eval_out_dev) { HIPCHK(h, hipStreamSynchronize(h->stream)); HIPCHK(h, hipFree(h->eval_out_dev)); }
-        h->eval_out_dev = nullptr; h->eval_out_rows = 0;
-        HIPCHK(h, hipMalloc(&h->eval_out_dev, (size_t)count * TCSFM_NEVAL * sizeof(double)));
-        h->eval_out_rows = (size_t)count;
-    }
+    // (a buffer that has to go may still be in use by the previous call's kernels on the stream)
+    if (h->eval_gt_dev.p && h->eval_gt_dev.cap < per_group * gt_plane) HIPCHK(h, hipStreamSynchronize(h->stream));
+    RESERVE(h, h->eval_gt_dev, per_group * gt_plane);
+    if (h->eval_out_dev.p && h->eval_out_dev.cap < (size_t)count * TCSFM_NEVAL) HIPCHK(h, hipStreamSynchronize(h->stream));
+    RESERVE(h, h->eval_out_dev, (size_t)count * TCSFM_NEVAL);
     const bool f64 = h->seq_disp_kept == TCSFM_SEQ_DISP_POST;
     const size_t plane = (size_t)h->H * h->W * (f64 ? sizeof(double) : sizeof(float));
     for (size_t g0 = 0; g0 < (size_t)count; g0 += per_group) {
         const size_t n = std::min(per_group, (size_t)count - g0);
         // (the stream orders this copy behind the kernel that read the previous group)
-        HIPCHK(h, hipMemcpyAsync(h->eval_gt_dev, (const char *)gt + g0 * gt_plane, n * gt_plane, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, launch_depth_eval(h->stream, e, (int)n, f64, h->H, h->W, (const char *)h->seq_disp_dev + ((size_t)first + g0) * plane, gt_h, gt_w,
-                                    (const float *)h->eval_gt_dev, h->eval_out_dev + g0 * TCSFM_NEVAL));
+        HIPCHK(h, hipMemcpyAsync(h->eval_gt_dev.p, (const char *)gt + g0 * gt_plane, n * gt_plane, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, launch_depth_eval(h->stream, e, (int)n, f64, h->H, h->W, h->seq_disp_dev.p + ((size_t)first + g0) * plane, gt_h, gt_w,
+                                    (const float *)h->eval_gt_dev.p, h->eval_out_dev.p + g0 * TCSFM_NEVAL));
     }
-    HIPCHK(h, hipMemcpyAsync(metrics_out, h->eval_out_dev, (size_t)count * TCSFM_NEVAL * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(metrics_out, h->eval_out_dev.p, (size_t)count * TCSFM_NEVAL * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return TCSFM_OK;
 }

@@ -836,7 +836,7 @@ int dn_group_disp_for_eigen(tcsfm_depthnet *dn, int g, const float *imgs, float 
     return TCSFM_OK;
 }
 
-// The depth stage of a sequence call (sequence_impl): disp_to_depth(net(imgs), 1 / min_disp, 1 / max_disp)[1] of the n raw frames at
+// The depth stage of a sequence call (sequence_host.h: seq_stage_chunk): disp_to_depth(net(imgs), 1 / min_disp, 1 / max_disp)[1] of the n raw frames at
 // `imgs` into the planes at `depth`, on `stream`, by the attached network's clone -- groups of max_images images, the same bits per
 // image by the network's contract (its work split depends on H x W only).  The head writes the depth: with the disparity stage off
 // (disp_mode = TCSFM_SEQ_DISP_OFF) no disparity plane exists.  TCSFM_SEQ_DISP_PLAIN: the same head launch also stores the scaled

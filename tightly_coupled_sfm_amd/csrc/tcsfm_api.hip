@@ -44,11 +44,12 @@ using namespace tc;
 namespace tcguard {
 constexpr size_t kBand = 4096;
 constexpr unsigned char kFill = 0xA5;
-struct Rec { char *base; size_t bytes; int line; bool reported; };
+struct Rec { char *base; size_t bytes; const char *file; int line; bool reported; };      // file: the call site's __FILE__
+inline const char *at_file(const Rec &r) { const char *s = strrchr(r.file, '/'); return s ? s + 1 : r.file; }      // its base name, for the messages
 inline std::mutex &mtx() { static std::mutex m; return m; }
 inline std::vector<Rec> &recs() { static std::vector<Rec> r; return r; }
 inline bool on() { static const bool v = getenv("TCSFM_DEBUG_GUARDS") && atoi(getenv("TCSFM_DEBUG_GUARDS")) != 0; return v; }
-inline hipError_t alloc(void **p, size_t bytes, int line) {
+inline hipError_t alloc(void **p, size_t bytes, const char *file, int line) {
     if (!on()) return (hipMalloc)(p, bytes);
     char *base = nullptr;
     const size_t padded = (bytes + 255) / 256 * 256;            // (the rear band starts at the next 256-byte boundary: the user pointer keeps hipMalloc's alignment)
@@ -58,7 +59,7 @@ inline hipError_t alloc(void **p, size_t bytes, int line) {
     if (e == hipSuccess) e = hipMemset(base + kBand + bytes, kFill, padded - bytes + kBand);
     if (e != hipSuccess) { (void)(hipFree)(base); return e; }
     std::lock_guard<std::mutex> lk(mtx());
-    recs().push_back({base, bytes, line, false});
+    recs().push_back({base, bytes, file, line, false});
     *p = base + kBand;
     return hipSuccess;
 }
@@ -80,7 +81,7 @@ inline hipError_t release(void *p) {
         if (recs()[i].base + kBand == (char *)p) {
             long off = 0;
             const long bad = recs()[i].reported ? 0 : damaged(recs()[i], &off);
-            if (bad > 0) fprintf(stderr, "tcsfm guard: allocation of %zu bytes (tcsfm_api.hip:%d) freed with %ld band bytes overwritten, first at offset %ld\n", recs()[i].bytes, recs()[i].line, bad, off);
+            if (bad > 0) fprintf(stderr, "tcsfm guard: allocation of %zu bytes (%s:%d) freed with %ld band bytes overwritten, first at offset %ld\n", recs()[i].bytes, at_file(recs()[i]), recs()[i].line, bad, off);
             char *base = recs()[i].base;
             recs().erase(recs().begin() + i);
             return (hipFree)(base);
@@ -102,14 +103,14 @@ inline int damaged_among(const std::vector<void *> &ps) {
                 if (bad > 0) {
                     bad_allocs++;
                     if (!r.reported)
-                        fprintf(stderr, "tcsfm guard: allocation of %zu bytes (tcsfm_api.hip:%d): %ld band bytes overwritten, first at offset %ld of the allocation\n", r.bytes, r.line, bad, off);
+                        fprintf(stderr, "tcsfm guard: allocation of %zu bytes (%s:%d): %ld band bytes overwritten, first at offset %ld of the allocation\n", r.bytes, tcguard::at_file(r), r.line, bad, off);
                     r.reported = true;
                 }
             }
     return bad_allocs;
 }
 }  // namespace tcguard
-#define hipMalloc(p, bytes) tcguard::alloc((void **)(p), (bytes), __LINE__)
+#define hipMalloc(p, bytes) tcguard::alloc((void **)(p), (bytes), __FILE__, __LINE__)
 #define hipFree(p) tcguard::release((void *)(p))
 
 namespace {
@@ -122,12 +123,27 @@ constexpr int TILE_W = 32, TILE_H = TC_TILE_H, TILE_NT = TILE_W * TILE_H;      /
 
 thread_local std::string g_create_error;
 
-struct HostStage {  // device staging for host-pointer calls
-    void *p = nullptr;
-    size_t cap = 0;
-};
-
 }  // namespace
+
+struct tcsfm_ctx;
+
+// One grow-only device buffer: p holds cap elements (byte buffers are DevBuf<char>).  reserve() -- through RESERVE, which hands the call
+// site to the guard bands -- keeps a buffer that is large enough; otherwise it frees it, leaves the buffer empty (so it stays after a
+// failed allocation) and allocates n elements.  Whoever may still be using the old buffer on a stream is the caller's to wait for.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    int reserve(tcsfm_ctx *h, size_t n, const char *file, int line);      // TCSFM_OK, or TCSFM_E_HIP with h->err set
+    void release() {       // tcsfm_destroy
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+};
+#define RESERVE(h, buf, n)                                                                           \
+    do {                                                                                             \
+        if (int rc_reserve_ = (buf).reserve((h), (n), __FILE__, __LINE__)) return rc_reserve_;       \
+    } while (0)
 
 struct tcsfm_ctx {
     int device = 0, H = 0, W = 0, max_pairs = 0;
@@ -171,7 +187,7 @@ struct tcsfm_ctx {
     float *pgrad_fwd = nullptr, *pgrad_cot = nullptr;
     unsigned *scale_keys = nullptr, *scale_hist = nullptr;   // scale recovery scratch (keys, 256 bins + 4 state words)
     long long *dbg_stamps = nullptr;  // TCSFM_DEBUG_STAMPS=1: 8 wall-clock stamps of the last k_solve launch (100 MHz ticks)
-    std::vector<HostStage> stage;
+    std::vector<DevBuf<char>> stage;    // device staging for host-pointer calls (Staging), in bytes
     std::string err;
     // event profiling (tcsfm_profile_*): one (start, stop, class) triple per bracketed launch
     int *err_host = nullptr, *err_dev = nullptr;   // host-mapped status word of the device-side guards (host / device address)
@@ -183,45 +199,38 @@ struct tcsfm_ctx {
     std::vector<hipEvent_t> marks;   // tcsfm_lane_event: a ring of events handed out to the caller
     size_t mark_next = 0;
     // tcsfm_refine_sequence: device ring of frames, copy stream, per-slot / per-window events, pose staging (allocated on first use)
-    float *seq_img = nullptr, *seq_depth = nullptr, *seq_pose_in = nullptr, *seq_pose_out = nullptr, *seq_ls_out = nullptr, *seq_K = nullptr;
-    int seq_slots = 0, seq_K_n = 0;    // ring slots + mirror slots allocated; copies of K held by seq_K
-    float4 *seq_fpack = nullptr;       // frame-level pack cache of the ring: [slots][H+2][W+2] (rgb, depth) + [slots][H][W] depth planes
-    float *seq_fdepth = nullptr;
+    DevBuf<float> seq_img, seq_depth;  // [slots][3][H][W] and [slots][H][W]: ring slots, then mirror slots
+    DevBuf<float> seq_pose_in, seq_pose_out, seq_ls_out;      // [windows][pairs][6 | 6 | 1], per call in the window form's stacked order
+    DevBuf<float> seq_K;               // one copy of K per window of a call
+    DevBuf<float4> seq_fpack;          // frame-level pack cache of the ring: [slots][H+2][W+2] (rgb, depth) + [slots][H][W] depth planes,
+    DevBuf<float> seq_fdepth;          // for as many slots as seq_depth holds
     int *pair_idx = nullptr;           // [2][max_pairs] ring slots of every pair's source pack / target depth plane (k_pack_cached)
-    float *seq_dense = nullptr;        // tcsfm_refine_dense_sequence: refined depth maps of all windows, per-window order (on a lane: the
-    size_t seq_dense_cap = 0;          // lane's stacked maps of one call)
-    float *seq_dense_tmp = nullptr;    // ... the handle's own stacked maps of one call (lane 0)
-    size_t seq_dense_tmp_cap = 0;
-    size_t seq_pose_cap = 0;           // windows x pairs the pose staging holds
+    DevBuf<float> seq_dense;           // tcsfm_refine_dense_sequence: refined depth maps of all windows, per-window order (the parent's only)
+    DevBuf<float> seq_dense_tmp;       // ... this context's stacked maps of one call (every lane's, lane 0 included)
     hipStream_t seq_copy = nullptr;
     std::vector<hipEvent_t> seq_copied, seq_done, seq_raw;      // per chunk: frames usable by the lanes / per call: done / per chunk: raw frames landed
     hipStream_t seq_pack = nullptr;    // k_frame_pack runs here, behind the chunk's copy (event), beside the next chunk's copy
     tcsfm_depthnet *seq_dn = nullptr;  // tcsfm_sequence_depthnet: the network whose clone computes the ring's depths on seq_pack when a sequence
                                        // call gets depths == NULL (not owned; tcsfm_depthnet_destroy detaches it)
     int seq_fmt = TCSFM_FRAMES_F32_CHW;  // tcsfm_sequence_frame_format: how the sequence calls read their `frames` argument
-    uint8_t *seq_u8 = nullptr;         // U8 formats: device ring of the frames' BYTES (R slots of 3 H W -- or, with a frame source set, of
-    size_t seq_u8_bytes = 0;           // 3 src_h src_w -- bytes, no mirror slots); k_frames_u8 / k_resize_u8 turns a chunk into the floats of seq_img on seq_pack
+    DevBuf<uint8_t> seq_u8;            // U8 formats: device ring of the frames' BYTES (R slots of 3 H W -- or, with a frame source set, of
+                                       // 3 src_h src_w -- bytes, no mirror slots); k_frames_u8 / k_resize_u8 turns a chunk into the floats of seq_img on seq_pack
     int seq_src_h = 0, seq_src_w = 0;  // tcsfm_sequence_frame_source: the camera's frame size (0, 0: none -- frames arrive at H x W)
     std::vector<ResizeTable> resize_tabs;      // coefficient tables of the source sizes seen so far, on the device (resize_table())
     // tcsfm_sequence_scale: the sequence calls' per-frame scale stage (k_ground + k_median_frames on seq_pack, once per chunk)
     float seq_cam_height = 0.f;        // > 0: the stage is on
-    unsigned *seq_scale_keys = nullptr;  // key planes of ONE chunk (not scale_keys: the operators on the handle's stream own that)
-    size_t seq_scale_keys_frames = 0;
-    float *seq_scale_dev = nullptr;    // results by ABSOLUTE frame index: [cap] scales | [cap] medians | [cap] counts (int32)
-    size_t seq_scale_cap = 0;
+    DevBuf<unsigned> seq_scale_keys;   // key planes of ONE chunk (not scale_keys: the operators on the handle's stream own that)
+    DevBuf<float> seq_scale_dev;       // results by ABSOLUTE frame index: [n] scales | [n] medians | [n] counts (int32), n = cap / 3
     std::vector<float> seq_scale_res;  // the last call's results on the host, same layout with cap = seq_scale_T (counts as bit patterns)
     int seq_scale_T = 0;               // 0: nothing kept
     // tcsfm_sequence_disparity: the sequence calls' disparity stage (the depth stage's head / a second, mirrored pass + k_disp_post on seq_pack)
     int seq_disp_mode = TCSFM_SEQ_DISP_OFF;
-    void *seq_disp_dev = nullptr;      // every frame's plane by ABSOLUTE frame index: [T][H][W] float32 (PLAIN) or float64 (POST)
-    size_t seq_disp_bytes = 0;
+    DevBuf<char> seq_disp_dev;         // every frame's plane by ABSOLUTE frame index: [T][H][W] float32 (PLAIN) or float64 (POST)
     int seq_disp_T = 0, seq_disp_kept = TCSFM_SEQ_DISP_OFF;      // the last call's T (0: nothing kept) and mode, for tcsfm_sequence_disparities
     double *flip_ramp = nullptr;       // l_mask [W] of the flip post-processing on the device (flip_ramp_device), built on first use
     // tcsfm_sequence_depth_eval: one group of staged ground truth and the call's metrics, grown when a call needs more
-    void *eval_gt_dev = nullptr;
-    size_t eval_gt_bytes = 0;
-    double *eval_out_dev = nullptr;
-    size_t eval_out_rows = 0;
+    DevBuf<char> eval_gt_dev;          // (bytes)
+    DevBuf<double> eval_out_dev;       // [frames][TCSFM_NEVAL]
     struct KOk { const float *p; int n; };
     KOk K_ok[4] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}};   // device intrinsics pointers (and counts) that already passed the pinhole check
     int K_ok_next = 0;
@@ -292,6 +301,20 @@ struct DeviceGuard {
             return TCSFM_E_HIP;                                                                      \
         }                                                                                            \
     } while (0)
+
+}  // namespace
+
+template <class T>
+int DevBuf<T>::reserve(tcsfm_ctx *h, size_t n, const char *file, int line) {
+    if (cap >= n) return TCSFM_OK;
+    if (p) HIPCHK(h, hipFree(p));
+    p = nullptr; cap = 0;
+    HIPCHK(h, tcguard::alloc((void **)&p, n * sizeof(T), file, line));
+    cap = n;
+    return TCSFM_OK;
+}
+
+namespace {
 
 // Captured call graphs bake in the handle's scratch pointers and run on the stream they were last launched on: whoever frees or
 // re-sizes such scratch, switches the stream or evicts an entry drains BOTH streams a replay can be on first.
@@ -398,15 +421,8 @@ struct Staging {
         const size_t i = slot++;
         if (rc) return nullptr;
         if (h->stage.size() <= i) h->stage.resize(i + 1);
-        if (h->stage[i].cap < bytes) rc = grow(h->stage[i], bytes);
+        rc = h->stage[i].reserve(h, bytes, __FILE__, __LINE__);
         return rc ? nullptr : h->stage[i].p;
-    }
-    int grow(HostStage &s, size_t bytes) {
-        if (s.p) HIPCHK(h, hipFree(s.p));
-        s.p = nullptr; s.cap = 0;
-        HIPCHK(h, hipMalloc(&s.p, bytes));
-        s.cap = bytes;
-        return TCSFM_OK;
     }
     template <typename T>
     const T *in(const char *name, const T *p, size_t count) {
@@ -1475,14 +1491,15 @@ void tcsfm_destroy(tcsfm_handle h) {
     void *ptrs[] = {h->stamp_buf, h->tgtpack, h->srcpack, h->depth_work, h->partials, h->blockrec, h->tickets, h->state, h->pconst, h->lin_out,
                     h->jrec, h->jrec_acc, h->jblockrec, h->jdepth_acc, h->jstate, h->jdelta, h->jpart, h->jtick, h->dref_norms, h->dref_ext, h->dref_export, h->qres_rho, h->qres_rec, h->pose_lin, h->dref_smooth, h->jrec_src, h->jstate_src, h->jdelta_src, h->dref_ext_src, h->qres_rho_src, h->qres_rec_src,
                     h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept, h->dbg_stamps, h->wgrad_rec, h->wgrad_fix, h->wgrad_gmax, h->pgrad_fwd, h->pgrad_cot,
-                    h->seq_fpack, h->seq_fdepth, h->pair_idx, h->seq_img, h->seq_depth, h->seq_pose_in, h->seq_pose_out, h->seq_ls_out, h->seq_K, h->seq_dense, h->seq_dense_tmp, h->seq_u8,
-                    h->seq_scale_keys, h->seq_scale_dev, h->seq_disp_dev, h->flip_ramp, h->eval_gt_dev, h->eval_out_dev};
+                    h->pair_idx, h->flip_ramp};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    for (DevBuf<float> *b : {&h->seq_img, &h->seq_depth, &h->seq_pose_in, &h->seq_pose_out, &h->seq_ls_out, &h->seq_K, &h->seq_fdepth, &h->seq_dense, &h->seq_dense_tmp, &h->seq_scale_dev})
+        b->release();
+    h->seq_fpack.release(); h->seq_u8.release(); h->seq_scale_keys.release(); h->seq_disp_dev.release(); h->eval_gt_dev.release(); h->eval_out_dev.release();
     for (auto &t : h->resize_tabs)
         if (t.dev) (void)hipFree(t.dev);
-    for (auto &s : h->stage)
-        if (s.p) (void)hipFree(s.p);
+    for (auto &s : h->stage) s.release();
     for (auto &e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->err_host) (void)hipHostFree(h->err_host);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -2856,7 +2873,7 @@ int tcsfm_debug_check_guards(int *n_allocations, int *n_damaged) {
         if (bad > 0) {
             bad_allocs++;
             if (!r.reported)
-                fprintf(stderr, "tcsfm guard: allocation of %zu bytes (tcsfm_api.hip:%d): %ld band bytes overwritten, first at offset %ld of the allocation\n", r.bytes, r.line, bad, off);
+                fprintf(stderr, "tcsfm guard: allocation of %zu bytes (%s:%d): %ld band bytes overwritten, first at offset %ld of the allocation\n", r.bytes, tcguard::at_file(r), r.line, bad, off);
             r.reported = true;
         }
     }
@@ -3031,456 +3048,7 @@ static const ResizeTable *resize_table(tcsfm_handle h, int src_h, int src_w) {
     return &h->resize_tabs.back();
 }
 
-// The reference's sequential driver (run_sequential_optimization.py:186-247) as ONE call: see include/tcsfm.h.  With `pn` the initial
-// poses of every window come from the coupled PoseNet loop (train_mono.py:64-80) on the window's lane instead of from the caller.
-static int sequence_impl(tcsfm_handle h, const tcsfm_opts *o_in, int T, int S, const float *frames, const float *depths, const float *K,
-                         const float *pose_init, tcsfm_posenet *pn, int num_iter, float *pose_init_out, float *pose_out,
-                         float *log_scale_out, int ring, int windows_per_call, int target_pos, const char *entry, float *dense_depth_out = nullptr) {
-    if (int rc_q = drain_queued(h)) return rc_q;
-    if (!h) return TCSFM_E_ARG;
-    h->seq_scale_T = 0;                                    // tcsfm_sequence_scales: only a call that succeeds with the stage on leaves results
-    h->seq_disp_T = 0;                                     // tcsfm_sequence_disparities: the same rule
-    if (!o_in) return fail(h, TCSFM_E_ARG, "opts is NULL");
-    const int N = 2 * S, L = h->lanes_serial ? 1 : (int)h->lanes.size() + 1;
-    if (S < 1 || T <= S || N > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: need S >= 1, T > S and 2*S <= max_pairs");
-    // depths == NULL: the attached depth network (tcsfm_sequence_depthnet) computes every frame's depth on the device as its chunk lands
-    const bool gen = !depths && h->seq_dn;
-    // tcsfm_sequence_frame_format: `frames` points at bytes; they go up as they are and k_frames_u8 makes the ring's floats on the device
-    const bool u8 = h->seq_fmt != TCSFM_FRAMES_F32_CHW;
-    const uint8_t *frames_u8 = (const uint8_t *)frames;
-    // tcsfm_sequence_frame_source: the bytes are camera-size frames; k_resize_u8 takes k_frames_u8's place and writes Pillow's H x W frames
-    const bool resize = h->seq_src_h > 0;
-    if (resize && !u8)
-        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": a frame source size (tcsfm_sequence_frame_source) needs a U8 frame format, not TCSFM_FRAMES_F32_CHW").c_str());
-    const size_t frame_bytes = resize ? (size_t)3 * h->seq_src_h * h->seq_src_w : (size_t)3 * h->H * h->W;      // of one frame of a U8 format
-    // tcsfm_sequence_disparity: every frame's disparity kept on the device; the stage needs the attached network's own output
-    const int disp_mode = h->seq_disp_mode;
-    if (disp_mode != TCSFM_SEQ_DISP_OFF && depths)
-        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": the disparity stage (tcsfm_sequence_disparity) needs depths == NULL: it keeps the attached depth network's own output").c_str());
-    if (disp_mode != TCSFM_SEQ_DISP_OFF && !h->seq_dn)
-        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": the disparity stage (tcsfm_sequence_disparity) needs an attached depth network (tcsfm_sequence_depthnet)").c_str());
-    if (!frames || (!depths && !gen) || !K || (!pose_init && !pn) || !pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: NULL input");
-    if (gen && o_in->depth_is_disp)
-        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": depths == NULL (the attached depth network produces depths) cannot go with opts.depth_is_disp").c_str());
-    if (gen && !(o_in->min_depth > 0 && o_in->max_depth > o_in->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
-    // tcsfm_sequence_scale: every frame's DNet scale from the ring's depth plane, on the pack stream
-    const bool scale_on = h->seq_cam_height > 0.f;
-    if (scale_on && o_in->depth_is_disp)
-        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": the scale stage (tcsfm_sequence_scale) needs depths, not disparities (opts.depth_is_disp)").c_str());
-    if (scale_on && (h->H < 5 || h->W < 5))
-        return fail(h, TCSFM_E_ARG, (std::string(entry) + ": the scale stage (tcsfm_sequence_scale): image too small").c_str());
-    if (windows_per_call < 0) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: windows_per_call < 0");
-    if (target_pos < -1 || target_pos > S || S > TC_MAX_SRC_OFF) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: target_pos must be -1 or 0..S, S at most 8");
-    {   // The overlap contract (include/tcsfm.h).  Host arrays that are streamed: frames and depths are still going up while results come
-        // back, so only the pose pair is honoured -- pose_init is on the device, and the copy stream drained, before the first window is
-        // issued (small_ev below), and pose_out is written after the last one has finished.
-        const size_t hw_b = (size_t)h->H * h->W * sizeof(float), np6 = (size_t)(T - S) * N * 6 * sizeof(float);
-        ArgRanges a;
-        a.in("frames", frames, u8 ? (size_t)T * frame_bytes : (size_t)T * 3 * hw_b);      // (a U8 format: T*3*H*W -- T*3*src_h*src_w -- bytes, not floats)
-        a.in("depths", depths, (size_t)T * hw_b); a.in("K", K, 9 * sizeof(float));
-        a.in("pose_init", pose_init, np6);
-        a.out("pose_init_out", pose_init_out, np6); a.out("pose_out", pose_out, np6);
-        if (o_in->refine == TCSFM_REFINE_POSE_SCALE && !dense_depth_out) a.out("log_scale_out", log_scale_out, (size_t)(T - S) * N * sizeof(float));
-        a.out("depth_out", dense_depth_out, (size_t)(T - S) * N * hw_b);
-        a.bless("pose_out", "pose_init");
-        std::string msg;
-        if (a.refused(entry, msg)) return fail(h, TCSFM_E_ARG, msg.c_str());
-    }
-    // position of the target inside a window's S + 1 consecutive frames: the reference's loaders take the middle one
-    // (data/kitti_loader.py:271-273: target_idx = int(len / 2), the sources are the others in order)
-    const int tp = target_pos < 0 ? (S + 1) / 2 : target_pos;
-    WinOff wo;
-    wo.on = 1;
-    for (int s_ = 0; s_ < TC_MAX_SRC_OFF; s_++) wo.off[s_] = s_ < tp ? s_ : s_ + 1;     // source s = frame w + off[s], relative to the window's first frame
-    if (pn && (num_iter < 1 || pn->h != h || !pn->loaded || N > pn->max_images || o_in->depth_is_disp))
-        return fail(h, TCSFM_E_ARG, "tcsfm_odometry_sequence: needs a loaded PoseNet of this handle with max_images >= 2*S, num_iter >= 1 and depths (not disparities)");
-    tcsfm_opts o = *o_in;
-    o.host_ptrs = 0;                                   // the lanes work on the device ring; this call does the staging itself
-    const int nwin = T - S;
-    // Windows per call: consecutive windows are independent, and the targets (frames w + tp ..) and every source (frames w + off[s] ..)
-    // of WB consecutive windows are runs of the ring -- the window form with explicit source positions (WinOff) -- so a lane refines
-    // WB windows per call: the kernels fill the chip (26 200 windows/s per call at WB = 8 against 13 900 at WB = 1) and the PoseNet
-    // runs on 2 S WB images at a third of the time per image.
-    int WB = windows_per_call > 0 ? windows_per_call : 8;
-    WB = std::min(WB, std::min(h->max_pairs / N, nwin));
-    if (pn) WB = std::min(WB, pn->max_images / N);
-    while (ring > 0 && WB > 1 && ring < WB + S + (ring >= WB + S + 8 ? 4 : 1)) WB--;      // an explicit small ring bounds the windows per call
-    int rc = check_common(h, &o, N * WB);
-    if (rc) return rc;
-    if (K[1] != 0.f || K[3] != 0.f || K[6] != 0.f || K[7] != 0.f || K[8] != 1.f || !(K[0] != 0.f) || !(K[4] != 0.f))
-        return fail(h, TCSFM_E_INTRINSICS, "intrinsics must be pinhole [fx 0 cx; 0 fy cy; 0 0 1]");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = pending_error(h)) return rc_;
-    // frames go up in chunks of C (one copy for the images, one for the depths: PCIe runs at 55 GB/s on 8-frame copies, at 36 GB/s
-    // on single frames, and the host issues a quarter of the calls); the ring holds a whole number of chunks
-    static const int chunk_env = getenv("TCSFM_SEQ_CHUNK") ? std::max(1, atoi(getenv("TCSFM_SEQ_CHUNK"))) : 0;      // (measurement hook)
-    // default ring: 4 frames per copy; 8 when a call takes 16 or more windows (the copies then run at 55 instead of 45 GB/s and a call
-    // still waits for no more than two of them: 21 800 -> 22 800 windows/s at 16 windows per call, nothing to gain at 8)
-    const int C = ring > 0 ? (ring >= WB + S + 8 ? 4 : 1) : (chunk_env ? chunk_env : (WB >= 16 ? 8 : 4));
-    const int R = ring > 0 ? (ring / C) * C : ((32 + (L + 1) * WB + S + C - 1) / C) * C;     // frames resident at once
-    const int M = WB + S - 1;                              // mirror slots behind the ring: the WB + S frames of a call never wrap
-    if (R < S + 2 || R < WB + S + C) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: ring must hold at least windows_per_call + S + 4 frames (S + 2 for one window per call)");
-    const size_t hw = (size_t)h->H * h->W;
-    // ---- scratch: ring + mirror slots, events, pose staging, WB copies of K
-    if (h->seq_slots < R + M) {
-        if (h->seq_img) HIPCHK(h, hipFree(h->seq_img));
-        if (h->seq_depth) HIPCHK(h, hipFree(h->seq_depth));
-        h->seq_img = h->seq_depth = nullptr; h->seq_slots = 0;
-        HIPCHK(h, hipMalloc(&h->seq_img, (size_t)(R + M) * 3 * hw * sizeof(float)));
-        HIPCHK(h, hipMalloc(&h->seq_depth, (size_t)(R + M) * hw * sizeof(float)));
-        if (h->seq_fpack) { HIPCHK(h, hipFree(h->seq_fpack)); h->seq_fpack = nullptr; }       // (re-allocated below for the new slot count)
-        if (h->seq_fdepth) { HIPCHK(h, hipFree(h->seq_fdepth)); h->seq_fdepth = nullptr; }
-        h->seq_slots = R + M;
-    }
-    if (u8 && h->seq_u8_bytes < (size_t)R * frame_bytes) {  // the byte ring: R slots, no mirror (the kernel writes the float mirror slots itself)
-        if (h->seq_u8) HIPCHK(h, hipFree(h->seq_u8));
-        h->seq_u8 = nullptr; h->seq_u8_bytes = 0;
-        HIPCHK(h, hipMalloc((void **)&h->seq_u8, (size_t)R * frame_bytes));
-        h->seq_u8_bytes = (size_t)R * frame_bytes;
-    }
-    const ResizeTable *rtab = nullptr;
-    if (resize && !(rtab = resize_table(h, h->seq_src_h, h->seq_src_w))) return TCSFM_E_HIP;
-    const bool use_cache = dense_depth_out == nullptr;      // (the dense modes rewrite per-pair depth planes: they keep the per-pair pack)
-    if (use_cache && !h->seq_fpack) {
-        HIPCHK(h, hipMalloc((void **)&h->seq_fpack, (size_t)h->seq_slots * (h->H + 2) * (h->W + 2) * sizeof(float4)));
-        HIPCHK(h, hipMalloc((void **)&h->seq_fdepth, (size_t)h->seq_slots * hw * sizeof(float)));
-    }
-    if (h->seq_pose_cap < (size_t)nwin * N) {
-        for (float **q : {&h->seq_pose_in, &h->seq_pose_out, &h->seq_ls_out})
-            if (*q) { HIPCHK(h, hipFree(*q)); *q = nullptr; }
-        h->seq_pose_cap = 0;
-        HIPCHK(h, hipMalloc(&h->seq_pose_in, (size_t)nwin * N * 6 * sizeof(float)));
-        HIPCHK(h, hipMalloc(&h->seq_pose_out, (size_t)nwin * N * 6 * sizeof(float)));
-        HIPCHK(h, hipMalloc(&h->seq_ls_out, (size_t)nwin * N * sizeof(float)));
-        h->seq_pose_cap = (size_t)nwin * N;
-    }
-    const bool dense = dense_depth_out != nullptr;
-    if (dense && h->seq_dense_cap < (size_t)nwin * N * hw) {
-        if (h->seq_dense) HIPCHK(h, hipFree(h->seq_dense));
-        h->seq_dense = nullptr; h->seq_dense_cap = 0;
-        HIPCHK(h, hipMalloc(&h->seq_dense, (size_t)nwin * N * hw * sizeof(float)));
-        h->seq_dense_cap = (size_t)nwin * N * hw;
-    }
-    if (dense && h->seq_dense_tmp_cap < (size_t)WB * N * hw) {
-        if (h->seq_dense_tmp) HIPCHK(h, hipFree(h->seq_dense_tmp));
-        h->seq_dense_tmp = nullptr; h->seq_dense_tmp_cap = 0;
-        HIPCHK(h, hipMalloc(&h->seq_dense_tmp, (size_t)WB * N * hw * sizeof(float)));
-        h->seq_dense_tmp_cap = (size_t)WB * N * hw;
-    }
-    if (h->seq_K_n < WB) {
-        if (h->seq_K) HIPCHK(h, hipFree(h->seq_K));
-        h->seq_K = nullptr; h->seq_K_n = 0;
-        HIPCHK(h, hipMalloc(&h->seq_K, (size_t)WB * 9 * sizeof(float)));
-        h->seq_K_n = WB;
-    }
-    if (scale_on && h->seq_scale_keys_frames < (size_t)C) {      // key planes of one chunk; results of every frame of the sequence
-        if (h->seq_scale_keys) HIPCHK(h, hipFree(h->seq_scale_keys));
-        h->seq_scale_keys = nullptr; h->seq_scale_keys_frames = 0;
-        HIPCHK(h, hipMalloc((void **)&h->seq_scale_keys, (size_t)C * hw * sizeof(unsigned)));
-        h->seq_scale_keys_frames = (size_t)C;
-    }
-    if (scale_on && h->seq_scale_cap < (size_t)T) {
-        if (h->seq_scale_dev) HIPCHK(h, hipFree(h->seq_scale_dev));
-        h->seq_scale_dev = nullptr; h->seq_scale_cap = 0;
-        HIPCHK(h, hipMalloc((void **)&h->seq_scale_dev, (size_t)3 * T * sizeof(float)));
-        h->seq_scale_cap = (size_t)T;
-    }
-    const double *disp_ramp = nullptr;
-    if (disp_mode != TCSFM_SEQ_DISP_OFF) {                  // every frame's plane, by absolute frame index; grown when a call needs more
-        const size_t need = (size_t)T * hw * (disp_mode == TCSFM_SEQ_DISP_POST ? sizeof(double) : sizeof(float));
-        if (h->seq_disp_bytes < need) {
-            if (h->seq_disp_dev) HIPCHK(h, hipFree(h->seq_disp_dev));
-            h->seq_disp_dev = nullptr; h->seq_disp_bytes = 0;
-            HIPCHK(h, hipMalloc(&h->seq_disp_dev, need));
-            h->seq_disp_bytes = need;
-        }
-        if (disp_mode == TCSFM_SEQ_DISP_POST) {             // the clone's two planes of one group and the ramp
-            if (int rc_ = dn_post_scratch(h->seq_dn->seq_clone, entry)) return rc_;
-            if (!(disp_ramp = flip_ramp_device(h))) return TCSFM_E_HIP;
-        }
-    }
-    if (!h->seq_copy) {   // high priority: a hardware queue outside the pool the normal-priority streams share (a copy stream that lands in
-        int lo = 0, hi = 0;   // a lane's queue parks its slot-recycling waits in front of that lane's kernels), and copies go first anyway
-        HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(h, hipStreamCreateWithPriority(&h->seq_copy, hipStreamNonBlocking, hi));
-    }
-    const size_t n_done = (size_t)2 * R + 2;               // a call's event is re-recorded long after its slots were recycled
-    const size_t ND = n_done - 1;
-    while (h->seq_copied.size() < (size_t)R) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_copied.push_back(e); }
-    const bool staged = use_cache || gen || u8 || scale_on;      // the chunk has a stage on seq_pack: k_frames_u8, the depth network, the scale stage and / or k_frame_pack
-    while (staged && h->seq_raw.size() < (size_t)R) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_raw.push_back(e); }
-    if (staged && !h->seq_pack) HIPCHK(h, hipStreamCreateWithFlags(&h->seq_pack, hipStreamNonBlocking));
-    while (h->seq_done.size() < n_done) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->seq_done.push_back(e); }
-    // Poses live on the device per CALL in the stacked order of the window form (forward pairs (s, b), then inverse pairs); the
-    // caller's arrays are per window.  at(): offset (in pairs) of pair j of window w inside the staging arrays.
-    auto at = [&](int w, int j) -> size_t {
-        const int c0 = (w / WB) * WB, nbw = std::min(WB, nwin - c0), b = w - c0;
-        return (size_t)c0 * N + (j < S ? (size_t)j * nbw + b : (size_t)S * nbw + (size_t)(j - S) * nbw + b);
-    };
-    // ---- small inputs: one copy each, on the copy stream; every lane waits for them once
-    hipStream_t cs = h->seq_copy;
-    std::vector<float> Kh((size_t)WB * 9), stage;
-    for (int b = 0; b < WB; b++) memcpy(&Kh[(size_t)b * 9], K, 9 * sizeof(float));
-    HIPCHK(h, hipMemcpyAsync(h->seq_K, Kh.data(), Kh.size() * sizeof(float), hipMemcpyHostToDevice, cs));
-    if (!pn) {
-        const float *src = pose_init;
-        if (WB > 1) {
-            stage.resize((size_t)nwin * N * 6);
-            for (int w = 0; w < nwin; w++)
-                for (int j = 0; j < N; j++) memcpy(&stage[at(w, j) * 6], pose_init + ((size_t)w * N + j) * 6, 6 * sizeof(float));
-            src = stage.data();
-        }
-        HIPCHK(h, hipMemcpyAsync(h->seq_pose_in, src, (size_t)nwin * N * 6 * sizeof(float), hipMemcpyHostToDevice, cs));
-    }
-    hipEvent_t small_ev = h->seq_done[n_done - 1];
-    HIPCHK(h, hipEventRecord(small_ev, cs));
-    HIPCHK(h, hipEventSynchronize(small_ev));              // Kh / stage are host temporaries (pageable): gone from here on
-    const float gen_min_disp = gen ? 1.f / o.max_depth : 0.f, gen_max_disp = gen ? 1.f / o.min_depth : 0.f;      // tcsfm_disp_to_depth's arguments
-    if (gen) {             // the network's weights may still be being written on the handle's stream (tcsfm_depthnet_load_device is asynchronous)
-        HIPCHK(h, hipEventRecord(small_ev, h->stream));    // (small_ev is free again: the host has just waited for it)
-        HIPCHK(h, hipStreamWaitEvent(h->seq_pack, small_ev, 0));
-    }
-    std::vector<tcsfm_ctx *> lane(L);
-    std::vector<tcsfm_posenet *> net(L, nullptr);
-    std::vector<hipStream_t> ls(L);
-    for (int l = 0; l < L; l++) {
-        lane[l] = l == 0 ? h : h->lanes[l - 1];
-        if (pn && !(net[l] = pn_for_lane(pn, lane[l]))) return fail(h, TCSFM_E_NOMEM, "tcsfm_odometry_sequence: no memory for a lane's PoseNet activations");
-        ls[l] = l == 0 ? h->stream : lane[l]->own_stream;
-        lane[l]->stream = ls[l];
-        k_add(lane[l], h->seq_K, WB);        // validated on the host above
-    }
-    std::vector<long long> slot_reader(R, -1);             // last CALL that reads the frame in this slot (-1: none pending)
-    const int np = np_of(&o);
-    const int ahead = S + L * WB + C;                      // frames kept in flight ahead of the first window of the call being issued
-    const long long depth = std::max(2 * L, 16 / WB);      // calls the host may run ahead of the GPU
-    int nxt = 0;                                           // first frame of the next copy chunk
-    long long ci = 0;                                      // call index
-    for (int c0 = 0; c0 < nwin; c0 += WB, ci++) {
-        const int nbw = std::min(WB, nwin - c0);
-        // the host stays a bounded number of calls ahead of the GPU: a deeper backlog buys nothing, and with one the runtime was seen to
-        // block a single hipMemcpyAsync of the copy stream for 7 ms while the lanes ran dry behind it
-        if (ci >= depth) HIPCHK(h, hipEventSynchronize(h->seq_done[(ci - depth) % ND]));
-        // a chunk may go up once every window that reads the frames it overwrites has been ISSUED (their events exist): nxt - R + C - 1 < c0
-        while (nxt < T && nxt <= c0 + nbw - 1 + ahead && nxt + C - 1 - R < c0) {
-            const int slot = nxt % R, nf = T - nxt < C ? T - nxt : C;
-            long long last = -1;                           // the slots' previous frames may still be read: the copy waits for their readers --
-            for (int k = 0; k < nf; k++) { if (slot_reader[slot + k] > last) last = slot_reader[slot + k]; slot_reader[slot + k] = -1; }
-            for (long long r = last; r >= 0 && r > last - L; r--)     // -- the latest of those calls on every lane (a lane's stream is in order)
-                HIPCHK(h, hipStreamWaitEvent(cs, h->seq_done[r % ND], 0));
-            if (u8) HIPCHK(h, hipMemcpyAsync(h->seq_u8 + (size_t)slot * frame_bytes, frames_u8 + (size_t)nxt * frame_bytes, (size_t)nf * frame_bytes, hipMemcpyHostToDevice, cs));
-            else HIPCHK(h, hipMemcpyAsync(h->seq_img + (size_t)slot * 3 * hw, frames + (size_t)nxt * 3 * hw, (size_t)nf * 3 * hw * sizeof(float), hipMemcpyHostToDevice, cs));
-            if (!gen) HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)slot * hw, depths + (size_t)nxt * hw, (size_t)nf * hw * sizeof(float), hipMemcpyHostToDevice, cs));
-            // mirror of the first M slots behind the ring (the frames of a call never wrap).  The frames cross PCIe ONCE: raw mirrors are
-            // device-to-device copies, and with the pack cache only the PoseNet reads raw frames -- otherwise the mirror exists as packs only
-            const int nm = slot < M ? (nf < M - slot ? nf : M - slot) : 0;
-            if (nm > 0 && (!use_cache || pn)) {
-                // (a U8 format: the floats do not exist yet -- k_frames_u8 below writes the raw mirror slots with the ring's)
-                if (!u8) HIPCHK(h, hipMemcpyAsync(h->seq_img + (size_t)(R + slot) * 3 * hw, h->seq_img + (size_t)slot * 3 * hw, (size_t)nm * 3 * hw * sizeof(float), hipMemcpyDeviceToDevice, cs));
-                if (!gen) HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)(R + slot) * hw, h->seq_depth + (size_t)slot * hw, (size_t)nm * hw * sizeof(float), hipMemcpyDeviceToDevice, cs));
-            }
-            if (staged) {         // the chunk's producer stage runs on the PACK stream, behind the raw frames (seq_raw), so that the next chunk's
-                                  // copy does not queue behind its kernels (a sequence with S = 1 is PCIe-bound: the copy stream is its critical path)
-                HIPCHK(h, hipEventRecord(h->seq_raw[slot / C], cs));
-                HIPCHK(h, hipStreamWaitEvent(h->seq_pack, h->seq_raw[slot / C], 0));
-            }
-            if (u8) {
-                // The chunk's bytes -> the ring's floats (and the raw mirror slots, where somebody reads them), ONE launch, first on the pack
-                // stream: the depth network and k_frame_pack below read its output in stream order.  Recycling, as for the depth stage below:
-                // the kernel's WRITES to seq_img[slot ..] (+ mirror) come after the reads of the slots' previous frames -- this chunk's copy
-                // waited for those calls' seq_done events (slot_reader above), and the kernel waits for that copy (seq_raw).  The NEXT copy
-                // into the same seq_u8 slots waits for the calls that read THIS chunk, those calls waited for seq_copied, and seq_copied is
-                // recorded on this stream after the kernel: so a byte slot is never overwritten while the kernel may still read it.
-                // With a frame source set the slots are 3 src_h src_w bytes and the launch is k_resize_u8: the same reads (this chunk's
-                // byte slots), the same writes (seq_img[slot ..] + mirror), the same place in the stream -- the argument holds as it stands.
-                float *mirror = nm > 0 && (!use_cache || pn) ? h->seq_img + (size_t)(R + slot) * 3 * hw : nullptr;
-                const bool hwc = h->seq_fmt == TCSFM_FRAMES_U8_HWC;
-                if (resize) HIPCHK(h, launch_resize_u8(h->seq_pack, *rtab, hwc, true, nf, h->seq_u8 + (size_t)slot * frame_bytes, h->seq_img + (size_t)slot * 3 * hw,
-                                                       mirror, mirror ? nm : 0));
-                else HIPCHK(h, launch_frames_u8(h->seq_pack, hwc, nf, h->seq_u8 + (size_t)slot * 3 * hw, h->seq_img + (size_t)slot * 3 * hw, mirror, mirror ? nm : 0, hw));
-            }
-            if (gen) {
-                // Depths of the frames that just landed, once per frame, by the attached network's clone on the pack stream -- neither the
-                // copy stream nor a lane's, so lane 0's windows on h->stream do not hold it up -- then the depth planes' mirror.
-                // Slot recycling needs no new event.  The stage WRITES seq_depth[slot ..] (+ mirror) and READS seq_img[slot ..]; it starts
-                // behind seq_raw, i.e. behind this chunk's copy, and that copy waited (above: slot_reader -> seq_done) for every call that
-                // read the slots' previous frames and depths -- so the stage's writes come after those reads.  The NEXT copy into these
-                // slots waits for the calls that read THIS chunk (slot_reader again: every frame is read by an issued call before its slot
-                // is reused, nxt + C - 1 - R < c0), and each of those calls waited for seq_copied, which this stream records after the
-                // stage: so the next copy also comes after the stage's reads of seq_img and its activations are free for the next chunk
-                // (one stream, in order).
-                // The disparity stage (tcsfm_sequence_disparity) is part of the same stage, in the same group loop, on this stream and
-                // before the chunk's seq_copied record: PLAIN adds a store to the head's launch; POST reads seq_img[slot ..] a second
-                // time (the mirrored pass) and writes the clone's own planes and the store, which is indexed by the ABSOLUTE frame and
-                // never recycled.  Its reads of seq_img precede seq_copied like the first pass's, so the argument covers them as it stands.
-                void *disp_at = disp_mode == TCSFM_SEQ_DISP_OFF ? nullptr
-                                : (char *)h->seq_disp_dev + (size_t)nxt * hw * (disp_mode == TCSFM_SEQ_DISP_POST ? sizeof(double) : sizeof(float));
-                if ((rc = dn_sequence_depths(h->seq_dn, h->seq_pack, nf, h->seq_img + (size_t)slot * 3 * hw, h->seq_depth + (size_t)slot * hw, gen_min_disp, gen_max_disp,
-                                             disp_mode, disp_at, disp_ramp))) break;
-                if (nm > 0 && (!use_cache || pn))
-                    HIPCHK(h, hipMemcpyAsync(h->seq_depth + (size_t)(R + slot) * hw, h->seq_depth + (size_t)slot * hw, (size_t)nm * hw * sizeof(float), hipMemcpyDeviceToDevice, h->seq_pack));
-            }
-            if (scale_on) {
-                // Scales of the frames that just landed: k_ground + k_median_frames, two launches per chunk, behind the depth stage in
-                // stream order -- or, with depths given, behind the chunk's copy (seq_raw).  The stage READS seq_depth[slot .. slot + nf)
-                // only (never a mirror slot) and WRITES its own key planes (one chunk's; the next chunk's stage follows on this stream)
-                // and the results, which are indexed by the ABSOLUTE frame: nothing about them is recycled.  It precedes this chunk's
-                // seq_copied record, so the recycling argument above covers it as it stands: the next copy into these slots waits for
-                // the calls that read this chunk, and those waited for seq_copied -- hence for these reads.
-                float *res = h->seq_scale_dev;
-                const size_t cap = h->seq_scale_cap;
-                launch_frame_scales(h, h->seq_pack, nf, h->seq_depth + (size_t)slot * hw, h->seq_K, 0, h->seq_scale_keys, h->seq_cam_height,
-                                    res + nxt, res + cap + nxt, (int *)(res + 2 * cap) + nxt);
-            }
-            if (use_cache) {      // pack the frames that just landed (and their mirrors), once
-                FramePackParams Fp;
-                Fp.H = h->H; Fp.W = h->W; Fp.depth_is_disp = o.depth_is_disp;
-                Fp.min_disp = o.depth_is_disp ? 1.f / o.max_depth : 0.f; Fp.max_disp = o.depth_is_disp ? 1.f / o.min_depth : 0.f;
-                auto pack = [&](int from, int to, int count) {
-                    Fp.img = h->seq_img + (size_t)from * 3 * hw; Fp.depth = h->seq_depth + (size_t)from * hw;
-                    Fp.fpack = h->seq_fpack + (size_t)to * (h->H + 2) * (h->W + 2); Fp.fdepth = h->seq_fdepth + (size_t)to * hw;
-                    hipLaunchKernelGGL(k_frame_pack, dim3((unsigned)((hw + 255) / 256), count), dim3(256), 0, h->seq_pack, Fp);
-                };
-                pack(slot, slot, nf);
-                if (nm > 0) pack(slot, R + slot, nm);
-            }
-            HIPCHK(h, hipEventRecord(h->seq_copied[slot / C], staged ? h->seq_pack : cs));
-            nxt += nf;
-        }
-        if (rc) break;
-        const int l = (int)(ci % L), s0 = c0 % R;
-        for (int k = c0 / C; k <= (c0 + nbw - 1 + S) / C; k++) HIPCHK(h, hipStreamWaitEvent(ls[l], h->seq_copied[(k * C % R) / C], 0));
-        tcsfm_ctx *c = lane[l];
-        const float *tg = h->seq_img + (size_t)(s0 + tp) * 3 * hw, *sr = h->seq_img + (size_t)s0 * 3 * hw;      // sources: by position (wo)
-        const float *dt = h->seq_depth + (size_t)(s0 + tp) * hw, *ds = h->seq_depth + (size_t)s0 * hw;
-        float *p_in = h->seq_pose_in + (size_t)c0 * N * 6, *p_out = h->seq_pose_out + (size_t)c0 * N * 6;
-        if (pn) {           // initial poses of these windows: PoseNet -> warp -> PoseNet correction, num_iter times, on the lane
-            rc = pose_loop(c, net[l], num_iter, nbw, S, tg, sr, dt, ds, h->seq_K, p_in, nullptr, &wo);
-            if (rc) { if (c != h) h->err = c->err; break; }
-        }
-        if (dense) {
-            // the call's maps come out stacked [pair index][window]; a small kernel puts them in the caller's per-window order, and ONE
-            // copy per call takes them to the host on the lane's stream (asynchronous when the destination is pinned)
-            if (c->seq_dense_cap < (size_t)WB * N * hw) {
-                if (c->seq_dense && c != h) HIPCHK(h, hipFree(c->seq_dense));
-                if (c != h) { c->seq_dense = nullptr; c->seq_dense_cap = 0; HIPCHK(h, hipMalloc(&c->seq_dense, (size_t)WB * N * hw * sizeof(float))); c->seq_dense_cap = (size_t)WB * N * hw; }
-            }
-            float *tmp = c == h ? h->seq_dense_tmp : c->seq_dense;
-            rc = dense_impl(c, &o, N * nbw, nbw, S, tg, sr, dt, ds, h->seq_K, p_in, p_out, tmp, nullptr, &wo);
-            if (!rc) {
-                float *ordered = h->seq_dense + (size_t)c0 * N * hw;
-                hipLaunchKernelGGL(k_maps_to_window_order, dim3((unsigned)((hw + 255) / 256), N * nbw), dim3(256), 0, ls[l], (const float *)tmp, ordered, nbw, N, (int)hw);
-                HIPCHK(h, hipMemcpyAsync(dense_depth_out + (size_t)c0 * N * hw, ordered, (size_t)nbw * N * hw * sizeof(float), hipMemcpyDeviceToHost, ls[l]));
-            }
-        } else {
-            FrameCache fcache = {h->seq_fpack, h->seq_fdepth, s0, tp};
-            rc = refine_impl(c, &o, N * nbw, nbw, S, tg, sr, dt, ds, h->seq_K, p_in, nullptr, p_out,
-                             np == 7 ? h->seq_ls_out + (size_t)c0 * N : nullptr, nullptr, &wo, use_cache ? &fcache : nullptr);
-        }
-        if (rc) { if (c != h) h->err = c->err; break; }
-        HIPCHK(h, hipEventRecord(h->seq_done[ci % ND], ls[l]));
-        for (int k = 0; k < nbw + S; k++) slot_reader[(c0 + k) % R] = ci;
-    }
-    // ---- drain: every lane, then the results in one copy each
-    for (int l = 0; l < L; l++) {
-        hipError_t e = hipStreamSynchronize(ls[l]);
-        if (e != hipSuccess && !rc) { h->err = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); rc = TCSFM_E_HIP; }
-    }
-    (void)hipStreamSynchronize(cs);
-    if (h->seq_pack) (void)hipStreamSynchronize(h->seq_pack);
-    if (rc) return rc;
-    for (int l = 0; l < L; l++)
-        if (int rc_ = pending_error(lane[l])) { if (lane[l] != h) h->err = lane[l]->err; return rc_; }
-    auto fetch = [&](float *dst, const float *dev, int per_pair) -> int {     // device (per call, stacked) -> caller (per window)
-        if (WB == 1) { HIPCHK(h, hipMemcpy(dst, dev, (size_t)nwin * N * per_pair * sizeof(float), hipMemcpyDeviceToHost)); return TCSFM_OK; }
-        stage.resize((size_t)nwin * N * per_pair);
-        HIPCHK(h, hipMemcpy(stage.data(), dev, stage.size() * sizeof(float), hipMemcpyDeviceToHost));
-        for (int w = 0; w < nwin; w++)
-            for (int j = 0; j < N; j++) memcpy(dst + ((size_t)w * N + j) * per_pair, &stage[at(w, j) * per_pair], per_pair * sizeof(float));
-        return TCSFM_OK;
-    };
-    if ((rc = fetch(pose_out, h->seq_pose_out, 6))) return rc;
-    if (pose_init_out && (rc = fetch(pose_init_out, h->seq_pose_in, 6))) return rc;
-    if (log_scale_out && np == 7 && !dense && (rc = fetch(log_scale_out, h->seq_ls_out, 1))) return rc;
-    if (scale_on) {       // the frames' scales: one copy, after the pack stream's final synchronisation above; kept for tcsfm_sequence_scales
-        h->seq_scale_res.resize((size_t)3 * T);
-        for (int a_ = 0; a_ < 3; a_++)
-            HIPCHK(h, hipMemcpy(h->seq_scale_res.data() + (size_t)a_ * T, h->seq_scale_dev + (size_t)a_ * h->seq_scale_cap, (size_t)T * sizeof(float), hipMemcpyDeviceToHost));
-        h->seq_scale_T = T;
-    }
-    if (disp_mode != TCSFM_SEQ_DISP_OFF) { h->seq_disp_T = T; h->seq_disp_kept = disp_mode; }      // (the pack stream was synchronised above)
-    return TCSFM_OK;
-}
-
-int tcsfm_refine_sequence(tcsfm_handle h, const tcsfm_opts *o, int T, int S, const float *frames, const float *depths, const float *K,
-                          const float *pose_init, float *pose_out, float *log_scale_out, int ring, int windows_per_call, int target_pos) {
-    if (h && !pose_init) return fail(h, TCSFM_E_ARG, "tcsfm_refine_sequence: NULL input");
-    return sequence_impl(h, o, T, S, frames, depths, K, pose_init, nullptr, 0, nullptr, pose_out, log_scale_out, ring, windows_per_call, target_pos, "tcsfm_refine_sequence");
-}
-
-int tcsfm_odometry_sequence(tcsfm_handle h, tcsfm_posenet *pn, int num_iter, const tcsfm_opts *o, int T, int S, const float *frames,
-                            const float *depths, const float *K, float *pose_init_out, float *pose_out, float *log_scale_out, int ring,
-                            int windows_per_call, int target_pos) {
-    if (h && !pn) return fail(h, TCSFM_E_ARG, "tcsfm_odometry_sequence: NULL PoseNet");
-    return sequence_impl(h, o, T, S, frames, depths, K, nullptr, pn, num_iter, pose_init_out, pose_out, log_scale_out, ring, windows_per_call, target_pos, "tcsfm_odometry_sequence");
-}
-
-int tcsfm_refine_dense_sequence(tcsfm_handle h, const tcsfm_opts *o, int T, int S, const float *frames, const float *depths, const float *K,
-                                const float *pose_init, float *pose_out, float *depth_out, int ring, int windows_per_call, int target_pos) {
-    if (h && (!pose_init || !depth_out)) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_sequence: NULL input");
-    return sequence_impl(h, o, T, S, frames, depths, K, pose_init, nullptr, 0, nullptr, pose_out, nullptr, ring, windows_per_call, target_pos, "tcsfm_refine_dense_sequence", depth_out);
-}
-
-int tcsfm_sequence_frame_format(tcsfm_handle h, int format) {
-    if (!h) return TCSFM_E_ARG;
-    if (format != TCSFM_FRAMES_F32_CHW && format != TCSFM_FRAMES_U8_CHW && format != TCSFM_FRAMES_U8_HWC)
-        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_frame_format: format must be TCSFM_FRAMES_F32_CHW, TCSFM_FRAMES_U8_CHW or TCSFM_FRAMES_U8_HWC");
-    h->seq_fmt = format;
-    return TCSFM_OK;
-}
-
-int tcsfm_sequence_scale(tcsfm_handle h, float real_cam_height) {
-    if (!h) return TCSFM_E_ARG;
-    if (!(real_cam_height >= 0.f) || std::isinf(real_cam_height))
-        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_scale: real_cam_height must be finite and > 0 (stage on) or 0 (off)");
-    h->seq_cam_height = real_cam_height;
-    return TCSFM_OK;
-}
-
-int tcsfm_sequence_scales(tcsfm_handle h, int T, void *scale_out, void *median_out, int *count_out) {
-    if (!h) return TCSFM_E_ARG;
-    if (!scale_out) return fail(h, TCSFM_E_ARG, "tcsfm_sequence_scales: NULL argument");
-    if (h->seq_scale_T == 0)
-        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_scales: nothing kept (the last sequence call failed or ran with the stage off: tcsfm_sequence_scale)");
-    if (T != h->seq_scale_T) return fail(h, TCSFM_E_ARG, "tcsfm_sequence_scales: T differs from the T of the last sequence call");
-    const float *r = h->seq_scale_res.data();
-    memcpy(scale_out, r, (size_t)T * sizeof(float));
-    if (median_out) memcpy(median_out, r + T, (size_t)T * sizeof(float));
-    if (count_out) memcpy(count_out, r + 2 * (size_t)T, (size_t)T * sizeof(int));
-    return TCSFM_OK;
-}
-
-int tcsfm_sequence_disparity(tcsfm_handle h, int mode) {
-    if (!h) return TCSFM_E_ARG;
-    if (mode != TCSFM_SEQ_DISP_OFF && mode != TCSFM_SEQ_DISP_PLAIN && mode != TCSFM_SEQ_DISP_POST)
-        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_disparity: mode must be TCSFM_SEQ_DISP_OFF, TCSFM_SEQ_DISP_PLAIN or TCSFM_SEQ_DISP_POST");
-    h->seq_disp_mode = mode;
-    return TCSFM_OK;
-}
-
-int tcsfm_sequence_disparities(tcsfm_handle h, int T, int first, int count, void *out, int *mode_out) {
-    if (!h) return TCSFM_E_ARG;
-    if (!out) return fail(h, TCSFM_E_ARG, "tcsfm_sequence_disparities: NULL argument");
-    if (h->seq_disp_T == 0)
-        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_disparities: nothing kept (the last sequence call failed or ran with the stage off: tcsfm_sequence_disparity)");
-    if (T != h->seq_disp_T) return fail(h, TCSFM_E_ARG, "tcsfm_sequence_disparities: T differs from the T of the last sequence call");
-    if (first < 0 || count < 1 || first > T - count) return fail(h, TCSFM_E_ARG, "tcsfm_sequence_disparities: need 0 <= first, count >= 1 and first + count <= T");
-    const size_t plane = (size_t)h->H * h->W * (h->seq_disp_kept == TCSFM_SEQ_DISP_POST ? sizeof(double) : sizeof(float));
-    DeviceGuard dev_guard(h->device);
-    HIPCHK(h, hipMemcpy(out, (const char *)h->seq_disp_dev + (size_t)first * plane, (size_t)count * plane, hipMemcpyDeviceToHost));
-    if (mode_out) *mode_out = h->seq_disp_kept;
-    return TCSFM_OK;
-}
+#include "sequence_host.h"
 
 int tcsfm_disp_post_process(tcsfm_handle h, const tcsfm_opts *o, int N, const void *l_disp, const void *r_disp_mirrored, void *out) {
     if (int rc_q = drain_queued(h)) return rc_q;
@@ -3529,16 +3097,6 @@ int tcsfm_frames_from_u8(tcsfm_handle h, const tcsfm_opts *o, int format, int N,
     DeviceGuard dev_guard(h->device);
     if (int rc_ = pending_error(h)) return rc_;
     HIPCHK(h, launch_frames_u8(h->stream, format == TCSFM_FRAMES_U8_HWC, N, (const uint8_t *)src, (float *)dst, nullptr, 0, hw));
-    return TCSFM_OK;
-}
-
-int tcsfm_sequence_frame_source(tcsfm_handle h, int src_h, int src_w) {
-    if (!h) return TCSFM_E_ARG;
-    if (src_h == 0 && src_w == 0) { h->seq_src_h = h->seq_src_w = 0; return TCSFM_OK; }
-    if (src_h <= 0 || src_w <= 0)
-        return fail(h, TCSFM_E_ARG, "tcsfm_sequence_frame_source: src_h and src_w must both be positive, or both 0 (no source size)");
-    if (const char *why = resize_refusal(src_h, src_w, h->H, h->W)) return fail(h, TCSFM_E_ARG, (std::string("tcsfm_sequence_frame_source: ") + why).c_str());
-    h->seq_src_h = src_h; h->seq_src_w = src_w;
     return TCSFM_OK;
 }
 
