@@ -32,17 +32,20 @@ BIG_IDS = [i for i in DX.IDS if DX.BY_ID[i].H >= 100]
 
 def test_constants_are_the_kernels():
     api, ker, joint, dref = (open(os.path.join(CSRC, f)).read() for f in ("tcsfm_api.hip", "kernels.h", "joint_kernel.h", "dense_ref_kernel.h"))
+    api += open(os.path.join(CSRC, "dense_host.h")).read()          # the dense drivers: part of the API file's translation unit
+    lay = open(os.path.join(CSRC, "layout.h")).read()               # the layout constants host arithmetic and kernels share: the joint tile lives there
     assert re.search(r"constexpr int FM = (\d+), WW = TW \+ 2 \* FM, WH = TH \+ 2 \* FM", ker).group(1) == str(DX.FM)
     assert re.search(r"constexpr double DREF_FIX = (\d+)\.0;", ker).group(1) == str(2 ** DX.DREF_FIX_BITS)
     assert "llrint((double)(f_dc * w4[k]) * DREF_FIX)" in ker and "llrint((double)(coef * w4[k]) * DREF_FIX)" in dref
-    tw, th = re.search(r"kJointTileW = (\d+)", api + joint), re.search(r"kJointTileH = (\w+)", api + joint)
+    tw, th = re.search(r"kJointTileW = (\d+)", lay), re.search(r"kJointTileH = (\w+)", lay)
     assert tw and int(tw.group(1)) == DX.JTILE_W and th
-    assert re.search(r"#define TC_JOINT_TILE_H (\d+)", api + joint).group(1) == str(DX.JTILE_H)
+    assert re.search(r"#define TC_JOINT_TILE_H (\d+)", lay).group(1) == str(DX.JTILE_H)
     assert "s += (r0 + k * PARTS < r_hi) ? (double)w[k] : 0.0;" in joint                     # k_solve_joint adds the records in double
     assert "for (int w = 0; w < NT / 64; w++) s += red[w * 32 + tid];" in joint              # joint_reduce_add: the wave partials in order
     assert "g_rho -= o_depth * o_depth * (r_dc * Edc - r_eph * Eph);" in joint
     # the export returns before the split of the record sum is configured: nsplit stays 0 (memset) on that path
-    assert api.index("if (ex) {        // one linearisation, exported") < api.index("auto split_of = [](int recs, int ns)")
+    assert re.search(r"if \(ex\) return export_once\(\);\n\s+params_solve\(\);", api) and api.count("params_solve()") == 2
+    assert re.search(r"void params_solve\(\) \{\n\s+auto split_of = \[\]\(int recs, int ns\)", api) and api.count("nsplit =") == 2
     assert "memset(&Sj, 0, sizeof(Sj));" in api and "const int G = P.nsplit > 1 ? P.nsplit : 1;" in joint
     assert [DX.additions_rho(S) for S in (1, 2, 3, 4)] == [21, 23, 25, 27]
     assert [DX.additions_xi(S) for S in (1, 2, 3, 4)] == [26, 27, 28, 29]

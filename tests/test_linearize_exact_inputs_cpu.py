@@ -22,10 +22,11 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 def test_reduction_constants_are_the_kernels():
     api, ker = (open(os.path.join(CSRC, f)).read() for f in ("tcsfm_api.hip", "kernels.h"))
-    assert re.search(r"constexpr int TILE_W = (\d+), TILE_H = TC_TILE_H, TILE_NT = TILE_W \* TILE_H;", api).group(1) == str(LX.TILE_W)
-    assert re.search(r"#define TC_TILE_H (\d+)", api).group(1) == str(LX.TILE_H) and LX.NT == LX.TILE_W * LX.TILE_H
+    lay = open(os.path.join(CSRC, "layout.h")).read()          # the layout constants host arithmetic and kernels share: the tile and RG live there
+    assert re.search(r"constexpr int TILE_W = (\d+), TILE_H = TC_TILE_H, TILE_NT = TILE_W \* TILE_H;", lay).group(1) == str(LX.TILE_W)
+    assert re.search(r"#define TC_TILE_H (\d+)", lay).group(1) == str(LX.TILE_H) and LX.NT == LX.TILE_W * LX.TILE_H
     assert re.search(r"int direct_records\(const tcsfm_ctx \*h\) \{ return h->nblk <= (\d+); \}", api).group(1) == str(LX.DIRECT_MAX_TILES)
-    assert re.search(r"constexpr int RG = (\d+);", ker).group(1) == str(LX.RG)
+    assert re.search(r"constexpr int RG = (\d+);", lay).group(1) == str(LX.RG)
     assert "static_assert(NCEN % NT == 0" in ker                                         # whole pixels per thread: PPT = NCEN / NT
     assert "? (double)v[j] : 0.0;" in ker                                                  # k_solve adds in double
     assert [LX.n_tiles(H, W) for H, W in LX.SHAPES] == [1, 1, 4, 6, 15, 256, 260]

@@ -294,8 +294,7 @@ struct QresParams {
     int H, W, B, S, rec_stride, rec_first;
     float rho_lo, rho_hi;
 };
-constexpr int QRES_CELLS_PER_WG = 16;      // 4 waves x 4 cells: the cells of a wave are loaded together (a first version walked 16 cells per wave
-                                           // one dependent load after the other: 25 us per linearisation at 240x320)
+// (QRES_CELLS_PER_WG, the cells of one workgroup of k_qres_schur: layout.h)
 
 // weight of cell c in the x4 upsampling taps of pixel x (torch area_pixel_compute_source_index, align_corners = False)
 __device__ __forceinline__ float up4_weight(int x, int c, int nq) {

@@ -24,15 +24,7 @@
 
 namespace tc {
 
-constexpr int JMAXS = 4;                       // sources per target the joint kernels are instantiated for (1 .. JMAXS) under the reference's loss
-constexpr int JMAXS_OWN = 3;                   // ... and in the library's own joint mode (opts.dense_joint with window rule PAIR: 2 .. 3)
-template <int NS> struct JointLayout {
-    static constexpr int NP = 6 * NS;
-    static constexpr int NHJ = NP * (NP + 1) / 2;
-    static constexpr int OFF_G = NHJ, OFF_S = NHJ + NP, OFF_SHARE = OFF_S + 3, OFF_NM = OFF_SHARE + NS, NACC = OFF_NM + NS;
-    static constexpr int JREC = (2 + 6 * NS + 3) / 4 * 4;     // floats per pixel record: g_rho, Dd, B[NS][6], padded to float4s
-    __host__ __device__ static constexpr int tri(int r, int c) { return r >= c ? r * (r + 1) / 2 + c : c * (c + 1) / 2 + r; }
-};
+// (JMAXS, JMAXS_OWN and JointLayout<NS>, the records of a target with NS sources: layout.h)
 
 struct JointParams {
     float *jrec;             // [B][H*W][JREC]

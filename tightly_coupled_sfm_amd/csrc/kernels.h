@@ -25,6 +25,7 @@
 //   k_ssim, k_disp_to_depth: SSIM_Loss / disp_to_depth drop-ins.  dense_kernel.h, scale_kernel.h: dense mode, DNet scale.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "layout.h"
 #include "se3_math.h"
 #include "wave_reduce.h"
 
@@ -340,7 +341,6 @@ __device__ __forceinline__ void write_const_lanes(int lane, const double *K, con
 // over their 2 S B ncall directed pairs; every call keeps its own buffers, the kernels reach them through this pointer table.
 // Batch pair n in the stacked order over Bt = ncall cB targets (forward n = s Bt + b, inverse S Bt + s Bt + b); target b belongs to
 // call b / cB as its local target b % cB.  Results per window are the bits of the call run on its own (the kernels are batch-independent).
-constexpr int TC_MAX_COAL = 16;
 struct CoalTab {
     int ncall, cB, cS, pad;
     const float *tgt[TC_MAX_COAL], *src[TC_MAX_COAL], *dt[TC_MAX_COAL], *ds[TC_MAX_COAL], *K[TC_MAX_COAL], *pose[TC_MAX_COAL];
@@ -845,15 +845,9 @@ __global__ __launch_bounds__(256) void k_warp(WarpParams P) {
 // neighbourhood and accumulates J'J and J'r in registers; one wave-reduce + LDS reduce per workgroup, one
 // partial-sum record per workgroup to HBM (deterministic: no atomics).
 
-constexpr int RG = 16;       // workgroups per in-launch reduction group
 constexpr int LDS_REC = 28;  // floats per staged pixel: 24 used (six 16-byte rows, NP = 7 included), stride 28 for the banks (28 l mod 64 visits every bank group once)
 
-template <int NP>
-struct AccLayout {
-    static constexpr int NH = NP * (NP + 1) / 2;
-    static constexpr int OFF_HP = 0, OFF_GP = NH, OFF_HD = NH + NP, OFF_GD = 2 * NH + NP, OFF_S = 2 * NH + 2 * NP;
-    static constexpr int NACC = 2 * NH + 2 * NP + 3;  // + sum(M W diff), sum(M), sum(dd)
-};
+// (RG, the workgroups per in-launch reduction group, and AccLayout<NP>, the accumulator record: layout.h)
 
 enum { MODE_COST = 0, MODE_LIN = 1, MODE_MAPS = 2 };
 

@@ -7,6 +7,7 @@
 //   twists are [rho, phi], translation first, as liegroups.SE3 (validate.py:65).
 #pragma once
 #include <math.h>
+#include <stddef.h>
 
 #ifdef __HIPCC__
 #define TC_HD __host__ __device__ inline
@@ -274,6 +275,42 @@ TC_HD void apply_step(int param, const double *H, const double *g, double lambda
         pose_to_T(pose, Tout);
     }
     *sout = sin_ + (N == 7 ? delta[N - 1] : 0.0);
+}
+
+// l_pose_consist (optimizer.py:95-96) of ONE linearisation at the 2 SB input poses (forward pairs, then their inverses), host only, in
+// double: value c sum |p_fwd + p_inv|, c = w / (6 SB); gradient c r / max(|r|, eps) in pose coordinates carried to the left perturbation
+// by A^-T, A^-1 = [[-I, Tx], [0, -Je^-1]] (the oracle's pose_consist_term; the refinement's kernels hold the same term).  Adds the
+// gradient to g_pose [2 SB][6] and returns the value.
+inline double pose_consist_linearised(const float *poses, int SB, double w, double eps, double *g_pose) {
+    const int N = 2 * SB;
+    const double c = w / (6.0 * SB);
+    double total = 0.0;
+    for (int m = 0; m < N; m++) {
+        const float *pm = &poses[(size_t)m * 6], *pp = &poses[(size_t)(m < SB ? m + SB : m - SB) * 6];
+        const double cx = cos(-(double)pm[3]), sx = sin(-(double)pm[3]), cy = cos(-(double)pm[4]), sy = sin(-(double)pm[4]);
+        const double Je[9] = {1, 0, sy, 0, cx, -sx * cy, 0, sx, cx * cy}, id = 1.0 / cy;
+        const double Ji[9] = {(Je[4] * Je[8] - Je[5] * Je[7]) * id, -(Je[1] * Je[8] - Je[2] * Je[7]) * id, (Je[1] * Je[5] - Je[2] * Je[4]) * id,
+                              -(Je[3] * Je[8] - Je[5] * Je[6]) * id, (Je[0] * Je[8] - Je[2] * Je[6]) * id, -(Je[0] * Je[5] - Je[2] * Je[3]) * id,
+                              (Je[3] * Je[7] - Je[4] * Je[6]) * id, -(Je[0] * Je[7] - Je[1] * Je[6]) * id, (Je[0] * Je[4] - Je[1] * Je[3]) * id};
+        const double tq[3] = {-(double)pm[0], -(double)pm[1], -(double)pm[2]};
+        const double Tx[9] = {0, -tq[2], tq[1], tq[2], 0, -tq[0], -tq[1], tq[0], 0};
+        double Ai[36] = {0}, gp[6];
+        for (int i = 0; i < 3; i++) {
+            Ai[6 * i + i] = -1;
+            for (int j = 0; j < 3; j++) { Ai[6 * i + 3 + j] = Tx[3 * i + j]; Ai[6 * (3 + i) + 3 + j] = -Ji[3 * i + j]; }
+        }
+        for (int j = 0; j < 6; j++) {
+            const double r = (double)pm[j] + (double)pp[j], a = fabs(r), den = a > eps ? a : eps;
+            total += 0.5 * c * a;
+            gp[j] = c * r / den;
+        }
+        for (int i = 0; i < 6; i++) {
+            double v = 0.0;
+            for (int k = 0; k < 6; k++) v += Ai[6 * k + i] * gp[k];
+            g_pose[(size_t)m * 6 + i] += v;
+        }
+    }
+    return total;
 }
 
 }  // namespace tc

@@ -32,6 +32,7 @@
 #include "resize_u8_kernel.h"
 #include "disp_post_kernel.h"
 #include "depth_eval_kernel.h"
+#include "dense_plan.h"
 
 using namespace tc;
 
@@ -115,11 +116,7 @@ inline int damaged_among(const std::vector<void *> &ps) {
 
 namespace {
 
-// tile geometry of the hot kernel (one place to retune)
-#ifndef TC_TILE_H
-#define TC_TILE_H 16
-#endif
-constexpr int TILE_W = 32, TILE_H = TC_TILE_H, TILE_NT = TILE_W * TILE_H;      // (A/B builds: -DTC_TILE_H=8 -> 32 x 8 tiles of 256 threads)
+// (the tile geometry of the hot kernel and the layout constants: layout.h)
 
 thread_local std::string g_create_error;
 
@@ -145,6 +142,43 @@ struct DevBuf {
         if (int rc_reserve_ = (buf).reserve((h), (n), __FILE__, __LINE__)) return rc_reserve_;       \
     } while (0)
 
+// The scratch of the dense modes (dense_host.h), allocated by whichever mode first needs a buffer, at the handle's capacity for it
+// (dense_plan.h: dense_caps): never re-sized while the handle lives, captured call graphs bake the pointers in.
+struct DenseScratch {
+    DevBuf<float> sel_maps;                            // dense window modes: the forward pairs' diff | valid maps, [2][max_pairs][H*W]
+    DevBuf<float> dense_rec, depth0;                   // per-pixel records and prior centres of the pair-form dense kernels
+    DevBuf<double> delta;                              // ... and their pose steps
+    DevBuf<float> dense_rec2, depth_alt;               // ... second record / depth buffers of the fused back-substitution (ping-pong)
+    DevBuf<float> dense_rec_acc, depth_acc;            // dense LM: accepted per-pixel records / depth maps
+    DevBuf<int> lm_accept;
+    // joint dense modes (one depth map per target shared by its S forward pairs): per-pixel records, workgroup records, per-target state
+    DevBuf<float> jrec, jrec_acc, jblockrec, jdepth_acc;
+    DevBuf<JointState> jstate;
+    DevBuf<double> jdelta;
+    DevBuf<double> jpart;                              // split record sums of the joint solve (JointSolveParams::nsplit): [2][8][NACC] fp64
+    DevBuf<int> jtick;                                 // ... and their tickets, zero between launches
+    // dense mode on the reference's loss (dense_ref_kernel.h): mask counts, fixed-point scatter sums, linearisation export
+    DevBuf<int> dref_norms;
+    DevBuf<long long> dref_ext;
+    DevBuf<double> dref_export;
+    DevBuf<float> dref_smooth;                         // l_smooth: [targets][2] mean of the sigmoid disparity, the target's whole term (k_dref_smooth)
+    DevBuf<float> qres_rho, qres_rec;                  // TCSFM_DEPTH_QUARTER: [2][targets][H/4 * W/4] cell unknowns, [targets][cells][JREC] cell records
+    // free source depth maps (opts.free_source_depths): the inverse pairs as groups of one source
+    DevBuf<float> jrec_src;
+    DevBuf<JointState> jstate_src;
+    DevBuf<double> jdelta_src;
+    DevBuf<long long> dref_ext_src;
+    DevBuf<float> qres_rho_src, qres_rec_src;          // ... in the quarter-resolution parametrisation
+    void release() {       // tcsfm_destroy
+        for (DevBuf<float> *b : {&sel_maps, &dense_rec, &depth0, &dense_rec2, &depth_alt, &dense_rec_acc, &depth_acc, &jrec, &jrec_acc, &jblockrec, &jdepth_acc,
+                                 &dref_smooth, &qres_rho, &qres_rec, &jrec_src, &qres_rho_src, &qres_rec_src})
+            b->release();
+        for (DevBuf<double> *b : {&delta, &jdelta, &jpart, &dref_export, &jdelta_src}) b->release();
+        for (DevBuf<int> *b : {&lm_accept, &jtick, &dref_norms}) b->release();
+        dref_ext.release(); dref_ext_src.release(); jstate.release(); jstate_src.release();
+    }
+};
+
 struct tcsfm_ctx {
     int device = 0, H = 0, W = 0, max_pairs = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -158,25 +192,10 @@ struct tcsfm_ctx {
     float *pose_dev = nullptr, *ls_dev = nullptr, *K_dev = nullptr, *stats_dev = nullptr;
     int tiles_x = 0, tiles_y = 0, nblk = 0, ngrp = 0, ngrp_pad = 0, stats_cap_iters = 0;
     int nblk_alloc = 0, ngrp_alloc = 0;   // scratch capacity of the pose path and of the pair-form dense kernels (16 x 16 tiles or coarser)
-    int jrec_alloc = 0;                    // workgroup records per target jblockrec holds: joint_records_per_target (the joint kernels' own grid)
-    float *dense_rec = nullptr, *depth0 = nullptr;   // dense mode scratch, allocated on first use
-    float *dense_rec2 = nullptr, *depth_alt = nullptr;   // ... second record / depth buffers of the fused back-substitution (ping-pong)
-    float *dense_rec_acc = nullptr, *depth_acc = nullptr;   // dense LM: accepted per-pixel records / depth maps
-    int *lm_accept = nullptr;
-    double *delta = nullptr;
-    // joint dense mode (one depth map per target shared by its S forward pairs): per-pixel records, workgroup records, per-target state
-    float *jrec = nullptr, *jrec_acc = nullptr, *jblockrec = nullptr, *jdepth_acc = nullptr;
-    JointState *jstate = nullptr;
-    double *jdelta = nullptr;
-    double *jpart = nullptr; int *jtick = nullptr;     // split record sums of the joint solve (JointSolveParams::nsplit): [2 targets][8][NACC] fp64, tickets
-    int jrec_S = 0;
-    // dense mode on the reference's loss (dense_ref_kernel.h): mask counts, fixed-point scatter sums, linearisation export
-    int *dref_norms = nullptr;
-    long long *dref_ext = nullptr;
-    double *dref_export = nullptr;
+    DenseScratch dense;                    // the dense modes' scratch, allocated on first use
+    DenseCaps caps;                        // ... and every buffer's capacity (dense_plan.h), fixed at create
     hipStream_t aux_stream = nullptr;  // joint dense mode: the inverse pairs' refinement runs beside the forward group's (fork / join by events)
     hipEvent_t aux_fork = nullptr, aux_join = nullptr;
-    float *sel_maps = nullptr;   // dense window modes: the forward pairs' diff | valid maps, [2][max_pairs][H*W], allocated on first use
     // tcsfm_warp_backward (warp_grad_kernel.h), allocated on first use: workgroup records of the pose gradient [max_pairs][blocks][12],
     // fixed-point scatter sums [max_pairs][H*W], per-item max |g_proj_depth| (bit patterns)
     double *wgrad_rec = nullptr;
@@ -245,17 +264,12 @@ struct tcsfm_ctx {
     // tcsfm_refine_window_queued: calls of one shape waiting to run as ONE launch sequence (tcsfm_set_coalesce / tcsfm_flush)
     struct PendingCall { const float *tgt, *srcs, *dt, *ds, *K, *pose_in; float *pose_out; float *depth_out; const float *ls_in; float *ls_out; };
                                        // depth_out: dense calls; ls_in / ls_out: pose + scale calls (or null)
-    float *dref_smooth = nullptr;      // l_smooth: [targets][2] mean of the sigmoid disparity, the target's whole term (k_dref_smooth)
     bool lanes_serial = false;         // tcsfm_set_lanes' self-probe found that this process's streams do NOT run side by side (they slow each other
                                        // down: include/tcsfm.h "lanes"): the *_async calls run on the handle's own stream, one after the other
     float lane_probe[2] = {0.f, 0.f};  // the probe's figures: ms of the stand-in launches on ONE stream / alternating over TWO streams
     bool dref_dirty = true;            // the scatter sums (dref_ext, dref_ext_src) may be non-zero: a call that ran to its end leaves them zero
                                        // (k_dense_joint clears what it consumes); a fresh allocation, an export or a failed call does not
-    // free source depth maps (opts.free_source_depths): the inverse pairs as groups of one source
-    float *jrec_src = nullptr; JointState *jstate_src = nullptr; double *jdelta_src = nullptr; long long *dref_ext_src = nullptr;
-    float *qres_rho_src = nullptr, *qres_rec_src = nullptr;      // ... in the quarter-resolution parametrisation
     double *pose_lin = nullptr;        // l_pose_consist: [2][max_pairs][12] transforms at the linearisation (k_solve, kernels.h)
-    float *qres_rho = nullptr, *qres_rec = nullptr;      // TCSFM_DEPTH_QUARTER: [targets][H/4 * W/4] cell unknowns, [targets][cells][JREC] cell records
     int coal_max = 0;
     int pend_dense = 0;                // the waiting calls are dense-mode calls (tcsfm_refine_dense_window_queued)
     int coal_lanes = 1;                // merged sequences alternate over this many of the handle's streams (tcsfm_set_coalesce_lanes)
@@ -362,8 +376,6 @@ int pending_error(tcsfm_ctx *h) {
     return TCSFM_OK;
 }
 
-constexpr int kMaxAcc = AccLayout<7>::NACC;
-constexpr int kLinOut = 7 * 7 + 7 + 4;
 
 int check_common(tcsfm_ctx *h, const tcsfm_opts *o, int N) {
     if (!h) return TCSFM_E_ARG;
@@ -702,254 +714,6 @@ SolveParams solve_params(tcsfm_ctx *h, const tcsfm_opts *o, int np, int shared) 
 }  // namespace
 
 namespace {
-// Scratch of the joint dense kernels, allocated ONCE on first use (a captured call graph -- tcsfm_set_graph_replay -- bakes these pointers
-// in, so they are never freed or re-sized while the handle lives).  The per-PIXEL records (jrec, jrec_acc, the quarter-resolution cell records)
-// and the per-target record arrays (workgroup records, split partial sums) are sized for the largest layout any call can need: a call of S
-// sources has at most max_pairs / (2 S) targets of JREC(S) floats per pixel and NACC(S) per record, so the capacity is the maximum over
-// S = 1 .. JMAXS of (targets at S) x JREC(S) -- 8 x max_pairs / 2 at S = 1 and S = 2, 28 x max_pairs / 8 at S = 4 -- not JREC(JMAXS) x the most
-// targets (the per-pixel records of a handle are smaller than the S <= 3 layouts had them: 20 x max_pairs / 4).  The workgroup records also
-// hold, behind the forward groups', the free-source mode's S B inverse groups of one source.  The per-TARGET arrays (state, step, accepted
-// depth) are sized for the most targets any call can have: (max_pairs + 1) / 2, reached at S = 1 (they were sized for S >= 2 and
-// the S = 1 reference-loss mode indexed past them).
-constexpr int kJointSplitMax = 8;
-static_assert(JMAXS == 4, "joint_max_over_S lists the layouts S = 1 .. 4");
-constexpr size_t joint_jrec(int S) { return S == 1 ? JointLayout<1>::JREC : S == 2 ? JointLayout<2>::JREC : S == 3 ? JointLayout<3>::JREC : JointLayout<4>::JREC; }
-constexpr size_t joint_nacc(int S) { return S == 1 ? JointLayout<1>::NACC : S == 2 ? JointLayout<2>::NACC : S == 3 ? JointLayout<3>::NACC : JointLayout<4>::NACC; }
-// what 0: floats per pixel of jrec / jrec_acc / qres_rec; 1: accumulator rows of one half of jpart (and the forward groups' share of a
-// jblockrec row); 2: one jblockrec row = forward groups + the free-source mode's inverse groups
-constexpr size_t joint_max_over_S(size_t n, int what) {
-    size_t m = 0;
-    for (int S = 1; S <= JMAXS; S++) {
-        const size_t t = S == 1 ? (n + 1) / 2 : n / (2 * S);          // targets of a call with S sources (2 B S <= max_pairs)
-        const size_t v = t * (what == 0 ? joint_jrec(S) : what == 1 ? joint_nacc(S) : joint_nacc(S) + S * joint_nacc(1));
-        m = v > m ? v : m;
-    }
-    return m;
-}
-// tile height of k_dense_joint's own grid (32 x 8 tiles of 256 threads by default; 16: the round-4 grid shared with the pair-form kernels)
-#ifndef TC_JOINT_TILE_H
-#define TC_JOINT_TILE_H 8
-#endif
-constexpr int kJointTileW = 32, kJointTileH = TC_JOINT_TILE_H;      // k_dense_joint / k_dense_joint2's tiles (both joint modes launch on them)
-inline int joint_tiles(const tcsfm_ctx *h) { return ((h->W + kJointTileW - 1) / kJointTileW) * ((h->H + kJointTileH - 1) / kJointTileH); }
-// k_qres_*'s cell groups: their records follow the joint kernel's tiles' in a target's row of jblockrec
-inline int qres_groups(const tcsfm_ctx *h) { return ((h->H / 4) * (h->W / 4) + QRES_CELLS_PER_WG - 1) / QRES_CELLS_PER_WG; }
-// workgroup records of one target, the most any call can write: the joint tiles, then the quarter-resolution unknown's cell groups.  (Not the
-// pose path's 16 x 16 tile count: that is the smaller one whenever ceil(W / 16) is odd and ceil(H / 8) even -- 16 x 48, 28 x 48, 192 x 624.)
-inline int joint_records_per_target(const tcsfm_ctx *h) { return joint_tiles(h) + qres_groups(h); }
-inline size_t joint_rec_floats(size_t n) { return joint_max_over_S(n, 0); }
-inline size_t joint_acc_floats(size_t n) { return joint_max_over_S(n, 1); }
-inline size_t joint_blockrec_floats(size_t n) { return joint_max_over_S(n, 2); }
-int joint_scratch(tcsfm_ctx *h) {
-    if (h->jrec) return TCSFM_OK;
-    const size_t hw = (size_t)h->H * h->W, n = h->max_pairs;
-    const size_t nt = (n + 1) / 2, nrec = joint_rec_floats(n), nacc = joint_acc_floats(n), nblkrec = joint_blockrec_floats(n);
-    HIPCHK(h, hipMalloc((void **)&h->jrec, hw * nrec * sizeof(float)));
-    HIPCHK(h, hipMalloc((void **)&h->jrec_acc, hw * nrec * sizeof(float)));
-    HIPCHK(h, hipMalloc((void **)&h->jdepth_acc, nt * hw * sizeof(float)));
-    h->jrec_alloc = joint_records_per_target(h);
-    HIPCHK(h, hipMalloc((void **)&h->jblockrec, (size_t)h->jrec_alloc * nblkrec * sizeof(float)));      // (tile records + the quarter-resolution mode's cell-group records)
-    HIPCHK(h, hipMalloc((void **)&h->jstate, nt * sizeof(JointState)));
-    HIPCHK(h, hipMalloc((void **)&h->jdelta, nt * 6 * JMAXS * sizeof(double)));
-    HIPCHK(h, hipMalloc((void **)&h->jpart, 2 * kJointSplitMax * nacc * sizeof(double)));      // (forward groups, then the free-source mode's inverse groups)
-    HIPCHK(h, hipMalloc((void **)&h->jtick, 2 * nt * sizeof(int)));
-    HIPCHK(h, hipMemset(h->jtick, 0, 2 * nt * sizeof(int)));
-    h->jrec_S = JMAXS;
-    return TCSFM_OK;
-}
-// capacity of that scratch for a call with B targets of NS sources each (explicit: the sizes above are derived, not per call)
-template <int NS>
-bool joint_scratch_fits(const tcsfm_ctx *h, int B, int recs_per_target) {
-    using JL = JointLayout<NS>;
-    const size_t n = h->max_pairs, nt = (n + 1) / 2;
-    return (size_t)B <= nt && (size_t)B * JL::JREC <= joint_rec_floats(n) && (size_t)B * JL::NACC <= joint_acc_floats(n) &&
-           recs_per_target <= h->jrec_alloc && (size_t)B * recs_per_target * JL::NACC <= (size_t)h->jrec_alloc * joint_blockrec_floats(n);
-}
-
-// Scratch of the dense modes, allocated on first use by whichever mode needs it (dense_body, dense_joint_run, dense_ref_run).  Like the joint
-// scratch above it is never freed or re-sized while the handle lives: captured call graphs bake the pointers in.
-int ensure_dense_rec(tcsfm_ctx *h) {        // per-pixel records, prior centres and steps of the pair-form dense kernels
-    if (h->dense_rec) return TCSFM_OK;
-    const size_t hw = (size_t)h->H * h->W, n = h->max_pairs;
-    HIPCHK(h, hipMalloc((void **)&h->dense_rec, n * hw * 8 * sizeof(float)));
-    HIPCHK(h, hipMalloc((void **)&h->depth0, n * hw * sizeof(float)));
-    HIPCHK(h, hipMalloc((void **)&h->delta, n * 8 * sizeof(double)));
-    return TCSFM_OK;
-}
-int ensure_dense_lm(tcsfm_ctx *h) {         // dense LM: accepted per-pixel records / depth maps, accept flags
-    if (h->dense_rec_acc) return TCSFM_OK;
-    const size_t hw = (size_t)h->H * h->W, n = h->max_pairs;
-    HIPCHK(h, hipMalloc((void **)&h->dense_rec_acc, n * hw * 8 * sizeof(float)));
-    HIPCHK(h, hipMalloc((void **)&h->depth_acc, n * hw * sizeof(float)));
-    HIPCHK(h, hipMalloc((void **)&h->lm_accept, n * sizeof(int)));
-    return TCSFM_OK;
-}
-int ensure_sel_maps(tcsfm_ctx *h) {         // the forward pairs' diff | valid maps
-    if (!h->sel_maps) HIPCHK(h, hipMalloc((void **)&h->sel_maps, (size_t)2 * h->max_pairs * h->H * h->W * sizeof(float)));
-    return TCSFM_OK;
-}
-
-// JOINT dense mode of a window (include/tcsfm.h, tcsfm_refine_dense_window): the S forward pairs of every target share one depth map
-// and are solved together (k_dense_joint / k_solve_joint / k_dense_joint_update); the inverse pairs run the pair-form dense kernels on
-// offset views of the same scratch.  Inputs already on the device.
-template <int NS>
-int dense_joint_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, const float *d_src, const float *d_dt, const float *d_ds,
-                           const float *d_K, const float *d_pose_in, float *d_pose_out, float *d_depth_out, float *d_stats, const WinOff *wo) {
-    using JL = JointLayout<NS>;
-    constexpr int S = NS;
-    const int SB = S * B, N = 2 * SB;
-    const size_t hw = (size_t)h->H * h->W, n = h->max_pairs;
-    const bool lm = o->solver == TCSFM_SOLVER_LM;
-    const int n_sel = (o->argmin) ? SB : 0;
-    int rc;
-    constexpr int DTW = 32, DTH = 16, DNT = 512;
-    const int tiles_x = (h->W + DTW - 1) / DTW, tiles_y = (h->H + DTH - 1) / DTH, nblk = tiles_x * tiles_y;
-    // the joint kernel runs on its own tile grid, as under the reference's loss (third session of round 5): 256-thread workgroups, for S = 2 the
-    // LEAN form of the kernel (161 VGPRs: three workgroups per CU instead of one 512-thread workgroup at 212-232)
-    constexpr int JTW = kJointTileW, JTH = kJointTileH, JNT = JTW * JTH;
-    const int jtiles_x = (h->W + JTW - 1) / JTW, jtiles_y = (h->H + JTH - 1) / JTH, jnblk = jtiles_x * jtiles_y;      // = joint_tiles(h)
-    if ((n_sel && (rc = ensure_sel_maps(h))) || (rc = ensure_dense_rec(h)) || (lm && (rc = ensure_dense_lm(h))) || (rc = joint_scratch(h))) return rc;
-    if ((size_t)nblk > (size_t)h->nblk_alloc) return fail(h, TCSFM_E_ARG, "internal: dense tile grid exceeds scratch");
-    if (!joint_scratch_fits<NS>(h, B, jnblk)) return fail(h, TCSFM_E_ARG, "internal: the joint dense scratch does not hold this many targets");
-    tcsfm_opts oo = *o;
-    oo.refine = TCSFM_REFINE_POSE;
-    oo.window_rule = TCSFM_WINDOW_PAIR;          // (the pose-mode coupling; the joint kernel takes the rule through JointParams)
-    InitParams I = init_params(h, &oo, N, d_pose_in, nullptr, d_K, 0);
-    I.K_mod = B;
-    if ((rc = run_pack(h, &oo, N, d_tgt, d_src, d_dt, d_ds, &I, B, S, h->depth0, wo))) return rc;
-    // ---- forward group: joint
-    LinParams Pj = lin_params(h, &oo, 6);
-    Pj.tiles_x = jtiles_x; Pj.tiles_y = jtiles_y; Pj.ngrp = (jnblk + RG - 1) / RG; Pj.direct = 1;
-    float *sel_diff = h->sel_maps, *sel_valid = h->sel_maps ? h->sel_maps + (size_t)h->max_pairs * hw : nullptr;
-    if (n_sel) { Pj.ext_diff = sel_diff; Pj.ext_valid = sel_valid; Pj.n_ext = n_sel; Pj.ext_B = B; Pj.ext_S = S; }
-    JointParams J;
-    memset(&J, 0, sizeof(J));
-    J.jrec = h->jrec; J.depth0 = h->depth0; J.jblockrec = h->jblockrec; J.lambda_depth = o->lambda_depth; J.w_prior = o->prior_depth;
-    J.B = B; J.S = S; J.argmin = o->argmin ? 1 : 0;
-    J.automask = 0;                             // own masks only without argmin, where the reference's forward term has no auto-mask (:71-73)
-    JointSolveParams Sj;
-    memset(&Sj, 0, sizeof(Sj));
-    Sj.jblockrec = h->jblockrec; Sj.js = h->jstate; Sj.st = h->state; Sj.pc = h->pconst; Sj.stats = d_stats; Sj.nblk = jnblk; Sj.B = B;
-    Sj.n_iters = o->n_iters; Sj.solver = o->solver; Sj.lambda_up = o->lambda_up; Sj.lambda_down = o->lambda_down; Sj.lambda_min = o->lambda_min;
-    Sj.lambda0 = o->lambda0; Sj.delta_out = h->jdelta; Sj.accept_out = lm ? h->lm_accept : nullptr;
-    JointUpdateParams Uj;
-    memset(&Uj, 0, sizeof(Uj));
-    Uj.jrec = h->jrec; Uj.jrec_acc = lm ? h->jrec_acc : nullptr; Uj.depth_acc = lm ? h->jdepth_acc : nullptr; Uj.delta = h->jdelta;
-    Uj.accept = lm ? h->lm_accept : nullptr; Uj.depth = h->depth_work; Uj.depth_out = nullptr; Uj.hw = (int)hw; Uj.B = B; Uj.S = S; Uj.mode = 0;
-    Uj.rho_lo = 1.f / o->max_depth; Uj.rho_hi = 1.f / o->min_depth;
-    // ---- inverse pairs: the pair-form dense kernels on views offset by S B pairs
-    LinParams Pi = lin_params(h, &oo, 6);
-    Pi.tiles_x = tiles_x; Pi.tiles_y = tiles_y; Pi.ngrp = (nblk + RG - 1) / RG; Pi.direct = 1;
-    Pi.tgtpack += (size_t)SB * hw; Pi.srcpack += (size_t)SB * (h->H + 2) * (h->W + 2); Pi.depth_t += (size_t)SB * hw; Pi.pc += SB;
-    Pi.blockrec += (size_t)SB * nblk * AccLayout<6>::NACC;
-    SolveParams Si = solve_params(h, &oo, 6, 0);
-    Si.partials = Pi.blockrec; Si.ngrp = nblk; Si.st = h->state + SB; Si.pc = h->pconst + SB;
-    Si.stats = d_stats ? d_stats + (size_t)SB * (o->n_iters + 1) * TCSFM_NSTAT : nullptr;
-    Si.delta_out = h->delta + (size_t)SB * 8; Si.accept_out = lm ? h->lm_accept + SB : nullptr;
-    DenseParams Dn;
-    Dn.dense_rec = h->dense_rec + (size_t)SB * hw * 8; Dn.depth0 = h->depth0 + (size_t)SB * hw; Dn.lambda_depth = o->lambda_depth; Dn.w_prior = o->prior_depth;
-    Dn.prev_rec = nullptr; Dn.prev_delta = h->delta; Dn.depth_next = nullptr; Dn.rho_lo = Uj.rho_lo; Dn.rho_hi = Uj.rho_hi;
-    DenseUpdateParams Ui;
-    memset(&Ui, 0, sizeof(Ui));          // (no coalesce table: c_ncall = 0)
-    Ui.dense_rec = Dn.dense_rec; Ui.delta = Si.delta_out; Ui.depth = h->depth_work + (size_t)SB * hw; Ui.depth_out = h->depth_work + (size_t)SB * hw; Ui.hw = (int)hw;
-    Ui.rho_lo = Uj.rho_lo; Ui.rho_hi = Uj.rho_hi;
-    DenseLmParams Ul;
-    Ul.rec_try = Dn.dense_rec; Ul.rec_acc = lm ? h->dense_rec_acc + (size_t)SB * hw * 8 : nullptr; Ul.depth_acc = lm ? h->depth_acc + (size_t)SB * hw : nullptr;
-    Ul.depth = h->depth_work + (size_t)SB * hw; Ul.delta = Si.delta_out; Ul.accept = lm ? h->lm_accept + SB : nullptr; Ul.hw = (int)hw; Ul.rho_lo = Uj.rho_lo; Ul.rho_hi = Uj.rho_hi;
-    const dim3 px_t((unsigned)((hw + 255) / 256), B), px_i((unsigned)((hw + 255) / 256), SB);
-    // The inverse pairs' refinement never meets the forward group's (different pairs, different scratch views): it runs on a second
-    // stream beside it -- fork after the pack, join before the results are copied out -- so a call costs max(forward chain, inverse
-    // chain) per iteration instead of their sum (80 -> ~50 us per iteration for the KITTI window at 640x192).  Under graph capture both
-    // chains go on the handle's stream instead: a replayed graph with parallel branches needs more hardware queues than a process may
-    // be given, and the chains never touch each other's data, so the results are the same bits.
-    if (!h->aux_stream) {
-        HIPCHK(h, hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-        HIPCHK(h, hipEventCreateWithFlags(&h->aux_fork, hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&h->aux_join, hipEventDisableTiming));
-    }
-    hipStream_t fs = h->stream, is = h->capturing ? h->stream : h->aux_stream;
-    const bool tr = h->trace_bits != nullptr;
-    if ((rc = trace_check(h, o, N))) return rc;
-    if (is != fs) {
-        HIPCHK(h, hipEventRecord(h->aux_fork, fs));
-        HIPCHK(h, hipStreamWaitEvent(is, h->aux_fork, 0));
-    }
-    // ---- inverse pairs, all iterations, on the second stream
-    auto lin_inv = [&](int lin) {
-        Pi.trace = tr ? h->trace_bits + ((size_t)lin * N + SB) * hw : nullptr;
-        Si.trace_decide = h->trace_decide ? h->trace_decide + (size_t)lin * N + SB : nullptr;
-        Pi.stamp = nullptr;
-        if (tr) hipLaunchKernelGGL((k_dense_linearize<DTW, DTH, DNT, true>), dim3(nblk, SB), dim3(DNT), 0, is, Pi, Dn);
-        else hipLaunchKernelGGL((k_dense_linearize<DTW, DTH, DNT>), dim3(nblk, SB), dim3(DNT), 0, is, Pi, Dn);
-    };
-    for (int it = 0; it < o->n_iters; it++) {
-        lin_inv(it);
-        const bool last = !lm && it == o->n_iters - 1;
-        Si.it = it; Si.mode = 0; Si.pose_out = last ? d_pose_out + (size_t)SB * 6 : nullptr; Si.log_scale_out = nullptr;
-        hipLaunchKernelGGL((k_solve<6>), dim3(SB), dim3(TC_SOLVE_NT), 0, is, Si);
-        if (lm) hipLaunchKernelGGL(k_dense_update_lm, px_i, dim3(256), 0, is, Ul);
-        else hipLaunchKernelGGL(k_dense_update, px_i, dim3(256), 0, is, Ui);
-    }
-    if (lm && o->n_iters > 0) {
-        lin_inv(o->n_iters);
-        Si.it = o->n_iters; Si.mode = 1; Si.pose_out = d_pose_out + (size_t)SB * 6; Si.log_scale_out = nullptr;
-        hipLaunchKernelGGL((k_solve<6>), dim3(SB), dim3(TC_SOLVE_NT), 0, is, Si);
-        hipLaunchKernelGGL(k_dense_final_lm, px_i, dim3(256), 0, is, (const int *)(h->lm_accept + SB), (const float *)(h->depth_acc + (size_t)SB * hw),
-                           h->depth_work + (size_t)SB * hw, (int)hw);
-    }
-    if (is != fs) HIPCHK(h, hipEventRecord(h->aux_join, is));
-    // ---- forward group, jointly, on the handle's stream
-    auto lin_fwd = [&](int lin) {
-        Pj.trace = tr ? h->trace_bits + (size_t)lin * N * hw : nullptr;
-        Sj.trace_decide = h->trace_decide ? h->trace_decide + (size_t)lin * N : nullptr;
-        if (n_sel) {       // selection masks of the forward pairs at the current poses and the current SHARED depth
-            LinParams M = lin_params(h, &oo, 6);
-            M.o_diff = sel_diff; M.o_valid = sel_valid;
-            launch_lin(h, M, n_sel, 6, false, MODE_MAPS, 2);      // (the selection itself: ext_selected, inside the joint kernel)
-        }
-        take_stamp(h, Pj, (size_t)jnblk * B);
-        ProfScope prof(h, 0);
-        if (tr) hipLaunchKernelGGL((k_dense_joint<NS, JTW, JTH, JNT, true>), dim3(jnblk, B), dim3(JNT), 0, fs, Pj, J);
-        else hipLaunchKernelGGL((k_dense_joint<NS, JTW, JTH, JNT>), dim3(jnblk, B), dim3(JNT), 0, fs, Pj, J);
-    };
-    constexpr int SOLVE_NT = JSOLVE_NT;
-    for (int it = 0; it < o->n_iters; it++) {
-        lin_fwd(it);
-        const bool last = !lm && it == o->n_iters - 1;
-        Sj.it = it; Sj.mode = 0; Sj.pose_out = last ? d_pose_out : nullptr;
-        hipLaunchKernelGGL((k_solve_joint<NS>), dim3(B), dim3(SOLVE_NT), 0, fs, Sj);
-        hipLaunchKernelGGL((k_dense_joint_update<NS>), px_t, dim3(256), 0, fs, Uj);
-    }
-    if (lm && o->n_iters > 0) {
-        lin_fwd(o->n_iters);
-        Sj.it = o->n_iters; Sj.mode = 1; Sj.pose_out = d_pose_out;
-        hipLaunchKernelGGL((k_solve_joint<NS>), dim3(B), dim3(SOLVE_NT), 0, fs, Sj);
-        Uj.mode = 1;
-        hipLaunchKernelGGL((k_dense_joint_update<NS>), px_t, dim3(256), 0, fs, Uj);
-    }
-    if (is != fs) HIPCHK(h, hipStreamWaitEvent(fs, h->aux_join, 0));
-    HIPCHK(h, hipGetLastError());
-    if (o->n_iters == 0) {
-        FinishParams F;
-        F.st = h->state; F.pose_out = d_pose_out; F.log_scale_out = nullptr; F.N = N;
-        hipLaunchKernelGGL(k_finish, dim3((N + 63) / 64), dim3(64), 0, h->stream, F);
-    }
-    HIPCHK(h, hipMemcpyAsync(d_depth_out, h->depth_work, N * hw * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    return TCSFM_OK;
-}
-
-
-// the fixed-point scatter sums of the reference-loss dense mode are zero between calls (their consumer clears them); after a fresh
-// allocation, an export or a call that failed midway they are cleared here
-int dref_clean(tcsfm_ctx *h) {
-    if (!h->dref_dirty) return TCSFM_OK;
-    const size_t hw = (size_t)h->H * h->W, n = h->max_pairs;
-    if (h->dref_ext) HIPCHK(h, hipMemsetAsync(h->dref_ext, 0, ((n + 1) / 2) * hw * 2 * sizeof(long long), h->stream));
-    if (h->dref_ext_src) HIPCHK(h, hipMemsetAsync(h->dref_ext_src, 0, (n / 2) * hw * 2 * sizeof(long long), h->stream));
-    if (h->jtick) HIPCHK(h, hipMemsetAsync(h->jtick, 0, 2 * ((n + 1) / 2) * sizeof(int), h->stream));      // (a call that failed midway may have left tickets behind)
-    h->dref_dirty = false;
-    return TCSFM_OK;
-}
 
 // tiny export kernel of tcsfm_linearize_dense_window: d loss / d rho = a_f x the joint kernel's per-pixel record
 __global__ __launch_bounds__(256) void k_dref_export_grho(const float *jrec, int jrec_stride, const double *exp_out, int exp_stride, float *out, int hw) {
@@ -958,420 +722,9 @@ __global__ __launch_bounds__(256) void k_dref_export_grho(const float *jrec, int
     out[(size_t)b * hw + idx] = (float)(exp_out[(size_t)b * exp_stride + 1] * (double)jrec[((size_t)b * hw + idx) * jrec_stride]);
 }
 
-// Dense window mode on the REFERENCE's loss (include/tcsfm.h, dense_ref_kernel.h).  Inputs on the device.  lin_export != nullptr: ONE
-// linearisation at the given poses, nothing updated: host outputs of tcsfm_linearize_dense_window.
-struct DrefExport { double *scal, *g_pose; float *d_g_rho; const float *d_depth0; float *d_g_rho_src; /* [S B][H W] or null: tcsfm_linearize_dense_window_sources */ };
-template <int NS>
-int dense_ref_run(tcsfm_ctx *h, const tcsfm_opts *o, int B, const float *d_tgt, const float *d_src, const float *d_dt, const float *d_ds,
-                  const float *d_K, const float *d_pose_in, float *d_pose_out, float *d_depth_out, float *d_stats, const WinOff *wo, const DrefExport *ex,
-                  const CoalTab *ct = nullptr, float *const *ct_pose = nullptr, float *const *ct_depth = nullptr, bool out_on_input = false) {
-    using JL = JointLayout<NS>;
-    constexpr int S = NS;
-    // B: targets of the launch sequence.  Coalesced calls (ct): ncall queued calls of cB targets each run as ONE sequence over B = ncall cB
-    // targets; the loss couples the windows of ONE call (batch normalisers, means over the call's maps): every call is a normaliser group of
-    // its own (norm_B = cB targets), the per-map weights take the CALL's batch size Bc, inputs and outputs go through the pointer table.
-    const int Bc = ct ? ct->cB : B, ngroups = ct ? ct->ncall : 1, norm_B = ct ? ct->cB : 0;
-    const int SB = S * B, N = 2 * SB;
-    const size_t hw = (size_t)h->H * h->W, n = h->max_pairs;
-    int rc;
-    if (ct && (ex || o->free_source_depths != 0 || o->n_iters < 1 || d_stats || h->trace_bits)) return fail(h, TCSFM_E_ARG, "internal: merged reference-loss calls are plain refinements with fixed source maps");
-    // The joint kernel's own tile grid (round 5): 32 x 8 tiles of 256 threads by default.  At 256 VGPRs the kernel holds 8 waves per CU either
-    // way; as TWO independent 4-wave workgroups their barriers and load phases no longer coincide (one workgroup's gathers run under the
-    // other's arithmetic), which a single 8-wave workgroup cannot do -- at the price of a larger halo share (TC_JOINT_TILE_H=16: the round-4 grid).
-    constexpr int DTW = kJointTileW, DTH = kJointTileH, DNT = DTW * DTH;
-    const int jtiles_x = (h->W + DTW - 1) / DTW, jtiles_y = (h->H + DTH - 1) / DTH;
-    const int nblk = jtiles_x * jtiles_y;              // workgroup records per target of the joint kernel (= joint_tiles(h))
-    const int nblk_lin = h->nblk;                      // ... and of k_linearize (the inverse pairs' systems, the FRONT launch)
-    const bool sel = o->argmin && S > 1, dc = o->w_dc > 0.f;
-    if ((rc = ensure_sel_maps(h)) || (rc = ensure_dense_rec(h)) || (rc = joint_scratch(h))) return rc;
-    if (!h->dref_norms) {
-        HIPCHK(h, hipMalloc((void **)&h->dref_norms, 2 * TC_MAX_COAL * sizeof(int)));             // (one (K_f, K_i) pair per normaliser group)
-        HIPCHK(h, hipMalloc((void **)&h->dref_ext, ((n + 1) / 2) * hw * 2 * sizeof(long long)));  // (targets <= max_pairs / 2; two sums per pixel)
-        HIPCHK(h, hipMalloc((void **)&h->dref_export, ((n + 1) / 2) * (2 + 6 * JMAXS) * sizeof(double)));
-        HIPCHK(h, hipMalloc((void **)&h->dref_smooth, ((n + 1) / 2) * 2 * sizeof(float)));
-    }
-    // the reference's parametrisation (optimizer.py:194-198, 235-239): quarter-resolution unknown, x4 bilinear upsampling (dense_ref_kernel.h)
-    const bool qres = !ex && o->depth_param == TCSFM_DEPTH_QUARTER;
-    const int nq = (h->H / 4) * (h->W / 4), nqblk = qres ? qres_groups(h) : 0;
-    if (qres && !h->qres_rho) {
-        const size_t nb = (n + 1) / 2;
-        HIPCHK(h, hipMalloc((void **)&h->qres_rho, 2 * nb * nq * sizeof(float)));       // (two buffers: k_qres_step_up ping-pongs)
-        HIPCHK(h, hipMalloc((void **)&h->qres_rec, nq * joint_rec_floats(n) * sizeof(float)));
-    }
-    if (!joint_scratch_fits<NS>(h, B, nblk + nqblk)) return fail(h, TCSFM_E_ARG, "internal: the joint dense scratch does not hold this many targets");
-    // opts.free_source_depths: the inverse pairs as S B groups of one source (the joint kernel / solve / update on views offset by S B pairs)
-    const bool free_src = !ex && o->free_source_depths != 0;
-    if (free_src && !h->jrec_src) {
-        const size_t ng = n / 2;          // groups <= max_pairs / 2
-        HIPCHK(h, hipMalloc((void **)&h->jrec_src, ng * hw * JointLayout<1>::JREC * sizeof(float)));
-        HIPCHK(h, hipMalloc((void **)&h->jstate_src, ng * sizeof(JointState)));
-        HIPCHK(h, hipMalloc((void **)&h->jdelta_src, ng * 6 * JMAXS * sizeof(double)));
-        HIPCHK(h, hipMalloc((void **)&h->dref_ext_src, ng * hw * 2 * sizeof(long long)));
-        h->dref_dirty = true;
-    }
-    if (free_src && qres && !h->qres_rho_src) {
-        const size_t ng = n / 2;
-        HIPCHK(h, hipMalloc((void **)&h->qres_rho_src, 2 * ng * nq * sizeof(float)));      // (two buffers: k_qres_step_up ping-pongs)
-        HIPCHK(h, hipMalloc((void **)&h->qres_rec_src, ng * nq * JointLayout<1>::JREC * sizeof(float)));
-    }
-    // (the inverse groups' workgroup records follow the forward groups' in jblockrec: both joint launches of a linearisation run before the solve)
-    const size_t jrec2_off = (size_t)B * (nblk + nqblk) * JL::NACC;
-    if (free_src && jrec2_off + (size_t)SB * (nblk + nqblk) * JointLayout<1>::NACC > (size_t)h->jrec_alloc * joint_blockrec_floats(n))
-        return fail(h, TCSFM_E_ARG, "internal: the inverse groups' records exceed the scratch");
-    tcsfm_opts oo = *o;
-    oo.refine = TCSFM_REFINE_POSE;
-    oo.window_rule = TCSFM_WINDOW_PAIR;          // (the couplings are set explicitly below)
-    oo.w_pose_consist = 0.f;                     // (... and so is l_pose_consist: `pc` below)
-    const bool pc = o->w_pose_consist > 0.f && !ex;      // optimizer.py:95-96 as a term of this mode (the export of one linearisation leaves it out)
-    InitParams I = init_params(h, &oo, N, d_pose_in, nullptr, d_K, 0);
-    I.K_mod = B;
-    if (pc) I.pose_lin = h->pose_lin;            // buffer 0 of [2][N][12]: every pair's transform at the first linearisation
-    // the pack also zeroes the batch counters and -- plain refinement with fixed source maps -- leaves the inputs in the caller's depth
-    // output: its inverse slots (the source maps) are final, the forward slots are overwritten by the last back-substitution
-    // ... unless the caller's depth_out lies on depth_t or depth_s (out_on_input: honoured, include/tcsfm.h; refine_overlap finds it): output
-    // slot s B + b and input slot s B + b hold different maps and other workgroups of the pack are still reading, so such a call leaves
-    // depth_out alone until the final copy from the work buffer, as the modes without a direct output do (a merged sequence carries no
-    // such call: the queued form runs it at once)
-    const bool direct_out = !ex && !(o->free_source_depths != 0) && o->n_iters > 0 && (d_depth_out != nullptr || ct != nullptr) && !out_on_input;
-    if ((rc = run_pack(h, &oo, N, d_tgt, d_src, d_dt, d_ds, &I, ct ? 0 : B, S, h->depth0, wo, ct, direct_out && !ct ? d_depth_out : nullptr, h->dref_norms, 2 * TC_MAX_COAL,
-                       ct ? ct_depth : nullptr))) return rc;
-    if (ex && ex->d_depth0)       // the prior's centre given explicitly (slots of the forward pairs (0, b): index b)
-        HIPCHK(h, hipMemcpyAsync(h->depth0, ex->d_depth0, (size_t)B * hw * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    if ((rc = trace_check(h, o, N))) return rc;
-    const bool tr = h->trace_bits != nullptr;
-    float *maps_diff = h->sel_maps, *maps_valid = h->sel_maps + (size_t)h->max_pairs * hw;
-    // ---- residual maps of all pairs
-    LinParams M = lin_params(h, &oo, 6);
-    M.o_diff = maps_diff; M.o_valid = maps_valid;
-    // ---- prepass: counts and the scatter of the inverse pairs' depth samples
-    LinParams Pp = lin_params(h, &oo, 6);
-    Pp.ext_diff = maps_diff; Pp.ext_valid = maps_valid; Pp.n_ext = SB; Pp.ext_B = B; Pp.ext_S = S;
-    DrefPrepassParams Dp;
-    Dp.diff = maps_diff; Dp.valid = maps_valid; Dp.norms = h->dref_norms; Dp.ext = h->dref_ext; Dp.B = B; Dp.S = S;
-    Dp.argmin = o->argmin ? 1 : 0; Dp.automask = o->automask; Dp.eps = o->irls_eps;
-    Dp.b_dc = o->w_dc / ((float)(S * Bc) * (float)hw);
-    Dp.plain_dif = (!ex && o->free_source_depths != 0) ? 1 : 0;
-    // ---- inverse pairs: pose kernels on views offset by S B pairs, window rule REFERENCE (all of them are the rule's inverse group)
-    LinParams Pi = lin_params(h, &oo, 6);
-    const int nacc6 = AccLayout<6>::NACC;
-    Pi.tgtpack += (size_t)SB * hw; Pi.srcpack += (size_t)SB * (h->H + 2) * (h->W + 2); Pi.depth_t += (size_t)SB * hw; Pi.pc += SB;
-    Pi.blockrec += (size_t)SB * h->nblk * nacc6; Pi.tickets += (size_t)SB * h->ngrp; Pi.partials += (size_t)SB * h->ngrp * nacc6;
-    SolveParams Si = solve_params(h, &oo, 6, 0);
-    Si.partials = direct_records(h) ? Pi.blockrec : Pi.partials;
-    Si.st = h->state + SB; Si.pc = h->pconst + SB; Si.lin_out = h->lin_out + (size_t)SB * kLinOut;
-    Si.rule = 1; Si.grp_fwd = 0; Si.n_pairs = SB; Si.scale_fwd = 1.0; Si.scale_inv = 0.25;
-    Si.b_dc = (double)o->w_dc / ((double)(S * Bc) * (double)hw);
-    Si.stats = d_stats ? d_stats + (size_t)SB * (o->n_iters + 1) * TCSFM_NSTAT : nullptr;
-    // ---- forward group: the joint kernel under the reference's rule
-    LinParams Pj = lin_params(h, &oo, 6);
-    Pj.tiles_x = jtiles_x; Pj.tiles_y = jtiles_y; Pj.ngrp = (nblk + RG - 1) / RG; Pj.direct = 1;
-    if (sel) { Pj.ext_diff = maps_diff; Pj.ext_valid = maps_valid; Pj.n_ext = SB; Pj.ext_B = B; Pj.ext_S = S; }
-    JointParams J;
-    memset(&J, 0, sizeof(J));
-    J.jrec = h->jrec; J.depth0 = h->depth0; J.jblockrec = h->jblockrec; J.w_prior = 0.f;
-    J.lambda_depth = ex ? 1e20f : o->lambda_depth;      // (export: depth block frozen, the reduced right-hand side IS the pose gradient)
-    J.B = B; J.S = S; J.argmin = o->argmin ? 1 : 0;
-    J.automask = o->argmin ? o->automask : 0;     // own masks: with one source the min is the source itself; without argmin no auto-mask (:71-73)
-    J.norms = h->dref_norms; J.norm_B = norm_B; J.ext2 = h->dref_ext; J.c_f = o->argmin ? 1.f : 0.25f;
-    J.dbg = h->dbg_stamps; Si.dbg = nullptr;       // (diagnostic stamps: the joint kernel's phases in this mode, not the pair solve's)
-    J.b_dc = o->w_dc / ((float)(S * Bc) * (float)hw); J.w_init_px = o->prior_init / ((float)Bc * (float)hw);
-    J.sig_lo = 1.f / o->max_depth; J.sig_ir = 1.f / (1.f / o->min_depth - 1.f / o->max_depth);
-    DrefSmoothParams Ds;
-    memset(&Ds, 0, sizeof(Ds));
-    const bool smooth = o->w_smooth > 0.f && h->H > 1 && h->W > 1;
-    if (smooth) {       // optimizer.py:92-93: l_smooth_weight x [mean over B H (W-1) x-edges + mean over B (H-1) W y-edges]
-        J.smooth = h->dref_smooth;
-        J.w_smooth_x = o->w_smooth / ((float)Bc * (float)h->H * (float)(h->W - 1)); J.w_smooth_y = o->w_smooth / ((float)Bc * (float)(h->H - 1) * (float)h->W);
-        Ds.depth = h->depth_work; Ds.tgtpack = h->tgtpack; Ds.out = h->dref_smooth; Ds.H = h->H; Ds.W = h->W;
-        Ds.sig_lo = J.sig_lo; Ds.sig_ir = J.sig_ir; Ds.wx = J.w_smooth_x; Ds.wy = J.w_smooth_y;
-    }
-    JointSolveParams Sj;
-    memset(&Sj, 0, sizeof(Sj));
-    {   // TCSFM_DEBUG_STAMPS=2: the phases of target 0's joint SOLVE instead (scripts/diag/solve_front_stamps.py)
-        static const int which = [] { const char *e = getenv("TCSFM_DEBUG_STAMPS"); return e ? atoi(e) : 0; }();
-        if (which == 2) { Sj.dbg = h->dbg_stamps; J.dbg = nullptr; }
-    }
-    Sj.jblockrec = h->jblockrec; Sj.js = h->jstate; Sj.st = h->state; Sj.pc = h->pconst; Sj.stats = d_stats; Sj.nblk = nblk; Sj.B = B;
-    Sj.n_iters = o->n_iters; Sj.solver = TCSFM_SOLVER_GN; Sj.lambda_up = o->lambda_up; Sj.lambda_down = o->lambda_down; Sj.lambda_min = o->lambda_min;
-    Sj.lambda0 = o->lambda0; Sj.delta_out = h->jdelta; Sj.accept_out = nullptr;
-    Sj.norms = h->dref_norms; Sj.norm_B = norm_B; Sj.c_f = J.c_f;
-    if (ct) {
-        Sj.c_ncall = ct->ncall; Sj.c_B = ct->cB; Sj.c_S = ct->cS;
-        Si.c_ncall = ct->ncall; Si.c_B = ct->cB; Si.c_S = ct->cS; Si.c_n0 = SB;
-        for (int i = 0; i < ct->ncall; i++) { Sj.c_pose_out[i] = ct_pose[i]; Si.c_pose_out[i] = ct_pose[i]; Si.c_ls_out[i] = nullptr; }
-    }
-    JointUpdateParams Uj;
-    memset(&Uj, 0, sizeof(Uj));
-    Uj.jrec = h->jrec; Uj.delta = h->jdelta; Uj.depth = h->depth_work; Uj.hw = (int)hw; Uj.B = B; Uj.S = S; Uj.mode = 0;
-    Uj.rho_lo = 1.f / o->max_depth; Uj.rho_hi = 1.f / o->min_depth;
-    Uj.srcpack_inv = h->srcpack + (size_t)SB * (h->H + 2) * (h->W + 2); Uj.W = h->W; Uj.H = h->H;
-    const dim3 px_t((unsigned)((hw + 255) / 256), B), px_all((unsigned)((hw + 255) / 256), N);
-    hipStream_t st = h->stream;
-    QresParams Q;
-    memset(&Q, 0, sizeof(Q));
-    if (qres) {
-        J.qres = 1; J.rec_stride = nblk + nqblk; Sj.nblk = nblk + nqblk;
-        Q.jrec = h->jrec; Q.qrec = h->qres_rec; Q.rho_q = h->qres_rho; Q.jblockrec = h->jblockrec; Q.delta = h->jdelta; Q.depth = h->depth_work;
-        Q.srcpack_inv = Uj.srcpack_inv; Q.H = h->H; Q.W = h->W; Q.B = B; Q.S = S; Q.rec_stride = nblk + nqblk; Q.rec_first = nblk;
-        Q.rho_lo = Uj.rho_lo; Q.rho_hi = Uj.rho_hi;
-        // the start is the quarter-resolution projection of the input map, upsampled again (optimizer.py:194-196, 235); the prior's centre
-        // stays the full-resolution input (`self.target_disparity`, :89-90)
-        hipLaunchKernelGGL(k_qres_init, dim3((unsigned)((nq + 255) / 256), B), dim3(256), 0, st, Q);
-        hipLaunchKernelGGL(k_qres_upsample, px_t, dim3(256), 0, st, Q);
-        Q.norms_zero = h->dref_norms; Q.norms_n = 2 * ngroups;
-    }
-    QresParams Q2 = Q;
-    if (qres && free_src) {      // the source maps in the same parametrisation: their quarter-resolution projection is the start (optimizer.py:194-196)
-        Q2.jrec = h->jrec_src; Q2.qrec = h->qres_rec_src; Q2.rho_q = h->qres_rho_src; Q2.delta = h->jdelta_src;
-        Q2.depth = h->depth_work + (size_t)SB * hw; Q2.srcpack_inv = h->srcpack; Q2.B = SB; Q2.S = 1; Q2.norms_zero = nullptr;
-        hipLaunchKernelGGL(k_qres_init, dim3((unsigned)((nq + 255) / 256), SB), dim3(256), 0, st, Q2);
-        hipLaunchKernelGGL(k_qres_upsample, dim3((unsigned)((hw + 255) / 256), SB), dim3(256), 0, st, Q2);
-    }
-    // (one stream: running the inverse pairs' linearise + solve on a second stream beside the forward group's, forked behind the scatter and
-    // joined after the depth update, was measured SLOWER -- 261 vs 232 us per 240x320 window, 383 vs 361 at 192x640 S=2: the event hops cost
-    // more than the ~18 us of overlap they buy)
-    // the counters and the scatter sums are zero when a linearisation starts: zeroed here once per call, and by their consumers afterwards
-    // (k_dense_joint clears every sum it reads, k_dense_joint_update the counters) -- two memset launches per iteration cost 10 us
-    if ((rc = dref_clean(h))) return rc;
-    h->dref_dirty = true;          // (until this call has issued its last consumer)
-    Uj.norms_zero = h->dref_norms; Uj.norms_n = 2 * ngroups;
-    LinParams Pj2 = lin_params(h, &oo, 6);
-    JointParams J2 = J;
-    JointSolveParams Sj2 = Sj;
-    JointUpdateParams Uj2 = Uj;
-    if (free_src) {
-        Pj2.tgtpack += (size_t)SB * hw; Pj2.srcpack += (size_t)SB * (h->H + 2) * (h->W + 2); Pj2.depth_t += (size_t)SB * hw; Pj2.pc += SB;
-        Pj2.tiles_x = jtiles_x; Pj2.tiles_y = jtiles_y; Pj2.ngrp = (nblk + RG - 1) / RG; Pj2.direct = 1;
-        J2.jrec = h->jrec_src; J2.depth0 = nullptr; J2.B = SB; J2.S = 1; J2.argmin = 0; J2.automask = o->automask;
-        J2.norms = h->dref_norms + 1;                 // the group's normaliser is K_i, its factor 0.25 (optimizer.py:79)
-        J2.c_f = 0.25f; J2.w_init_px = 0.f; J2.smooth = nullptr; J2.w_smooth_x = J2.w_smooth_y = 0.f; J2.qres = 0; J2.rec_stride = 0;
-        J2.ext2 = h->dref_ext_src; J2.ext_norm = h->dref_norms; J2.ext_c = J.c_f;
-        J2.jblockrec = h->jblockrec + jrec2_off; Sj2.jblockrec = h->jblockrec + jrec2_off; Q2.jblockrec = h->jblockrec + jrec2_off;
-        if (qres) { J2.qres = 1; J2.rec_stride = nblk + nqblk; }
-        Sj2.js = h->jstate_src; Sj2.st = h->state + SB; Sj2.pc = h->pconst + SB; Sj2.B = SB; Sj2.nblk = qres ? nblk + nqblk : nblk;
-        Sj2.stats = d_stats ? d_stats + (size_t)SB * (o->n_iters + 1) * TCSFM_NSTAT : nullptr;
-        Sj2.delta_out = h->jdelta_src; Sj2.norms = h->dref_norms + 1; Sj2.c_f = 0.25;
-        Uj2.jrec = h->jrec_src; Uj2.delta = h->jdelta_src; Uj2.depth = h->depth_work + (size_t)SB * hw; Uj2.B = SB; Uj2.S = 1;
-        Uj2.norms_zero = nullptr;                     // (the forward update zeroes the counters: it runs after both solves)
-        Uj2.srcpack_inv = h->srcpack;                 // forward pair m samples source map m: the depth channel of ITS pack
-    }
-    // Round 5: with the source maps fixed a linearisation OPENS with one launch over all 2 S B pairs (k_linearize<FRONT>: the forward pairs'
-    // selection and K_f, the inverse pairs' systems, K_i and their adjoint scatter) in place of the residual-map, count, scatter and
-    // inverse-linearisation launches; the free-source-map mode keeps those (its inverse pairs are linearised by the joint kernel).
-    // (second session: the free-source-map mode opens with the same launch -- every row light there, the forward rows scattering the adjoint
-    // of their samples of the source maps -- and its two joint groups share ONE solve launch and ONE update launch)
-    const bool front = true;
-    LinParams F = lin_params(h, &oo, 6);
-    if (front) {
-        F.front_fwd = SB; F.front_Bt = B; F.norm_B = norm_B; F.norms = h->dref_norms; F.ext2 = h->dref_ext;
-        F.front_light = free_src ? 1 : 0; F.ext2_src = h->dref_ext_src;
-        F.fwd_noauto = o->argmin ? 0 : SB;                       // optimizer.py:71-73: without argmin the forward term has no auto-mask
-        F.one_generation = (size_t)nblk_lin * (SB + (sel ? B : SB)) <= 512;
-        if (sel) { F.sel_B = B; F.sel_S = S; F.sel_out = maps_valid; Pj.ext_diff = nullptr; Pj.ext_valid = nullptr; Pj.n_ext = 0; Pj.sel_in = maps_valid; }
-        Si.norms = h->dref_norms; Si.norm_Bt = B; Si.norm_B = norm_B;
-    }
-    auto launch_front = [&](int lin) {
-        F.trace = tr ? h->trace_bits + (size_t)lin * N * hw : nullptr;
-        F.stamp = nullptr;
-        ProfScope prof(h, 2);
-        const dim3 grid(nblk_lin, SB + (sel ? B : SB)), block(TILE_NT);     // inverse pairs, then the forward rows (under the selection: one per target)
-        if (tr) {
-            if (sel) hipLaunchKernelGGL((k_linearize<6, true, MODE_LIN, TILE_W, TILE_H, TILE_NT, true, true, false, true>), grid, block, 0, st, F);
-            else hipLaunchKernelGGL((k_linearize<6, true, MODE_LIN, TILE_W, TILE_H, TILE_NT, false, true, false, true>), grid, block, 0, st, F);
-        } else if (sel) hipLaunchKernelGGL((k_linearize<6, true, MODE_LIN, TILE_W, TILE_H, TILE_NT, true, false, false, true>), grid, block, 0, st, F);
-        else hipLaunchKernelGGL((k_linearize<6, true, MODE_LIN, TILE_W, TILE_H, TILE_NT, false, false, false, true>), grid, block, 0, st, F);
-    };
-    auto linearise = [&](int lin) -> int {
-        Pi.trace = tr ? h->trace_bits + ((size_t)lin * N + SB) * hw : nullptr;
-        Si.trace_decide = h->trace_decide ? h->trace_decide + (size_t)lin * N + SB : nullptr;
-        launch_front(lin);
-        Pj.trace = tr ? h->trace_bits + (size_t)lin * N * hw : nullptr;
-        Sj.trace_decide = h->trace_decide ? h->trace_decide + (size_t)lin * N : nullptr;
-        if (smooth) hipLaunchKernelGGL(k_dref_smooth, dim3(B), dim3(1024), 0, st, Ds);
-        const bool both = free_src && !smooth;       // free source maps: the forward groups and the inverse pairs' groups of one source in ONE launch
-        take_stamp(h, Pj, (size_t)nblk * (both ? B + SB : B));
-        ProfScope prof(h, 0);
-        if (both) {
-            Pj2.trace = tr ? h->trace_bits + ((size_t)lin * N + SB) * hw : nullptr;
-            Pj2.stamp = Pj.stamp;                    // (stamps are indexed by the launch's grid)
-            if (tr) hipLaunchKernelGGL((k_dense_joint2<NS, DTW, DTH, DNT, true>), dim3(nblk, B + SB), dim3(DNT), 0, st, Pj, J, Pj2, J2);
-            else hipLaunchKernelGGL((k_dense_joint2<NS, DTW, DTH, DNT, false>), dim3(nblk, B + SB), dim3(DNT), 0, st, Pj, J, Pj2, J2);
-            if (qres) hipLaunchKernelGGL((k_qres_schur2<NS>), dim3(nqblk, B + SB), dim3(256), 0, st, Q, Q2);      // both groups' cells
-            return TCSFM_OK;
-        }
-        // (l_smooth is compiled into its own instantiations: without it -- the reference's drivers -- the S = 2 kernel is the LEAN form, three workgroups per CU)
-        if (smooth) {
-            if (tr) hipLaunchKernelGGL((k_dense_joint<NS, DTW, DTH, DNT, true, true, true>), dim3(nblk, B), dim3(DNT), 0, st, Pj, J);
-            else hipLaunchKernelGGL((k_dense_joint<NS, DTW, DTH, DNT, false, true, true>), dim3(nblk, B), dim3(DNT), 0, st, Pj, J);
-        } else if (tr) hipLaunchKernelGGL((k_dense_joint<NS, DTW, DTH, DNT, true, true, false>), dim3(nblk, B), dim3(DNT), 0, st, Pj, J);
-        else hipLaunchKernelGGL((k_dense_joint<NS, DTW, DTH, DNT, false, true, false>), dim3(nblk, B), dim3(DNT), 0, st, Pj, J);
-        if (qres && !free_src) hipLaunchKernelGGL((k_qres_schur<NS>), dim3(nqblk, B), dim3(256), 0, st, Q);
-        if (free_src) {
-            // every inverse pair as a group of one source WITHOUT argmin: that is the reference's inverse term (0.25 / K_i, own weights,
-            // valid x auto-mask, its depth-consistency term), its local unknowns the pair's pose and the source map it back-projects.
-            // Independent of the forward groups' launch above (own records behind theirs in jblockrec): one solve launch serves both.
-            Pj2.trace = tr ? h->trace_bits + ((size_t)lin * N + SB) * hw : nullptr;
-            if (tr) hipLaunchKernelGGL((k_dense_joint<1, DTW, DTH, DNT, true, true, false>), dim3(nblk, SB), dim3(DNT), 0, st, Pj2, J2);
-            else hipLaunchKernelGGL((k_dense_joint<1, DTW, DTH, DNT, false, true, false>), dim3(nblk, SB), dim3(DNT), 0, st, Pj2, J2);
-            if (qres) hipLaunchKernelGGL((k_qres_schur2<NS>), dim3(nqblk, B + SB), dim3(256), 0, st, Q, Q2);      // both groups' cells
-        }
-        return TCSFM_OK;
-    };
-    if (ex) {        // one linearisation, exported
-        if ((rc = linearise(0))) return rc;
-        Si.mode = 2; Si.it = 0;
-        launch_solve(h, Si, SB, 6);
-        Sj.it = 0; Sj.mode = 0; Sj.export_out = h->dref_export;
-        hipLaunchKernelGGL((k_solve_joint<NS>), dim3(B), dim3(JSOLVE_NT), 0, st, Sj);
-        hipLaunchKernelGGL(k_dref_export_grho, px_t, dim3(256), 0, st, (const float *)h->jrec, (int)JL::JREC, (const double *)h->dref_export, 2 + 6 * JMAXS, ex->d_g_rho, (int)hw);
-        if (ex->d_g_rho_src) {
-            // The gradient w.r.t. the SOURCE inverse-depth maps (held fixed by the refinement; leaves of the reference's optimize_depth_pred).
-            // Their role mirrors the target map's: local in the inverse pair -- the joint kernel run on the inverse pairs as S = 1 groups
-            // without argmin IS the reference's inverse term (0.25 / K_i, own weights, valid x auto-mask, its depth-consistency term) --
-            // and sampled by the forward pair: k_dref_scatter_src, in units of the forward factor a_f.  Oracle: dref_source_depth_gradient.
-            HIPCHK(h, hipMemsetAsync(h->dref_ext, 0, (size_t)SB * hw * 2 * sizeof(long long), st));
-            const dim3 px_f((unsigned)((hw + 255) / 256), SB);
-            launch_lin(h, M, N, 6, false, MODE_MAPS, 2);          // (the forward pairs' residual maps: what k_dref_scatter_src weighs the samples with)
-            hipLaunchKernelGGL(k_dref_scatter_src, px_f, dim3(256), 0, st, Pp, Dp, h->dref_ext, J.c_f);
-            LinParams Pj2 = lin_params(h, &oo, 6);
-            Pj2.tgtpack += (size_t)SB * hw; Pj2.srcpack += (size_t)SB * (h->H + 2) * (h->W + 2); Pj2.depth_t += (size_t)SB * hw; Pj2.pc += SB;
-            Pj2.tiles_x = jtiles_x; Pj2.tiles_y = jtiles_y; Pj2.ngrp = (nblk + RG - 1) / RG; Pj2.direct = 1;
-            JointParams J2 = J;
-            J2.jrec = h->jrec_acc; J2.depth0 = nullptr; J2.B = SB; J2.S = 1; J2.argmin = 0; J2.automask = o->automask;
-            J2.norms = h->dref_norms + 1;                 // the group's normaliser is K_i, its factor 0.25 (optimizer.py:79)
-            J2.c_f = 0.25f; J2.w_init_px = 0.f; J2.smooth = nullptr; J2.w_smooth_x = J2.w_smooth_y = 0.f; J2.qres = 0; J2.rec_stride = 0;
-            J2.ext2 = h->dref_ext; J2.ext_norm = h->dref_norms; J2.ext_c = J.c_f;
-            hipLaunchKernelGGL((k_dense_joint<1, DTW, DTH, DNT, false, true, false>), dim3(nblk, SB), dim3(DNT), 0, st, Pj2, J2);
-            hipLaunchKernelGGL(k_dref_export_grho_src, px_f, dim3(256), 0, st, (const float *)h->jrec_acc, (int)JointLayout<1>::JREC, (const int *)h->dref_norms, ex->d_g_rho_src, (int)hw);
-        }
-        HIPCHK(h, hipGetLastError());
-        constexpr int kLin6 = 6 * 6 + 6 + 4;          // k_solve<6> mode 2: H [36], g [6], cost, cost_photo, cost_dc, n_mask
-        std::vector<double> lin((size_t)SB * kLin6), jx((size_t)B * (2 + 6 * JMAXS));
-        int norms[4];
-        HIPCHK(h, hipMemcpyAsync(lin.data(), Si.lin_out, lin.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(jx.data(), h->dref_export, jx.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(norms, h->dref_norms, sizeof(norms), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-        double fwd = 0, inv_p = 0, inv_d = 0;
-        for (int b = 0; b < B; b++) {
-            fwd += jx[(size_t)b * (2 + 6 * JMAXS)];
-            for (int s_ = 0; s_ < S; s_++)
-                for (int j = 0; j < 6; j++) ex->g_pose[(size_t)(s_ * B + b) * 6 + j] = jx[(size_t)b * (2 + 6 * JMAXS) + 2 + 6 * s_ + j];
-        }
-        for (int m = 0; m < SB; m++) {
-            const double *q = &lin[(size_t)m * kLin6];
-            for (int j = 0; j < 6; j++) ex->g_pose[(size_t)(SB + m) * 6 + j] = q[36 + j];
-            inv_p += q[36 + 6 + 1]; inv_d += q[36 + 6 + 2];
-        }
-        double pc_total = 0.0;
-        if (o->w_pose_consist > 0.f) {
-            // l_pose_consist (optimizer.py:95-96) of the exported linearisation: a closed form of the 2 S B input poses, added on the host in double --
-            // value c sum |p_fwd + p_inv|, c = w / (6 S B); gradient c r / max(|r|, eps) in pose coordinates carried to the left perturbation
-            // by A^-T, A^-1 = [[-I, Tx], [0, -Je^-1]] (the oracle's pose_consist_term; the refinement's kernels hold the same term)
-            std::vector<float> ph((size_t)N * 6);
-            HIPCHK(h, hipMemcpy(ph.data(), d_pose_in, ph.size() * sizeof(float), hipMemcpyDeviceToHost));
-            const double c = (double)o->w_pose_consist / (6.0 * SB), eps = (double)o->irls_eps;
-            for (int m = 0; m < N; m++) {
-                const float *pm = &ph[(size_t)m * 6], *pp = &ph[(size_t)(m < SB ? m + SB : m - SB) * 6];
-                const double cx = cos(-(double)pm[3]), sx = sin(-(double)pm[3]), cy = cos(-(double)pm[4]), sy = sin(-(double)pm[4]);
-                const double Je[9] = {1, 0, sy, 0, cx, -sx * cy, 0, sx, cx * cy}, id = 1.0 / cy;
-                const double Ji[9] = {(Je[4] * Je[8] - Je[5] * Je[7]) * id, -(Je[1] * Je[8] - Je[2] * Je[7]) * id, (Je[1] * Je[5] - Je[2] * Je[4]) * id,
-                                      -(Je[3] * Je[8] - Je[5] * Je[6]) * id, (Je[0] * Je[8] - Je[2] * Je[6]) * id, -(Je[0] * Je[5] - Je[2] * Je[3]) * id,
-                                      (Je[3] * Je[7] - Je[4] * Je[6]) * id, -(Je[0] * Je[7] - Je[1] * Je[6]) * id, (Je[0] * Je[4] - Je[1] * Je[3]) * id};
-                const double tq[3] = {-(double)pm[0], -(double)pm[1], -(double)pm[2]};
-                const double Tx[9] = {0, -tq[2], tq[1], tq[2], 0, -tq[0], -tq[1], tq[0], 0};
-                double Ai[36] = {0}, gp[6];
-                for (int i = 0; i < 3; i++) {
-                    Ai[6 * i + i] = -1;
-                    for (int j = 0; j < 3; j++) { Ai[6 * i + 3 + j] = Tx[3 * i + j]; Ai[6 * (3 + i) + 3 + j] = -Ji[3 * i + j]; }
-                }
-                for (int j = 0; j < 6; j++) {
-                    const double r = (double)pm[j] + (double)pp[j], a = fabs(r), den = a > eps ? a : eps;
-                    pc_total += 0.5 * c * a;
-                    gp[j] = c * r / den;
-                }
-                for (int i = 0; i < 6; i++) {
-                    double v = 0.0;
-                    for (int k = 0; k < 6; k++) v += Ai[6 * k + i] * gp[k];
-                    ex->g_pose[(size_t)m * 6 + i] += v;
-                }
-            }
-        }
-        ex->scal[0] = fwd + inv_p + inv_d + pc_total; ex->scal[1] = fwd; ex->scal[2] = inv_p; ex->scal[3] = inv_d;
-        ex->scal[4] = norms[0]; ex->scal[5] = norms[1]; ex->scal[6] = jx[1]; ex->scal[7] = pc_total;
-        return TCSFM_OK;
-    }
-    // the targets' record sums are split over several workgroups (JointSolveParams::nsplit: the last arriver solves) when a target has MANY records
-    // -- the quarter-resolution unknown's tile + cell-group records.  Measured (scripts/dense_ref_timing.py, TCSFM_JOINT_SPLIT=1 switches it off):
-    // 600-960 records: -2 ... -8 % per call; 150-480 records: the ticket costs what the faster fetch buys (+0 ... +2 %): not split -- except the S >= 2
-    // targets' 480 records of 97+ floats, which two workgroups sum in one batch of loads each (third session: -0.8 % per B=1 KITTI window, -2.8 % at
-    // minibatch 6; with one source the 32-float records are one batch already and splitting costs 2-4 %: profiles/r05_joint_split_sweep.txt)
-    // (after the S = 1 solve took 32 record subsets its 600-900 quarter-resolution records are best summed by ONE workgroup -- 185 -> 175 us per 240x320
-    // call -- and the S >= 2 targets' by four: profiles/r05_joint_split_sweep.txt)
-    auto split_of = [](int recs, int ns) { return ns == 1 ? 1 : (recs >= 512 ? 4 : (recs >= 400 ? 2 : 1)); };
-    static const int split_env = getenv("TCSFM_JOINT_SPLIT") ? atoi(getenv("TCSFM_JOINT_SPLIT")) : -1;       // (A/B hook: 1 = off)
-    {
-        const size_t nt = (n + 1) / 2;
-        Sj.nsplit = split_env > 0 ? std::min(split_env, kJointSplitMax) : split_of(Sj.nblk, NS); Sj.jpart = h->jpart; Sj.jtick = h->jtick;
-        Sj2.nsplit = split_env > 0 ? std::min(split_env, kJointSplitMax) : split_of(Sj2.nblk, 1); Sj2.jpart = h->jpart + kJointSplitMax * joint_acc_floats(n); Sj2.jtick = h->jtick + nt;
-    }
-    if (pc) {     // c = weight / (6 S B) of the CALL (merged calls never carry the term); forward pairs at [0, SB), inverse pairs at [SB, 2 SB) of a buffer
-        const double c = (double)o->w_pose_consist / (6.0 * SB);
-        Sj.w_pc = c; Sj.pc_eps = (double)o->irls_eps; Sj.pose_lin = h->pose_lin; Sj.pc_np = N; Sj.pc_self0 = 0; Sj.pc_part0 = SB;
-        Sj2.w_pc = c; Sj2.pc_eps = (double)o->irls_eps; Sj2.pose_lin = h->pose_lin; Sj2.pc_np = N; Sj2.pc_self0 = SB; Sj2.pc_part0 = 0;
-        Si.w_pc = c; Si.pc_eps = (double)o->irls_eps; Si.pose_lin = h->pose_lin; Si.pc_np = N; Si.pc_self0 = SB; Si.pc_part0 = 0;
-    }
-    for (int it = 0; it < o->n_iters; it++) {
-        if ((rc = linearise(it))) return rc;
-        const bool last = it == o->n_iters - 1;
-        Si.it = it; Si.mode = 0; Si.pose_out = last ? d_pose_out + (size_t)SB * 6 : nullptr; Si.log_scale_out = nullptr;
-        Sj.it = it; Sj.mode = 0; Sj.pose_out = last ? d_pose_out : nullptr;
-        if (free_src) {   // the forward groups' 6S x 6S systems and the inverse groups' (pose + source map) 6 x 6 systems: one launch
-            ProfScope prof(h, 1);
-            Sj2.it = it; Sj2.mode = 0; Sj2.pose_out = last ? d_pose_out + (size_t)SB * 6 : nullptr;
-            Sj2.trace_decide = h->trace_decide ? h->trace_decide + (size_t)it * N + SB : nullptr;
-            if (pc) hipLaunchKernelGGL((k_solve_joint2<NS, true>), dim3(B * Sj.nsplit + SB * Sj2.nsplit), dim3(JSOLVE_NT), 0, st, Sj, Sj2);
-            else hipLaunchKernelGGL((k_solve_joint2<NS>), dim3(B * Sj.nsplit + SB * Sj2.nsplit), dim3(JSOLVE_NT), 0, st, Sj, Sj2);
-        } else {          // the target groups' and the inverse pairs' systems: independent, one launch
-            ProfScope prof(h, 1);
-            if (pc) hipLaunchKernelGGL((k_solve_front<NS, true>), dim3(B * Sj.nsplit + SB), dim3(JSOLVE_NT), 0, st, Sj, Si);
-            else hipLaunchKernelGGL((k_solve_front<NS>), dim3(B * Sj.nsplit + SB), dim3(JSOLVE_NT), 0, st, Sj, Si);
-        }
-        if (direct_out && last) {      // the last back-substitution also writes the caller's map (coalesced calls: every call's own)
-            Uj.depth_out = d_depth_out; Q.depth_out = d_depth_out;
-            if (ct) {
-                Uj.c_ncall = Q.c_ncall = ct->ncall; Uj.c_B = Q.c_B = ct->cB;
-                for (int i = 0; i < ct->ncall; i++) { Uj.c_depth_out[i] = ct_depth[i]; Q.c_depth_out[i] = ct_depth[i]; }
-            }
-        }
-        const unsigned qsu_tiles = (unsigned)(((h->W + QSU_TW - 1) / QSU_TW) * ((h->H + QSU_TH - 1) / QSU_TH));
-        if (qres) {       // cell step + x4 upsampling in one launch; the cell values ping-pong between the two halves of qres_rho
-            const size_t half = ((n + 1) / 2) * (size_t)nq;
-            Q.rho_q = h->qres_rho + (it & 1) * half; Q.rho_q_next = h->qres_rho + ((it + 1) & 1) * half;
-            if (free_src) {       // ... and the source maps' cells in the same launch (their upsampling refreshes the packs the forward pairs sample)
-                const size_t half2 = (n / 2) * (size_t)nq;
-                Q2.rho_q = h->qres_rho_src + (it & 1) * half2; Q2.rho_q_next = h->qres_rho_src + ((it + 1) & 1) * half2;
-                hipLaunchKernelGGL((k_qres_step_up2<NS>), dim3(qsu_tiles, B + SB), dim3(QSU_TW * QSU_TH), 0, st, Q, Q2);
-            } else hipLaunchKernelGGL((k_qres_step_up<NS>), dim3(qsu_tiles, B), dim3(QSU_TW * QSU_TH), 0, st, Q);
-        } else if (free_src)      // the targets' maps and the source maps (the inverse pairs' own depth slots AND the depth channel of the packs the
-                                  // forward pairs sample) in one launch
-            hipLaunchKernelGGL((k_dense_joint_update2<NS>), dim3((unsigned)((hw + 255) / 256), B + SB), dim3(256), 0, st, Uj, Uj2);
-        else hipLaunchKernelGGL((k_dense_joint_update<NS>), px_t, dim3(256), 0, st, Uj);
-    }
-    HIPCHK(h, hipGetLastError());
-    if (o->n_iters == 0) {
-        FinishParams F;
-        F.st = h->state; F.pose_out = d_pose_out; F.log_scale_out = nullptr; F.N = N;
-        hipLaunchKernelGGL(k_finish, dim3((N + 63) / 64), dim3(64), 0, st, F);
-    }
-    if (!direct_out) HIPCHK(h, hipMemcpyAsync(d_depth_out, h->depth_work, N * hw * sizeof(float), hipMemcpyDeviceToDevice, st));
-    h->dref_dirty = o->n_iters == 0;      // (every linearisation's sums were consumed and cleared; with no iteration the pack's zeroed counters are all there is)
-    return TCSFM_OK;
-}
-// dense_ref_run of a window with S = 1 .. JMAXS sources: dense_ref_runs[S - 1]
-constexpr decltype(&dense_ref_run<1>) dense_ref_runs[JMAXS] = {dense_ref_run<1>, dense_ref_run<2>, dense_ref_run<3>, dense_ref_run<4>};
-
 }  // namespace
+
+#include "dense_host.h"
 
 // =================================================================================================
 // Entry points: include/tcsfm.h declares every one of them extern "C", so the definitions below have C linkage.
@@ -1419,13 +772,9 @@ int tcsfm_create(tcsfm_handle *out, int device, int H, int W, int max_pairs) {
     }
     tcsfm_ctx *h = new tcsfm_ctx();
     h->device = device; h->H = H; h->W = W; h->max_pairs = max_pairs;
-    h->tiles_x = (W + TILE_W - 1) / TILE_W; h->tiles_y = (H + TILE_H - 1) / TILE_H; h->nblk = h->tiles_x * h->tiles_y;
-    h->ngrp = (h->nblk + RG - 1) / RG;
-    h->nblk_alloc = ((W + 15) / 16) * ((H + 15) / 16);   // the finest tiling of the pose path and the pair-form dense kernels (16 x 16); the
-                                                          // joint kernels' 32 x 8 tiles size their own scratch (joint_records_per_target)
-    if (h->nblk_alloc < h->nblk) h->nblk_alloc = h->nblk;
-    h->ngrp_alloc = (h->nblk_alloc + RG - 1) / RG;
-    h->ngrp_pad = (h->ngrp_alloc + 63) / 64 * 64;
+    h->tiles_x = (W + TILE_W - 1) / TILE_W; h->tiles_y = (H + TILE_H - 1) / TILE_H;
+    const DenseCaps &cp = h->caps = dense_caps(H, W, max_pairs);      // (dense_plan.h: the pose grid and what the record buffers below hold per pair)
+    h->nblk = cp.nblk; h->ngrp = cp.ngrp; h->nblk_alloc = cp.nblk_alloc; h->ngrp_alloc = cp.ngrp_alloc; h->ngrp_pad = cp.ngrp_pad;
     size_t hw = (size_t)H * W, n = max_pairs;
     DeviceGuard dev_guard(device);
     int cur = -1;
@@ -1489,11 +838,11 @@ void tcsfm_destroy(tcsfm_handle h) {
     for (auto &e : h->seq_done) (void)hipEventDestroy(e);
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
     void *ptrs[] = {h->stamp_buf, h->tgtpack, h->srcpack, h->depth_work, h->partials, h->blockrec, h->tickets, h->state, h->pconst, h->lin_out,
-                    h->jrec, h->jrec_acc, h->jblockrec, h->jdepth_acc, h->jstate, h->jdelta, h->jpart, h->jtick, h->dref_norms, h->dref_ext, h->dref_export, h->qres_rho, h->qres_rec, h->pose_lin, h->dref_smooth, h->jrec_src, h->jstate_src, h->jdelta_src, h->dref_ext_src, h->qres_rho_src, h->qres_rec_src,
-                    h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->dense_rec, h->depth0, h->dense_rec2, h->depth_alt, h->delta, h->scale_keys, h->scale_hist, h->sel_maps, h->dense_rec_acc, h->depth_acc, h->lm_accept, h->dbg_stamps, h->wgrad_rec, h->wgrad_fix, h->wgrad_gmax, h->pgrad_fwd, h->pgrad_cot,
+                    h->pose_lin, h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->scale_keys, h->scale_hist, h->dbg_stamps, h->wgrad_rec, h->wgrad_fix, h->wgrad_gmax, h->pgrad_fwd, h->pgrad_cot,
                     h->pair_idx, h->flip_ramp};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    h->dense.release();
     for (DevBuf<float> *b : {&h->seq_img, &h->seq_depth, &h->seq_pose_in, &h->seq_pose_out, &h->seq_ls_out, &h->seq_K, &h->seq_fdepth, &h->seq_dense, &h->seq_dense_tmp, &h->seq_scale_dev})
         b->release();
     h->seq_fpack.release(); h->seq_u8.release(); h->seq_scale_keys.release(); h->seq_disp_dev.release(); h->eval_gt_dev.release(); h->eval_out_dev.release();
@@ -2428,129 +1777,24 @@ static int dense_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int
     if (st.rc) return st.rc;
     const int nimg_t = ct ? ct->cB : (win_B ? win_B : N), nimg_s = ct ? ct->cB * ct->cS : (win_B ? win_B * win_S : N);   // image sets behind tgt / src
     if (!ct && (rc = check_intrinsics(h, o, K, nimg_t))) return rc;
-    const size_t hw = (size_t)h->H * h->W, n = h->max_pairs;
+    const size_t hw = (size_t)h->H * h->W;
     const int n_sel = (win_B && win_S > 1 && o->argmin) ? win_B * win_S : 0;
     if (ct && !ref_mode && (n_sel || o->solver != TCSFM_SOLVER_GN || o->host_ptrs || o->n_iters < 1 || (o->dense_joint && win_S >= 2)))
         return fail(h, TCSFM_E_ARG, "internal: only per-pair Gauss-Newton dense calls on device pointers are merged");
     if (ct && ref_mode && (o->host_ptrs || o->n_iters < 1 || stats_out)) return fail(h, TCSFM_E_ARG, "internal: merged reference-loss calls take device pointers and no statistics");
-    const bool lm = o->solver == TCSFM_SOLVER_LM;
-    if ((n_sel && (rc = ensure_sel_maps(h))) || (lm && (rc = ensure_dense_lm(h))) || (rc = ensure_dense_rec(h))) return rc;
     const float *d_tgt = st.in("tgt", tgt, nimg_t * 3 * hw), *d_src = st.in("src", src, nimg_s * 3 * hw), *d_dt = st.in("depth_t", depth_t, nimg_t * hw);
     const float *d_ds = st.in("depth_s", depth_s, nimg_s * hw), *d_K = st.in("K", K, (size_t)nimg_t * 9), *d_pose_in = st.in("pose_in", pose_in, (size_t)N * 6);
     const size_t nstats = (size_t)N * (o->n_iters + 1) * TCSFM_NSTAT;
     float *d_pose_out = st.out("pose_out", pose_out, (size_t)N * 6), *d_depth_out = st.out("depth_out", depth_out, N * hw), *d_stats = st.out("stats_out", stats_out, nstats);
     if (st.ready(nullptr)) return st.rc;
     if (d_stats) HIPCHK(h, hipMemsetAsync(d_stats, 0, nstats * sizeof(float), h->stream));
-    if (ref_mode) {
-        if ((rc = dense_ref_runs[win_S - 1](h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, nullptr, ct, ct_pose, ct_depth, depth_on_input)))
-            return rc;
-    } else if (win_B && o->dense_joint && win_S >= 2 && win_S <= JMAXS_OWN) {   // one depth map per target, 6S x 6S reduced system (joint_kernel.h)
-        // (the library's own joint mode stays at S <= JMAXS_OWN = 3: wider windows there keep the per-pair depth copies below)
-        rc = win_S == 2 ? dense_joint_run<2>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo)
-                        : dense_joint_run<3>(h, o, win_B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo);
-        if (rc) return rc;
-    } else {
-        tcsfm_opts oo = *o;
-        oo.refine = TCSFM_REFINE_POSE;
-        oo.window_rule = TCSFM_WINDOW_PAIR;
-        InitParams I = init_params(h, &oo, N, d_pose_in, nullptr, d_K, 0);
-        I.K_mod = win_B;
-        // Gauss-Newton in the pair form: the back-substitution of iteration k is fused into the linearisation of iteration k+1 (depth
-        // maps and per-pixel records ping-pong between two buffers); LM rolls maps back and the min over sources needs the current map
-        // materialised before the linearisation, so those keep the separate update launch
-        const bool fuse = !lm && !n_sel && o->n_iters > 0;
-        if (fuse && !h->dense_rec2) {
-            HIPCHK(h, hipMalloc((void **)&h->dense_rec2, n * hw * 8 * sizeof(float)));
-            HIPCHK(h, hipMalloc((void **)&h->depth_alt, n * hw * sizeof(float)));
-        }
-        // every pair gets its OWN copy of its target's depth; the pack also leaves the prior centre depth0
-        if ((rc = run_pack(h, &oo, N, d_tgt, d_src, d_dt, d_ds, &I, win_B, win_S, h->depth0, wo, ct))) return rc;
-        // the dense kernel's own tile grid (32x16 tiles of 512 threads, as k_linearize; 16x16 / 256 threads measured slower except
-        // for 320x240 at B=1: 10.9 vs 11.8 us per launch there, 234 vs 200 us with the chip full) and reduction-group count
-        constexpr int DTW = 32, DTH = 16, DNT = 512;
-        LinParams P = lin_params(h, &oo, 6);
-        P.tiles_x = (h->W + DTW - 1) / DTW; P.tiles_y = (h->H + DTH - 1) / DTH;
-        const int nblk = P.tiles_x * P.tiles_y;
-        P.ngrp = (nblk + RG - 1) / RG;
-        if ((size_t)nblk > (size_t)h->nblk_alloc || P.ngrp > h->ngrp_alloc) return fail(h, TCSFM_E_ARG, "internal: dense tile grid exceeds scratch");
-        SolveParams S = solve_params(h, &oo, 6, 0);
-        P.direct = nblk <= 512;
-        S.partials = P.direct ? h->blockrec : h->partials; S.ngrp = P.direct ? nblk : P.ngrp;
-        S.stats = d_stats; S.delta_out = h->delta;
-        if (ct) {
-            S.c_ncall = ct->ncall; S.c_B = ct->cB; S.c_S = ct->cS;
-            for (int i = 0; i < ct->ncall; i++) S.c_pose_out[i] = ct_pose[i];
-        }
-        DenseParams Dn;
-        Dn.dense_rec = h->dense_rec; Dn.depth0 = h->depth0; Dn.lambda_depth = o->lambda_depth; Dn.w_prior = o->prior_depth;
-        Dn.prev_rec = nullptr; Dn.prev_delta = h->delta; Dn.depth_next = nullptr;
-        Dn.rho_lo = 1.f / o->max_depth; Dn.rho_hi = 1.f / o->min_depth;
-        DenseUpdateParams U;
-        memset(&U, 0, sizeof(U));
-        U.dense_rec = h->dense_rec; U.delta = h->delta; U.depth = h->depth_work; U.depth_out = h->depth_work; U.hw = (int)hw;
-        U.rho_lo = Dn.rho_lo; U.rho_hi = Dn.rho_hi;
-        float *Dbuf[2] = {h->depth_work, h->depth_alt}, *Rbuf[2] = {h->dense_rec, h->dense_rec2};
-        // min over the sources (window form): selection masks of the forward pairs from their residual maps at the current poses
-        // AND current depth copies, rebuilt before every linearisation (same two launches as in the pose mode)
-        float *sel_diff = h->sel_maps, *sel_valid = h->sel_maps ? h->sel_maps + (size_t)h->max_pairs * hw : nullptr;
-        if (n_sel) { P.ext_diff = sel_diff; P.ext_valid = sel_valid; P.n_ext = n_sel; P.ext_B = win_B; P.ext_S = win_S; }
-        auto select_pass = [&]() {
-            LinParams M = lin_params(h, &oo, 6);
-            M.o_diff = sel_diff; M.o_valid = sel_valid;
-            launch_lin(h, M, n_sel, 6, false, MODE_MAPS, 2);          // (the selection itself: ext_selected, inside the dense kernel)
-        };
-        auto linearize = [&]() {
-            if (n_sel) select_pass();
-            take_stamp(h, P, (size_t)nblk * N);
-            ProfScope prof(h, 0);
-            if (P.trace != nullptr) hipLaunchKernelGGL((k_dense_linearize<DTW, DTH, DNT, true>), dim3(nblk, N), dim3(DNT), 0, h->stream, P, Dn);
-            else hipLaunchKernelGGL((k_dense_linearize<DTW, DTH, DNT>), dim3(nblk, N), dim3(DNT), 0, h->stream, P, Dn);
-        };
-        DenseLmParams Ul;
-        Ul.rec_try = h->dense_rec; Ul.rec_acc = h->dense_rec_acc; Ul.depth_acc = h->depth_acc; Ul.depth = h->depth_work; Ul.delta = h->delta;
-        Ul.accept = h->lm_accept; Ul.hw = (int)hw; Ul.rho_lo = U.rho_lo; Ul.rho_hi = U.rho_hi;
-        S.accept_out = lm ? h->lm_accept : nullptr;
-        const dim3 px_grid((unsigned)((hw + 255) / 256), N);
-        if ((rc = trace_check(h, o, N))) return rc;
-        for (int it = 0; it < o->n_iters; it++) {
-            trace_at(h, it, N, P, S);
-            if (fuse) {   // reads depth_{it-1} + the records / step of iteration it-1, leaves depth_it and the records of iteration it
-                P.depth_t = Dbuf[it & 1]; Dn.depth_next = Dbuf[(it + 1) & 1];
-                Dn.dense_rec = Rbuf[it & 1]; Dn.prev_rec = it > 0 ? Rbuf[(it - 1) & 1] : nullptr;
-            }
-            linearize();
-            S.it = it; S.mode = 0;
-            const bool last = !lm && it == o->n_iters - 1;
-            S.pose_out = last ? d_pose_out : nullptr; S.log_scale_out = nullptr;
-            launch_solve(h, S, N, 6);
-            if (lm) hipLaunchKernelGGL(k_dense_update_lm, px_grid, dim3(256), 0, h->stream, Ul);
-            else if (!fuse) hipLaunchKernelGGL(k_dense_update, px_grid, dim3(256), 0, h->stream, U);
-        }
-        if (fuse) {   // the last back-substitution writes the caller's depth map directly
-            const int nit = o->n_iters;
-            U.dense_rec = Rbuf[(nit - 1) & 1]; U.depth = Dbuf[nit & 1]; U.depth_out = d_depth_out;
-            if (ct) {
-                U.c_ncall = ct->ncall; U.c_B = ct->cB; U.c_S = ct->cS;
-                for (int i = 0; i < ct->ncall; i++) U.c_depth_out[i] = ct_depth[i];
-            }
-            hipLaunchKernelGGL(k_dense_update, px_grid, dim3(256), 0, h->stream, U);
-        }
-        if (lm && o->n_iters > 0) {   // evaluate the last trial once more; keep it only if it lowered the cost (pose and depth map)
-            trace_at(h, o->n_iters, N, P, S);
-            linearize();
-            S.it = o->n_iters; S.mode = 1;
-            S.pose_out = d_pose_out; S.log_scale_out = nullptr;
-            launch_solve(h, S, N, 6);
-            hipLaunchKernelGGL(k_dense_final_lm, px_grid, dim3(256), 0, h->stream, (const int *)h->lm_accept, (const float *)h->depth_acc, h->depth_work, (int)hw);
-        }
-        HIPCHK(h, hipGetLastError());
-        if (o->n_iters == 0) {
-            FinishParams F;
-            F.st = h->state; F.pose_out = d_pose_out; F.log_scale_out = nullptr; F.N = N;
-            hipLaunchKernelGGL(k_finish, dim3((N + 63) / 64), dim3(64), 0, h->stream, F);
-        }
-        if (!fuse) HIPCHK(h, hipMemcpyAsync(d_depth_out, h->depth_work, N * hw * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    }
+    const DenseCall c{h, o, win_B ? win_B : N, win_S, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, ct, ct_pose, ct_depth, depth_on_input, nullptr};
+    if (ref_mode) rc = dense_ref_run(c);
+    // one depth map per target, 6S x 6S reduced system (joint_kernel.h); the library's own joint mode stays at S <= JMAXS_OWN = 3: wider windows
+    // there keep the per-pair depth copies of the pair form
+    else if (win_B && o->dense_joint && win_S >= 2 && win_S <= JMAXS_OWN) rc = dense_joint_run(c);
+    else rc = dense_pair_run(c);
+    if (rc) return rc;
     return st.finish();
 }
 
@@ -2781,7 +2025,7 @@ static int linearize_dense_window_impl(tcsfm_handle h, const tcsfm_opts *o, int 
     tcsfm_opts oo = *o;
     oo.n_iters = 1; oo.solver = TCSFM_SOLVER_GN;
     DrefExport ex{scal_out, g_pose_out, d_g, d_d0, d_gs};
-    if ((rc = dense_ref_runs[S - 1](h, &oo, B, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, &ex, nullptr, nullptr, nullptr, false))) return rc;
+    if ((rc = dense_ref_run(DenseCall{h, &oo, B, S, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, &ex}))) return rc;
     return st.finish();
 }
 
