@@ -1076,6 +1076,52 @@ typedef struct tcsfm_debug_solve_args {
 int tcsfm_debug_solve(tcsfm_handle h, const tcsfm_opts *opts, tcsfm_debug_solve_args *args);
 /* sizeof(PairState), sizeof(PairConst) as the library was compiled (host, no GPU needed) */
 int tcsfm_debug_solve_layout(int *sizeof_pair_state, int *sizeof_pair_const);
+/* Test hook: ONE launch of a production JOINT solve kernel (the 6 NS x 6 NS reduced camera system of a target's NS forward pairs) on records
+ * and optimiser state the caller gives (tests/test_gpu_joint_solve_exact.py compares it with exact arithmetic).  As tcsfm_debug_solve: every
+ * array is HOST memory, copied into guarded device allocations of the entry's own, one launch on the handle's stream, one synchronisation,
+ * every in/out and out array copied back WHOLE, the entry's guard bands read back before they are freed.  variant: 0 k_solve_joint<NS>;
+ * 1 / 2 the joint role of k_solve_front<NS> without / with the pose-consistency code (no workgroup takes the pair role); 3 / 4
+ * k_solve_joint2<NS> without / with it: group `a` has NS sources per target, group `b` ONE (the free-source mode's inverse groups).
+ * Variants 0 to 2 use group `a` only.  The solver, the damping schedule (lambda0, lambda_up, lambda_down, lambda_min) and n_iters come from
+ * `opts`; mode: 0 iteration step, 1 final LM cost check; a group whose export_out is given takes the export path (cost, factor, gradient:
+ * nothing else written).  Forward pair (s, b) of a group is pair n0 + s B + b of the shared per-pair arrays.  Anything that would index
+ * outside a given array or reach a compiled-out branch is refused with TCSFM_E_ARG before anything is launched. */
+typedef struct tcsfm_debug_joint_group {
+    int32_t B, b_alloc;           /* targets solved; targets every per-target array below holds (>= B): B .. b_alloc - 1 are never touched */
+    int32_t nblk, nsplit;         /* records per target; workgroups that share a target's record sum (1 .. 8) */
+    int32_t n0;                   /* index of the group's first pair in the shared per-pair arrays */
+    int32_t norm_n, norm_B;       /* norms [norm_n][2]; targets per normaliser group (0: one group) */
+    int32_t pc_self0, pc_part0;   /* pose_lin slots of the group's pair 0 and of its partner */
+    int32_t pad;
+    double c_f;
+    const float *records;         /* [b_alloc][nblk][NACC] */
+    const int32_t *norms;         /* or NULL: 1 / K from the records */
+    void *js;                     /* [b_alloc] JointState, in and out */
+    double *delta_out;            /* [b_alloc][24] or NULL */
+    int32_t *accept_out;          /* [b_alloc] or NULL */
+    double *export_out;           /* [b_alloc][26] or NULL; given: the export path */
+    double *jpart;                /* [b_alloc][nsplit][NACC], out; required when nsplit > 1 */
+    int32_t *jtick;               /* [b_alloc], in and out; required and all zero when nsplit > 1 */
+} tcsfm_debug_joint_group;
+typedef struct tcsfm_debug_solve_joint_args {
+    int32_t variant, NS, it, mode;
+    int32_t n_alloc;              /* pairs every shared per-pair array holds */
+    int32_t pc_np;                /* pose_lin [2][pc_np][12] */
+    int32_t c_ncall, c_B, c_S, pad;
+    int32_t c_len[16];            /* pairs the per-call arrays hold */
+    double w_pc, pc_eps;
+    tcsfm_debug_joint_group a, b;
+    void *state;                  /* [n_alloc] PairState, in and out */
+    void *pconst;                 /* [n_alloc] PairConst, in and out */
+    float *stats;                 /* [n_alloc][n_iters + 1][TCSFM_NSTAT] or NULL */
+    float *pose_out;              /* [n_alloc][6] or NULL (NULL: no launch emits a pose) */
+    int32_t *trace_decide;        /* [n_alloc] or NULL */
+    double *pose_lin;             /* in and out; required by variants 2 and 4 */
+    float *c_pose_out[16];        /* c_ncall > 0 (variants 0 to 2): [c_len[i]][6] per call */
+} tcsfm_debug_solve_joint_args;
+int tcsfm_debug_solve_joint(tcsfm_handle h, const tcsfm_opts *opts, tcsfm_debug_solve_joint_args *args);
+/* ... and sizeof(JointState) (host, no GPU needed); any pointer may be NULL */
+int tcsfm_debug_solve_joint_layout(int *sizeof_pair_state, int *sizeof_pair_const, int *sizeof_joint_state);
 
 /* ---- SE(3) utilities, host, double (replace liegroups.SE3 at data/kitti_loader_stereo.py:129-147,
  *      validate.py:65-71; liegroups is an absent third-party dependency, version unpinned) ---------- */

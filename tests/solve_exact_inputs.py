@@ -913,6 +913,11 @@ def _judge_const(bad, meas, t, c, pc, pc_in, K, T, s):
         bad(t + "6 unknowns: pconst.es changed")
 
 
+# public names of the helpers tests/joint_solve_exact_inputs.py shares with this module
+exact_sum, mpf, frac, euler_left_jacobian, damped_step, pivots_positive = _exact_sum, _mpf, _frac, _euler_left_jacobian, _damped_step, _pivots_positive
+pose64, exp64, mul64, jac64, Emax, eq, judge_pose, judge_const = _pose64, _exp64, _mul64, _jac64, _Emax, _eq, _judge_pose, _judge_const
+
+
 # ----------------------------------------------------------------------------------------------------------------------- case lists
 def _allowed(variant, npar, w_pc=0.0, param=0):
     return not ((variant >= 1 and param != 0) or (variant in (1, 2) and w_pc > 0) or (variant >= 2 and npar == 7) or (w_pc > 0 and npar == 7))

@@ -30,12 +30,19 @@ def test_args_struct_matches_the_header():
     from tightly_coupled_sfm_amd import _lib
     names = ["c_len", "scale_fwd", "records", "state", "lin_out", "trace_decide", "c_pose_out", "c_ls_out", "stats", "pose_lin"]
     src = '#include <stdio.h>\n#include <stddef.h>\n#include "tcsfm.h"\nint main(void){printf("%zu", sizeof(tcsfm_debug_solve_args));' + \
-          "".join(f'printf(" %zu", offsetof(tcsfm_debug_solve_args, {n}));' for n in names) + "return 0;}"
+          "".join(f'printf(" %zu", offsetof(tcsfm_debug_solve_args, {n}));' for n in names) + \
+          'printf(" %zu %zu", sizeof(tcsfm_debug_joint_group), sizeof(tcsfm_debug_solve_joint_args));' \
+          "int (*p1)(tcsfm_handle, const tcsfm_opts *, tcsfm_debug_solve_args *); int (*p2)(tcsfm_handle, const tcsfm_opts *, tcsfm_debug_solve_joint_args *);" \
+          "int (*p3)(int *, int *); int (*p4)(int *, int *, int *);" \
+          "(void)sizeof(p1 = tcsfm_debug_solve); (void)sizeof(p2 = tcsfm_debug_solve_joint); (void)sizeof(p3 = tcsfm_debug_solve_layout);" \
+          "(void)sizeof(p4 = tcsfm_debug_solve_joint_layout);" \
+          "return 0;}"
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "s.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-std=c99", "-I" + os.path.join(REPO, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
+        subprocess.check_call(["gcc", "-std=c99", "-Werror=incompatible-pointer-types", "-I" + os.path.join(REPO, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         got = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
-    assert got == [C.sizeof(_lib.DebugSolveArgs)] + [getattr(_lib.DebugSolveArgs, n).offset for n in names]
+    assert got == [C.sizeof(_lib.DebugSolveArgs)] + [getattr(_lib.DebugSolveArgs, n).offset for n in names] + \
+        [C.sizeof(_lib.DebugJointGroup), C.sizeof(_lib.DebugSolveJointArgs)]      # (the joint hook's field offsets: test_joint_solve_exact_inputs_cpu.py)
     assert _lib.DebugSolveArgs.c_pose_out.size == SX.TC_MAX_COAL * C.sizeof(C.c_void_p)
 
 

@@ -139,6 +139,25 @@ class DebugSolveArgs(C.Structure):
                [("c_pose_out", _P * 16), ("c_ls_out", _P * 16), ("stats", _P), ("pose_lin", _P)]
 
 
+class JointState(C.Structure):
+    """mirror of struct JointState (csrc/joint_kernel.h): LM bookkeeping and the accepted reduced system [S | -gS], 24 x 25 at most"""
+    _fields_ = [("lam", C.c_double), ("cost_cur", C.c_double), ("have_cur", C.c_int32), ("pad", C.c_int32), ("M", C.c_double * 600)]
+
+
+class DebugJointGroup(C.Structure):
+    """mirror of struct tcsfm_debug_joint_group"""
+    _fields_ = [(k, C.c_int32) for k in ("B", "b_alloc", "nblk", "nsplit", "n0", "norm_n", "norm_B", "pc_self0", "pc_part0", "pad")] + \
+               [("c_f", C.c_double)] + \
+               [(k, _P) for k in ("records", "norms", "js", "delta_out", "accept_out", "export_out", "jpart", "jtick")]
+
+
+class DebugSolveJointArgs(C.Structure):
+    """mirror of struct tcsfm_debug_solve_joint_args"""
+    _fields_ = [(k, C.c_int32) for k in ("variant", "NS", "it", "mode", "n_alloc", "pc_np", "c_ncall", "c_B", "c_S", "pad")] + \
+               [("c_len", C.c_int32 * 16), ("w_pc", C.c_double), ("pc_eps", C.c_double), ("a", DebugJointGroup), ("b", DebugJointGroup)] + \
+               [(k, _P) for k in ("state", "pconst", "stats", "pose_out", "trace_decide", "pose_lin")] + [("c_pose_out", _P * 16)]
+
+
 _SIGNATURES = {
     "tcsfm_lane_probe": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "tcsfm_debug_check_guards": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -252,6 +271,8 @@ _SIGNATURES = {
     "tcsfm_debug_trace": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64]),
     "tcsfm_debug_solve": (C.c_int, [_P, C.POINTER(Opts), C.POINTER(DebugSolveArgs)]),
     "tcsfm_debug_solve_layout": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tcsfm_debug_solve_joint": (C.c_int, [_P, C.POINTER(Opts), C.POINTER(DebugSolveJointArgs)]),
+    "tcsfm_debug_solve_joint_layout": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tcsfm_pose_to_matrix": (None, [_P, _P]),
     "tcsfm_matrix_to_pose": (None, [_P, _P]),
     "tcsfm_se3_exp": (None, [_P, _P]),
@@ -299,6 +320,13 @@ def debug_solve_layout():
     a, b = C.c_int(0), C.c_int(0)
     load().tcsfm_debug_solve_layout(C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+def debug_solve_joint_layout():
+    """(sizeof(PairState), sizeof(PairConst), sizeof(JointState)) as the library was compiled (tcsfm_debug_solve_joint_layout; no GPU needed)"""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    load().tcsfm_debug_solve_joint_layout(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
 
 
 def depth_eval_opts(protocol="eigen", median_scaling=True, min_depth=1e-3, max_depth=80.0, depth_unit=30.0, lds_pairs=-1) -> DepthEvalOpts:

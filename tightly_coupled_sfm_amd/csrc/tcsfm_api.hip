@@ -2452,29 +2452,13 @@ int tcsfm_debug_solve_layout(int *sizeof_pair_state, int *sizeof_pair_const) {
     return TCSFM_OK;
 }
 
-namespace {
-// the device copies of tcsfm_debug_solve: allocations of the entry's own (guarded like every other), freed when it returns
-struct DebugBufs {
-    std::vector<void *> dev;
-    struct Back { void *host; void *dev; size_t bytes; };
-    std::vector<Back> back;
-    ~DebugBufs() { for (void *p : dev) (void)hipFree(p); }
-    // host == nullptr: nullptr.  Otherwise a device copy of `bytes` bytes; out: copied back after the launch
-    hipError_t up(const void *host, size_t bytes, bool out, void **res) {
-        *res = nullptr;
-        if (!host || bytes == 0) return hipSuccess;
-        void *d = nullptr;
-        hipError_t e = hipMalloc(&d, bytes);
-        if (e != hipSuccess) return e;
-        dev.push_back(d);
-        e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return e;
-        if (out) back.push_back({const_cast<void *>(host), d, bytes});
-        *res = d;
-        return hipSuccess;
-    }
-};
-}  // namespace
+#include "debug_solve_host.h"      // DebugBufs, the joint entry
+
+int tcsfm_debug_solve_joint_layout(int *sizeof_pair_state, int *sizeof_pair_const, int *sizeof_joint_state) {
+    if (sizeof_joint_state) *sizeof_joint_state = (int)sizeof(JointState);
+    return tcsfm_debug_solve_layout(sizeof_pair_state, sizeof_pair_const);
+}
+int tcsfm_debug_solve_joint(tcsfm_handle h, const tcsfm_opts *o, tcsfm_debug_solve_joint_args *a) { return debug_solve_joint_run(h, o, a); }
 
 int tcsfm_debug_solve(tcsfm_handle h, const tcsfm_opts *o, tcsfm_debug_solve_args *a) {
     if (int rc_q = drain_queued(h)) return rc_q;

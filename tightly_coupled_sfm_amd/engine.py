@@ -366,6 +366,12 @@ class Engine:
         self._bind()
         return int(self.lib.tcsfm_debug_solve(self._h, C.byref(opts), C.byref(args)))
 
+    def debug_solve_joint(self, opts, args) -> int:
+        """test hook (tcsfm_debug_solve_joint): ONE launch of a production joint solve kernel on the host records and state of `args`
+        (_lib.DebugSolveJointArgs; numpy arrays behind its pointers, outputs filled in place).  -> the return code, as debug_solve"""
+        self._bind()
+        return int(self.lib.tcsfm_debug_solve_joint(self._h, C.byref(opts), C.byref(args)))
+
     @property
     def dev(self) -> torch.device:
         return torch.device("cuda", self.device)
