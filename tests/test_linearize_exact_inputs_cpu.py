@@ -22,6 +22,7 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 def test_reduction_constants_are_the_kernels():
     api, ker = (open(os.path.join(CSRC, f)).read() for f in ("tcsfm_api.hip", "kernels.h"))
+    api += open(os.path.join(CSRC, "pose_host.h")).read()      # the pose driver and its launch helpers: part of the API file's translation unit
     lay = open(os.path.join(CSRC, "layout.h")).read()          # the layout constants host arithmetic and kernels share: the tile and RG live there
     assert re.search(r"constexpr int TILE_W = (\d+), TILE_H = TC_TILE_H, TILE_NT = TILE_W \* TILE_H;", lay).group(1) == str(LX.TILE_W)
     assert re.search(r"#define TC_TILE_H (\d+)", lay).group(1) == str(LX.TILE_H) and LX.NT == LX.TILE_W * LX.TILE_H

@@ -2,7 +2,7 @@
 // drivers behind dense_body -- the pair form (DensePair), the library's joint mode (DenseJoint) and the reference's loss (DenseRef).  The
 // arithmetic -- capacities, tile grids, which part of which buffer a launch works on, the refusals -- is dense_plan.h's (no HIP there);
 // here is what is launched, in which order, on which stream.  Part of tcsfm_api.hip, the library's only translation unit: included after
-// run_pack, lin_params, solve_params, launch_lin, launch_solve and the trace helpers.
+// pose_host.h, whose run_pack, lin_params, solve_params, launch_lin, launch_solve and trace helpers it uses.
 //
 // A driver is a per-call struct: reserve (every buffer the mode needs, every call: a no-op from the second identical call on, so nothing
 // is allocated or freed under stream capture), pack, the parameter blocks, then linearise(lin) / solve(it) / update(it) per iteration.

@@ -276,15 +276,15 @@ int SeqCall::issue_call(const SeqSchedule &sched, long long ci, int c0, int nbw)
         // the call's maps come out stacked [pair index][window]; a small kernel puts them in the caller's per-window order, and ONE
         // copy per call takes them to the host on the lane's stream (asynchronous when the destination is pinned)
         float *tmp = c->seq_dense_tmp.p, *ordered = h->seq_dense.p + (size_t)c0 * N * hw;
-        failed = dense_impl(c, &o, N * nbw, nbw, S, tg, sr, dt, ds, h->seq_K.p, p_in, p_out, tmp, nullptr, &wo);
+        failed = dense_impl(c, &o, N * nbw, nbw, S, CallArgs{tg, sr, dt, ds, h->seq_K.p, p_in, nullptr, p_out, nullptr, tmp, nullptr}, &wo);
         if (!failed) {
             hipLaunchKernelGGL(k_maps_to_window_order, dim3((unsigned)((hw + 255) / 256), N * nbw), dim3(256), 0, ls[l], (const float *)tmp, ordered, nbw, N, (int)hw);
             HIPCHK(h, hipMemcpyAsync(dense_depth_out + (size_t)c0 * N * hw, ordered, (size_t)nbw * N * hw * sizeof(float), hipMemcpyDeviceToHost, ls[l]));
         }
     } else if (!failed) {
         FrameCache fcache = {h->seq_fpack.p, h->seq_fdepth.p, s0, p.tp};
-        failed = refine_impl(c, &o, N * nbw, nbw, S, tg, sr, dt, ds, h->seq_K.p, p_in, nullptr, p_out, np == 7 ? h->seq_ls_out.p + (size_t)c0 * N : nullptr,
-                             nullptr, &wo, use_cache ? &fcache : nullptr);
+        failed = refine_impl(c, &o, N * nbw, nbw, S, CallArgs{tg, sr, dt, ds, h->seq_K.p, p_in, nullptr, p_out, np == 7 ? h->seq_ls_out.p + (size_t)c0 * N : nullptr, nullptr, nullptr},
+                             &wo, use_cache ? &fcache : nullptr);
     }
     if (failed) { if (c != h) h->err = c->err; return TCSFM_OK; }
     HIPCHK(h, hipEventRecord(h->seq_done[sched.done_event(ci)], ls[l]));

@@ -1,5 +1,7 @@
 // tcsfm_api.hip -- C ABI (include/tcsfm.h) over the gfx950 kernels in kernels.h.
-// Host logic only: argument checking, scratch management, kernel sequencing on one HIP stream.
+// Host logic only: the guard bands, the handle, staging and the argument checks, create / destroy / stream entries and the operator entry
+// points.  The drivers are headers of this translation unit, included where their helpers are first needed: pose_host.h (the pose modes),
+// dense_host.h (the dense modes), call_host.h (graph replay, queued calls, lanes), sequence_host.h and the networks' hosts.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -33,6 +35,7 @@
 #include "disp_post_kernel.h"
 #include "depth_eval_kernel.h"
 #include "dense_plan.h"
+#include "call_plan.h"
 
 using namespace tc;
 
@@ -253,31 +256,17 @@ struct tcsfm_ctx {
     struct KOk { const float *p; int n; };
     KOk K_ok[4] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}};   // device intrinsics pointers (and counts) that already passed the pinhole check
     int K_ok_next = 0;
-    // tcsfm_set_graph_replay: repeated device-pointer refine calls (same arguments) replayed as ONE captured HIP graph
-    struct CallKey { tcsfm_opts o; int N, win_B, win_S, pad; const void *p[10]; };
-    struct CallGraph { CallKey key; hipGraphExec_t exec; int seen; unsigned long long used; };
-    int graph_slots = 0;               // 0: off
-    std::vector<CallGraph> graphs;
-    unsigned long long graph_clock = 0;
-    int graph_captures = 0, graph_replays = 0;
-    bool capturing = false;
-    // tcsfm_refine_window_queued: calls of one shape waiting to run as ONE launch sequence (tcsfm_set_coalesce / tcsfm_flush)
-    struct PendingCall { const float *tgt, *srcs, *dt, *ds, *K, *pose_in; float *pose_out; float *depth_out; const float *ls_in; float *ls_out; };
-                                       // depth_out: dense calls; ls_in / ls_out: pose + scale calls (or null)
+    // The routing of the refine calls (call_host.h), by the rules of call_plan.h:
+    GraphCache<hipGraphExec_t> graphs; // tcsfm_set_graph_replay: repeated device-pointer refine calls (same arguments) replayed as ONE captured HIP graph
+    bool capturing = false;            // ... a capture is under way on the handle's stream
+    CallQueue<CallArgs> queue;         // the *_queued entries: calls of one shape waiting to run as ONE launch sequence (tcsfm_set_coalesce / tcsfm_flush)
+    LaneRotation rot;                  // ... and the streams their merged sequences alternate over (tcsfm_set_coalesce_lanes)
     bool lanes_serial = false;         // tcsfm_set_lanes' self-probe found that this process's streams do NOT run side by side (they slow each other
                                        // down: include/tcsfm.h "lanes"): the *_async calls run on the handle's own stream, one after the other
     float lane_probe[2] = {0.f, 0.f};  // the probe's figures: ms of the stand-in launches on ONE stream / alternating over TWO streams
     bool dref_dirty = true;            // the scatter sums (dref_ext, dref_ext_src) may be non-zero: a call that ran to its end leaves them zero
                                        // (k_dense_joint clears what it consumes); a fresh allocation, an export or a failed call does not
     double *pose_lin = nullptr;        // l_pose_consist: [2][max_pairs][12] transforms at the linearisation (k_solve, kernels.h)
-    int coal_max = 0;
-    int pend_dense = 0;                // the waiting calls are dense-mode calls (tcsfm_refine_dense_window_queued)
-    int coal_lanes = 1;                // merged sequences alternate over this many of the handle's streams (tcsfm_set_coalesce_lanes)
-    unsigned coal_dirty = 0;           // bit l: lane l ran a merged sequence the handle's stream has not been ordered behind yet
-    std::vector<PendingCall> pending;
-    tcsfm_opts pend_opts;
-    int pend_B = 0, pend_S = 0;
-    int coal_batches = 0, coal_calls = 0;
     unsigned short *trace_bits = nullptr;   // tcsfm_debug_trace: caller-owned device buffers (null = off)
     int *trace_decide = nullptr;
     long long trace_bits_cap = 0, trace_decide_cap = 0;
@@ -330,19 +319,6 @@ int DevBuf<T>::reserve(tcsfm_ctx *h, size_t n, const char *file, int line) {
 
 namespace {
 
-// Captured call graphs bake in the handle's scratch pointers and run on the stream they were last launched on: whoever frees or
-// re-sizes such scratch, switches the stream or evicts an entry drains BOTH streams a replay can be on first.
-void sync_graph_streams(tcsfm_ctx *c) {
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->own_stream && c->own_stream != c->stream) (void)hipStreamSynchronize(c->own_stream);
-}
-void drop_graphs(tcsfm_ctx *c) {
-    if (c->graphs.empty()) return;
-    sync_graph_streams(c);
-    for (auto &g : c->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    c->graphs.clear();
-}
-
 int fail(tcsfm_ctx *h, int code, const char *msg) {
     h->err = msg;
     return code;
@@ -376,7 +352,6 @@ int pending_error(tcsfm_ctx *h) {
     return TCSFM_OK;
 }
 
-
 int check_common(tcsfm_ctx *h, const tcsfm_opts *o, int N) {
     if (!h) return TCSFM_E_ARG;
     if (!o) return fail(h, TCSFM_E_ARG, "opts is NULL");
@@ -393,17 +368,34 @@ int check_common(tcsfm_ctx *h, const tcsfm_opts *o, int N) {
     return TCSFM_OK;
 }
 
-// TCSFM_WINDOW_REFERENCE (window forms only): the coupling of the pairs' costs, see include/tcsfm.h
-void apply_window_rule(const tcsfm_ctx *h, const tcsfm_opts *o, int win_B, int win_S, int N, LinParams &P, SolveParams &S) {
-    if (!win_B || o->window_rule != TCSFM_WINDOW_REFERENCE) return;
-    P.rule = 1;
-    P.fwd_noauto = o->argmin ? 0 : win_B * win_S;      // optimizer.py:71-73: without argmin the forward term has no auto-mask
-    S.rule = 1; S.grp_fwd = win_B * win_S; S.n_pairs = N;
-    S.scale_fwd = o->argmin ? 1.0 : 0.25; S.scale_inv = 0.25;
-    S.b_dc = (double)o->w_dc / ((double)win_B * win_S * (double)h->H * (double)h->W);   // :83-86: mean over all S*B maps
-    if (o->w_pose_consist > 0.f) {       // :95-96: 0.1 (poses + poses_inv).abs().mean() over the S B x 6 entries
-        S.w_pc = (double)o->w_pose_consist / (6.0 * win_B * win_S); S.pc_eps = (double)o->irls_eps; S.pose_lin = h->pose_lin;
-    }
+// The overlap contract (include/tcsfm.h) for the refine family, pose and dense modes, applied by every public form on its own behalf
+// before anything else happens (a graph replay and a queued call never reach the bodies' own staging with the caller's pointers).  The
+// arrays' extents are the call plan's (call_plan.h).
+// Honoured: pose_out at pose_in, and the dense depth_out anywhere over depth_t / depth_s -- *depth_on_input then says so (device pointers).  Arguments the
+// later validation refuses (NULL handle or options, sizes out of range) are left to it.
+int refine_overlap(tcsfm_ctx *h, const char *entry, const tcsfm_opts *o, int N, int win_B, int win_S, const CallArgs &c, bool dense,
+                   bool *depth_on_input = nullptr) {
+    if (depth_on_input) *depth_on_input = false;
+    if (!h || !o || N < 1 || N > h->max_pairs || o->n_iters < 0 || o->n_iters > 1000) return TCSFM_OK;
+    const PosePlan pl = pose_plan(N, win_B, win_S, 0, 0, 0, o->solver, o->n_iters, o->refine, o->argmin);
+    const size_t hw = (size_t)h->H * h->W, f = sizeof(float);
+    const bool scale = !dense && pl.np == 7;
+    ArgRanges a;
+    a.io_free = o->host_ptrs != 0;
+    a.in("tgt", c.tgt, pl.tgt(hw) * f); a.in(win_B ? "srcs" : "src", c.src, pl.src(hw) * f); a.in("depth_t", c.depth_t, pl.depth_t(hw) * f);
+    a.in("depth_s", c.depth_s, pl.depth_s(hw) * f); a.in("K", c.K, pl.K() * f); a.in("pose_in", c.pose_in, pl.pose() * f);
+    if (scale) a.in("log_scale_in", c.log_scale_in, pl.log_scale() * f);
+    a.out("pose_out", c.pose_out, pl.pose() * f);
+    if (scale) a.out("log_scale_out", c.log_scale_out, pl.log_scale() * f);
+    if (dense) a.out("depth_out", c.depth_out, pl.maps(hw) * f);
+    a.out("stats_out", c.stats_out, pl.stats() * f);
+    a.bless("pose_out", "pose_in");
+    if (dense) { a.bless_any("depth_out", "depth_t"); a.bless_any("depth_out", "depth_s"); }
+    std::string msg;
+    if (a.refused(entry, msg)) return fail(h, TCSFM_E_ARG, msg.c_str());
+    // (staged host arrays land in the library's own, disjoint device buffers: nothing to avoid there)
+    if (depth_on_input) *depth_on_input = dense && !a.io_free && (a.overlap("depth_out", "depth_t") || a.overlap("depth_out", "depth_s"));
+    return TCSFM_OK;
 }
 
 // The array arguments of one call.  With opts.host_ptrs in() stages a host array on the device and out() hands out a device buffer
@@ -532,186 +524,9 @@ void take_stamp(tcsfm_ctx *h, LinParams &P, size_t workgroups) {
     }
 }
 
-// k_linearize's SSIM gradient in its adjoint form (kernels.h, ADJ) or as the round-3 neighbour-visiting pass B: TCSFM_ADJOINT=0/1,
-// read once per process (default: see adjoint_default below; both forms are exact, they differ in rounding only)
-constexpr int kAdjointDefault = 0;
-bool use_adjoint() {
-    static const int v = [] { const char *e = getenv("TCSFM_ADJOINT"); return e ? (atoi(e) != 0) : (kAdjointDefault != 0); }();
-    return v != 0;
-}
-
-template <int NP, bool DC, int MODE, bool ADJ>
-void launch_lin_a(tcsfm_ctx *h, const LinParams &P, int N) {
-    dim3 grid(h->nblk, N), block(TILE_NT);
-    const bool sel = MODE != MODE_MAPS && P.sel_S > 1;   // window form with the min over sources: selection inside the kernel
-    if (MODE != MODE_MAPS && P.trace != nullptr) {       // parity tests: the decision-recording build
-        if (sel) hipLaunchKernelGGL((k_linearize<NP, DC, MODE, TILE_W, TILE_H, TILE_NT, true, true, ADJ>), grid, block, 0, h->stream, P);
-        else hipLaunchKernelGGL((k_linearize<NP, DC, MODE, TILE_W, TILE_H, TILE_NT, false, true, ADJ>), grid, block, 0, h->stream, P);
-    } else if (MODE != MODE_MAPS && !ADJ && P.tshare != 0) {       // window forms of the pose modes: the shared-pack instantiations (kernels.h TSH)
-        if (sel) hipLaunchKernelGGL((k_linearize<NP, DC, MODE, TILE_W, TILE_H, TILE_NT, true, false, false, false, MODE != MODE_MAPS>), grid, block, 0, h->stream, P);
-        else hipLaunchKernelGGL((k_linearize<NP, DC, MODE, TILE_W, TILE_H, TILE_NT, false, false, false, false, MODE != MODE_MAPS>), grid, block, 0, h->stream, P);
-    } else if (sel)
-        hipLaunchKernelGGL((k_linearize<NP, DC, MODE, TILE_W, TILE_H, TILE_NT, true, false, ADJ>), grid, block, 0, h->stream, P);
-    else
-        hipLaunchKernelGGL((k_linearize<NP, DC, MODE, TILE_W, TILE_H, TILE_NT, false, false, ADJ>), grid, block, 0, h->stream, P);
-}
-template <int NP, bool DC, int MODE>
-void launch_lin_t(tcsfm_ctx *h, const LinParams &P, int N) {
-    if (MODE == MODE_LIN && use_adjoint()) launch_lin_a<NP, DC, MODE, MODE == MODE_LIN>(h, P, N);
-    else launch_lin_a<NP, DC, MODE, false>(h, P, N);
-}
-
-void launch_lin(tcsfm_ctx *h, const LinParams &P_in, int N, int np, bool dc, int mode, int prof_class = 0) {
-    LinParams P = P_in;
-    if (prof_class == 0) take_stamp(h, P, (size_t)h->nblk * N); else P.stamp = nullptr;
-    P.one_generation = (size_t)h->nblk * N <= 512;          // 256 CUs x 2 resident workgroups
-    ProfScope prof(h, prof_class);
-    if (np == 6) {
-        if (mode == MODE_MAPS) launch_lin_t<6, false, MODE_MAPS>(h, P, N);
-        else if (mode == MODE_COST) launch_lin_t<6, false, MODE_COST>(h, P, N);
-        else if (dc) launch_lin_t<6, true, MODE_LIN>(h, P, N);
-        else launch_lin_t<6, false, MODE_LIN>(h, P, N);
-    } else {
-        if (mode == MODE_MAPS) launch_lin_t<7, false, MODE_MAPS>(h, P, N);
-        else if (mode == MODE_COST) launch_lin_t<7, false, MODE_COST>(h, P, N);
-        else if (dc) launch_lin_t<7, true, MODE_LIN>(h, P, N);
-        else launch_lin_t<7, false, MODE_LIN>(h, P, N);
-    }
-}
-
-// TCSFM_SOLVE_LEAN=1: the 1024-thread form of the solve kernel for SE(3) calls without the pose-consistency term -- measured SLOWER than
-// the 256-thread kernel (6.0 vs 5.3 us in-kernel, profiles/r05_solve_ab.txt): default off, kept for A/B runs
-bool use_lean_solve() {
-    static const int v = [] { const char *e = getenv("TCSFM_SOLVE_LEAN"); return e ? atoi(e) : 0; }();
-    return v != 0;
-}
-// lean: k_solve_lean (the caller has checked that the call is on the SE(3) chart and carries no pose-consistency term)
-void launch_solve_as(tcsfm_ctx *h, const SolveParams &S, int N, int np, bool lean) {
-    ProfScope prof(h, 1);
-    if (np == 6) { if (lean) hipLaunchKernelGGL((k_solve_lean<6>), dim3(N), dim3(1024), 0, h->stream, S); else hipLaunchKernelGGL((k_solve<6>), dim3(N), dim3(TC_SOLVE_NT), 0, h->stream, S); }
-    else { if (lean) hipLaunchKernelGGL((k_solve_lean<7>), dim3(N), dim3(1024), 0, h->stream, S); else hipLaunchKernelGGL((k_solve<7>), dim3(N), dim3(TC_SOLVE_NT), 0, h->stream, S); }
-}
-void launch_solve(tcsfm_ctx *h, const SolveParams &S, int N, int np) {
-    launch_solve_as(h, S, N, np, S.param == TCSFM_PARAM_SE3 && !(S.w_pc > 0.0) && use_lean_solve());      // (decided by the options of the call: every launch of a call takes the same kernel)
-}
-
-// decision trace (tcsfm_debug_trace) of linearisation `lin` of a call over N pairs: [lin][N][H*W] bits, [lin][N] decisions
-void trace_at(const tcsfm_ctx *h, int lin, int N, LinParams &P, SolveParams &S) {
-    const size_t hw = (size_t)h->H * h->W;
-    P.trace = h->trace_bits ? h->trace_bits + (size_t)lin * N * hw : nullptr;
-    S.trace_decide = h->trace_decide ? h->trace_decide + (size_t)lin * N : nullptr;
-}
-int trace_check(tcsfm_ctx *h, const tcsfm_opts *o, int N) {
-    const long long n_lin = o->n_iters + (o->solver == TCSFM_SOLVER_LM && o->n_iters > 0 ? 1 : 0);
-    if (h->trace_bits && n_lin * N * (long long)h->H * h->W > h->trace_bits_cap) return fail(h, TCSFM_E_ARG, "tcsfm_debug_trace: bits buffer too small for this call");
-    if (h->trace_decide && n_lin * N > h->trace_decide_cap) return fail(h, TCSFM_E_ARG, "tcsfm_debug_trace: decide buffer too small for this call");
-    return TCSFM_OK;
-}
-// tcsfm_linearize / tcsfm_linearize_window under a trace: ONE linearisation, bits [0][N][H*W]; no decision is taken, `decide` stays untouched
-int trace_lin_once(tcsfm_ctx *h, int N, LinParams &P) {
-    if (h->trace_bits && N * (long long)h->H * h->W > h->trace_bits_cap) return fail(h, TCSFM_E_ARG, "tcsfm_debug_trace: bits buffer too small for this call");
-    P.trace = h->trace_bits;
-    return TCSFM_OK;
-}
-
-int np_of(const tcsfm_opts *o) { return o->refine == TCSFM_REFINE_POSE_SCALE ? 7 : 6; }
-int nacc_of(int np) { return np == 6 ? AccLayout<6>::NACC : AccLayout<7>::NACC; }
-
-InitParams init_params(tcsfm_ctx *h, const tcsfm_opts *o, int N, const float *pose, const float *ls, const float *K, int shared) {
-    InitParams I;
-    I.pose = pose; I.log_scale = ls; I.K = K; I.st = h->state; I.pc = h->pconst; I.N = N; I.shared_image = shared;
-    I.lambda0 = o->lambda0;
-    I.K_mod = 0;
-    I.err = h->err_dev;
-    I.pose_lin = (o->window_rule == TCSFM_WINDOW_REFERENCE && o->w_pose_consist > 0.f) ? h->pose_lin : nullptr;
-    return I;
-}
-
-// init == nullptr: pack only.  Otherwise the pair initialisation rides in the same launch (needs N == Nimg).
-int run_pack(tcsfm_ctx *h, const tcsfm_opts *o, int Nimg, const float *tgt, const float *src, const float *dt, const float *ds,
-             const InitParams *init = nullptr, int win_B = 0, int win_S = 0, float *depth_copy = nullptr, const WinOff *wo = nullptr,
-             const CoalTab *ct = nullptr, float *depth_copy3 = nullptr, int *zero_ints = nullptr, int zero_n = 0, float *const *ct_depth3 = nullptr,
-             bool tshare = false) {
-    PackParams P;
-    P.depth_out2 = depth_copy; P.depth_out3 = depth_copy3; P.zero_ints = zero_ints; P.zero_n = zero_n;
-    P.tshare = tshare ? 1 : 0;
-    if (tshare && !(ct || win_B > 0)) return fail(h, TCSFM_E_ARG, "internal: the shared-pack form needs a window-form pack");
-    P.c_out3 = (ct && ct_depth3) ? 1 : 0;
-    for (int i = 0; i < TC_MAX_COAL; i++) P.c_depth_out3[i] = (ct && ct_depth3 && i < ct->ncall) ? ct_depth3[i] : nullptr;
-    if (wo) P.win_off = *wo; else P.win_off.on = 0;
-    memset(&P.init, 0, sizeof(P.init));
-    P.win_B = win_B; P.win_S = win_S;
-    if (init) {
-        // group tickets must be zero when k_linearize starts: zeroed at create, re-zeroed by the reducers after every launch;
-        // only a call that failed midway can leave them dirty
-        if (h->tickets_dirty) {
-            HIPCHK(h, hipMemsetAsync(h->tickets, 0, (size_t)h->max_pairs * h->ngrp_alloc * sizeof(int), h->stream));
-            h->tickets_dirty = false;
-        }
-        P.init = *init;
-    }
-    P.tgt = tgt; P.src = src; P.depth_t = dt; P.depth_s = ds;
-    P.tgtpack = h->tgtpack; P.srcpack = h->srcpack; P.depth_out = h->depth_work;
-    P.H = h->H; P.W = h->W; P.N = Nimg;
-    P.wl = o->w_l1 / 3.f; P.ws = o->w_ssim / 3.f;
-    P.depth_is_disp = o->depth_is_disp;
-    P.min_disp = o->depth_is_disp ? 1.f / o->max_depth : 0.f;
-    P.max_disp = o->depth_is_disp ? 1.f / o->min_depth : 0.f;
-    int hw = h->H * h->W;
-    if (ct ? Nimg != 2 * ct->cS * ct->ncall * ct->cB : (win_B > 0 && Nimg != 2 * win_S * win_B))
-        return fail(h, TCSFM_E_ARG, "internal: a window-form pack covers the 2 S B directed pairs of its windows");
-    {
-        ProfScope prof(h, 2);
-        // window forms: one row of workgroups per FORWARD pair, which packs its inverse too (pack_body)
-        const int rows = (ct || win_B > 0) ? Nimg / 2 : Nimg;
-        const unsigned ptiles = (unsigned)(((h->W + PT_W - 1) / PT_W) * ((h->H + PT_H - 1) / PT_H));       // 64 x 4 pixel tiles (pack_body)
-        if (ct) hipLaunchKernelGGL(k_pack_coal, dim3(ptiles, rows), dim3(256), 0, h->stream, P, *ct);
-        else hipLaunchKernelGGL(k_pack, dim3(ptiles, rows), dim3(256), 0, h->stream, P);
-    }
-    HIPCHK(h, hipGetLastError());
-    return TCSFM_OK;
-}
-
-int run_init(tcsfm_ctx *h, const tcsfm_opts *o, int N, const float *pose, const float *ls, const float *K, int shared) {
-    // group tickets must be zero when k_linearize starts; the reducers re-zero them, this covers an aborted earlier call
-    HIPCHK(h, hipMemsetAsync(h->tickets, 0, (size_t)h->max_pairs * h->ngrp_alloc * sizeof(int), h->stream));
-    InitParams I = init_params(h, o, N, pose, ls, K, shared);
-    hipLaunchKernelGGL(k_init, dim3((N + 63) / 64), dim3(64), 0, h->stream, I);
-    HIPCHK(h, hipGetLastError());
-    return TCSFM_OK;
-}
-
-// Small tile grids (KITTI 640x192: 240 workgroups per pair) skip the in-launch group reduction: the solve kernel sums the
-// workgroup records itself with all loads in flight (one batch of <= 32 per thread), which is cheaper than the
-// publish / ticket / last-arriver tail of every linearisation.  Larger grids keep the two-level reduction.
-int direct_records(const tcsfm_ctx *h) { return h->nblk <= 256; }
-
-LinParams lin_params(tcsfm_ctx *h, const tcsfm_opts *o, int np) {
-    LinParams P;
-    memset(&P, 0, sizeof(P));
-    P.tgtpack = h->tgtpack; P.srcpack = h->srcpack; P.depth_t = h->depth_work; P.pc = h->pconst; P.partials = h->partials; P.blockrec = h->blockrec; P.tickets = h->tickets;
-    P.H = h->H; P.W = h->W; P.tiles_x = h->tiles_x; P.tiles_y = h->tiles_y; P.nacc = nacc_of(np); P.ngrp = h->ngrp; P.ngrp_pad = h->ngrp_pad;
-    P.wl = o->w_l1 / 3.f; P.ws = o->w_ssim / 3.f; P.eps = o->irls_eps; P.automask = o->automask;
-    P.direct = direct_records(h);
-    return P;
-}
-
-SolveParams solve_params(tcsfm_ctx *h, const tcsfm_opts *o, int np, int shared) {
-    SolveParams S;
-    memset(&S, 0, sizeof(S));
-    S.partials = h->partials; S.st = h->state; S.pc = h->pconst; S.stats = nullptr; S.lin_out = h->lin_out;
-    S.ngrp = h->ngrp; S.nacc = nacc_of(np); S.np = np; S.has_dc = o->w_dc > 0.f;
-    if (direct_records(h)) { S.partials = h->blockrec; S.ngrp = h->nblk; }
-    S.n_iters = o->n_iters; S.solver = o->solver; S.param = o->param;
-    S.b_dc = (double)o->w_dc / ((double)h->H * (double)h->W);
-    S.lambda_up = o->lambda_up; S.lambda_down = o->lambda_down; S.lambda_min = o->lambda_min;
-    S.prior_scale = np == 7 ? (double)o->prior_scale : 0.0;
-    S.shared_image = shared;
-    S.dbg = h->dbg_stamps;
-    return S;
-}
-
 }  // namespace
+
+#include "pose_host.h"      // the pose modes: launch helpers, PoseDriver, pose_refine / pose_evaluate
 
 namespace {
 
@@ -726,20 +541,55 @@ __global__ __launch_bounds__(256) void k_dref_export_grho(const float *jrec, int
 
 #include "dense_host.h"
 
-// =================================================================================================
-// Entry points: include/tcsfm.h declares every one of them extern "C", so the definitions below have C linkage.
-static int flush_pending(tcsfm_ctx *h);
-static int join_coalesce_lanes(tcsfm_ctx *h);
-// Calls noted by the *_queued entry points are launched -- and the handle's stream ordered behind the merged sequences that ran on lanes --
-// before ANY other entry point puts work on the handle's stream, switches that stream or destroys the handle: a plain call never overtakes
-// a call queued before it (producers and consumers of the caller's pose / depth buffers keep their program order; include/tcsfm.h).
-static int drain_queued(tcsfm_ctx *h) {
-    if (!h || (h->pending.empty() && !h->coal_dirty)) return TCSFM_OK;
-    DeviceGuard dev_guard(h->device);
-    if (int rc = flush_pending(h)) return rc;
-    return join_coalesce_lanes(h);
+// shared body of tcsfm_refine_dense (win_B == 0), tcsfm_refine_dense_window and the merged sequence of queued dense calls (m: per-pair
+// Gauss-Newton form or reference loss only, every array comes per call from the tables and `a` is the first call's): the argument checks
+// and the staging; the launches are the three drivers' (dense_host.h)
+static int dense_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int win_S, const CallArgs &a, const WinOff *wo, bool depth_on_input = false,
+                      const MergedCalls *m = nullptr) {
+    int rc = check_common(h, o, N);
+    if (rc) return rc;
+    if (!a.tgt || !a.src || !a.depth_t || !a.depth_s || !a.pose_in || !a.pose_out || !a.depth_out || !a.K) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: NULL argument");
+    const bool ref_mode = win_B && o->window_rule == TCSFM_WINDOW_REFERENCE;      // the reference's own loss (dense_ref_kernel.h)
+    if (o->w_dc > 0.f && !ref_mode) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: w_dc must be 0 (use prior_depth), except under window_rule = TCSFM_WINDOW_REFERENCE");
+    if (ref_mode && (win_S > JMAXS || o->solver != TCSFM_SOLVER_GN || !(o->prior_init >= 0.f)))
+        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window: window_rule REFERENCE needs S <= 4, the Gauss-Newton solver and prior_init >= 0");
+    if (!(o->w_pose_consist >= 0.f) || (o->w_pose_consist > 0.f && (!ref_mode || o->param != TCSFM_PARAM_SE3)))
+        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: w_pose_consist needs the window form under window_rule = TCSFM_WINDOW_REFERENCE and the SE(3) chart");
+    if (o->free_source_depths != 0 && !ref_mode)
+        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: free_source_depths needs the window form under window_rule = TCSFM_WINDOW_REFERENCE");
+    if (!(o->w_smooth >= 0.f) || (o->w_smooth > 0.f && !ref_mode))
+        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: w_smooth needs the window form under window_rule = TCSFM_WINDOW_REFERENCE");
+    if (o->depth_param != TCSFM_DEPTH_FULL && !(o->depth_param == TCSFM_DEPTH_QUARTER && ref_mode && h->H % 4 == 0 && h->W % 4 == 0))
+        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: depth_param QUARTER needs window_rule = TCSFM_WINDOW_REFERENCE (window form) and H, W multiples of 4");
+    if (o->param != TCSFM_PARAM_SE3) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: SE(3) chart only");
+    if (!(o->min_depth > 0 && o->max_depth > o->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
+    Staging st(h, o);
+    if (st.rc) return st.rc;
+    const PosePlan pl = pose_plan_of(o, N, win_B, win_S, m);      // (the image sets and extents of a dense call are the pose call's)
+    if (!m && (rc = check_intrinsics(h, o, a.K, pl.nimg_t))) return rc;
+    const size_t hw = (size_t)h->H * h->W;
+    if (m && !ref_mode && (pl.n_sel || o->solver != TCSFM_SOLVER_GN || o->host_ptrs || o->n_iters < 1 || (o->dense_joint && win_S >= 2)))
+        return fail(h, TCSFM_E_ARG, "internal: only per-pair Gauss-Newton dense calls on device pointers are merged");
+    if (m && ref_mode && (o->host_ptrs || o->n_iters < 1 || a.stats_out)) return fail(h, TCSFM_E_ARG, "internal: merged reference-loss calls take device pointers and no statistics");
+    const float *d_tgt = st.in("tgt", a.tgt, pl.tgt(hw)), *d_src = st.in("src", a.src, pl.src(hw)), *d_dt = st.in("depth_t", a.depth_t, pl.depth_t(hw));
+    const float *d_ds = st.in("depth_s", a.depth_s, pl.depth_s(hw)), *d_K = st.in("K", a.K, pl.K()), *d_pose_in = st.in("pose_in", a.pose_in, pl.pose());
+    float *d_pose_out = st.out("pose_out", a.pose_out, pl.pose()), *d_depth_out = st.out("depth_out", a.depth_out, pl.maps(hw)), *d_stats = st.out("stats_out", a.stats_out, pl.stats());
+    if (st.ready(nullptr)) return st.rc;
+    if (d_stats) HIPCHK(h, hipMemsetAsync(d_stats, 0, pl.stats() * sizeof(float), h->stream));
+    const DenseCall c{h, o, win_B ? win_B : N, win_S, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, m ? &m->ct : nullptr, m ? m->pose_out : nullptr, m ? m->depth_out : nullptr, depth_on_input, nullptr};
+    if (ref_mode) rc = dense_ref_run(c);
+    // one depth map per target, 6S x 6S reduced system (joint_kernel.h); the library's own joint mode stays at S <= JMAXS_OWN = 3: wider windows
+    // there keep the per-pair depth copies of the pair form
+    else if (win_B && o->dense_joint && win_S >= 2 && win_S <= JMAXS_OWN) rc = dense_joint_run(c);
+    else rc = dense_pair_run(c);
+    if (rc) return rc;
+    return st.finish();
 }
 
+#include "call_host.h"      // the routing of the refine calls: graph replay, the queue of the *_queued entries, lanes
+
+// =================================================================================================
+// Entry points: include/tcsfm.h declares every one of them extern "C", so the definitions below have C linkage.
 void tcsfm_default_opts(tcsfm_opts *o) {
     memset(o, 0, sizeof(*o));
     o->n_iters = 4; o->solver = TCSFM_SOLVER_GN; o->param = TCSFM_PARAM_SE3; o->refine = TCSFM_REFINE_POSE;
@@ -771,7 +621,7 @@ int tcsfm_create(tcsfm_handle *out, int device, int H, int W, int max_pairs) {
         return TCSFM_E_ARG;
     }
     tcsfm_ctx *h = new tcsfm_ctx();
-    h->device = device; h->H = H; h->W = W; h->max_pairs = max_pairs;
+    h->device = device; h->H = H; h->W = W; h->max_pairs = h->queue.max_pairs = max_pairs;
     h->tiles_x = (W + TILE_W - 1) / TILE_W; h->tiles_y = (H + TILE_H - 1) / TILE_H;
     const DenseCaps &cp = h->caps = dense_caps(H, W, max_pairs);      // (dense_plan.h: the pose grid and what the record buffers below hold per pair)
     h->nblk = cp.nblk; h->ngrp = cp.ngrp; h->nblk_alloc = cp.nblk_alloc; h->ngrp_alloc = cp.ngrp_alloc; h->ngrp_pad = cp.ngrp_pad;
@@ -827,12 +677,7 @@ void tcsfm_destroy(tcsfm_handle h) {
     if (h->aux_fork) (void)hipEventDestroy(h->aux_fork);
     if (h->aux_join) (void)hipEventDestroy(h->aux_join);
     if (h->seq_pack) { (void)hipStreamSynchronize(h->seq_pack); (void)hipStreamDestroy(h->seq_pack); }
-    if (!h->graphs.empty()) {             // a replay may still be running: drain the streams it can be on before the executables go
-        if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
-        if (h->stream && h->stream != h->own_stream) (void)hipStreamSynchronize(h->stream);
-        for (auto &g : h->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        h->graphs.clear();
-    }
+    drop_graphs(h);                       // (a replay may still be running: it drains the streams one can be on before the executables go)
     for (auto &e : h->seq_copied) (void)hipEventDestroy(e);
     for (auto &e : h->seq_raw) (void)hipEventDestroy(e);
     for (auto &e : h->seq_done) (void)hipEventDestroy(e);
@@ -859,7 +704,7 @@ int tcsfm_set_stream(tcsfm_handle h, void *hip_stream) {
     if (!h) return TCSFM_E_ARG;
     if ((hipStream_t)hip_stream != h->stream)           // queued calls were noted while bound to the old stream: they run there, behind its producers
         if (int rc_q = drain_queued(h)) return rc_q;
-    if ((hipStream_t)hip_stream != h->stream && !h->graphs.empty()) {   // captured calls may still be running on the old stream, and a graph
+    if ((hipStream_t)hip_stream != h->stream && !h->graphs.entries.empty()) {   // captured calls may still be running on the old stream, and a graph
         DeviceGuard dev_guard(h->device);                              // captured there is not replayed on another producer's stream
         drop_graphs(h);
     }
@@ -1176,40 +1021,6 @@ int tcsfm_photometric(tcsfm_handle h, const tcsfm_opts *o, int N, const float *t
     return st.finish();
 }
 
-// shared by tcsfm_linearize and tcsfm_loss_surface: one evaluation at given poses, results to host doubles
-static int eval_once(tcsfm_ctx *h, const tcsfm_opts *o, int N, int Nimg, const float *d_tgt, const float *d_src, const float *d_dt,
-                     const float *d_ds, const float *d_pose, const float *d_ls, const float *d_K, int mode, std::vector<double> &host) {
-    int rc, np = np_of(o), shared = (Nimg == 1 && N > 1) ? 1 : 0;
-    if ((rc = run_pack(h, o, Nimg, d_tgt, d_src, d_dt, d_ds))) return rc;
-    if ((rc = run_init(h, o, N, d_pose, d_ls, d_K, shared))) return rc;
-    LinParams P = lin_params(h, o, np);
-    P.shared_image = shared;
-    if (mode == MODE_LIN && (rc = trace_lin_once(h, N, P))) return rc;      // (tcsfm_loss_surface records nothing)
-    launch_lin(h, P, N, np, o->w_dc > 0.f, mode);
-    HIPCHK(h, hipGetLastError());
-    SolveParams S = solve_params(h, o, np, shared);
-    S.mode = 2;
-    if (mode == MODE_COST) S.has_dc = 0;  // only the three scalar sums are live in cost mode
-    launch_solve(h, S, N, np);
-    HIPCHK(h, hipGetLastError());
-    int rec = np * np + np + 4;
-    host.resize((size_t)N * rec);
-    HIPCHK(h, hipMemcpyAsync(host.data(), h->lin_out, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return TCSFM_OK;
-}
-
-// the per-pair records of a linearisation (k_solve mode 2: H [np][np], g [np], 4 statistics) into the caller's arrays (each optional)
-static void unpack_lin_records(const std::vector<double> &host, int N, int np, double *Hmat, double *g, double *stats) {
-    const int rec = np * np + np + 4;
-    for (int n = 0; n < N; n++) {
-        const double *r = &host[(size_t)n * rec];
-        if (Hmat) memcpy(Hmat + (size_t)n * np * np, r, sizeof(double) * np * np);
-        if (g) memcpy(g + (size_t)n * np, r + np * np, sizeof(double) * np);
-        if (stats) memcpy(stats + (size_t)n * 4, r + np * np + np, sizeof(double) * 4);
-    }
-}
-
 int tcsfm_linearize(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *src, const float *depth_t,
                     const float *depth_s, const float *pose, const float *log_scale, const float *K, double *Hmat, double *g,
                     double *stats) {
@@ -1221,15 +1032,16 @@ int tcsfm_linearize(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt
     if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt = st.in("tgt", tgt, N * 3 * hw), *d_src = st.in("src", src, N * 3 * hw), *d_dt = st.in("depth_t", depth_t, N * hw), *d_ds = st.in("depth_s", depth_s, N * hw);
-    const float *d_pose = st.in("pose", pose, (size_t)N * 6), *d_K = st.in("K", K, (size_t)N * 9), *d_ls = st.in("log_scale", log_scale, (size_t)N);
+    PoseCall c{h, o, N, 0, 0};
+    c.tgt = st.in("tgt", tgt, N * 3 * hw); c.src = st.in("src", src, N * 3 * hw); c.dt = st.in("depth_t", depth_t, N * hw); c.ds = st.in("depth_s", depth_s, N * hw);
+    c.pose_in = st.in("pose", pose, (size_t)N * 6); c.K = st.in("K", K, (size_t)N * 9); c.ls_in = st.in("log_scale", log_scale, (size_t)N);
     {
         const size_t np_ = (size_t)np_of(o);
         st.host_out("Hmat", Hmat, N * np_ * np_ * sizeof(double)); st.host_out("g", g, N * np_ * sizeof(double)); st.host_out("stats", stats, (size_t)N * 4 * sizeof(double));
     }
     if (st.ready("tcsfm_linearize")) return st.rc;
     std::vector<double> host;
-    if ((rc = eval_once(h, o, N, N, d_tgt, d_src, d_dt, d_ds, d_pose, d_ls, d_K, MODE_LIN, host))) return rc;
+    if ((rc = pose_evaluate(c, N, MODE_LIN, host))) return rc;
     unpack_lin_records(host, N, np_of(o), Hmat, g, stats);
     return TCSFM_OK;
 }
@@ -1249,27 +1061,16 @@ int tcsfm_linearize_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, co
     if ((rc = check_intrinsics(h, o, K, B))) return rc;
     const size_t hw = (size_t)h->H * h->W;
     const int np = np_of(o);
-    const float *d_tgt = st.in("tgt", tgt, B * 3 * hw), *d_src = st.in("srcs", srcs, (size_t)B * S * 3 * hw), *d_dt = st.in("depth_t", depth_t, B * hw);
-    const float *d_ds = st.in("depth_s", depth_s, (size_t)B * S * hw), *d_K = st.in("K", K, (size_t)B * 9), *d_pose = st.in("pose", pose, (size_t)N * 6);
+    PoseCall c{h, o, N, B, S};
+    c.tgt = st.in("tgt", tgt, B * 3 * hw); c.src = st.in("srcs", srcs, (size_t)B * S * 3 * hw); c.dt = st.in("depth_t", depth_t, B * hw);
+    c.ds = st.in("depth_s", depth_s, (size_t)B * S * hw); c.K = st.in("K", K, (size_t)B * 9); c.pose_in = st.in("pose", pose, (size_t)N * 6);
     const float *d_ls = st.in("log_scale", log_scale, (size_t)N);
+    c.ls_in = np == 7 ? d_ls : nullptr;
     st.host_out("Hmat", Hmat, (size_t)N * np * np * sizeof(double)); st.host_out("g", g, (size_t)N * np * sizeof(double));
     st.host_out("stats", stats, (size_t)N * 4 * sizeof(double));
     if (st.ready("tcsfm_linearize_window")) return st.rc;
-    InitParams I = init_params(h, o, N, d_pose, np == 7 ? d_ls : nullptr, d_K, 0);
-    I.K_mod = B;
-    if ((rc = run_pack(h, o, N, d_tgt, d_src, d_dt, d_ds, &I, B, S))) return rc;
-    LinParams P = lin_params(h, o, np);
-    SolveParams Sv = solve_params(h, o, np, 0);
-    if (S > 1 && o->argmin) { P.sel_B = B; P.sel_S = S; }
-    apply_window_rule(h, o, B, S, N, P, Sv);
-    if ((rc = trace_lin_once(h, N, P))) return rc;
-    launch_lin(h, P, N, np, o->w_dc > 0.f, MODE_LIN);
-    Sv.mode = 2;
-    launch_solve(h, Sv, N, np);
-    HIPCHK(h, hipGetLastError());
-    std::vector<double> host((size_t)N * (np * np + np + 4));
-    HIPCHK(h, hipMemcpyAsync(host.data(), h->lin_out, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<double> host;
+    if ((rc = pose_evaluate(c, N, MODE_LIN, host))) return rc;
     unpack_lin_records(host, N, np, Hmat, g, stats);
     return TCSFM_OK;
 }
@@ -1284,234 +1085,27 @@ int tcsfm_loss_surface(tcsfm_handle h, const tcsfm_opts *o, const float *tgt, co
     if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, 1))) return rc;
     size_t hw = (size_t)h->H * h->W;
-    const float *d_tgt = st.in("tgt", tgt, 3 * hw), *d_src = st.in("src", src, 3 * hw), *d_dt = st.in("depth_t", depth_t, hw), *d_ds = st.in("depth_s", depth_s, hw);
-    const float *d_pose = st.in("poses", poses, (size_t)P * 6), *d_K = st.in("K", K, (size_t)9);
+    tcsfm_opts oo = *o;
+    oo.refine = TCSFM_REFINE_POSE;
+    PoseCall c{h, &oo, P, 0, 0};
+    c.tgt = st.in("tgt", tgt, 3 * hw); c.src = st.in("src", src, 3 * hw); c.dt = st.in("depth_t", depth_t, hw); c.ds = st.in("depth_s", depth_s, hw);
+    c.pose_in = st.in("poses", poses, (size_t)P * 6); c.K = st.in("K", K, (size_t)9); c.ls_in = nullptr;
     st.host_out("cost_out", cost_out, (size_t)P * sizeof(double));
     if (st.ready("tcsfm_loss_surface")) return st.rc;
     std::vector<double> host;
-    tcsfm_opts oo = *o;
-    oo.refine = TCSFM_REFINE_POSE;
-    if ((rc = eval_once(h, &oo, P, 1, d_tgt, d_src, d_dt, d_ds, d_pose, nullptr, d_K, MODE_COST, host))) return rc;
+    if ((rc = pose_evaluate(c, 1, MODE_COST, host))) return rc;
     const int rec = 6 * 6 + 6 + 4;
     for (int i = 0; i < P; i++) cost_out[i] = host[(size_t)i * rec + 42];
     return TCSFM_OK;
-}
-
-// The overlap contract (include/tcsfm.h) for the refine family, pose and dense modes, applied by every public form on its own behalf
-// before anything else happens (a graph replay and a queued call never reach the bodies' own staging with the caller's pointers).
-// Honoured: pose_out at pose_in, and the dense depth_out anywhere over depth_t / depth_s -- *depth_on_input then says so (device pointers).  Arguments the
-// later validation refuses (NULL handle or options, sizes out of range) are left to it.
-static int refine_overlap(tcsfm_ctx *h, const char *entry, const tcsfm_opts *o, int N, int win_B, int win_S, const float *tgt, const float *src,
-                          const float *depth_t, const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in,
-                          float *pose_out, float *log_scale_out, float *stats_out, float *depth_out, bool dense, bool *depth_on_input = nullptr) {
-    if (depth_on_input) *depth_on_input = false;
-    if (!h || !o || N < 1 || N > h->max_pairs || o->n_iters < 0 || o->n_iters > 1000) return TCSFM_OK;
-    const size_t hw = (size_t)h->H * h->W * sizeof(float), nt = win_B ? win_B : N, ns = win_B ? (size_t)win_B * win_S : N;
-    const bool scale = !dense && o->refine == TCSFM_REFINE_POSE_SCALE;
-    ArgRanges a;
-    a.io_free = o->host_ptrs != 0;
-    a.in("tgt", tgt, nt * 3 * hw); a.in(win_B ? "srcs" : "src", src, ns * 3 * hw); a.in("depth_t", depth_t, nt * hw); a.in("depth_s", depth_s, ns * hw);
-    a.in("K", K, nt * 9 * sizeof(float)); a.in("pose_in", pose_in, (size_t)N * 6 * sizeof(float));
-    if (scale) a.in("log_scale_in", log_scale_in, (size_t)N * sizeof(float));
-    a.out("pose_out", pose_out, (size_t)N * 6 * sizeof(float));
-    if (scale) a.out("log_scale_out", log_scale_out, (size_t)N * sizeof(float));
-    if (dense) a.out("depth_out", depth_out, (size_t)N * hw);
-    a.out("stats_out", stats_out, (size_t)N * (o->n_iters + 1) * TCSFM_NSTAT * sizeof(float));
-    a.bless("pose_out", "pose_in");
-    if (dense) { a.bless_any("depth_out", "depth_t"); a.bless_any("depth_out", "depth_s"); }
-    std::string msg;
-    if (a.refused(entry, msg)) return fail(h, TCSFM_E_ARG, msg.c_str());
-    // (staged host arrays land in the library's own, disjoint device buffers: nothing to avoid there)
-    if (depth_on_input) *depth_on_input = dense && !a.io_free && (a.overlap("depth_out", "depth_t") || a.overlap("depth_out", "depth_s"));
-    return TCSFM_OK;
-}
-
-// shared body of tcsfm_refine (win_B == 0: one image set per pair) and tcsfm_refine_window (win_B x win_S window)
-// frame-level pack cache of a sequence call (kernels.h k_frame_pack / k_pack_cached): the ring's packed frames, and where this call's windows start
-struct FrameCache { const float4 *fpack; const float *fdepth; int slot0, tpos; };
-
-static int refine_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int win_S, const float *tgt, const float *src,
-                       const float *depth_t, const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in,
-                       float *pose_out, float *log_scale_out, float *stats_out, const WinOff *wo, const FrameCache *fc,
-                       const CoalTab *ct = nullptr, float *const *ct_out = nullptr, float *const *ct_ls_out = nullptr) {
-    int rc = check_common(h, o, N);
-    if (rc) return rc;
-    if (ct) {        // coalesced calls (flush_pending): every array argument comes from the table; device pointers, validated at enqueue
-        tgt = ct->tgt[0]; src = ct->src[0]; depth_t = ct->dt[0]; depth_s = ct->ds[0]; K = ct->K[0]; pose_in = ct->pose[0]; pose_out = ct_out[0];
-    }
-    if (!tgt || !src || !depth_t || !depth_s || !pose_in || !pose_out || !K) return fail(h, TCSFM_E_ARG, "tcsfm_refine: NULL input");
-    Staging st(h, o);
-    if (st.rc) return st.rc;
-    const int nimg_t = ct ? ct->cB : (win_B ? win_B : N), nimg_s = ct ? ct->cB * ct->cS : (win_B ? win_B * win_S : N);   // image sets behind tgt / src
-    if (!ct && (rc = check_intrinsics(h, o, K, nimg_t))) return rc;
-    const size_t hw = (size_t)h->H * h->W;
-    const int np = np_of(o);
-    const float *d_tgt = st.in("tgt", tgt, nimg_t * 3 * hw), *d_src = st.in("src", src, nimg_s * 3 * hw), *d_dt = st.in("depth_t", depth_t, nimg_t * hw);
-    const float *d_ds = st.in("depth_s", depth_s, nimg_s * hw), *d_K = st.in("K", K, (size_t)nimg_t * 9), *d_pose_in = st.in("pose_in", pose_in, (size_t)N * 6);
-    const float *d_ls_in = st.in("log_scale_in", log_scale_in, (size_t)N);
-    const size_t nstats = (size_t)N * (o->n_iters + 1) * TCSFM_NSTAT;
-    float *d_pose_out = st.out("pose_out", pose_out, (size_t)N * 6), *d_ls_out = st.out("log_scale_out", np == 7 ? log_scale_out : nullptr, (size_t)N);
-    float *d_stats = st.out("stats_out", stats_out, nstats);
-    if (st.ready(nullptr)) return st.rc;
-    if (d_stats) HIPCHK(h, hipMemsetAsync(d_stats, 0, nstats * sizeof(float), h->stream));
-    // per-pixel min over the sources: the forward pairs also evaluate the other sources' residuals (k_linearize<SEL>)
-    const int n_sel = (win_B && win_S > 1 && o->argmin) ? win_B * win_S : 0;
-
-    InitParams I = init_params(h, o, N, d_pose_in, np == 7 ? d_ls_in : nullptr, d_K, 0);
-    I.K_mod = win_B;
-    LinParams P = lin_params(h, o, np);
-    if (fc) {      // sequence call: rgb + depth were packed once per frame when they landed; only the pair-specific part is formed here
-        if (h->tickets_dirty) {
-            HIPCHK(h, hipMemsetAsync(h->tickets, 0, (size_t)h->max_pairs * h->ngrp_alloc * sizeof(int), h->stream));
-            h->tickets_dirty = false;
-        }
-        PackCachedParams C;
-        C.fpack = fc->fpack; C.tgtpack = h->tgtpack; C.pair_src = h->pair_idx; C.pair_dep = h->pair_idx + h->max_pairs;
-        C.H = h->H; C.W = h->W; C.N = N; C.win_B = win_B; C.win_S = win_S; C.slot0 = fc->slot0; C.tpos = fc->tpos; C.win_off = *wo;
-        C.wl = o->w_l1 / 3.f; C.ws = o->w_ssim / 3.f; C.init = I;
-        {
-            ProfScope prof(h, 2);
-            hipLaunchKernelGGL(k_pack_cached, dim3((unsigned)((hw + 255) / 256), N / 2), dim3(256), 0, h->stream, C);      // (a row per forward pair)
-        }
-        HIPCHK(h, hipGetLastError());
-        P.srcpack = fc->fpack; P.depth_t = fc->fdepth; P.pair_src = C.pair_src; P.pair_dep = C.pair_dep;
-    } else {
-        // window forms: every image packed ONCE (LinParams::tshare, kernels.h) -- TCSFM_TSHARE=0 keeps the round-4 layout (A/B hook)
-        static const bool tshare_env = !(getenv("TCSFM_TSHARE") && atoi(getenv("TCSFM_TSHARE")) == 0);
-        const bool tshare = tshare_env && (win_B > 0 || ct != nullptr);
-        if ((rc = run_pack(h, o, N, d_tgt, d_src, d_dt, d_ds, &I, win_B, win_S, nullptr, wo, ct, nullptr, nullptr, 0, nullptr, tshare))) return rc;
-        if (tshare) { P.tshare = 1; P.tshare_sb = N / 2; }
-    }
-    SolveParams S = solve_params(h, o, np, 0);
-    S.stats = d_stats;
-    if (ct) {
-        S.c_ncall = ct->ncall; S.c_B = ct->cB; S.c_S = ct->cS;
-        for (int i = 0; i < ct->ncall; i++) { S.c_pose_out[i] = ct_out[i]; S.c_ls_out[i] = ct_ls_out ? ct_ls_out[i] : nullptr; }
-    }
-    const bool dc = o->w_dc > 0.f;
-    const bool lm = o->solver == TCSFM_SOLVER_LM;
-    if (n_sel) { P.sel_B = win_B; P.sel_S = win_S; }   // min over the sources: evaluated inside k_linearize<SEL>
-    apply_window_rule(h, o, win_B, win_S, N, P, S);
-    if ((rc = trace_check(h, o, N))) return rc;
-    for (int it = 0; it < o->n_iters; it++) {
-        trace_at(h, it, N, P, S);
-        launch_lin(h, P, N, np, dc, MODE_LIN);
-        S.it = it; S.mode = 0;
-        const bool last = !lm && it == o->n_iters - 1;   // the last solve also emits the refined pose
-        S.pose_out = last ? d_pose_out : nullptr; S.log_scale_out = last ? d_ls_out : nullptr;
-        launch_solve(h, S, N, np);
-    }
-    if (lm && o->n_iters > 0) {  // cost-only pass deciding whether the last step is kept
-        trace_at(h, o->n_iters, N, P, S);
-        launch_lin(h, P, N, np, dc, MODE_COST);
-        S.it = o->n_iters; S.mode = 1;
-        S.pose_out = d_pose_out; S.log_scale_out = d_ls_out;
-        launch_solve(h, S, N, np);
-    }
-    HIPCHK(h, hipGetLastError());
-    if (o->n_iters == 0) {  // nothing to solve: round-trip the pose through SE(3)
-        FinishParams F;
-        F.st = h->state; F.pose_out = d_pose_out; F.log_scale_out = d_ls_out; F.N = N;
-        hipLaunchKernelGGL(k_finish, dim3((N + 63) / 64), dim3(64), 0, h->stream, F);
-        HIPCHK(h, hipGetLastError());
-    }
-    return st.finish(o->host_ptrs == 1);   // host_ptrs == 2: pinned + asynchronous, the caller synchronises
-}
-
-// Graph replay (tcsfm_set_graph_replay).  A B = 1 refinement is nine short launches: ~42 us of host time against ~40 us of GPU time
-// per call with three calls in flight -- on a slow host the launches, not the kernels, set the rate.  A call whose arguments (options,
-// sizes, every pointer) equal those of an earlier call on this handle / lane is captured once (the second time it is seen: the first
-// run validates the intrinsics and allocates scratch, which a capture must not) and replayed with ONE hipGraphLaunch from then on.
-// The kernels, their order and their arguments are exactly those of the plain path (`body`): results are bit-identical.
-// kind: 0 pose refinement, 1 dense refinement (the joint dense mode, which forks its inverse pairs onto a second stream when it runs
-// plainly, keeps them on the captured stream: every graph is one chain of launches).
-template <class Body>
-static int replay_or_run(tcsfm_ctx *h, const tcsfm_opts *o, int kind, int N, int win_B, int win_S, const void *const *ptrs, const float *K,
-                         bool bypass, Body body) {
-    const bool eligible = h && o && h->graph_slots > 0 && !h->capturing && !o->host_ptrs && !bypass && !h->profiling && !h->trace_bits &&
-                          !h->trace_decide && !h->dbg_stamps && h->stream != nullptr;
-    if (!eligible) return body();
-    tcsfm_ctx::CallKey key;
-    memset(&key, 0, sizeof(key));
-    key.o = *o; key.N = N; key.win_B = win_B; key.win_S = win_S; key.pad = kind;
-    memcpy(key.p, ptrs, sizeof(key.p));
-    tcsfm_ctx::CallGraph *e = nullptr;
-    for (auto &g : h->graphs) if (!memcmp(&g.key, &key, sizeof(key))) { e = &g; break; }
-    if (e && e->exec) {                                    // replay
-        int rc = check_common(h, o, N);
-        if (rc) return rc;
-        DeviceGuard dev_guard(h->device);
-        if (int rc_ = pending_error(h)) return rc_;
-        e->used = ++h->graph_clock;
-        if (h->tickets_dirty) {                            // (a failed call may have left group tickets non-zero: what run_pack would do)
-            HIPCHK(h, hipMemsetAsync(h->tickets, 0, (size_t)h->max_pairs * h->ngrp_alloc * sizeof(int), h->stream));
-            h->tickets_dirty = false;
-        }
-        if (kind == 1) { if (int rc_ = dref_clean(h)) return rc_; }      // (what dense_ref_run does before its first launch)
-        HIPCHK(h, hipGraphLaunch(e->exec, h->stream));
-        h->graph_replays++;
-        return TCSFM_OK;
-    }
-    if (!e) {                                              // first sighting: plain run, remember the call
-        if ((int)h->graphs.size() >= h->graph_slots) {     // evict the least recently used entry
-            size_t lru = 0;
-            for (size_t i = 1; i < h->graphs.size(); i++) if (h->graphs[i].used < h->graphs[lru].used) lru = i;
-            if (h->graphs[lru].exec) { sync_graph_streams(h); (void)hipGraphExecDestroy(h->graphs[lru].exec); }      // (it may still be running)
-            h->graphs.erase(h->graphs.begin() + lru);
-        }
-        tcsfm_ctx::CallGraph g;
-        g.key = key; g.exec = nullptr; g.seen = 1; g.used = ++h->graph_clock;
-        h->graphs.push_back(g);
-        return body();
-    }
-    e->used = ++h->graph_clock;
-    const int nimg_t = win_B ? win_B : N;
-    if (e->seen != 1 || !k_known(h, K, nimg_t))           // marked uncapturable, or the intrinsics would be re-validated (a blocking copy)
-        return body();
-    {                                                      // second sighting: capture the plain path's launches
-        DeviceGuard dev_guard(h->device);
-        if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            e->seen = -1;
-            return body();
-        }
-        h->capturing = true;
-        const std::string err_before = h->err;
-        int rc = body();
-        h->capturing = false;
-        hipGraph_t graph = nullptr;
-        hipError_t ce = hipStreamEndCapture(h->stream, &graph);
-        hipGraphExec_t exec = nullptr;
-        if (rc == TCSFM_OK && ce == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-            (void)hipGraphDestroy(graph);
-            e->exec = exec;
-            h->graph_captures++;
-            HIPCHK(h, hipGraphLaunch(exec, h->stream));
-            return TCSFM_OK;
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-        (void)hipGetLastError();
-        e->seen = -1;                                      // not capturable in this configuration: plain launches from now on
-        h->err = err_before;
-    }
-    return body();
-}
-
-static int refine_impl(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int win_S, const float *tgt, const float *src,
-                       const float *depth_t, const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in,
-                       float *pose_out, float *log_scale_out, float *stats_out, const WinOff *wo = nullptr, const FrameCache *fc = nullptr) {
-    const void *ptrs[10] = {tgt, src, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out};
-    return replay_or_run(h, o, 0, N, win_B, win_S, ptrs, K, wo != nullptr || fc != nullptr, [&]() {
-        return refine_body(h, o, N, win_B, win_S, tgt, src, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out, wo, fc);
-    });
 }
 
 int tcsfm_refine(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *src, const float *depth_t,
                  const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in, float *pose_out,
                  float *log_scale_out, float *stats_out) {
     if (int rc_q = drain_queued(h)) return rc_q;
-    if (int rc_a = refine_overlap(h, "tcsfm_refine", o, N, 0, 0, tgt, src, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out, nullptr, false)) return rc_a;
-    return refine_impl(h, o, N, 0, 0, tgt, src, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out);
+    const CallArgs a{tgt, src, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, nullptr, stats_out};
+    if (int rc_a = refine_overlap(h, "tcsfm_refine", o, N, 0, 0, a, false)) return rc_a;
+    return refine_impl(h, o, N, 0, 0, a);
 }
 
 int tcsfm_refine_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
@@ -1520,8 +1114,9 @@ int tcsfm_refine_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const
     if (int rc_q = drain_queued(h)) return rc_q;
     if (!h) return TCSFM_E_ARG;
     if (B < 1 || S < 1 || (long long)2 * B * S > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_window: need 1 <= 2*B*S <= max_pairs");
-    if (int rc_a = refine_overlap(h, "tcsfm_refine_window", o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out, nullptr, false)) return rc_a;
-    return refine_impl(h, o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out);
+    const CallArgs a{tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, nullptr, stats_out};
+    if (int rc_a = refine_overlap(h, "tcsfm_refine_window", o, 2 * B * S, B, S, a, false)) return rc_a;
+    return refine_impl(h, o, 2 * B * S, B, S, a);
 }
 
 int tcsfm_scale_recovery(tcsfm_handle h, const tcsfm_opts *o, int N, const float *depth, const float *K, float real_cam_height,
@@ -1747,73 +1342,14 @@ int tcsfm_window_loss_backward(tcsfm_handle h, const tcsfm_opts *o, int B, int S
     return st.finish();
 }
 
-// shared body of tcsfm_refine_dense (win_B == 0) and tcsfm_refine_dense_window
-static int dense_body(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int win_S, const float *tgt, const float *src,
-                      const float *depth_t, const float *depth_s, const float *K, const float *pose_in, float *pose_out,
-                      float *depth_out, float *stats_out, const WinOff *wo, const CoalTab *ct = nullptr, float *const *ct_pose = nullptr,
-                      float *const *ct_depth = nullptr, bool depth_on_input = false) {
-    int rc = check_common(h, o, N);
-    if (rc) return rc;
-    if (ct) {        // coalesced dense calls (flush_pending): per-pair Gauss-Newton form only, every array argument comes from the table
-        tgt = ct->tgt[0]; src = ct->src[0]; depth_t = ct->dt[0]; depth_s = ct->ds[0]; K = ct->K[0]; pose_in = ct->pose[0];
-        pose_out = ct_pose[0]; depth_out = ct_depth[0];
-    }
-    if (!tgt || !src || !depth_t || !depth_s || !pose_in || !pose_out || !depth_out || !K) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: NULL argument");
-    const bool ref_mode = win_B && o->window_rule == TCSFM_WINDOW_REFERENCE;      // the reference's own loss (dense_ref_kernel.h)
-    if (o->w_dc > 0.f && !ref_mode) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: w_dc must be 0 (use prior_depth), except under window_rule = TCSFM_WINDOW_REFERENCE");
-    if (ref_mode && (win_S > JMAXS || o->solver != TCSFM_SOLVER_GN || !(o->prior_init >= 0.f)))
-        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window: window_rule REFERENCE needs S <= 4, the Gauss-Newton solver and prior_init >= 0");
-    if (!(o->w_pose_consist >= 0.f) || (o->w_pose_consist > 0.f && (!ref_mode || o->param != TCSFM_PARAM_SE3)))
-        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: w_pose_consist needs the window form under window_rule = TCSFM_WINDOW_REFERENCE and the SE(3) chart");
-    if (o->free_source_depths != 0 && !ref_mode)
-        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: free_source_depths needs the window form under window_rule = TCSFM_WINDOW_REFERENCE");
-    if (!(o->w_smooth >= 0.f) || (o->w_smooth > 0.f && !ref_mode))
-        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: w_smooth needs the window form under window_rule = TCSFM_WINDOW_REFERENCE");
-    if (o->depth_param != TCSFM_DEPTH_FULL && !(o->depth_param == TCSFM_DEPTH_QUARTER && ref_mode && h->H % 4 == 0 && h->W % 4 == 0))
-        return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: depth_param QUARTER needs window_rule = TCSFM_WINDOW_REFERENCE (window form) and H, W multiples of 4");
-    if (o->param != TCSFM_PARAM_SE3) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense: SE(3) chart only");
-    if (!(o->min_depth > 0 && o->max_depth > o->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
-    Staging st(h, o);
-    if (st.rc) return st.rc;
-    const int nimg_t = ct ? ct->cB : (win_B ? win_B : N), nimg_s = ct ? ct->cB * ct->cS : (win_B ? win_B * win_S : N);   // image sets behind tgt / src
-    if (!ct && (rc = check_intrinsics(h, o, K, nimg_t))) return rc;
-    const size_t hw = (size_t)h->H * h->W;
-    const int n_sel = (win_B && win_S > 1 && o->argmin) ? win_B * win_S : 0;
-    if (ct && !ref_mode && (n_sel || o->solver != TCSFM_SOLVER_GN || o->host_ptrs || o->n_iters < 1 || (o->dense_joint && win_S >= 2)))
-        return fail(h, TCSFM_E_ARG, "internal: only per-pair Gauss-Newton dense calls on device pointers are merged");
-    if (ct && ref_mode && (o->host_ptrs || o->n_iters < 1 || stats_out)) return fail(h, TCSFM_E_ARG, "internal: merged reference-loss calls take device pointers and no statistics");
-    const float *d_tgt = st.in("tgt", tgt, nimg_t * 3 * hw), *d_src = st.in("src", src, nimg_s * 3 * hw), *d_dt = st.in("depth_t", depth_t, nimg_t * hw);
-    const float *d_ds = st.in("depth_s", depth_s, nimg_s * hw), *d_K = st.in("K", K, (size_t)nimg_t * 9), *d_pose_in = st.in("pose_in", pose_in, (size_t)N * 6);
-    const size_t nstats = (size_t)N * (o->n_iters + 1) * TCSFM_NSTAT;
-    float *d_pose_out = st.out("pose_out", pose_out, (size_t)N * 6), *d_depth_out = st.out("depth_out", depth_out, N * hw), *d_stats = st.out("stats_out", stats_out, nstats);
-    if (st.ready(nullptr)) return st.rc;
-    if (d_stats) HIPCHK(h, hipMemsetAsync(d_stats, 0, nstats * sizeof(float), h->stream));
-    const DenseCall c{h, o, win_B ? win_B : N, win_S, d_tgt, d_src, d_dt, d_ds, d_K, d_pose_in, d_pose_out, d_depth_out, d_stats, wo, ct, ct_pose, ct_depth, depth_on_input, nullptr};
-    if (ref_mode) rc = dense_ref_run(c);
-    // one depth map per target, 6S x 6S reduced system (joint_kernel.h); the library's own joint mode stays at S <= JMAXS_OWN = 3: wider windows
-    // there keep the per-pair depth copies of the pair form
-    else if (win_B && o->dense_joint && win_S >= 2 && win_S <= JMAXS_OWN) rc = dense_joint_run(c);
-    else rc = dense_pair_run(c);
-    if (rc) return rc;
-    return st.finish();
-}
-
-static int dense_impl(tcsfm_handle h, const tcsfm_opts *o, int N, int win_B, int win_S, const float *tgt, const float *src,
-                      const float *depth_t, const float *depth_s, const float *K, const float *pose_in, float *pose_out,
-                      float *depth_out, float *stats_out, const WinOff *wo = nullptr, bool depth_on_input = false) {
-    const void *ptrs[10] = {tgt, src, depth_t, depth_s, K, pose_in, nullptr, pose_out, depth_out, stats_out};
-    return replay_or_run(h, o, 1, N, win_B, win_S, ptrs, K, wo != nullptr, [&]() {
-        return dense_body(h, o, N, win_B, win_S, tgt, src, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out, wo, nullptr, nullptr, nullptr, depth_on_input);
-    });
-}
-
 int tcsfm_refine_dense(tcsfm_handle h, const tcsfm_opts *o, int N, const float *tgt, const float *src, const float *depth_t,
                        const float *depth_s, const float *K, const float *pose_in, float *pose_out, float *depth_out,
                        float *stats_out) {
     if (int rc_q = drain_queued(h)) return rc_q;
+    const CallArgs a{tgt, src, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr, depth_out, stats_out};
     bool on_input = false;
-    if (int rc_a = refine_overlap(h, "tcsfm_refine_dense", o, N, 0, 0, tgt, src, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr, stats_out, depth_out, true, &on_input)) return rc_a;
-    return dense_impl(h, o, N, 0, 0, tgt, src, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out, nullptr, on_input);
+    if (int rc_a = refine_overlap(h, "tcsfm_refine_dense", o, N, 0, 0, a, true, &on_input)) return rc_a;
+    return dense_impl(h, o, N, 0, 0, a, nullptr, on_input);
 }
 
 int tcsfm_refine_dense_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
@@ -1822,183 +1358,10 @@ int tcsfm_refine_dense_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S,
     if (int rc_q = drain_queued(h)) return rc_q;
     if (!h) return TCSFM_E_ARG;
     if (B < 1 || S < 1 || (long long)2 * B * S > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window: need 1 <= 2*B*S <= max_pairs");
+    const CallArgs a{tgt, srcs, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr, depth_out, stats_out};
     bool on_input = false;
-    if (int rc_a = refine_overlap(h, "tcsfm_refine_dense_window", o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr, stats_out, depth_out, true, &on_input)) return rc_a;
-    return dense_impl(h, o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out, nullptr, on_input);
-}
-
-// ---- coalesced calls: queued B-window calls of one shape as ONE launch sequence (include/tcsfm.h)
-// the handle's stream is ordered behind the merged sequences that ran on lanes (consumers queued on it see their poses)
-static int join_coalesce_lanes(tcsfm_ctx *h) {
-    for (int l = 1; l <= (int)h->lanes.size() && h->coal_dirty; l++)
-        if (h->coal_dirty & (1u << l)) {
-            HIPCHK(h, hipStreamWaitEvent(h->stream, h->lanes[l - 1]->done_ev, 0));
-            h->coal_dirty &= ~(1u << l);
-        }
-    return TCSFM_OK;
-}
-
-static int flush_pending(tcsfm_ctx *h) {
-    if (h->pending.empty()) return TCSFM_OK;
-    std::vector<tcsfm_ctx::PendingCall> calls;
-    calls.swap(h->pending);
-    const tcsfm_opts o = h->pend_opts;
-    const int B = h->pend_B, S = h->pend_S, n = (int)calls.size();
-    // merged sequences alternate over coal_lanes streams (tcsfm_set_coalesce_lanes): sequence k runs on lane k mod coal_lanes, behind
-    // everything queued on the handle's stream so far; the short tail kernels of one sequence (k_solve: 20 workgroups, 6 us) then
-    // overlap the other's chip-filling launches.  tcsfm_flush / tcsfm_synchronize order the handle's stream behind them.
-    const int nl = h->lanes_serial ? 1 : std::min(h->coal_lanes, (int)h->lanes.size() + 1), l = nl > 1 ? h->coal_batches % nl : 0;
-    tcsfm_ctx *c = l == 0 ? h : h->lanes[l - 1];
-    h->coal_batches++; h->coal_calls += n;
-    if (c != h) {
-        HIPCHK(h, hipEventRecord(c->in_ev, h->stream));
-        HIPCHK(h, hipStreamWaitEvent(c->own_stream, c->in_ev, 0));
-        c->stream = c->own_stream;
-    }
-    int rc;
-    const bool dense = h->pend_dense != 0;
-    if (n == 1) {
-        const auto &q = calls[0];
-        rc = dense ? dense_impl(c, &o, 2 * B * S, B, S, q.tgt, q.srcs, q.dt, q.ds, q.K, q.pose_in, q.pose_out, q.depth_out, nullptr)
-                   : refine_impl(c, &o, 2 * B * S, B, S, q.tgt, q.srcs, q.dt, q.ds, q.K, q.pose_in, q.ls_in, q.pose_out, q.ls_out, nullptr);
-    } else if (dense) {
-        CoalTab ct;
-        memset(&ct, 0, sizeof(ct));
-        ct.ncall = n; ct.cB = B; ct.cS = S;
-        float *outs[TC_MAX_COAL], *douts[TC_MAX_COAL];
-        for (int i = 0; i < n; i++) {
-            ct.tgt[i] = calls[i].tgt; ct.src[i] = calls[i].srcs; ct.dt[i] = calls[i].dt; ct.ds[i] = calls[i].ds; ct.K[i] = calls[i].K; ct.pose[i] = calls[i].pose_in;
-            outs[i] = calls[i].pose_out; douts[i] = calls[i].depth_out;
-        }
-        rc = dense_body(c, &o, 2 * B * S * n, B * n, S, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ct, outs, douts);
-    } else {
-        CoalTab ct;
-        memset(&ct, 0, sizeof(ct));
-        ct.ncall = n; ct.cB = B; ct.cS = S;
-        float *outs[TC_MAX_COAL];
-        for (int i = 0; i < n; i++) {
-            ct.tgt[i] = calls[i].tgt; ct.src[i] = calls[i].srcs; ct.dt[i] = calls[i].dt; ct.ds[i] = calls[i].ds; ct.K[i] = calls[i].K; ct.pose[i] = calls[i].pose_in;
-            outs[i] = calls[i].pose_out;
-        }
-        float *louts[TC_MAX_COAL];
-        for (int i = 0; i < n; i++) { ct.ls[i] = calls[i].ls_in; louts[i] = calls[i].ls_out; }
-        rc = refine_body(c, &o, 2 * B * S * n, B * n, S, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ct, outs, louts);
-    }
-    if (c != h) {
-        if (rc) { h->err = c->err; return rc; }
-        HIPCHK(h, hipEventRecord(c->done_ev, c->own_stream));
-        h->coal_dirty |= 1u << l;
-    }
-    return rc;
-}
-
-int tcsfm_set_coalesce(tcsfm_handle h, int max_calls) {
-    if (!h) return TCSFM_E_ARG;
-    if (max_calls < 0 || max_calls > TC_MAX_COAL) return fail(h, TCSFM_E_ARG, "tcsfm_set_coalesce: 0 <= max_calls <= 16");
-    int rc = flush_pending(h);
-    h->coal_max = max_calls;
-    return rc;
-}
-
-int tcsfm_set_coalesce_lanes(tcsfm_handle h, int n_streams) {
-    if (!h) return TCSFM_E_ARG;
-    if (n_streams < 1 || n_streams > (int)h->lanes.size() + 1) return fail(h, TCSFM_E_ARG, "tcsfm_set_coalesce_lanes: 1 <= n_streams <= lanes of the handle (tcsfm_set_lanes)");
-    DeviceGuard dev_guard(h->device);
-    int rc = flush_pending(h);
-    if (!rc) rc = join_coalesce_lanes(h);
-    h->coal_lanes = n_streams;
-    return rc;
-}
-
-int tcsfm_flush(tcsfm_handle h) {
-    if (!h) return TCSFM_E_ARG;
-    DeviceGuard dev_guard(h->device);
-    int rc = flush_pending(h);
-    return rc ? rc : join_coalesce_lanes(h);
-}
-
-int tcsfm_coalesce_counts(tcsfm_handle h, int *batches, int *calls) {
-    if (!h) return TCSFM_E_ARG;
-    if (batches) *batches = h->coal_batches;
-    if (calls) *calls = h->coal_calls;
-    return TCSFM_OK;
-}
-
-static int refine_window_queued(tcsfm_handle h, const char *entry, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
-                                const float *depth_t, const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in,
-                                float *pose_out, float *log_scale_out);
-
-int tcsfm_refine_window_queued(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs, const float *depth_t,
-                               const float *depth_s, const float *K, const float *pose_in, float *pose_out) {
-    return refine_window_queued(h, "tcsfm_refine_window_queued", o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr);
-}
-
-int tcsfm_refine_window_scale_queued(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs, const float *depth_t,
-                                     const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in, float *pose_out,
-                                     float *log_scale_out) {
-    return refine_window_queued(h, "tcsfm_refine_window_scale_queued", o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out);
-}
-
-static int refine_window_queued(tcsfm_handle h, const char *entry, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
-                                const float *depth_t, const float *depth_s, const float *K, const float *pose_in, const float *log_scale_in,
-                                float *pose_out, float *log_scale_out) {
-    if (!h) return TCSFM_E_ARG;
-    if (B < 1 || S < 1 || (long long)2 * B * S > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_window_queued: need 1 <= 2*B*S <= max_pairs");
-    int rc = check_common(h, o, 2 * B * S);
-    if (rc) return rc;
-    if (!tgt || !srcs || !depth_t || !depth_s || !K || !pose_in || !pose_out) return fail(h, TCSFM_E_ARG, "tcsfm_refine_window_queued: NULL argument");
-    if (o->host_ptrs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_window_queued: device pointers only");
-    if (o->refine != TCSFM_REFINE_POSE_SCALE) { log_scale_in = nullptr; log_scale_out = nullptr; }
-    if ((rc = refine_overlap(h, entry, o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, nullptr, nullptr, false))) return rc;
-    // the REFERENCE rule couples the windows of a call through its batch normalisers: such calls are never merged with others
-    // (a profile session does not stop the merging: the merged launches are bracketed like any other -- bench.py's roofline.timed_mode)
-    const bool mergeable = h->coal_max > 1 && o->window_rule == TCSFM_WINDOW_PAIR && !h->trace_bits && !h->trace_decide;
-    DeviceGuard dev_guard(h->device);
-    if ((rc = check_intrinsics(h, o, K, B))) return rc;            // (blocking only the first time a pointer is seen)
-    if (!h->pending.empty() && (h->pend_dense || memcmp(&h->pend_opts, o, sizeof(*o)) != 0 || h->pend_B != B || h->pend_S != S ||
-                                (long long)2 * B * S * ((long long)h->pending.size() + 1) > h->max_pairs))
-        if ((rc = flush_pending(h))) return rc;
-    h->pend_opts = *o; h->pend_B = B; h->pend_S = S; h->pend_dense = 0;
-    h->pending.push_back({tgt, srcs, depth_t, depth_s, K, pose_in, pose_out, nullptr, log_scale_in, log_scale_out});
-    if (!mergeable || (int)h->pending.size() >= h->coal_max || (long long)2 * B * S * ((long long)h->pending.size() + 1) > h->max_pairs)
-        return flush_pending(h);
-    return TCSFM_OK;
-}
-
-// the dense counterpart of tcsfm_refine_window_queued: per-pair Gauss-Newton dense calls with ONE source per target are merged (k_pack_coal,
-// per-call pose and depth outputs through the pointer table); every other dense call flushes what is waiting and runs at once
-int tcsfm_refine_dense_window_queued(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs, const float *depth_t,
-                                     const float *depth_s, const float *K, const float *pose_in, float *pose_out, float *depth_out) {
-    if (!h) return TCSFM_E_ARG;
-    if (B < 1 || S < 1 || (long long)2 * B * S > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window_queued: need 1 <= 2*B*S <= max_pairs");
-    int rc = check_common(h, o, 2 * B * S);
-    if (rc) return rc;
-    if (!tgt || !srcs || !depth_t || !depth_s || !K || !pose_in || !pose_out || !depth_out) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window_queued: NULL argument");
-    if (o->host_ptrs) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window_queued: device pointers only");
-    const bool plain = h->coal_max > 1 && o->solver == TCSFM_SOLVER_GN && o->n_iters >= 1 && o->param == TCSFM_PARAM_SE3 && !h->trace_bits && !h->trace_decide;
-    // (round 5) the reference-loss mode with fixed source maps merges too: every call is a normaliser group of its own inside the merged sequence
-    const bool merge_ref = plain && o->window_rule == TCSFM_WINDOW_REFERENCE && S <= JMAXS && o->free_source_depths == 0 && o->prior_init >= 0.f && o->w_smooth >= 0.f &&
-                           o->w_pose_consist == 0.f && (o->depth_param == TCSFM_DEPTH_FULL || (o->depth_param == TCSFM_DEPTH_QUARTER && h->H % 4 == 0 && h->W % 4 == 0)) &&
-                           o->min_depth > 0 && o->max_depth > o->min_depth;
-    // a call whose depth_out lies on its own depth inputs is honoured by the path that writes depth_out last: it is not merged
-    bool depth_on_input = false;
-    if ((rc = refine_overlap(h, "tcsfm_refine_dense_window_queued", o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr, nullptr,
-                             depth_out, true, &depth_on_input))) return rc;
-    const bool mergeable = !depth_on_input && (merge_ref || (plain && S == 1 && o->window_rule == TCSFM_WINDOW_PAIR && o->w_dc == 0.f));
-    DeviceGuard dev_guard(h->device);
-    if (!mergeable) {
-        if ((rc = flush_pending(h))) return rc;
-        return tcsfm_refine_dense_window(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, pose_out, depth_out, nullptr);
-    }
-    if ((rc = check_intrinsics(h, o, K, B))) return rc;            // (blocking only the first time a pointer is seen)
-    if (!h->pending.empty() && (!h->pend_dense || memcmp(&h->pend_opts, o, sizeof(*o)) != 0 || h->pend_B != B || h->pend_S != S ||
-                                (long long)2 * B * S * ((long long)h->pending.size() + 1) > h->max_pairs))
-        if ((rc = flush_pending(h))) return rc;
-    h->pend_opts = *o; h->pend_B = B; h->pend_S = S; h->pend_dense = 1;
-    h->pending.push_back({tgt, srcs, depth_t, depth_s, K, pose_in, pose_out, depth_out, nullptr, nullptr});
-    if ((int)h->pending.size() >= h->coal_max || (long long)2 * B * S * ((long long)h->pending.size() + 1) > h->max_pairs)
-        return flush_pending(h);
-    return TCSFM_OK;
+    if (int rc_a = refine_overlap(h, "tcsfm_refine_dense_window", o, 2 * B * S, B, S, a, true, &on_input)) return rc_a;
+    return dense_impl(h, o, 2 * B * S, B, S, a, nullptr, on_input);
 }
 
 static int linearize_dense_window_impl(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
@@ -2039,68 +1402,6 @@ int tcsfm_linearize_dense_window_sources(tcsfm_handle h, const tcsfm_opts *o, in
                                          double *scal_out, double *g_pose_out, float *g_rho_out, float *g_rho_src_out) {
     if (!g_rho_src_out) return h ? fail(h, TCSFM_E_ARG, "tcsfm_linearize_dense_window_sources: NULL argument") : TCSFM_E_ARG;
     return linearize_dense_window_impl(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose, depth0, scal_out, g_pose_out, g_rho_out, g_rho_src_out, "tcsfm_linearize_dense_window_sources");
-}
-
-// ---- lane self-probe.  MEASURED HAZARD (round 4): how well the streams of a process run side by side depends on the order
-// in which the process created them -- a handle created before the process's first device work gave four lanes that were SLOWER than one
-// (10 k against 13.5 k frame-pairs/s; kernels of overlapping lanes 40-55 us instead of 11).  The mechanism inside the runtime was not
-// identified, so the library measures the real thing: B = 1 refinements (the handle's own kernels, 4 Gauss-Newton iterations) on stand-in
-// images, first one after the other on the handle's stream, then round-robin over all lanes -- a stand-in kernel on two streams does NOT
-// show the state (it overlapped fine in a process whose four lanes ran at 0.72 of one: the first version of this probe).  Lanes that do
-// not beat one stream are switched off: their calls run on the handle's own stream.  ~5 ms, once per tcsfm_set_lanes.
-static int probe_lanes(tcsfm_ctx *h) {
-    h->lanes_serial = false;
-    h->lane_probe[0] = h->lane_probe[1] = 0.f;
-    if (h->lanes.empty()) return TCSFM_OK;
-    if (const char *e = getenv("TCSFM_LANE_PROBE")) { if (atoi(e) == 0) return TCSFM_OK; }
-    const size_t hw = (size_t)h->H * h->W;
-    const int L = (int)h->lanes.size() + 1;
-    float *buf = nullptr;                                       // tgt | src [3 H W each], depth_t | depth_s [H W each], K [9], pose in [12], pose out [L][12]
-    const size_t nfl = 8 * hw + 9 + 12 + (size_t)L * 12;
-    HIPCHK(h, hipMalloc((void **)&buf, nfl * sizeof(float)));
-    float *tgt = buf, *src = buf + 3 * hw, *dt = buf + 6 * hw, *ds = buf + 7 * hw, *K = buf + 8 * hw, *pin = K + 9, *pout = pin + 12;
-    {
-        std::vector<float> img(8 * hw);
-        for (size_t i = 0; i < 6 * hw; i++) { const size_t p = i % hw; img[i] = 0.5f + 0.25f * sinf(0.05f * (float)(p % h->W) + 0.3f * (float)(i / hw)) * cosf(0.07f * (float)(p / h->W)); }
-        for (size_t i = 6 * hw; i < 8 * hw; i++) img[i] = 0.5f + 0.001f * (float)((i % hw) / h->W);
-        const float Kh[9] = {0.58f * h->W, 0.f, 0.5f * h->W, 0.f, 1.9f * h->H, 0.5f * h->H, 0.f, 0.f, 1.f};
-        const float ph[12] = {0.002f, -0.001f, -0.03f, 0.001f, -0.002f, 0.0005f, -0.002f, 0.001f, 0.03f, -0.001f, 0.002f, -0.0005f};
-        HIPCHK(h, hipMemcpy(buf, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(K, Kh, sizeof(Kh), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(pin, ph, sizeof(ph), hipMemcpyHostToDevice));
-    }
-    tcsfm_opts o; tcsfm_default_opts(&o);
-    hipStream_t keep = h->stream;
-    h->stream = h->own_stream;
-    int rc = TCSFM_OK;
-    auto run = [&](int nl, int calls, float *ms) -> int {
-        for (int pass = 0; pass < 2 && !rc; pass++) {           // (first pass: warm-up -- scratch allocations, intrinsics check)
-            HIPCHK(h, hipDeviceSynchronize());
-            const auto t0 = std::chrono::steady_clock::now();
-            for (int k = 0; k < calls && !rc; k++)
-                rc = tcsfm_refine_window_async(h, k % nl, &o, 1, 1, tgt, src, dt, ds, K, pin, nullptr, pout + (size_t)(k % nl) * 12, nullptr, nullptr);
-            HIPCHK(h, hipDeviceSynchronize());
-            *ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        }
-        return rc;
-    };
-    const int calls = 24;
-    if (h->max_pairs >= 2) {
-        rc = run(1, calls, &h->lane_probe[0]);
-        if (!rc) rc = run(L, calls, &h->lane_probe[1]);
-    }
-    h->stream = keep;
-    (void)hipFree(buf);
-    k_forget(h);
-    for (tcsfm_ctx *c : h->lanes) k_forget(c);
-    if (rc) return rc;
-    if (h->lane_probe[1] > 0.95f * h->lane_probe[0] && h->lane_probe[0] > 0.f) {
-        h->lanes_serial = true;
-        fprintf(stderr, "tcsfm: lanes do not overlap in this process (probe: %d B=1 refinements take %.0f us on one stream, %.0f us over %d lanes): lane "
-                        "calls run on the handle's own stream; use the queued calls (tcsfm_set_coalesce) to keep the chip busy\n", calls,
-                h->lane_probe[0] * 1e3, h->lane_probe[1] * 1e3, L);
-    }
-    return TCSFM_OK;
 }
 
 int tcsfm_debug_check_guards(int *n_allocations, int *n_damaged) {
@@ -2145,102 +1446,6 @@ int tcsfm_debug_guard_selftest(int *detected) {
     (void)hipFree(q);
     (void)hipFree(p);
     if (detected) *detected = found;
-    return TCSFM_OK;
-}
-
-int tcsfm_lane_probe(tcsfm_handle h, int *serial, float *one_stream_ms, float *two_streams_ms) {
-    if (!h) return TCSFM_E_ARG;
-    if (serial) *serial = h->lanes_serial ? 1 : 0;
-    if (one_stream_ms) *one_stream_ms = h->lane_probe[0];
-    if (two_streams_ms) *two_streams_ms = h->lane_probe[1];
-    return TCSFM_OK;
-}
-
-int tcsfm_set_lanes(tcsfm_handle h, int n_lanes) {
-    if (!h) return TCSFM_E_ARG;
-    if (n_lanes < 1 || n_lanes > 8) return fail(h, TCSFM_E_ARG, "tcsfm_set_lanes: 1 <= n_lanes <= 8");
-    DeviceGuard dev_guard(h->device);
-    if (int rc_ = flush_pending(h)) return rc_;
-    if (int rc_ = join_coalesce_lanes(h)) return rc_;
-    if ((int)h->lanes.size() + 1 > n_lanes) HIPCHK(h, hipStreamSynchronize(h->stream));     // (a lane about to go may still run a merged sequence)
-    while ((int)h->lanes.size() + 1 > n_lanes) { tcsfm_destroy(h->lanes.back()); h->lanes.pop_back(); }
-    h->coal_lanes = std::min(h->coal_lanes, n_lanes);
-    while ((int)h->lanes.size() + 1 < n_lanes) {
-        tcsfm_ctx *c = nullptr;
-        int rc = tcsfm_create(&c, h->device, h->H, h->W, h->max_pairs);
-        if (rc) return fail(h, rc, "tcsfm_set_lanes: could not create a lane");
-        hipError_t e = hipEventCreateWithFlags(&c->in_ev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming);
-        if (e != hipSuccess) { tcsfm_destroy(c); return fail(h, TCSFM_E_HIP, "tcsfm_set_lanes: hipEventCreate failed"); }
-        c->graph_slots = h->graph_slots;
-        h->lanes.push_back(c);
-    }
-    return probe_lanes(h);
-}
-
-int tcsfm_set_graph_replay(tcsfm_handle h, int max_graphs) {
-    if (!h) return TCSFM_E_ARG;
-    if (max_graphs < 0 || max_graphs > 64) return fail(h, TCSFM_E_ARG, "tcsfm_set_graph_replay: 0 <= max_graphs <= 64");
-    DeviceGuard dev_guard(h->device);
-    h->graph_slots = max_graphs;
-    if ((int)h->graphs.size() > max_graphs) drop_graphs(h);
-    for (tcsfm_ctx *c : h->lanes) { c->graph_slots = max_graphs; if ((int)c->graphs.size() > max_graphs) drop_graphs(c); }
-    return TCSFM_OK;
-}
-
-int tcsfm_graph_replay_counts(tcsfm_handle h, int *captures, int *replays) {
-    if (!h) return TCSFM_E_ARG;
-    int c_ = h->graph_captures, r_ = h->graph_replays;
-    for (tcsfm_ctx *c : h->lanes) { c_ += c->graph_captures; r_ += c->graph_replays; }
-    if (captures) *captures = c_;
-    if (replays) *replays = r_;
-    return TCSFM_OK;
-}
-
-static tcsfm_ctx *lane_of(tcsfm_ctx *h, int lane) {
-    if (!h || lane < 0 || lane > (int)h->lanes.size()) return nullptr;
-    return lane == 0 ? h : h->lanes[lane - 1];
-}
-
-int tcsfm_refine_window_async(tcsfm_handle h, int lane, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
-                              const float *depth_t, const float *depth_s, const float *K, const float *pose_in,
-                              const float *log_scale_in, float *pose_out, float *log_scale_out, float *stats_out) {
-    if (int rc_q = drain_queued(h)) return rc_q;
-    tcsfm_ctx *c = lane_of(h, lane);
-    if (!c) return h ? fail(h, TCSFM_E_ARG, "tcsfm_refine_window_async: no such lane (tcsfm_set_lanes)") : TCSFM_E_ARG;
-    if (o && o->host_ptrs == 1) return fail(h, TCSFM_E_ARG, "tcsfm_refine_window_async: host_ptrs must be 0 (device) or 2 (pinned host, asynchronous)");
-    if (B >= 1 && S >= 1 && (long long)2 * B * S <= h->max_pairs)
-        if (int rc_a = refine_overlap(h, "tcsfm_refine_window_async", o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out, nullptr, false)) return rc_a;
-    if (c == h || h->lanes_serial) return tcsfm_refine_window(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out);
-    DeviceGuard dev_guard(h->device);
-    // the lane starts behind everything queued on the parent's stream so far (the producers of the caller's device buffers) ...
-    HIPCHK(h, hipEventRecord(c->in_ev, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(c->own_stream, c->in_ev, 0));
-    c->stream = c->own_stream;
-    int rc = tcsfm_refine_window(c, o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, log_scale_in, pose_out, log_scale_out, stats_out);
-    if (rc) { h->err = c->err; return rc; }
-    // ... and marks its end for tcsfm_lane_wait / tcsfm_lane_synchronize
-    HIPCHK(h, hipEventRecord(c->done_ev, c->own_stream));
-    return TCSFM_OK;
-}
-
-int tcsfm_refine_dense_window_async(tcsfm_handle h, int lane, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
-                                    const float *depth_t, const float *depth_s, const float *K, const float *pose_in, float *pose_out,
-                                    float *depth_out, float *stats_out) {
-    if (int rc_q = drain_queued(h)) return rc_q;
-    tcsfm_ctx *c = lane_of(h, lane);
-    if (!c) return h ? fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window_async: no such lane (tcsfm_set_lanes)") : TCSFM_E_ARG;
-    if (o && o->host_ptrs == 1) return fail(h, TCSFM_E_ARG, "tcsfm_refine_dense_window_async: host_ptrs must be 0 (device) or 2 (pinned host, asynchronous)");
-    if (B >= 1 && S >= 1 && (long long)2 * B * S <= h->max_pairs)
-        if (int rc_a = refine_overlap(h, "tcsfm_refine_dense_window_async", o, 2 * B * S, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, nullptr, pose_out, nullptr, stats_out, depth_out, true)) return rc_a;
-    if (c == h || h->lanes_serial) return tcsfm_refine_dense_window(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out);
-    DeviceGuard dev_guard(h->device);
-    HIPCHK(h, hipEventRecord(c->in_ev, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(c->own_stream, c->in_ev, 0));
-    c->stream = c->own_stream;
-    int rc = tcsfm_refine_dense_window(c, o, B, S, tgt, srcs, depth_t, depth_s, K, pose_in, pose_out, depth_out, stats_out);
-    if (rc) { h->err = c->err; return rc; }
-    HIPCHK(h, hipEventRecord(c->done_ev, c->own_stream));
     return TCSFM_OK;
 }
 
