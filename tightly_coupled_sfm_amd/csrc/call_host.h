@@ -2,7 +2,7 @@
 // tcsfm_set_lanes and the *_async entries).  Every rule -- what is captured, replayed and evicted, when queued calls run and which of
 // them merge, which lane a merged sequence takes -- is call_plan.h's (no HIP there); here is what is done about it: the capture, the
 // events, the launches through pose_refine (pose_host.h) and dense_body.  Part of tcsfm_api.hip, the library's only translation unit:
-// included after dense_host.h and dense_body, before the entry points.
+// included after context.h, dense_host.h and dense_body, before the entry points.
 #pragma once
 #include "call_plan.h"
 
@@ -244,9 +244,9 @@ static int probe_lanes(tcsfm_ctx *h) {
     if (const char *e = getenv("TCSFM_LANE_PROBE")) { if (atoi(e) == 0) return TCSFM_OK; }
     const size_t hw = (size_t)h->H * h->W;
     const int L = (int)h->lanes.size() + 1;
-    float *buf = nullptr;                                       // tgt | src [3 H W each], depth_t | depth_s [H W each], K [9], pose in [12], pose out [L][12]
+    DevBuf<float> buf;                                          // tgt | src [3 H W each], depth_t | depth_s [H W each], K [9], pose in [12], pose out [L][12]
     const size_t nfl = 8 * hw + 9 + 12 + (size_t)L * 12;
-    HIPCHK(h, hipMalloc((void **)&buf, nfl * sizeof(float)));
+    RESERVE(h, buf, nfl);
     float *tgt = buf, *src = buf + 3 * hw, *dt = buf + 6 * hw, *ds = buf + 7 * hw, *K = buf + 8 * hw, *pin = K + 9, *pout = pin + 12;
     {
         std::vector<float> img(8 * hw);
@@ -259,8 +259,12 @@ static int probe_lanes(tcsfm_ctx *h) {
         HIPCHK(h, hipMemcpy(pin, ph, sizeof(ph), hipMemcpyHostToDevice));
     }
     tcsfm_opts o; tcsfm_default_opts(&o);
-    hipStream_t keep = h->stream;
-    h->stream = h->own_stream;
+    struct OnOwnStream {                                        // the probe runs on the handle's own stream; every way out hands the caller's back
+        tcsfm_ctx *h;
+        hipStream_t keep;
+        explicit OnOwnStream(tcsfm_ctx *h_) : h(h_), keep(h_->stream) { h->stream = h->own_stream; }
+        ~OnOwnStream() { h->stream = keep; }
+    } on_own_stream(h);
     int rc = TCSFM_OK;
     auto run = [&](int nl, int calls, float *ms) -> int {
         for (int pass = 0; pass < 2 && !rc; pass++) {           // (first pass: warm-up -- scratch allocations, intrinsics check)
@@ -278,8 +282,6 @@ static int probe_lanes(tcsfm_ctx *h) {
         rc = run(1, calls, &h->lane_probe[0]);
         if (!rc) rc = run(L, calls, &h->lane_probe[1]);
     }
-    h->stream = keep;
-    (void)hipFree(buf);
     k_forget(h);
     for (tcsfm_ctx *c : h->lanes) k_forget(c);
     if (rc) return rc;
@@ -313,8 +315,8 @@ int tcsfm_set_lanes(tcsfm_handle h, int n_lanes) {
         tcsfm_ctx *c = nullptr;
         int rc = tcsfm_create(&c, h->device, h->H, h->W, h->max_pairs);
         if (rc) return fail(h, rc, "tcsfm_set_lanes: could not create a lane");
-        hipError_t e = hipEventCreateWithFlags(&c->in_ev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming);
+        hipError_t e = c->in_ev.create();
+        if (e == hipSuccess) e = c->done_ev.create();
         if (e != hipSuccess) { tcsfm_destroy(c); return fail(h, TCSFM_E_HIP, "tcsfm_set_lanes: hipEventCreate failed"); }
         c->graphs.slots = h->graphs.slots;
         h->lanes.push_back(c);

@@ -1,7 +1,7 @@
 // Host side of the solve test hooks (include/tcsfm.h: tcsfm_debug_solve, tcsfm_debug_solve_joint): ONE launch of a production solve kernel on
 // host arrays the caller gives.  Here: the device copies both entries work on (DebugBufs), the argument checks of the joint entry (plain C++,
 // no HIP: debug_joint_refusal) and the joint entry itself.  Part of tcsfm_api.hip, the library's only translation unit: included after
-// fail, HIPCHK, DeviceGuard, pending_error, drain_queued and the guard-band helpers.  Production launches and kernels are not touched: the
+// context.h (fail, HIPCHK, DeviceGuard, pending_error; DevBuf and the guard-band helpers of device_owned.h) and drain_queued.  Production launches and kernels are not touched: the
 // entry instantiates k_solve_joint<NS>, k_solve_front<NS, PC> and k_solve_joint2<NS, PC> at NS = 1 .. JMAXS, as dense_host.h does.
 #pragma once
 
@@ -9,17 +9,18 @@ namespace {
 
 // the device copies of a debug entry: allocations of the entry's own (guarded like every other), freed when it returns
 struct DebugBufs {
-    std::vector<void *> dev;
+    std::vector<DevBuf<char>> bufs;
+    std::vector<void *> dev;      // their pointers, for tcguard::damaged_among
     struct Back { void *host; void *dev; size_t bytes; };
     std::vector<Back> back;
-    ~DebugBufs() { for (void *p : dev) (void)hipFree(p); }
     // host == nullptr: nullptr.  Otherwise a device copy of `bytes` bytes; out: copied back after the launch
     hipError_t up(const void *host, size_t bytes, bool out, void **res) {
         *res = nullptr;
         if (!host || bytes == 0) return hipSuccess;
-        void *d = nullptr;
-        hipError_t e = hipMalloc(&d, bytes);
+        bufs.emplace_back();
+        hipError_t e = DEV_RESERVE(bufs.back(), bytes);
         if (e != hipSuccess) return e;
+        void *d = bufs.back().p;
         dev.push_back(d);
         e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
         if (e != hipSuccess) return e;

@@ -180,9 +180,9 @@ struct DenseJoint : DenseDriver {
     // be given, and the chains never touch each other's data, so the results are the same bits.
     int fork() {
         if (!h->aux_stream) {
-            HIPCHK(h, hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-            HIPCHK(h, hipEventCreateWithFlags(&h->aux_fork, hipEventDisableTiming));
-            HIPCHK(h, hipEventCreateWithFlags(&h->aux_join, hipEventDisableTiming));
+            HIPCHK(h, h->aux_stream.create());
+            HIPCHK(h, h->aux_fork.create());
+            HIPCHK(h, h->aux_join.create());
         }
         fs = h->stream; is = h->capturing ? h->stream : h->aux_stream;
         if (int rc = trace_check(h, o, N)) return rc;
@@ -342,7 +342,7 @@ struct DenseRef : DenseDriver {
     int reserve_zeroed(DevBuf<int> &b, size_t n) {
         if (b.cap) return TCSFM_OK;
         RESERVE(h, b, n);
-        if (hipMemset(b.p, 0, n * sizeof(int)) != hipSuccess) { b.release(); return fail(h, TCSFM_E_HIP, "hipMemset of the joint solve's tickets failed"); }
+        if (hipMemset(b.p, 0, n * sizeof(int)) != hipSuccess) { (void)b.release(); return fail(h, TCSFM_E_HIP, "hipMemset of the joint solve's tickets failed"); }
         return TCSFM_OK;
     }
     int reserve_sums(DevBuf<long long> &b, size_t n) {      // ... and fresh scatter sums are cleared before their first use (dref_clean)

@@ -1,9 +1,10 @@
 // Host side of the depth network (models/depth_w_access.py, num_scales = 1): ResNet18 encoder + U-Net decoder -- the topology, the work
 // split, the forward walks, the tapes of the training forward, the backward walks and the tcsfm_depthnet_* entry points.
-// Part of tcsfm_api.hip, the library's only translation unit: included after the context helpers (tcsfm_ctx, fail, HIPCHK, DeviceGuard,
-// drain_queued) and the kernels' headers, and before the sequence driver, whose depth stage is dn_sequence_depths.  include/tcsfm.h
+// Part of tcsfm_api.hip, the library's only translation unit: included after context.h (tcsfm_ctx, fail, fail_alloc, HIPCHK, DEV_RESERVE, DeviceGuard)
+// and call_host.h (drain_queued) and the kernels' headers, and before the sequence driver, whose depth stage is dn_sequence_depths.  include/tcsfm.h
 // declares the entry points, so they have C linkage here.
 #pragma once
+#include <memory>
 
 namespace {
 constexpr int DN_BLOCKS = 8, DN_UPS = 5;                       // residual blocks of the encoder, up-steps of the decoder
@@ -27,11 +28,9 @@ struct DnLayer {
     int ih = 0, iw = 0, oh = 0, ow = 0;
     DnSplit sp = {1, 1, 1};             // of k_dn_conv: dn_split(oh * ow, coutp / 16)
     std::string wname, bname, bn;       // state_dict names: conv weight, conv bias ("" = none), BatchNorm prefix ("" = none)
-    dn_f4 *w4 = nullptr;
-    float *bias = nullptr;
-    // training (tcsfm_depthnet_load_device): the transposed weight image of the data gradient (not for conv1), the raw parameters'
-    // snapshot (w [cout][cin][ks][ks], then conv bias, gamma, beta, mean, var [cout] each) and the folded-gradient accumulators
-    // (dw' [cout][cin ks ks], db' [cout])
+    // training (tcsfm_depthnet_load_device), views into the instance's DnTrain: the transposed weight image of the data gradient (not for
+    // conv1), the raw parameters' snapshot (w [cout][cin][ks][ks], then conv bias, gamma, beta, mean, var [cout] each) and the
+    // folded-gradient accumulators (dw' [cout][cin ks ks], db' [cout])
     dn_f4 *wt4 = nullptr;
     float *raw = nullptr, *gw = nullptr, *gb = nullptr;
     int taps() const { return ks * ks; }
@@ -43,6 +42,23 @@ struct DnLayer {
 // A residual block of the encoder: convolutions li (conv1) and li + 1 (conv2), and li + 2, the 1x1 downsample of its input, if `down`.
 // Block j reads block j - 1's output (block 0 the pooled map); `skip`: which skip its output is (-1: none).
 struct DnBlock { int li, down, skip; };
+
+// What a load fills and every instance's launches read, per layer of tcsfm_depthnet::L: the folded weight image and the bias [coutp];
+// predict_disps.0 weight [1,8,3,3] / bias [1].  A reload fills them in place.
+struct DnWeights {
+    std::vector<DevBuf<dn_f4>> w4;
+    std::vector<DevBuf<float>> bias;
+    DevBuf<float> pw, pb;
+};
+
+// The training state (allocated by the first tcsfm_depthnet_load_device; the primary's only)
+struct DnTrain {
+    DevBuf<float> tbuf;                 // one allocation: the layers' raw / gw / gb regions and the head's gradient accumulator
+    float *hacc = nullptr;              // head: d predict_disps weight [DN_HEAD_W] + bias [1] (a view into tbuf)
+    DevBuf<float> part, bpart, hpart;   // weight / bias / head partials of one image group
+    DevBuf<float> gA, gB, gC, gD, gV;   // data-gradient scratch
+    std::vector<DevBuf<dn_f4>> wt4;     // per layer: DnLayer::wt4
+};
 }  // namespace
 
 struct tcsfm_depthnet {
@@ -54,26 +70,22 @@ struct tcsfm_depthnet {
     int up(int i) const { return enc_end + 2 * i; }       // up-convolution / iconv of up-step i, feature_convs.0
     int iconv(int i) const { return up(i) + 1; }
     int feat() const { return up(DN_UPS); }
-    float *pw = nullptr, *pb = nullptr; // predict_disps.0 weight [1,8,3,3] / bias [1]
-    float *skip[5] = {};                // tcsfm_depthnet_forward's own skips, NHWC
-    float *pool = nullptr, *t1 = nullptr, *t2 = nullptr, *ds = nullptr;   // encoder scratch, N * H * W * 4 floats each
-    float *u = nullptr, *x = nullptr;   // decoder scratch, N * H * W * 32 floats each
+    DnWeights own;                      // the primary's weights (empty in the clone)
+    const DnWeights *w = &own;          // the weights the launches read: the primary's
+    DevBuf<float> skip_own[5];          // tcsfm_depthnet_forward's own skips, NHWC ...
+    float *skip[5] = {};                // ... as the table the walks take
+    DevBuf<float> pool, t1, t2, ds;     // encoder scratch, N * H * W * 4 floats each
+    DevBuf<float> u, x;                 // decoder scratch, N * H * W * 32 floats each
     // tcsfm_depthnet_disp_for_eigen / the sequence calls' disparity stage: scaled-disparity planes of ONE group of max_images images,
     // the straight pass's and the mirrored pass's (still mirrored); allocated on first use (dn_post_scratch), owned by the instance
-    float *post_l = nullptr, *post_r = nullptr;
-    // training state (allocated by the first tcsfm_depthnet_load_device)
+    DevBuf<float> post_l, post_r;
     int train_loaded = 0;
-    float *tbuf = nullptr;              // one allocation: the layers' raw / gw / gb regions and the head's gradient accumulator
-    float *hacc = nullptr;              // head: d predict_disps weight [DN_HEAD_W] + bias [1]
-    float *part = nullptr, *bpart = nullptr, *hpart = nullptr;   // weight / bias / head partials of one image group
-    float *gA = nullptr, *gB = nullptr, *gC = nullptr, *gD = nullptr, *gV = nullptr;   // data-gradient scratch
-    std::vector<float **> train_bufs() { return {&tbuf, &part, &bpart, &hpart, &gA, &gB, &gC, &gD, &gV}; }
-    // tcsfm_sequence_depthnet: the sequence calls' depth stage runs on `seq_clone` -- this network's weights (owns_weights = false: the
-    // device pointers of L[].w4 / bias, pw, pb, which a reload fills in place), its own activations, and its forward launches on
-    // `stream` (the handle's seq_pack) instead of the handle's stream -- so it needs neither this instance nor the handle's stream
-    bool owns_weights = true;
+    DnTrain train;
+    // tcsfm_sequence_depthnet: the sequence calls' depth stage runs on `seq_clone` -- an instance of its own that READS this network's
+    // weights through `w` (a reload fills them in place), with its own activations and no training state, and whose forward launches go
+    // to `stream` (the handle's seq_pack) instead of the handle's stream.  It goes before this instance's weights do.
     hipStream_t stream = nullptr;       // forward launches go here when set (dn_stream)
-    tcsfm_depthnet *seq_clone = nullptr;
+    std::unique_ptr<tcsfm_depthnet> seq_clone;
 };
 
 namespace {
@@ -119,51 +131,38 @@ void dn_layers(tcsfm_depthnet *dn) {
     L.push_back(dn_layer(32, 8, 3, 1, h, w, 0, 1, DN_EPI_ELU, "feature_convs.0.0.conv.weight", "feature_convs.0.0.conv.bias", ""));
 }
 
-// the training buffers (and the layers' views into them); dn_train_alloc's failure path and dn_free
+// dn_train_alloc's failure path: the training buffers go, and the layers' views into them
 void dn_train_free(tcsfm_depthnet *dn) {
-    for (DnLayer &l : dn->L) { if (l.wt4) (void)hipFree(l.wt4); l.wt4 = nullptr; l.raw = l.gw = l.gb = nullptr; }
-    for (float **p : dn->train_bufs()) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    dn->train = DnTrain();
+    for (DnLayer &l : dn->L) { l.wt4 = nullptr; l.raw = l.gw = l.gb = nullptr; }
 }
 
 hipError_t dn_alloc_scratch(tcsfm_depthnet *dn) {
     const size_t N = (size_t)dn->max_images, hw = (size_t)dn->h->H * dn->h->W;
     hipError_t e = hipSuccess;
-    for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipMalloc((void **)&dn->skip[k], N * (hw >> (2 * (k + 1))) * DN_SKIP_C[k] * sizeof(float));
-    float **enc[] = {&dn->pool, &dn->t1, &dn->t2, &dn->ds};
-    for (float **p : enc) if (e == hipSuccess) e = hipMalloc((void **)p, N * hw * 4 * sizeof(float));       // (H/4)(W/4) x 64 = H W x 4
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->u, N * hw * 32 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->x, N * hw * 32 * sizeof(float));
-    return e;
-}
-
-void dn_free(tcsfm_depthnet *dn) {
-    if (dn->seq_clone) { dn_free(dn->seq_clone); delete dn->seq_clone; dn->seq_clone = nullptr; }
-    if (dn->owns_weights) {
-        for (DnLayer &l : dn->L) { if (l.w4) (void)hipFree(l.w4); if (l.bias) (void)hipFree(l.bias); l.w4 = nullptr; l.bias = nullptr; }
-        dn_train_free(dn);
-        if (dn->pw) (void)hipFree(dn->pw);
-        if (dn->pb) (void)hipFree(dn->pb);
+    for (int k = 0; k < 5 && e == hipSuccess; k++) {
+        e = DEV_RESERVE(dn->skip_own[k], N * (hw >> (2 * (k + 1))) * DN_SKIP_C[k]);
+        dn->skip[k] = dn->skip_own[k];
     }
-    float *bufs[] = {dn->skip[0], dn->skip[1], dn->skip[2], dn->skip[3], dn->skip[4], dn->pool, dn->t1, dn->t2, dn->ds, dn->u, dn->x, dn->post_l, dn->post_r};
-    for (float *p : bufs) if (p) (void)hipFree(p);
+    for (DevBuf<float> *p : {&dn->pool, &dn->t1, &dn->t2, &dn->ds}) if (e == hipSuccess) e = DEV_RESERVE(*p, N * hw * 4);       // (H/4)(W/4) x 64 = H W x 4
+    if (e == hipSuccess) e = DEV_RESERVE(dn->u, N * hw * 32);
+    if (e == hipSuccess) e = DEV_RESERVE(dn->x, N * hw * 32);
+    return e;
 }
 
 // forward launches of an instance: the handle's stream, or the sequence calls' stage stream for the clone they run
 hipStream_t dn_stream(const tcsfm_depthnet *dn) { return dn->stream ? dn->stream : dn->h->stream; }
 
-// the instance the sequence calls run `dn`'s network on (pn_for_lane's pattern): geometry, work split and weight pointers of `dn`, its
-// own skips and scratch, no training state.  The caller binds its `stream` per call.
+// the instance the sequence calls run `dn`'s network on (pn_for_lane's pattern): the geometry and work split of `dn`'s handle, `dn`'s
+// weights to read, its own skips and scratch, no training state.  The caller binds its `stream` per call.
 tcsfm_depthnet *dn_sequence_clone(tcsfm_depthnet *dn) {
-    if (dn->seq_clone) return dn->seq_clone;
-    tcsfm_depthnet *q = new tcsfm_depthnet(*dn);
-    q->owns_weights = false; q->seq_clone = nullptr; q->train_loaded = 0;
-    for (DnLayer &l : q->L) { l.wt4 = nullptr; l.raw = l.gw = l.gb = nullptr; }
-    for (float **p : q->train_bufs()) *p = nullptr;
-    q->hacc = nullptr;
-    for (int k = 0; k < 5; k++) q->skip[k] = nullptr;
-    q->pool = q->t1 = q->t2 = q->ds = q->u = q->x = q->post_l = q->post_r = nullptr;
-    if (dn_alloc_scratch(q) != hipSuccess) { dn_free(q); delete q; return nullptr; }
-    return dn->seq_clone = q;
+    if (dn->seq_clone) return dn->seq_clone.get();
+    std::unique_ptr<tcsfm_depthnet> q(new tcsfm_depthnet());
+    q->h = dn->h; q->max_images = dn->max_images; q->loaded = dn->loaded; q->w = dn->w;
+    dn_layers(q.get());
+    if (dn_alloc_scratch(q.get()) != hipSuccess) return nullptr;
+    dn->seq_clone = std::move(q);
+    return dn->seq_clone.get();
 }
 
 // ---- the split kernels' dispatch: k_dn_conv (pixels = oh ow, blocks = coutp / 16) and k_dnb_dgrad (pixels = lane grid, blocks = cin / 16)
@@ -196,7 +195,7 @@ void dn_launch_split(int ks, DnSplit s, int pixels, int cblocks, int N, const Pa
 void dn_conv(tcsfm_depthnet *dn, int li, int N, const float *in, const float *res, float *out, float *aux = nullptr) {
     const DnLayer &l = dn->L[li];
     DnConvParams P;
-    P.in = in; P.w4 = l.w4; P.bias = l.bias; P.res = res; P.out = out; P.aux = aux;
+    P.in = in; P.w4 = dn->w->w4[li]; P.bias = dn->w->bias[li]; P.res = res; P.out = out; P.aux = aux;
     P.cin = l.cin; P.cout = l.cout; P.coutp = l.coutp; P.ih = l.ih; P.iw = l.iw; P.oh = l.oh; P.ow = l.ow;
     P.stride = l.stride; P.pad = l.pad; P.up = l.up; P.reflect = l.reflect; P.epi = l.epi;
     dn_launch_split<DnConvKernel>(l.ks, l.sp, l.oh * l.ow, l.coutp / 16, N, P, dn_stream(dn));
@@ -283,7 +282,7 @@ int dn_encode(tcsfm_depthnet *dn, int N, const float *imgs, int flip, const DnEn
     tcsfm_ctx *h = dn->h;
     const DnLayer &c1 = dn->L[0];
     DnConv1Params P1;
-    P1.img = imgs; P1.w4 = c1.w4; P1.bias = c1.bias; P1.out = d.conv1; P1.ih = h->H; P1.iw = h->W; P1.oh = c1.oh; P1.ow = c1.ow; P1.flip = flip ? 1 : 0;
+    P1.img = imgs; P1.w4 = dn->w->w4[0]; P1.bias = dn->w->bias[0]; P1.out = d.conv1; P1.ih = h->H; P1.iw = h->W; P1.oh = c1.oh; P1.ow = c1.ow; P1.flip = flip ? 1 : 0;
     hipLaunchKernelGGL(k_dn_conv1<2>, dim3((c1.oh * c1.ow + 127) / 128, 1, N), dim3(256), 0, dn_stream(dn), P1);
     const int ph = c1.oh / 2, pw = c1.ow / 2;
     hipLaunchKernelGGL(k_dn_maxpool, dim3(dn_blocks((long long)N * ph * pw * 16)), dim3(256), 0, dn_stream(dn), (const float *)d.conv1, d.pool, N, 64, c1.oh,
@@ -312,16 +311,16 @@ int dn_decode(tcsfm_depthnet *dn, int N, const float *const sk[5], const DnDecDs
     dn_conv(dn, dn->feat(), N, x, nullptr, d.feat);                                              // feature_convs.0: 32 -> 8, ELU
     const dim3 head_grid(dn_blocks((long long)N * h->H * h->W));
     if (d.scaled_only)
-        hipLaunchKernelGGL(k_dn_head<DN_HEAD_SCALED>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->pw, (const float *)dn->pb,
+        hipLaunchKernelGGL(k_dn_head<DN_HEAD_SCALED>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->w->pw, (const float *)dn->w->pb,
                            d.disp, (float *)nullptr, N, h->H, h->W, d.min_disp, d.max_disp);
     else if (d.as_depth && d.scaled)
-        hipLaunchKernelGGL(k_dn_head<DN_HEAD_DEPTH_SCALED>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->pw, (const float *)dn->pb,
+        hipLaunchKernelGGL(k_dn_head<DN_HEAD_DEPTH_SCALED>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->w->pw, (const float *)dn->w->pb,
                            d.disp, d.scaled, N, h->H, h->W, d.min_disp, d.max_disp);
     else if (d.as_depth)
-        hipLaunchKernelGGL(k_dn_predict<true>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->pw, (const float *)dn->pb,
+        hipLaunchKernelGGL(k_dn_predict<true>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->w->pw, (const float *)dn->w->pb,
                            d.disp, N, h->H, h->W, d.min_disp, d.max_disp);
     else
-        hipLaunchKernelGGL(k_dn_predict<false>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->pw, (const float *)dn->pb,
+        hipLaunchKernelGGL(k_dn_predict<false>, head_grid, dim3(256), 0, dn_stream(dn), (const float *)d.feat, (const float *)dn->w->pw, (const float *)dn->w->pb,
                            d.disp, N, h->H, h->W, 0.f, 0.f);
     HIPCHK(h, hipGetLastError());
     return TCSFM_OK;
@@ -413,7 +412,7 @@ size_t dn_cinT(const DnLayer &l) { return l.ks == 7 ? 147 : (size_t)l.cin * l.ta
 void dn_padded_grid(const DnLayer &l, int &gh, int &gw) { gh = (l.ih << l.up) + 2 * l.pad; gw = (l.iw << l.up) + 2 * l.pad; }
 
 int dn_train_alloc(tcsfm_depthnet *dn) {
-    if (dn->tbuf) return TCSFM_OK;
+    if (dn->train.tbuf) return TCSFM_OK;
     tcsfm_ctx *h = dn->h;
     const size_t N = dn->max_images, hw = (size_t)h->H * h->W;
     size_t tot = 0, part = 0, bpart = 0, gv = 0;
@@ -425,31 +424,34 @@ int dn_train_alloc(tcsfm_depthnet *dn) {
         if (l.reflect) { int gh, gw; dn_padded_grid(l, gh, gw); gv = std::max(gv, N * gh * gw * l.cin); }
     }
     tot += DN_HEAD_N;
-    hipError_t e = hipMalloc((void **)&dn->tbuf, tot * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->part, part * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->bpart, bpart * sizeof(float));
+    DnTrain &t = dn->train;
+    hipError_t e = DEV_RESERVE(t.tbuf, tot);
+    if (e == hipSuccess) e = DEV_RESERVE(t.part, part);
+    if (e == hipSuccess) e = DEV_RESERVE(t.bpart, bpart);
     const int hch = (int)((hw + DNB_HEAD_CHUNK - 1) / DNB_HEAD_CHUNK);
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->hpart, N * hch * DN_HEAD_N * sizeof(float));
-    float **g32[] = {&dn->gA, &dn->gB, &dn->gC};
-    for (float **p : g32) if (e == hipSuccess) e = hipMalloc((void **)p, N * hw * 32 * sizeof(float));    // the largest activation: H W x 32
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->gD, N * hw * 4 * sizeof(float));                      // a downsample's input grid
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->gV, gv * sizeof(float));
+    if (e == hipSuccess) e = DEV_RESERVE(t.hpart, N * hch * DN_HEAD_N);
+    for (DevBuf<float> *p : {&t.gA, &t.gB, &t.gC}) if (e == hipSuccess) e = DEV_RESERVE(*p, N * hw * 32);    // the largest activation: H W x 32
+    if (e == hipSuccess) e = DEV_RESERVE(t.gD, N * hw * 4);                      // a downsample's input grid
+    if (e == hipSuccess) e = DEV_RESERVE(t.gV, gv);
+    t.wt4.resize(dn->L.size());
     size_t o = 0;
-    for (DnLayer &l : dn->L) {
-        l.raw = dn->tbuf + o; o += l.nw() + 5 * (size_t)l.cout;
-        l.gw = dn->tbuf + o; o += l.nw();
-        l.gb = dn->tbuf + o; o += l.cout;
+    for (size_t li = 0; li < dn->L.size(); li++) {
+        DnLayer &l = dn->L[li];
+        l.raw = dn->train.tbuf + o; o += l.nw() + 5 * (size_t)l.cout;
+        l.gw = dn->train.tbuf + o; o += l.nw();
+        l.gb = dn->train.tbuf + o; o += l.cout;
         if (l.ks != 7 && e == hipSuccess) {
             const size_t n4 = (size_t)l.taps() * l.coutp * l.cin;      // floats / 4 ... in dn_f4 units: taps * coutp/16 * 4 * cin
-            e = hipMalloc((void **)&l.wt4, n4 / 4 * sizeof(dn_f4) * 1);
+            e = DEV_RESERVE(t.wt4[li], n4 / 4);
+            l.wt4 = t.wt4[li];
             if (e == hipSuccess) e = hipMemsetAsync(l.wt4, 0, n4 * sizeof(float), h->stream);   // rows of channels >= cout stay zero
         }
-        if (e == hipSuccess) e = hipMemsetAsync(l.w4, 0, l.w4_count() * sizeof(dn_f4), h->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(dn->w->w4[li], 0, l.w4_count() * sizeof(dn_f4), h->stream);
     }
-    dn->hacc = dn->tbuf + o;
+    dn->train.hacc = dn->train.tbuf + o;
     if (e != hipSuccess) {
         dn_train_free(dn);
-        return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_depthnet_load_device: allocation failed");
+        return fail_alloc(h, e, "tcsfm_depthnet_load_device: allocation failed");
     }
     return TCSFM_OK;
 }
@@ -488,18 +490,18 @@ void dnb_wgrad(tcsfm_depthnet *dn, int li, int N, const float *dz, const float *
     const int npix = l.oh * l.ow, chunk = dn_wchunk(npix), nch = dn_nchunk(npix), parts = N * nch;
     if (wneed) {
         DnWgradParams P;
-        P.dz = dz; P.x = x; P.part = dn->part; P.cin = l.cin; P.cout = l.cout; P.ih = l.ih; P.iw = l.iw; P.oh = l.oh; P.ow = l.ow;
+        P.dz = dz; P.x = x; P.part = dn->train.part; P.cin = l.cin; P.cout = l.cout; P.ih = l.ih; P.iw = l.iw; P.oh = l.oh; P.ow = l.ow;
         P.stride = l.stride; P.pad = l.pad; P.up = l.up; P.reflect = l.reflect; P.chunk = chunk; P.nchunk = nch;
         if (l.ks == 7) hipLaunchKernelGGL((k_dnb_wgrad<7, 2, true>), dim3(parts, 2, l.coutp / 32), dim3(256), 0, s, P);
         else if (l.ks == 1) hipLaunchKernelGGL((k_dnb_wgrad<1, 2, false>), dim3(parts, l.cin / 16, l.coutp / 32), dim3(256), 0, s, P);
         else if (l.coutp % 32 == 0) hipLaunchKernelGGL((k_dnb_wgrad<9, 2, false>), dim3(parts, l.cin / 16, l.coutp / 32), dim3(256), 0, s, P);
         else hipLaunchKernelGGL((k_dnb_wgrad<9, 1, false>), dim3(parts, l.cin / 16, l.coutp / 16), dim3(256), 0, s, P);
         const long long E = (long long)l.cout * dn_cinT(l);
-        hipLaunchKernelGGL(k_dnb_wsum, dim3(dn_blocks(E)), dim3(256), 0, s, (const float *)dn->part, l.gw, E, parts, accumulate);
+        hipLaunchKernelGGL(k_dnb_wsum, dim3(dn_blocks(E)), dim3(256), 0, s, (const float *)dn->train.part, l.gw, E, parts, accumulate);
     }
     if (bneed) {
-        hipLaunchKernelGGL(k_dnb_bgrad, dim3(parts), dim3(256), 0, s, dz, dn->bpart, l.cout, npix, chunk, nch);
-        hipLaunchKernelGGL(k_dnb_wsum, dim3(dn_blocks(l.cout)), dim3(256), 0, s, (const float *)dn->bpart, l.gb, (long long)l.cout, parts, accumulate);
+        hipLaunchKernelGGL(k_dnb_bgrad, dim3(parts), dim3(256), 0, s, dz, dn->train.bpart, l.cout, npix, chunk, nch);
+        hipLaunchKernelGGL(k_dnb_wsum, dim3(dn_blocks(l.cout)), dim3(256), 0, s, (const float *)dn->train.bpart, l.gb, (long long)l.cout, parts, accumulate);
     }
 }
 
@@ -585,13 +587,13 @@ int dn_decode_backward(tcsfm_depthnet *dn, int N, const DnTape &t, int i0, const
     float *f = at(DN_TD_FEAT), *disp = at(DN_TD_DISP);
     if (head_req) {
         const int hch = (H * W + DNB_HEAD_CHUNK - 1) / DNB_HEAD_CHUNK;
-        hipLaunchKernelGGL(k_dnb_head_wgrad, dim3(N * hch), dim3(128), 0, h->stream, (const float *)f, (const float *)disp, ddisp, dn->hpart, H, W, hch);
-        hipLaunchKernelGGL(k_dnb_wsum, dim3(1), dim3(256), 0, h->stream, (const float *)dn->hpart, dn->hacc, (long long)DN_HEAD_N, N * hch, accumulate);
+        hipLaunchKernelGGL(k_dnb_head_wgrad, dim3(N * hch), dim3(128), 0, h->stream, (const float *)f, (const float *)disp, ddisp, dn->train.hpart, H, W, hch);
+        hipLaunchKernelGGL(k_dnb_wsum, dim3(1), dim3(256), 0, h->stream, (const float *)dn->train.hpart, dn->train.hacc, (long long)DN_HEAD_N, N * hch, accumulate);
     }
     if (!need_dgrad(HEAD)) return TCSFM_OK;
-    float *cur = dn->gA, *nxt = dn->gB;
+    float *cur = dn->train.gA, *nxt = dn->train.gB;
     hipLaunchKernelGGL(k_dnb_head, dim3(dn_blocks((long long)N * H * W)), dim3(256), 0, h->stream, (const float *)f, (const float *)disp, ddisp,
-                       (const float *)dn->pw, cur, N, H, W);
+                       (const float *)dn->w->pw, cur, N, H, W);
     for (int li = F; li >= E && need_dgrad(li + 1); li--) {
         const int i = (li - E) / 2;
         const bool feat = li == F, up = !feat && li == dn->up(i);
@@ -599,11 +601,11 @@ int dn_decode_backward(tcsfm_depthnet *dn, int N, const DnTape &t, int i0, const
         float *in = feat ? at(dn_td_x(DN_UPS - 1)) : up ? (i ? at(dn_td_x(i - 1)) : at(DN_TD_SKIP4)) : at(dn_td_u(i));
         if (req[li].any()) dnb_wgrad(dn, li, N, cur, in, req[li].wneed(), req[li].bneed(), accumulate);
         if (!need_dgrad(li)) break;
-        dnb_dgrad(dn, li, N, cur, dn->gV, false, nullptr, nullptr, nullptr, DN_ACT_NONE);
+        dnb_dgrad(dn, li, N, cur, dn->train.gV, false, nullptr, nullptr, nullptr, DN_ACT_NONE);
         // through the ELU that made the input; an iconv's input is ELU (+ skip): the folded sum is that skip's gradient
-        if (feat || (up && i > 0)) dnb_fold(dn, li, N, dn->gV, nullptr, in, DN_ACT_ELU, nxt, nullptr);
-        else if (!up) dnb_fold(dn, li, N, dn->gV, nullptr, at(dn_td_elu(i)), DN_ACT_ELU, nxt, dn_adds_skip(i) ? dsk[3 - i] : nullptr);
-        else dnb_fold(dn, li, N, dn->gV, nullptr, nullptr, DN_ACT_NONE, nullptr, dsk[4]);
+        if (feat || (up && i > 0)) dnb_fold(dn, li, N, dn->train.gV, nullptr, in, DN_ACT_ELU, nxt, nullptr);
+        else if (!up) dnb_fold(dn, li, N, dn->train.gV, nullptr, at(dn_td_elu(i)), DN_ACT_ELU, nxt, dn_adds_skip(i) ? dsk[3 - i] : nullptr);
+        else dnb_fold(dn, li, N, dn->train.gV, nullptr, nullptr, DN_ACT_NONE, nullptr, dsk[4]);
         std::swap(cur, nxt);
     }
     HIPCHK(h, hipGetLastError());
@@ -622,7 +624,7 @@ int dn_encode_backward(tcsfm_depthnet *dn, int N, const DnTape &t, int i0, const
         before[j + 1] = before[j] || req[B.li].any() || req[B.li + 1].any() || (B.down && req[B.li + 2].any());
     }
     if (!before[DN_BLOCKS]) return TCSFM_OK;
-    float *dz2 = dn->gA, *dz1 = dn->gB, *nx = dn->gC;
+    float *dz2 = dn->train.gA, *dz1 = dn->train.gB, *nx = dn->train.gC;
     const DnLayer &l4 = dn->L[dn->blk[DN_BLOCKS - 1].li + 1];
     dnb_ew(dn, N, l4.cout, l4.oh, l4.ow, dsk[4], nullptr, at(dn_te_out(DN_BLOCKS - 1)), DN_ACT_RELU, dz2);
     for (int j = DN_BLOCKS - 1; j >= 0; j--) {
@@ -637,8 +639,8 @@ int dn_encode_backward(tcsfm_depthnet *dn, int N, const DnTape &t, int i0, const
         dnb_dgrad(dn, c2, N, dz2, dz1, true, nullptr, nullptr, t1, DN_ACT_RELU);
         if (req[c1].any()) dnb_wgrad(dn, c1, N, dz1, hin, req[c1].wneed(), req[c1].bneed(), accumulate);
         if (!before[j]) break;
-        if (B.down) dnb_dgrad(dn, ds, N, dz2, dn->gD, true, nullptr, nullptr, nullptr, DN_ACT_NONE);
-        dnb_dgrad(dn, c1, N, dz1, nx, true, B.down ? dn->gD : dz2, skip_in >= 0 ? dsk[skip_in] : nullptr, hin, j == 0 ? DN_ACT_NONE : DN_ACT_RELU);
+        if (B.down) dnb_dgrad(dn, ds, N, dz2, dn->train.gD, true, nullptr, nullptr, nullptr, DN_ACT_NONE);
+        dnb_dgrad(dn, c1, N, dz1, nx, true, B.down ? dn->train.gD : dz2, skip_in >= 0 ? dsk[skip_in] : nullptr, hin, j == 0 ? DN_ACT_NONE : DN_ACT_RELU);
         std::swap(dz2, nx);
     }
     if (req[0].any()) {
@@ -660,7 +662,6 @@ void tcsfm_depthnet_destroy(tcsfm_depthnet *dn) {
     // an attached network (tcsfm_sequence_depthnet) is detached: a sequence call synchronises its stage stream before it returns, so the
     // clone has no work in flight here
     if (dn->h->seq_dn == dn) dn->h->seq_dn = nullptr;
-    dn_free(dn);
     delete dn;
 }
 
@@ -675,14 +676,15 @@ int tcsfm_depthnet_create(tcsfm_handle h, int max_images, tcsfm_depthnet **out) 
     dn->h = h; dn->max_images = max_images;
     dn_layers(dn);
     hipError_t e = hipSuccess;
-    for (DnLayer &l : dn->L) {
-        if (e == hipSuccess) e = hipMalloc((void **)&l.w4, l.w4_count() * sizeof(dn_f4));
-        if (e == hipSuccess) e = hipMalloc((void **)&l.bias, l.coutp * sizeof(float));
+    dn->own.w4.resize(dn->L.size()); dn->own.bias.resize(dn->L.size());
+    for (size_t li = 0; li < dn->L.size(); li++) {
+        if (e == hipSuccess) e = DEV_RESERVE(dn->own.w4[li], dn->L[li].w4_count());
+        if (e == hipSuccess) e = DEV_RESERVE(dn->own.bias[li], dn->L[li].coutp);
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->pw, DN_HEAD_W * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&dn->pb, sizeof(float));
+    if (e == hipSuccess) e = DEV_RESERVE(dn->own.pw, DN_HEAD_W);
+    if (e == hipSuccess) e = DEV_RESERVE(dn->own.pb, 1);
     if (e == hipSuccess) e = dn_alloc_scratch(dn);
-    if (e != hipSuccess) { tcsfm_depthnet_destroy(dn); return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_depthnet_create: allocation failed"); }
+    if (e != hipSuccess) { tcsfm_depthnet_destroy(dn); return fail_alloc(h, e, "tcsfm_depthnet_create: allocation failed"); }
     *out = dn;
     return TCSFM_OK;
 }
@@ -734,11 +736,11 @@ int tcsfm_depthnet_load(tcsfm_depthnet *dn, int n, const char *const names[], co
     if (int rc_q = drain_queued(h)) return rc_q;
     HIPCHK(h, hipStreamSynchronize(h->stream));     // weights may be in use by earlier calls on the stream
     for (size_t li = 0; li < dn->L.size(); li++) {
-        HIPCHK(h, hipMemcpy(dn->L[li].w4, w4s[li].data(), w4s[li].size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(dn->L[li].bias, biases[li].data(), biases[li].size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(dn->w->w4[li], w4s[li].data(), w4s[li].size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(dn->w->bias[li], biases[li].data(), biases[li].size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    HIPCHK(h, hipMemcpy(dn->pw, pw, DN_HEAD_W * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(dn->pb, pb, sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(dn->w->pw, pw, DN_HEAD_W * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(dn->w->pb, pb, sizeof(float), hipMemcpyHostToDevice));
     dn->loaded = 1;
     dn->train_loaded = 0;               // the training snapshot (tcsfm_depthnet_load_device) no longer matches the weights
     return TCSFM_OK;
@@ -809,11 +811,10 @@ int tcsfm_sequence_depthnet(tcsfm_handle h, tcsfm_depthnet *dn) {
 namespace {
 // the two scaled-disparity planes of one group (tcsfm_depthnet::post_l / post_r), allocated on first use
 int dn_post_scratch(tcsfm_depthnet *dn, const char *fn) {
-    if (dn->post_l && dn->post_r) return TCSFM_OK;
-    const size_t bytes = (size_t)dn->max_images * dn->h->H * dn->h->W * sizeof(float);
-    hipError_t e = dn->post_l ? hipSuccess : hipMalloc((void **)&dn->post_l, bytes);
-    if (e == hipSuccess && !dn->post_r) e = hipMalloc((void **)&dn->post_r, bytes);
-    if (e != hipSuccess) return fail(dn->h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, (std::string(fn) + ": no memory for the disparity planes").c_str());
+    const size_t n = (size_t)dn->max_images * dn->h->H * dn->h->W;
+    hipError_t e = DEV_RESERVE(dn->post_l, n);
+    if (e == hipSuccess) e = DEV_RESERVE(dn->post_r, n);
+    if (e != hipSuccess) return fail_alloc(dn->h, e, (std::string(fn) + ": no memory for the disparity planes").c_str());
     return TCSFM_OK;
 }
 
@@ -845,7 +846,7 @@ int dn_group_disp_for_eigen(tcsfm_depthnet *dn, int g, const float *imgs, float 
 // to have ready).  The depths are the same bits in all three modes: one expression on one value.
 int dn_sequence_depths(tcsfm_depthnet *dn, hipStream_t stream, int n, const float *imgs, float *depth, float min_disp, float max_disp,
                        int disp_mode = TCSFM_SEQ_DISP_OFF, void *disp_store = nullptr, const double *ramp = nullptr) {
-    tcsfm_depthnet *q = dn->seq_clone;
+    tcsfm_depthnet *q = dn->seq_clone.get();
     const size_t hw = (size_t)q->h->H * q->h->W;
     q->stream = stream;
     for (int i0 = 0; i0 < n; i0 += q->max_images) {
@@ -926,10 +927,10 @@ int tcsfm_depthnet_load_device(tcsfm_depthnet *dn, int n, const char *const name
         const bool bn = p.g != nullptr;
         hipLaunchKernelGGL(k_dnb_fold_params, dim3(dn_blocks((long long)l.nw())), dim3(256), 0, s, (const float *)l.raw, p.cb ? (const float *)v : nullptr,
                            bn ? (const float *)v + l.cout : nullptr, (const float *)v + 2 * l.cout, (const float *)v + 3 * l.cout,
-                           (const float *)v + 4 * l.cout, l.w4, l.wt4, l.bias, l.cout, l.cin, l.ks, l.coutp);
+                           (const float *)v + 4 * l.cout, dn->w->w4[li], l.wt4, dn->w->bias[li], l.cout, l.cin, l.ks, l.coutp);
     }
-    HIPCHK(h, hipMemcpyAsync(dn->pw, pw, DN_HEAD_W * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(dn->pb, pb, sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(dn->w->pw, pw, DN_HEAD_W * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(dn->w->pb, pb, sizeof(float), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipGetLastError());
     dn->loaded = 1;
     dn->train_loaded = 1;
@@ -1017,8 +1018,8 @@ int tcsfm_depthnet_decode_backward(tcsfm_depthnet *dn, int N, const float *tape,
             return dn_decode_backward(dn, n, t, i0, d_disp + (size_t)i0 * t.sz[DN_TD_DISP], dsk, req, hw_ || hb_, i0 > 0);
         })) return rc;
     dn_param_out(dn, req, dn->enc_end, (int)dn->L.size());
-    if (hw_) HIPCHK(h, hipMemcpyAsync(hw_, dn->hacc, DN_HEAD_W * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    if (hb_) HIPCHK(h, hipMemcpyAsync(hb_, dn->hacc + DN_HEAD_W, sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    if (hw_) HIPCHK(h, hipMemcpyAsync(hw_, dn->train.hacc, DN_HEAD_W * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    if (hb_) HIPCHK(h, hipMemcpyAsync(hb_, dn->train.hacc + DN_HEAD_W, sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(h, hipGetLastError());
     return TCSFM_OK;
 }

@@ -1,6 +1,7 @@
 // Host side of the device optimiser (optim_kernel.h): the tensor and work tables built at create, the per-step table staged through a
 // ring of pinned slots, the arenas of the moments and of the snapshot, and the tcsfm_optim_* entry points.  Part of tcsfm_api.hip, the
-// library's only translation unit: included after the networks' host headers.
+// library's only translation unit: included after context.h (the owners of device_owned.h, fail_alloc) and the networks'
+// host headers.
 #pragma once
 
 struct tcsfm_optim {
@@ -8,31 +9,23 @@ struct tcsfm_optim {
     int kind = 0, n = 0, nwork = 0;
     std::vector<OptTensor> T;            // host mirror of the device tensor table
     std::vector<long long> step;         // per tensor: optimiser steps taken (torch's state['step'])
-    OptTensor *T_dev = nullptr;
-    OptWork *work_dev = nullptr;
-    float *moments = nullptr, *snap = nullptr;     // arenas: [exp_avg | exp_avg_sq] (Adam only), the snapshot (allocated by the first snapshot)
+    DevBuf<OptTensor> T_dev;
+    DevBuf<OptWork> work_dev;
+    DevBuf<float> moments, snap;                   // arenas: [exp_avg | exp_avg_sq] (Adam only), the snapshot (allocated by the first snapshot)
     size_t arena = 0;                    // floats of one arena: every tensor at its parameter's 16-byte phase
     bool has_snapshot = false;
     // Per-step tables (gradient pointers and scalars) go host -> pinned slot -> device slot -> kernel, all on the stream.  A slot is
     // rewritten only once the step that used it has finished (its event), so steps issued back to back each keep their own table.
     static constexpr int kRing = 4;
-    OptStep *stage_host = nullptr, *stage_dev = nullptr;     // [kRing][n]
-    hipEvent_t ring_ev[kRing] = {};
+    PinnedBuf<OptStep> stage_host;       // [kRing][n]
+    DevBuf<OptStep> stage_dev;
+    Events ring_ev;                      // kRing of them
     bool ring_used[kRing] = {};
     unsigned long long seq = 0;
 };
 
 namespace {
 int opt_blocks(int nwork) { return std::min(nwork, OPT_MAX_BLOCKS); }
-
-void opt_free(tcsfm_optim *o) {
-    // the stream may still run a step that reads the tables and writes the arenas
-    if (o->h->stream) (void)hipStreamSynchronize(o->h->stream);
-    for (int k = 0; k < tcsfm_optim::kRing; k++)
-        if (o->ring_ev[k]) { (void)hipEventSynchronize(o->ring_ev[k]); (void)hipEventDestroy(o->ring_ev[k]); }
-    (void)hipFree(o->T_dev); (void)hipFree(o->work_dev); (void)hipFree(o->moments); (void)hipFree(o->snap); (void)hipFree(o->stage_dev);
-    if (o->stage_host) (void)hipHostFree(o->stage_host);
-}
 
 // copy the host tensor table to the device (create, and the first snapshot, which adds the snapshot pointers)
 int opt_upload_tensors(tcsfm_optim *o) {
@@ -54,7 +47,9 @@ void opt_launch(tcsfm_optim *o, const OptStep *steps, const OptScalars &C) {
 void tcsfm_optim_destroy(tcsfm_optim *o) {
     if (!o) return;
     DeviceGuard dev_guard(o->h->device);
-    opt_free(o);
+    // the stream may still run a step that reads the tables and writes the arenas
+    if (o->h->stream) (void)hipStreamSynchronize(o->h->stream);
+    for (size_t k = 0; k < o->ring_ev.size(); k++) (void)hipEventSynchronize(o->ring_ev[k]);
     delete o;
 }
 
@@ -94,23 +89,23 @@ int tcsfm_optim_create(tcsfm_handle h, int kind, int n, float *const params[], c
         const long long phase = ((uintptr_t)params[i] >> 2) & 3, chunks = ((long long)numel[i] + phase + OPT_CHUNK - 1) / OPT_CHUNK;
         for (long long c = 0; c < chunks; c++) work.push_back({i, (int)c});
     }
-    hipError_t e = hipMalloc((void **)&o->T_dev, n * sizeof(OptTensor));
-    if (e == hipSuccess) e = hipMalloc((void **)&o->work_dev, std::max<size_t>(work.size(), 1) * sizeof(OptWork));
-    if (e == hipSuccess) e = hipMalloc((void **)&o->stage_dev, (size_t)tcsfm_optim::kRing * n * sizeof(OptStep));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&o->stage_host, (size_t)tcsfm_optim::kRing * n * sizeof(OptStep), hipHostMallocDefault);
+    hipError_t e = DEV_RESERVE(o->T_dev, n);
+    if (e == hipSuccess) e = DEV_RESERVE(o->work_dev, std::max<size_t>(work.size(), 1));
+    if (e == hipSuccess) e = DEV_RESERVE(o->stage_dev, (size_t)tcsfm_optim::kRing * n);
+    if (e == hipSuccess) e = o->stage_host.create((size_t)tcsfm_optim::kRing * n, hipHostMallocDefault);
     if (e == hipSuccess && kind == TCSFM_OPTIM_ADAM) {
-        e = hipMalloc((void **)&o->moments, 2 * o->arena * sizeof(float));
+        e = DEV_RESERVE(o->moments, 2 * o->arena);
         if (e == hipSuccess) e = hipMemsetAsync(o->moments, 0, 2 * o->arena * sizeof(float), h->stream);
         for (int i = 0; i < n; i++) { T[i].m = o->moments + at[i]; T[i].v = o->moments + o->arena + at[i]; }
     }
-    for (int k = 0; k < tcsfm_optim::kRing && e == hipSuccess; k++) e = hipEventCreateWithFlags(&o->ring_ev[k], hipEventDisableTiming);
+    if (e == hipSuccess) e = o->ring_ev.grow(tcsfm_optim::kRing);
     if (e == hipSuccess && !work.empty()) e = hipMemcpy(o->work_dev, work.data(), work.size() * sizeof(OptWork), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(o->T_dev, T.data(), n * sizeof(OptTensor), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);       // the arenas are zero before the handle's stream can change
     o->T = std::move(T);
     if (e != hipSuccess) {
         tcsfm_optim_destroy(o);
-        return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_optim_create: allocation failed");
+        return fail_alloc(h, e, "tcsfm_optim_create: allocation failed");
     }
     *out = o;
     return TCSFM_OK;
@@ -168,9 +163,9 @@ int tcsfm_optim_snapshot(tcsfm_optim *o) {
     if (int rc = drain_queued(h)) return rc;
     DeviceGuard dev_guard(h->device);
     if (!o->snap) {
-        hipError_t e = hipMalloc((void **)&o->snap, o->arena * sizeof(float));
+        hipError_t e = DEV_RESERVE(o->snap, o->arena);
         if (e == hipSuccess) e = hipMemsetAsync(o->snap, 0, o->arena * sizeof(float), h->stream);
-        if (e != hipSuccess) return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_optim_snapshot: allocation failed");
+        if (e != hipSuccess) return fail_alloc(h, e, "tcsfm_optim_snapshot: allocation failed");
         size_t at = 0;
         for (int i = 0; i < o->n; i++) {              // the offsets of tcsfm_optim_create
             at = (at + 3) / 4 * 4 + (((uintptr_t)o->T[i].p >> 2) & 3);

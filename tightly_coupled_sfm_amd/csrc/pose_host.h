@@ -1,7 +1,7 @@
 // Host side of the pose modes (include/tcsfm.h: tcsfm_refine, tcsfm_refine_window, the merged pose sequence of the queued calls,
 // tcsfm_linearize, tcsfm_linearize_window, tcsfm_loss_surface): one driver (PoseDriver) in steps.  What a call stages and which steps its
 // schedule has is call_plan.h's (no HIP there); here is what is launched, in which order, on the handle's stream.  Part of tcsfm_api.hip,
-// the library's only translation unit: included after Staging, the argument checks and the profiling brackets, before dense_host.h, which
+// the library's only translation unit: included after context.h (tcsfm_ctx, Staging, the argument checks, the profiling brackets), before dense_host.h, which
 // uses the helpers below (run_pack, init_params, lin_params, solve_params, launch_lin, launch_solve, the trace helpers).
 #pragma once
 #include "call_plan.h"
@@ -114,7 +114,7 @@ InitParams init_params(tcsfm_ctx *h, const tcsfm_opts *o, int N, const float *po
     I.pose = pose; I.log_scale = ls; I.K = K; I.st = h->state; I.pc = h->pconst; I.N = N; I.shared_image = shared;
     I.lambda0 = o->lambda0;
     I.K_mod = 0;
-    I.err = h->err_dev;
+    I.err = h->err_word.dev;
     I.pose_lin = (o->window_rule == TCSFM_WINDOW_REFERENCE && o->w_pose_consist > 0.f) ? h->pose_lin : nullptr;
     return I;
 }

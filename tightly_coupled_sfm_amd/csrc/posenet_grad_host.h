@@ -8,7 +8,7 @@ namespace {
 int pn_check_train(tcsfm_posenet *pn, int N, const char *fn) {
     tcsfm_ctx *h = pn->h;
     if (!pn->loaded) return fail(h, TCSFM_E_ARG, (std::string(fn) + ": no weights loaded").c_str());
-    if (!pn->owns_weights) return fail(h, TCSFM_E_ARG, (std::string(fn) + ": pn is a lane clone (the training calls run on the handle's own stream)").c_str());
+    if (pn->is_clone()) return fail(h, TCSFM_E_ARG, (std::string(fn) + ": pn is a lane clone (the training calls run on the handle's own stream)").c_str());
     if (N < 1 || N > pn->max_images) return fail(h, TCSFM_E_ARG, (std::string(fn) + ": N out of range").c_str());
     return TCSFM_OK;
 }
@@ -19,19 +19,18 @@ int pnb_prepare(tcsfm_posenet *pn) {
     hipError_t e = hipSuccess;
     for (int l = 0; l < 7 && e == hipSuccess; l++) {
         const PnLayer &L = pn->L[l];
-        if (!pn->wt4[l]) e = hipMalloc((void **)&pn->wt4[l], (size_t)L.ks * L.ks * L.cin * L.cout * sizeof(float));
+        e = DEV_RESERVE(pn->wt4[l], (size_t)L.ks * L.ks * L.cin * L.cout / 4);
     }
     size_t map = 0;
     for (int l = 0; l < 7; l++) map = std::max(map, (size_t)pn->L[l].oh * pn->L[l].ow * pn->L[l].cout);
-    for (int k = 0; k < 2 && e == hipSuccess; k++)
-        if (!pn->gbuf[k]) e = hipMalloc((void **)&pn->gbuf[k], (size_t)pn->max_images * map * sizeof(float));
-    if (e == hipSuccess && !pn->gss) e = hipMalloc((void **)&pn->gss, (size_t)pn->max_images * 32 * sizeof(float));
-    if (e != hipSuccess) return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_posenet_backward: allocation failed");
+    for (int k = 0; k < 2 && e == hipSuccess; k++) e = DEV_RESERVE(pn->gbuf[k], (size_t)pn->max_images * map);
+    if (e == hipSuccess) e = DEV_RESERVE(pn->gss, (size_t)pn->max_images * 32);
+    if (e != hipSuccess) return fail_alloc(h, e, "tcsfm_posenet_backward: allocation failed");
     if (!pn->wt_valid) {
-        hipLaunchKernelGGL(k_pnb_prep_t1, dim3(dn_blocks(49 * 6 * 16)), dim3(256), 0, h->stream, (const pn_f4 *)pn->w4[0], reinterpret_cast<float *>(pn->wt4[0]));
+        hipLaunchKernelGGL(k_pnb_prep_t1, dim3(dn_blocks(49 * 6 * 16)), dim3(256), 0, h->stream, (const pn_f4 *)pn->w->w4[0], reinterpret_cast<float *>(pn->wt4[0].p));
         for (int l = 1; l < 7; l++) {
             const PnLayer &L = pn->L[l];
-            hipLaunchKernelGGL(k_pnb_prep_t, dim3(dn_blocks((long long)L.ks * L.ks * L.cin * L.cout)), dim3(256), 0, h->stream, (const pn_f4 *)pn->w4[l],
+            hipLaunchKernelGGL(k_pnb_prep_t, dim3(dn_blocks((long long)L.ks * L.ks * L.cin * L.cout)), dim3(256), 0, h->stream, (const pn_f4 *)pn->w->w4[l],
                                pn->wt4[l], L.cin, L.cout, L.ks);
         }
         HIPCHK(h, hipGetLastError());
@@ -91,11 +90,11 @@ int pnb_walk(tcsfm_posenet *pn, int N, const float *imgs, const float *tape, con
             if (req && (req->w[l] || req->b[l] || req->g[l] || req->be[l])) last = l;
         if (last == 7) { HIPCHK(h, hipGetLastError()); return TCSFM_OK; }
     }
-    hipLaunchKernelGGL(k_pnb_head, dim3(dn_blocks((long long)N * npix7 * 256)), dim3(256), 0, s, d_pose, (const float *)pn->head_w, da, N, npix7);
+    hipLaunchKernelGGL(k_pnb_head, dim3(dn_blocks((long long)N * npix7 * 256)), dim3(256), 0, s, d_pose, (const float *)pn->w->head_w, da, N, npix7);
     for (int l = 6; l >= last; l--) {
         const PnLayer &L = pn->L[l];
         PnbNormParams P;
-        P.da = da; P.raw = tape + tl[l].raw; P.scsh = tape + tl[l].scsh; P.mr = tape + tl[l].mr; P.gamma = pn->gamma[l];
+        P.da = da; P.raw = tape + tl[l].raw; P.scsh = tape + tl[l].scsh; P.mr = tape + tl[l].mr; P.gamma = pn->w->gamma[l];
         P.ss = pn->gss; P.dz = da; P.N = N; P.npix = L.oh * L.ow; P.cout = L.cout;
         if (req && (req->be[l] || req->g[l])) pnw_chan(pn, P, 0, req->be[l], req->g[l]);
         hipLaunchKernelGGL(k_pnb_gsum, dim3(N, 16), dim3(256), 0, s, P);
@@ -106,7 +105,7 @@ int pnb_walk(tcsfm_posenet *pn, int N, const float *imgs, const float *tape, con
             if (l == 0 && d_imgs) {
                 const int hh = (L.ih + 1) / 2, wh = (L.iw + 1) / 2;
                 hipLaunchKernelGGL(k_pnb_dgrad1, dim3(dn_blocks((long long)hh * wh), 4, N), dim3(256), 0, s, (const float *)da,
-                                   (const float *)reinterpret_cast<float *>(pn->wt4[0]), d_imgs, L.ih, L.iw, L.oh, L.ow);
+                                   (const float *)reinterpret_cast<float *>(pn->wt4[0].p), d_imgs, L.ih, L.iw, L.oh, L.ow);
             }
             break;
         }

@@ -1,56 +1,53 @@
 // Host side of the PoseNet (models/pose_models.py:88-147) and the coupled pose loop (train_mono.py:64-80): the tcsfm_posenet_* entry points,
-// pose_loop and tcsfm_solve_pose_iteratively.  Part of tcsfm_api.hip, the library's only translation unit: included after the context
-// helpers (tcsfm_ctx, fail, HIPCHK, DeviceGuard, drain_queued, check_intrinsics, init_params) and before the sequence driver, which runs
+// pose_loop and tcsfm_solve_pose_iteratively.  Part of tcsfm_api.hip, the library's only translation unit: included after context.h
+// (tcsfm_ctx, fail, fail_alloc, HIPCHK, DEV_RESERVE, DeviceGuard, check_intrinsics), drain_queued and init_params, and before the sequence driver, which runs
 // pose_loop on its lanes.  include/tcsfm.h declares the entry points, so they have C linkage here.
 #pragma once
 
-struct tcsfm_posenet {
+// What a load fills and every instance's launches read: the prepared and the raw convolution weights (conv2d_wn's chain rule needs the raw
+// ones: tcsfm_posenet_param_backward; kept by both load paths), the biases, the GroupNorm parameters and the head.
+struct PnWeights {
+    DevBuf<pn_f4> w4[7];
+    DevBuf<float> bias[7], gamma[7], beta[7], raww[7];
+    DevBuf<float> head_w, head_b;
+};
+
+// The layer geometry and the work split: a function of the handle's frame size only.
+struct PnGeometry {
+    PnLayer L[7];
+    int nb_cfg[2][7] = {}, ks_cfg[2][7] = {};   // (output-channel blocks per wave, K split) per layer: [0] few images (latency), [1] many
+};
+
+// One instance: the primary (tcsfm_posenet_create) owns the weights; tcsfm_odometry_sequence runs the network on the handle's lanes, and
+// clone k works on lane k with its own activations and READS the primary's weights through `w`.  The primary outlives its clones
+// (tcsfm_posenet_destroy destroys them first).
+struct tcsfm_posenet : PnGeometry {
     tcsfm_ctx *h = nullptr;
     int max_images = 0, loaded = 0;
     int last_N = 0;              // images of the most recent evaluation (tcsfm_debug_posenet_layer reads its activations)
-    PnLayer L[7];
-    int nb_cfg[2][7] = {}, ks_cfg[2][7] = {};   // (output-channel blocks per wave, K split) per layer: [0] few images (latency), [1] many
-    pn_f4 *w4[7] = {};
-    float *bias[7] = {}, *gamma[7] = {}, *beta[7] = {};
-    float *act[7] = {}, *scsh[7] = {}, *part[7] = {};
-    float *head_w = nullptr, *head_b = nullptr;
-    float *in_buf = nullptr;     // [max_images,6,H,W] (tgt * valid | img_rec) written by the warp kernel
-    float *pose = nullptr;       // [max_images,6] running pose of the coupled loop
-    // tcsfm_odometry_sequence runs the network on the handle's lanes: clone k works on lane k with its own activations and
-    // borrows this object's weights
-    bool owns_weights = true;
+    PnWeights own;               // the primary's weights (empty in a clone)
+    const PnWeights *w = &own;   // the weights the launches read: the primary's
+    bool is_clone() const { return w != &own; }
+    DevBuf<float> act[7], scsh[7], part[7];
+    DevBuf<float> in_buf;        // [max_images,6,H,W] (tgt * valid | img_rec) written by the warp kernel
+    DevBuf<float> pose;          // [max_images,6] running pose of the coupled loop
     std::vector<tcsfm_posenet *> clones;
-    // tcsfm_posenet_backward (posenet_grad_host.h), all built at the first backward after a load: the transposed images of the
-    // prepared weights (layer 1: the plain [ky][kx][ci][co] image), two gradient maps [max_images][largest layer output] and the
+    // tcsfm_posenet_backward (posenet_grad_host.h), the primary's only, all built at the first backward after a load: the transposed images
+    // of the prepared weights (layer 1: the plain [ky][kx][ci][co] image), two gradient maps [max_images][largest layer output] and the
     // per-group sums [max_images][16][2]
-    pn_f4 *wt4[7] = {};
+    DevBuf<pn_f4> wt4[7];
     int wt_valid = 0;
-    float *gbuf[2] = {}, *gss = nullptr;
-    // tcsfm_posenet_param_backward (posenet_wgrad_host.h): the RAW weights of the load (conv2d_wn's chain rule needs them; kept by both
-    // load paths), and, built at the first parameter backward, the weight-gradient partials and the per-channel double partials
-    float *raww[7] = {};
-    float *wpart = nullptr;
-    double *cpart = nullptr;
+    DevBuf<float> gbuf[2], gss;
+    // tcsfm_posenet_param_backward (posenet_wgrad_host.h), built at the first parameter backward: the weight-gradient partials and the
+    // per-channel double partials
+    DevBuf<float> wpart;
+    DevBuf<double> cpart;
 };
 
 void tcsfm_posenet_destroy(tcsfm_posenet *pn) {
     if (!pn) return;
     for (tcsfm_posenet *c : pn->clones) tcsfm_posenet_destroy(c);
     DeviceGuard dev_guard(pn->h->device);
-    for (int l = 0; l < 7; l++) {
-        void *weights[] = {pn->w4[l], pn->bias[l], pn->gamma[l], pn->beta[l]}, *scratch[] = {pn->act[l], pn->scsh[l], pn->part[l]};
-        if (pn->owns_weights) for (void *p : weights) if (p) (void)hipFree(p);
-        for (void *p : scratch) if (p) (void)hipFree(p);
-    }
-    void *weights[] = {pn->head_w, pn->head_b, pn->raww[0], pn->raww[1], pn->raww[2], pn->raww[3], pn->raww[4], pn->raww[5], pn->raww[6]};
-    void *scratch[] = {pn->in_buf, pn->pose};
-    if (pn->owns_weights) for (void *p : weights) if (p) (void)hipFree(p);
-    for (void *p : scratch) if (p) (void)hipFree(p);
-    if (pn->owns_weights) {
-        for (int l = 0; l < 7; l++) if (pn->wt4[l]) (void)hipFree(pn->wt4[l]);
-        void *grad[] = {pn->gbuf[0], pn->gbuf[1], pn->gss, pn->wpart, pn->cpart};
-        for (void *p : grad) if (p) (void)hipFree(p);
-    }
     delete pn;
 }
 
@@ -60,13 +57,13 @@ static hipError_t pn_alloc_scratch(tcsfm_posenet *pn) {
     const int max_images = pn->max_images;
     for (int l = 0; l < 7 && e == hipSuccess; l++) {
         const PnLayer &L = pn->L[l];
-        e = hipMalloc((void **)&pn->act[l], (size_t)L.ksplit * max_images * L.oh * L.ow * L.cout * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void **)&pn->scsh[l], (size_t)max_images * L.cout * 2 * sizeof(float));
+        e = DEV_RESERVE(pn->act[l], (size_t)L.ksplit * max_images * L.oh * L.ow * L.cout);
+        if (e == hipSuccess) e = DEV_RESERVE(pn->scsh[l], (size_t)max_images * L.cout * 2);
         if (e == hipSuccess && (pn->ks_cfg[0][l] == 1 || pn->ks_cfg[1][l] == 1))
-            e = hipMalloc((void **)&pn->part[l], (size_t)max_images * std::max((L.oh * L.ow + 63) / 64, L.oh * ((L.ow + 63) / 64)) * L.cout * 2 * sizeof(float));
+            e = DEV_RESERVE(pn->part[l], (size_t)max_images * std::max((L.oh * L.ow + 63) / 64, L.oh * ((L.ow + 63) / 64)) * L.cout * 2);
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&pn->in_buf, (size_t)max_images * 6 * pn->h->H * pn->h->W * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&pn->pose, (size_t)max_images * 6 * sizeof(float));
+    if (e == hipSuccess) e = DEV_RESERVE(pn->in_buf, (size_t)max_images * 6 * pn->h->H * pn->h->W);
+    if (e == hipSuccess) e = DEV_RESERVE(pn->pose, (size_t)max_images * 6);
     return e;
 }
 
@@ -75,13 +72,9 @@ static tcsfm_posenet *pn_for_lane(tcsfm_posenet *pn, tcsfm_ctx *c) {
     if (pn->h == c) return pn;
     for (tcsfm_posenet *q : pn->clones)
         if (q->h == c) return q;
-    tcsfm_posenet *q = new tcsfm_posenet(*pn);          // geometry, work split, weight pointers
-    q->h = c; q->owns_weights = false; q->clones.clear();
-    for (int l = 0; l < 7; l++) q->act[l] = q->scsh[l] = q->part[l] = nullptr;
-    q->in_buf = q->pose = nullptr;
-    for (int l = 0; l < 7; l++) q->wt4[l] = nullptr;
-    q->gbuf[0] = q->gbuf[1] = q->gss = nullptr; q->wt_valid = 0;
-    q->wpart = nullptr; q->cpart = nullptr;
+    tcsfm_posenet *q = new tcsfm_posenet();
+    static_cast<PnGeometry &>(*q) = *pn;
+    q->h = c; q->max_images = pn->max_images; q->loaded = pn->loaded; q->w = pn->w;
     if (pn_alloc_scratch(q) != hipSuccess) { tcsfm_posenet_destroy(q); return nullptr; }
     pn->clones.push_back(q);
     return q;
@@ -121,17 +114,15 @@ int tcsfm_posenet_create(tcsfm_handle h, int max_images, tcsfm_posenet **out) {
         L.ksplit = std::max(pn->ks_cfg[0][l], pn->ks_cfg[1][l]);     // allocation; the launch sets the split it uses
         if (L.oh < 1 || L.ow < 1) { tcsfm_posenet_destroy(pn); return fail(h, TCSFM_E_ARG, "tcsfm_posenet_create: image too small for seven stride-2 layers"); }
         const size_t nw4 = (size_t)L.kgroups * 4 * L.cout;
-        if (e == hipSuccess) e = hipMalloc((void **)&pn->w4[l], nw4 * sizeof(pn_f4));
-        if (e == hipSuccess) e = hipMalloc((void **)&pn->bias[l], L.cout * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void **)&pn->gamma[l], L.cout * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void **)&pn->beta[l], L.cout * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void **)&pn->raww[l], (size_t)L.cout * L.cin * L.ks * L.ks * sizeof(float));
+        if (e == hipSuccess) e = DEV_RESERVE(pn->own.w4[l], nw4);
+        for (DevBuf<float> *b : {&pn->own.bias[l], &pn->own.gamma[l], &pn->own.beta[l]}) if (e == hipSuccess) e = DEV_RESERVE(*b, L.cout);
+        if (e == hipSuccess) e = DEV_RESERVE(pn->own.raww[l], (size_t)L.cout * L.cin * L.ks * L.ks);
         ih = L.oh; iw = L.ow;
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&pn->head_w, 6 * 256 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&pn->head_b, 6 * sizeof(float));
+    if (e == hipSuccess) e = DEV_RESERVE(pn->own.head_w, 6 * 256);
+    if (e == hipSuccess) e = DEV_RESERVE(pn->own.head_b, 6);
     if (e == hipSuccess) e = pn_alloc_scratch(pn);
-    if (e != hipSuccess) { tcsfm_posenet_destroy(pn); return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_posenet_create: allocation failed"); }
+    if (e != hipSuccess) { tcsfm_posenet_destroy(pn); return fail_alloc(h, e, "tcsfm_posenet_create: allocation failed"); }
     *out = pn;
     return TCSFM_OK;
 }
@@ -146,16 +137,16 @@ int tcsfm_posenet_load(tcsfm_posenet *pn, const float *const conv_w[7], const fl
         const PnLayer &L = pn->L[l];
         if (!conv_w[l]) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_load: NULL convolution weight");
         const size_t nw = (size_t)L.cout * L.cin * L.ks * L.ks;
-        HIPCHK(h, hipMemcpyAsync(pn->raww[l], conv_w[l], nw * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_pn_prep, dim3(L.cout), dim3(256), 0, h->stream, (const float *)pn->raww[l], pn->w4[l], L.cin, L.cout, L.ks, l == 0 ? 1 : 0, 1);
+        HIPCHK(h, hipMemcpyAsync(pn->w->raww[l], conv_w[l], nw * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_pn_prep, dim3(L.cout), dim3(256), 0, h->stream, (const float *)pn->w->raww[l], pn->w->w4[l], L.cin, L.cout, L.ks, l == 0 ? 1 : 0, 1);
         HIPCHK(h, hipStreamSynchronize(h->stream));    // the caller's host arrays are free once this returns; loading happens once per model
         std::vector<float> ones(L.cout, 1.f), zeros(L.cout, 0.f);
-        HIPCHK(h, hipMemcpy(pn->bias[l], conv_b && conv_b[l] ? conv_b[l] : zeros.data(), L.cout * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(pn->gamma[l], gn_w && gn_w[l] ? gn_w[l] : ones.data(), L.cout * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(pn->beta[l], gn_b && gn_b[l] ? gn_b[l] : zeros.data(), L.cout * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(pn->w->bias[l], conv_b && conv_b[l] ? conv_b[l] : zeros.data(), L.cout * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(pn->w->gamma[l], gn_w && gn_w[l] ? gn_w[l] : ones.data(), L.cout * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(pn->w->beta[l], gn_b && gn_b[l] ? gn_b[l] : zeros.data(), L.cout * sizeof(float), hipMemcpyHostToDevice));
     }
-    HIPCHK(h, hipMemcpy(pn->head_w, head_w, 6 * 256 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(pn->head_b, head_b, 6 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(pn->w->head_w, head_w, 6 * 256 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(pn->w->head_b, head_b, 6 * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(h, hipGetLastError());
     pn->loaded = 1;
     pn->wt_valid = 0;        // the backward's transposed images follow w4: rebuilt at the next tcsfm_posenet_backward
@@ -169,7 +160,7 @@ int tcsfm_posenet_load_device(tcsfm_posenet *pn, const float *const conv_w[7], c
     if (!pn) return TCSFM_E_ARG;
     tcsfm_ctx *h = pn->h;
     if (!conv_w || !head_w || !head_b) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_load_device: NULL argument");
-    if (!pn->owns_weights) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_load_device: pn is a lane clone");
+    if (pn->is_clone()) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_load_device: pn is a lane clone");
     for (int l = 0; l < 7; l++)
         if (!conv_w[l]) return fail(h, TCSFM_E_ARG, "tcsfm_posenet_load_device: NULL convolution weight");
     if (int rc_q = drain_queued(h)) return rc_q;
@@ -178,17 +169,17 @@ int tcsfm_posenet_load_device(tcsfm_posenet *pn, const float *const conv_w[7], c
     for (int l = 0; l < 7; l++) {
         const PnLayer &L = pn->L[l];
         const size_t nw = (size_t)L.cout * L.cin * L.ks * L.ks, nc = L.cout * sizeof(float);
-        HIPCHK(h, hipMemcpyAsync(pn->raww[l], conv_w[l], nw * sizeof(float), hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(k_pn_prep, dim3(L.cout), dim3(256), 0, s, (const float *)pn->raww[l], pn->w4[l], L.cin, L.cout, L.ks, l == 0 ? 1 : 0, 1);
+        HIPCHK(h, hipMemcpyAsync(pn->w->raww[l], conv_w[l], nw * sizeof(float), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_pn_prep, dim3(L.cout), dim3(256), 0, s, (const float *)pn->w->raww[l], pn->w->w4[l], L.cin, L.cout, L.ks, l == 0 ? 1 : 0, 1);
         const float *src[3] = {conv_b ? conv_b[l] : nullptr, gn_w ? gn_w[l] : nullptr, gn_b ? gn_b[l] : nullptr};
-        float *dst[3] = {pn->bias[l], pn->gamma[l], pn->beta[l]};
+        float *dst[3] = {pn->w->bias[l], pn->w->gamma[l], pn->w->beta[l]};
         for (int k = 0; k < 3; k++) {
             if (src[k]) HIPCHK(h, hipMemcpyAsync(dst[k], src[k], nc, hipMemcpyDeviceToDevice, s));
             else hipLaunchKernelGGL(k_pnw_fill, dim3((L.cout + 255) / 256), dim3(256), 0, s, dst[k], L.cout, k == 1 ? 1.f : 0.f);
         }
     }
-    HIPCHK(h, hipMemcpyAsync(pn->head_w, head_w, 6 * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(pn->head_b, head_b, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(pn->w->head_w, head_w, 6 * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(pn->w->head_b, head_b, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipGetLastError());
     pn->loaded = 1;
     pn->wt_valid = 0;
@@ -241,7 +232,7 @@ int pn_run(tcsfm_posenet *pn, int N, const float *imgA, long long strideA, const
         P.imgA = imgA; P.imgB = imgB; P.strideA = strideA; P.strideB = strideB; P.win_B = win_B; P.win_S = win_S;
         if (wo) P.win_off = *wo;
         P.in = l > 0 ? pn->act[l - 1] : nullptr; P.scsh = l > 0 ? pn->scsh[l - 1] : nullptr;
-        P.w4 = pn->w4[l]; P.bias = pn->bias[l]; P.out = pn->act[l]; P.part = L.ksplit == 1 ? pn->part[l] : nullptr; P.L = L; P.N = N;
+        P.w4 = pn->w->w4[l]; P.bias = pn->w->bias[l]; P.out = pn->act[l]; P.part = L.ksplit == 1 ? pn->part[l] : nullptr; P.L = L; P.N = N;
         dim3 grid((L.oh * L.ow + 64 * pb - 1) / (64 * pb), L.cout / (16 * nb), N * L.ksplit);
         if (l == 0) {            // LDS-staged first layer: one workgroup per 64-pixel segment of two output rows
             grid = dim3(((L.oh + 1) / 2) * ((L.ow + 63) / 64), 1, N);
@@ -257,7 +248,7 @@ int pn_run(tcsfm_posenet *pn, int N, const float *imgA, long long strideA, const
         // evaluation (profiles/r03_posenet_fused_tail_kernel_stats.csv, _timing.jsonl) -- a separate 16 N-workgroup pass is faster.
         PnStatsParams S;
         S.part = P.part; S.tiles = (int)grid.x;
-        S.out = pn->act[l]; S.bias = pn->bias[l]; S.gamma = pn->gamma[l]; S.beta = pn->beta[l]; S.scsh = pn->scsh[l];
+        S.out = pn->act[l]; S.bias = pn->w->bias[l]; S.gamma = pn->w->gamma[l]; S.beta = pn->w->beta[l]; S.scsh = pn->scsh[l];
         S.N = N; S.npix = L.oh * L.ow; S.cout = L.cout; S.ksplit = L.ksplit;
         S.mr = tape ? tape + tl[l].mr : nullptr;
         hipLaunchKernelGGL(k_pn_stats, dim3(N, 16), dim3(256), 0, h->stream, S);
@@ -267,7 +258,7 @@ int pn_run(tcsfm_posenet *pn, int N, const float *imgA, long long strideA, const
         }
     }
     PnHeadParams Hd;
-    Hd.x = pn->act[6]; Hd.scsh = pn->scsh[6]; Hd.w = pn->head_w; Hd.b = pn->head_b; Hd.pose = pose; Hd.stacked = stacked;
+    Hd.x = pn->act[6]; Hd.scsh = pn->scsh[6]; Hd.w = pn->w->head_w; Hd.b = pn->w->head_b; Hd.pose = pose; Hd.stacked = stacked;
     Hd.npix = pn->L[6].oh * pn->L[6].ow; Hd.accumulate = accumulate; Hd.it = it; Hd.iters = iters;
     hipLaunchKernelGGL(k_pn_head, dim3(N), dim3(256), 0, h->stream, Hd);
     HIPCHK(h, hipGetLastError());

@@ -35,16 +35,16 @@ PnwSplit pnw_split(long long R, const PnLayer &L) {
 int pnw_prepare(tcsfm_posenet *pn) {
     tcsfm_ctx *h = pn->h;
     hipError_t e = hipSuccess;
-    if (!pn->wpart) {
+    {
         size_t fl = 0;
         for (int l = 0; l < 7; l++) {
             const PnLayer &L = pn->L[l];
             fl = std::max(fl, (size_t)pnw_want((long long)pn->max_images * L.oh * L.ow, L) * L.cout * L.cin * L.ks * L.ks);
         }
-        e = hipMalloc((void **)&pn->wpart, fl * sizeof(float));
+        e = DEV_RESERVE(pn->wpart, fl);
     }
-    if (e == hipSuccess && !pn->cpart) e = hipMalloc((void **)&pn->cpart, (size_t)16384 * 2 * sizeof(double));
-    if (e != hipSuccess) return fail(h, e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP, "tcsfm_posenet_param_backward: allocation failed");
+    if (e == hipSuccess) e = DEV_RESERVE(pn->cpart, (size_t)16384 * 2);
+    if (e != hipSuccess) return fail_alloc(h, e, "tcsfm_posenet_param_backward: allocation failed");
     return TCSFM_OK;
 }
 
@@ -76,6 +76,6 @@ void pnw_wgrad(tcsfm_posenet *pn, int l, int N, const float *dz, const float *x,
     const int n = L.cin * L.ks * L.ks;
     const long long E = (long long)L.cout * n;
     hipLaunchKernelGGL(k_pnw_psum, dim3(dn_blocks(E)), dim3(256), 0, s, (const float *)pn->wpart, dw, E, sp.parts);
-    hipLaunchKernelGGL(k_pnw_wstd, dim3(L.cout), dim3(256), 0, s, (const float *)pn->raww[l], dw, n);
+    hipLaunchKernelGGL(k_pnw_wstd, dim3(L.cout), dim3(256), 0, s, (const float *)pn->w->raww[l], dw, n);
 }
 }  // namespace

@@ -145,23 +145,19 @@ int SeqCall::reserve() {
     if (disp_mode != TCSFM_SEQ_DISP_OFF) {                 // every frame's plane, by absolute frame index; grown when a call needs more
         RESERVE(h, h->seq_disp_dev, (size_t)T * hw * (disp_mode == TCSFM_SEQ_DISP_POST ? sizeof(double) : sizeof(float)));
         if (disp_mode == TCSFM_SEQ_DISP_POST) {            // the clone's two planes of one group and the ramp
-            if (int rc = dn_post_scratch(h->seq_dn->seq_clone, entry)) return rc;
+            if (int rc = dn_post_scratch(h->seq_dn->seq_clone.get(), entry)) return rc;
             if (!(disp_ramp = flip_ramp_device(h))) return TCSFM_E_HIP;
         }
     }
     if (!h->seq_copy) {   // high priority: a hardware queue outside the pool the normal-priority streams share (a copy stream that lands in
         int lo = 0, hi = 0;   // a lane's queue parks its slot-recycling waits in front of that lane's kernels), and copies go first anyway
         HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(h, hipStreamCreateWithPriority(&h->seq_copy, hipStreamNonBlocking, hi));
+        HIPCHK(h, h->seq_copy.create_with_priority(hi));
     }
-    auto events = [&](std::vector<hipEvent_t> &v, size_t n) -> int {
-        while (v.size() < n) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); v.push_back(e); }
-        return TCSFM_OK;
-    };
-    if (int rc = events(h->seq_copied, (size_t)p.R)) return rc;
-    if (int rc = events(h->seq_raw, staged ? (size_t)p.R : 0)) return rc;
-    if (staged && !h->seq_pack) HIPCHK(h, hipStreamCreateWithFlags(&h->seq_pack, hipStreamNonBlocking));
-    if (int rc = events(h->seq_done, (size_t)p.ND + 1)) return rc;      // the calls' ND and one for the small inputs
+    HIPCHK(h, h->seq_copied.grow((size_t)p.R));
+    HIPCHK(h, h->seq_raw.grow(staged ? (size_t)p.R : 0));
+    if (staged && !h->seq_pack) HIPCHK(h, h->seq_pack.create());
+    HIPCHK(h, h->seq_done.grow((size_t)p.ND + 1));      // the calls' ND and one for the small inputs
     lane.resize(p.L); net.assign(p.L, nullptr); ls.resize(p.L);
     for (int l = 0; l < p.L; l++) {
         tcsfm_ctx *c = lane[l] = l == 0 ? h : h->lanes[l - 1];

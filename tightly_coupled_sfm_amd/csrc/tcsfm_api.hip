@@ -1,7 +1,8 @@
 // tcsfm_api.hip -- C ABI (include/tcsfm.h) over the gfx950 kernels in kernels.h.
-// Host logic only: the guard bands, the handle, staging and the argument checks, create / destroy / stream entries and the operator entry
-// points.  The drivers are headers of this translation unit, included where their helpers are first needed: pose_host.h (the pose modes),
-// dense_host.h (the dense modes), call_host.h (graph replay, queued calls, lanes), sequence_host.h and the networks' hosts.
+// Host logic only: create / destroy / stream entries and the operator entry points.  The handle, staging and the argument checks are
+// context.h's, over the owners and guard bands of device_owned.h.  The drivers are headers of this translation unit, included where their
+// helpers are first needed: pose_host.h (the pose modes), dense_host.h (the dense modes), call_host.h (graph replay, queued calls, lanes),
+// sequence_host.h and the networks' hosts.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -39,492 +40,7 @@
 
 using namespace tc;
 
-// ---- guard bands (TCSFM_DEBUG_GUARDS=1; tcsfm_debug_check_guards): every device allocation of this library gets 4 KB filled with a pattern
-// in front of it and behind it; the check reads the bands back and reports the allocations whose bands were written to.  A kernel's
-// out-of-bounds WRITE into neighbouring scratch corrupts results silently (ADVICE r04 #1 went unnoticed for a round: hipMalloc's granularity
-// hid it) and GPU AddressSanitizer is not available on this pool: the GPU test suite runs with the bands on instead (tests/conftest.py).
-// Off (the default) the two functions are hipMalloc / hipFree themselves.
-#include <mutex>
-namespace tcguard {
-constexpr size_t kBand = 4096;
-constexpr unsigned char kFill = 0xA5;
-struct Rec { char *base; size_t bytes; const char *file; int line; bool reported; };      // file: the call site's __FILE__
-inline const char *at_file(const Rec &r) { const char *s = strrchr(r.file, '/'); return s ? s + 1 : r.file; }      // its base name, for the messages
-inline std::mutex &mtx() { static std::mutex m; return m; }
-inline std::vector<Rec> &recs() { static std::vector<Rec> r; return r; }
-inline bool on() { static const bool v = getenv("TCSFM_DEBUG_GUARDS") && atoi(getenv("TCSFM_DEBUG_GUARDS")) != 0; return v; }
-inline hipError_t alloc(void **p, size_t bytes, const char *file, int line) {
-    if (!on()) return (hipMalloc)(p, bytes);
-    char *base = nullptr;
-    const size_t padded = (bytes + 255) / 256 * 256;            // (the rear band starts at the next 256-byte boundary: the user pointer keeps hipMalloc's alignment)
-    hipError_t e = (hipMalloc)((void **)&base, padded + 2 * kBand);
-    if (e != hipSuccess) return e;
-    e = hipMemset(base, kFill, kBand);
-    if (e == hipSuccess) e = hipMemset(base + kBand + bytes, kFill, padded - bytes + kBand);
-    if (e != hipSuccess) { (void)(hipFree)(base); return e; }
-    std::lock_guard<std::mutex> lk(mtx());
-    recs().push_back({base, bytes, file, line, false});
-    *p = base + kBand;
-    return hipSuccess;
-}
-// number of bytes of the two bands of r that no longer hold the pattern (device synchronised by the copies)
-inline long damaged(const Rec &r, long *first_off) {
-    const size_t padded = (r.bytes + 255) / 256 * 256, rear = padded - r.bytes + kBand;
-    std::vector<unsigned char> host(kBand + rear);
-    if (hipMemcpy(host.data(), r.base, kBand, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    if (hipMemcpy(host.data() + kBand, r.base + kBand + r.bytes, rear, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    long bad = 0;
-    for (size_t i = 0; i < host.size(); i++)
-        if (host[i] != kFill) { if (!bad && first_off) *first_off = i < kBand ? (long)i - (long)kBand : (long)(r.bytes + (i - kBand)); bad++; }
-    return bad;
-}
-inline hipError_t release(void *p) {
-    if (!on() || !p) return (hipFree)(p);
-    std::lock_guard<std::mutex> lk(mtx());
-    for (size_t i = 0; i < recs().size(); i++)
-        if (recs()[i].base + kBand == (char *)p) {
-            long off = 0;
-            const long bad = recs()[i].reported ? 0 : damaged(recs()[i], &off);
-            if (bad > 0) fprintf(stderr, "tcsfm guard: allocation of %zu bytes (%s:%d) freed with %ld band bytes overwritten, first at offset %ld\n", recs()[i].bytes, at_file(recs()[i]), recs()[i].line, bad, off);
-            char *base = recs()[i].base;
-            recs().erase(recs().begin() + i);
-            return (hipFree)(base);
-        }
-    return (hipFree)(p);      // (not one of ours)
-}
-// how many of the live allocations `ps` have a damaged band (reported on stderr once each); -1: a copy failed; guards off: 0.  For an entry that
-// frees its allocations before it returns: tcsfm_debug_check_guards sees live records only, and release() can only print
-inline int damaged_among(const std::vector<void *> &ps) {
-    if (!on()) return 0;
-    std::lock_guard<std::mutex> lk(mtx());
-    int bad_allocs = 0;
-    for (void *p : ps)
-        for (auto &r : recs())
-            if (r.base + kBand == (char *)p) {
-                long off = 0;
-                const long bad = damaged(r, &off);
-                if (bad < 0) return -1;
-                if (bad > 0) {
-                    bad_allocs++;
-                    if (!r.reported)
-                        fprintf(stderr, "tcsfm guard: allocation of %zu bytes (%s:%d): %ld band bytes overwritten, first at offset %ld of the allocation\n", r.bytes, tcguard::at_file(r), r.line, bad, off);
-                    r.reported = true;
-                }
-            }
-    return bad_allocs;
-}
-}  // namespace tcguard
-#define hipMalloc(p, bytes) tcguard::alloc((void **)(p), (bytes), __FILE__, __LINE__)
-#define hipFree(p) tcguard::release((void *)(p))
-
-namespace {
-
-// (the tile geometry of the hot kernel and the layout constants: layout.h)
-
-thread_local std::string g_create_error;
-
-}  // namespace
-
-struct tcsfm_ctx;
-
-// One grow-only device buffer: p holds cap elements (byte buffers are DevBuf<char>).  reserve() -- through RESERVE, which hands the call
-// site to the guard bands -- keeps a buffer that is large enough; otherwise it frees it, leaves the buffer empty (so it stays after a
-// failed allocation) and allocates n elements.  Whoever may still be using the old buffer on a stream is the caller's to wait for.
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    int reserve(tcsfm_ctx *h, size_t n, const char *file, int line);      // TCSFM_OK, or TCSFM_E_HIP with h->err set
-    void release() {       // tcsfm_destroy
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-    }
-};
-#define RESERVE(h, buf, n)                                                                           \
-    do {                                                                                             \
-        if (int rc_reserve_ = (buf).reserve((h), (n), __FILE__, __LINE__)) return rc_reserve_;       \
-    } while (0)
-
-// The scratch of the dense modes (dense_host.h), allocated by whichever mode first needs a buffer, at the handle's capacity for it
-// (dense_plan.h: dense_caps): never re-sized while the handle lives, captured call graphs bake the pointers in.
-struct DenseScratch {
-    DevBuf<float> sel_maps;                            // dense window modes: the forward pairs' diff | valid maps, [2][max_pairs][H*W]
-    DevBuf<float> dense_rec, depth0;                   // per-pixel records and prior centres of the pair-form dense kernels
-    DevBuf<double> delta;                              // ... and their pose steps
-    DevBuf<float> dense_rec2, depth_alt;               // ... second record / depth buffers of the fused back-substitution (ping-pong)
-    DevBuf<float> dense_rec_acc, depth_acc;            // dense LM: accepted per-pixel records / depth maps
-    DevBuf<int> lm_accept;
-    // joint dense modes (one depth map per target shared by its S forward pairs): per-pixel records, workgroup records, per-target state
-    DevBuf<float> jrec, jrec_acc, jblockrec, jdepth_acc;
-    DevBuf<JointState> jstate;
-    DevBuf<double> jdelta;
-    DevBuf<double> jpart;                              // split record sums of the joint solve (JointSolveParams::nsplit): [2][8][NACC] fp64
-    DevBuf<int> jtick;                                 // ... and their tickets, zero between launches
-    // dense mode on the reference's loss (dense_ref_kernel.h): mask counts, fixed-point scatter sums, linearisation export
-    DevBuf<int> dref_norms;
-    DevBuf<long long> dref_ext;
-    DevBuf<double> dref_export;
-    DevBuf<float> dref_smooth;                         // l_smooth: [targets][2] mean of the sigmoid disparity, the target's whole term (k_dref_smooth)
-    DevBuf<float> qres_rho, qres_rec;                  // TCSFM_DEPTH_QUARTER: [2][targets][H/4 * W/4] cell unknowns, [targets][cells][JREC] cell records
-    // free source depth maps (opts.free_source_depths): the inverse pairs as groups of one source
-    DevBuf<float> jrec_src;
-    DevBuf<JointState> jstate_src;
-    DevBuf<double> jdelta_src;
-    DevBuf<long long> dref_ext_src;
-    DevBuf<float> qres_rho_src, qres_rec_src;          // ... in the quarter-resolution parametrisation
-    void release() {       // tcsfm_destroy
-        for (DevBuf<float> *b : {&sel_maps, &dense_rec, &depth0, &dense_rec2, &depth_alt, &dense_rec_acc, &depth_acc, &jrec, &jrec_acc, &jblockrec, &jdepth_acc,
-                                 &dref_smooth, &qres_rho, &qres_rec, &jrec_src, &qres_rho_src, &qres_rec_src})
-            b->release();
-        for (DevBuf<double> *b : {&delta, &jdelta, &jpart, &dref_export, &jdelta_src}) b->release();
-        for (DevBuf<int> *b : {&lm_accept, &jtick, &dref_norms}) b->release();
-        dref_ext.release(); dref_ext_src.release(); jstate.release(); jstate_src.release();
-    }
-};
-
-struct tcsfm_ctx {
-    int device = 0, H = 0, W = 0, max_pairs = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    float4 *tgtpack = nullptr, *srcpack = nullptr;
-    float *depth_work = nullptr;
-    float *partials = nullptr, *blockrec = nullptr;
-    int *tickets = nullptr;
-    PairState *state = nullptr;
-    PairConst *pconst = nullptr;
-    double *lin_out = nullptr;   // device [max_pairs][7*7+7+4]
-    float *pose_dev = nullptr, *ls_dev = nullptr, *K_dev = nullptr, *stats_dev = nullptr;
-    int tiles_x = 0, tiles_y = 0, nblk = 0, ngrp = 0, ngrp_pad = 0, stats_cap_iters = 0;
-    int nblk_alloc = 0, ngrp_alloc = 0;   // scratch capacity of the pose path and of the pair-form dense kernels (16 x 16 tiles or coarser)
-    DenseScratch dense;                    // the dense modes' scratch, allocated on first use
-    DenseCaps caps;                        // ... and every buffer's capacity (dense_plan.h), fixed at create
-    hipStream_t aux_stream = nullptr;  // joint dense mode: the inverse pairs' refinement runs beside the forward group's (fork / join by events)
-    hipEvent_t aux_fork = nullptr, aux_join = nullptr;
-    // tcsfm_warp_backward (warp_grad_kernel.h), allocated on first use: workgroup records of the pose gradient [max_pairs][blocks][12],
-    // fixed-point scatter sums [max_pairs][H*W], per-item max |g_proj_depth| (bit patterns)
-    double *wgrad_rec = nullptr;
-    long long *wgrad_fix = nullptr;
-    unsigned *wgrad_gmax = nullptr;
-    // tcsfm_photometric_backward (photo_grad_kernel.h), allocated on first use: the warp's forward (img_rec | proj_depth | comp_depth) and
-    // the cotangents that reach it (g_rec | g_proj_depth | g_comp_depth), each [max_pairs][5][H*W]
-    float *pgrad_fwd = nullptr, *pgrad_cot = nullptr;
-    unsigned *scale_keys = nullptr, *scale_hist = nullptr;   // scale recovery scratch (keys, 256 bins + 4 state words)
-    long long *dbg_stamps = nullptr;  // TCSFM_DEBUG_STAMPS=1: 8 wall-clock stamps of the last k_solve launch (100 MHz ticks)
-    std::vector<DevBuf<char>> stage;    // device staging for host-pointer calls (Staging), in bytes
-    std::string err;
-    // event profiling (tcsfm_profile_*): one (start, stop, class) triple per bracketed launch
-    int *err_host = nullptr, *err_dev = nullptr;   // host-mapped status word of the device-side guards (host / device address)
-    // lanes (tcsfm_set_lanes): lane k >= 1 is a child handle with its own stream and scratch, so that several refine calls are
-    // in flight at once; lane 0 is this handle.  in_ev orders a lane behind the work queued on the parent's stream at call time,
-    // done_ev is what tcsfm_lane_wait makes the parent's stream wait for.
-    std::vector<tcsfm_ctx *> lanes;
-    hipEvent_t in_ev = nullptr, done_ev = nullptr;
-    std::vector<hipEvent_t> marks;   // tcsfm_lane_event: a ring of events handed out to the caller
-    size_t mark_next = 0;
-    // tcsfm_refine_sequence: device ring of frames, copy stream, per-slot / per-window events, pose staging (allocated on first use)
-    DevBuf<float> seq_img, seq_depth;  // [slots][3][H][W] and [slots][H][W]: ring slots, then mirror slots
-    DevBuf<float> seq_pose_in, seq_pose_out, seq_ls_out;      // [windows][pairs][6 | 6 | 1], per call in the window form's stacked order
-    DevBuf<float> seq_K;               // one copy of K per window of a call
-    DevBuf<float4> seq_fpack;          // frame-level pack cache of the ring: [slots][H+2][W+2] (rgb, depth) + [slots][H][W] depth planes,
-    DevBuf<float> seq_fdepth;          // for as many slots as seq_depth holds
-    int *pair_idx = nullptr;           // [2][max_pairs] ring slots of every pair's source pack / target depth plane (k_pack_cached)
-    DevBuf<float> seq_dense;           // tcsfm_refine_dense_sequence: refined depth maps of all windows, per-window order (the parent's only)
-    DevBuf<float> seq_dense_tmp;       // ... this context's stacked maps of one call (every lane's, lane 0 included)
-    hipStream_t seq_copy = nullptr;
-    std::vector<hipEvent_t> seq_copied, seq_done, seq_raw;      // per chunk: frames usable by the lanes / per call: done / per chunk: raw frames landed
-    hipStream_t seq_pack = nullptr;    // k_frame_pack runs here, behind the chunk's copy (event), beside the next chunk's copy
-    tcsfm_depthnet *seq_dn = nullptr;  // tcsfm_sequence_depthnet: the network whose clone computes the ring's depths on seq_pack when a sequence
-                                       // call gets depths == NULL (not owned; tcsfm_depthnet_destroy detaches it)
-    int seq_fmt = TCSFM_FRAMES_F32_CHW;  // tcsfm_sequence_frame_format: how the sequence calls read their `frames` argument
-    DevBuf<uint8_t> seq_u8;            // U8 formats: device ring of the frames' BYTES (R slots of 3 H W -- or, with a frame source set, of
-                                       // 3 src_h src_w -- bytes, no mirror slots); k_frames_u8 / k_resize_u8 turns a chunk into the floats of seq_img on seq_pack
-    int seq_src_h = 0, seq_src_w = 0;  // tcsfm_sequence_frame_source: the camera's frame size (0, 0: none -- frames arrive at H x W)
-    std::vector<ResizeTable> resize_tabs;      // coefficient tables of the source sizes seen so far, on the device (resize_table())
-    // tcsfm_sequence_scale: the sequence calls' per-frame scale stage (k_ground + k_median_frames on seq_pack, once per chunk)
-    float seq_cam_height = 0.f;        // > 0: the stage is on
-    DevBuf<unsigned> seq_scale_keys;   // key planes of ONE chunk (not scale_keys: the operators on the handle's stream own that)
-    DevBuf<float> seq_scale_dev;       // results by ABSOLUTE frame index: [n] scales | [n] medians | [n] counts (int32), n = cap / 3
-    std::vector<float> seq_scale_res;  // the last call's results on the host, same layout with cap = seq_scale_T (counts as bit patterns)
-    int seq_scale_T = 0;               // 0: nothing kept
-    // tcsfm_sequence_disparity: the sequence calls' disparity stage (the depth stage's head / a second, mirrored pass + k_disp_post on seq_pack)
-    int seq_disp_mode = TCSFM_SEQ_DISP_OFF;
-    DevBuf<char> seq_disp_dev;         // every frame's plane by ABSOLUTE frame index: [T][H][W] float32 (PLAIN) or float64 (POST)
-    int seq_disp_T = 0, seq_disp_kept = TCSFM_SEQ_DISP_OFF;      // the last call's T (0: nothing kept) and mode, for tcsfm_sequence_disparities
-    double *flip_ramp = nullptr;       // l_mask [W] of the flip post-processing on the device (flip_ramp_device), built on first use
-    // tcsfm_sequence_depth_eval: one group of staged ground truth and the call's metrics, grown when a call needs more
-    DevBuf<char> eval_gt_dev;          // (bytes)
-    DevBuf<double> eval_out_dev;       // [frames][TCSFM_NEVAL]
-    struct KOk { const float *p; int n; };
-    KOk K_ok[4] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}};   // device intrinsics pointers (and counts) that already passed the pinhole check
-    int K_ok_next = 0;
-    // The routing of the refine calls (call_host.h), by the rules of call_plan.h:
-    GraphCache<hipGraphExec_t> graphs; // tcsfm_set_graph_replay: repeated device-pointer refine calls (same arguments) replayed as ONE captured HIP graph
-    bool capturing = false;            // ... a capture is under way on the handle's stream
-    CallQueue<CallArgs> queue;         // the *_queued entries: calls of one shape waiting to run as ONE launch sequence (tcsfm_set_coalesce / tcsfm_flush)
-    LaneRotation rot;                  // ... and the streams their merged sequences alternate over (tcsfm_set_coalesce_lanes)
-    bool lanes_serial = false;         // tcsfm_set_lanes' self-probe found that this process's streams do NOT run side by side (they slow each other
-                                       // down: include/tcsfm.h "lanes"): the *_async calls run on the handle's own stream, one after the other
-    float lane_probe[2] = {0.f, 0.f};  // the probe's figures: ms of the stand-in launches on ONE stream / alternating over TWO streams
-    bool dref_dirty = true;            // the scatter sums (dref_ext, dref_ext_src) may be non-zero: a call that ran to its end leaves them zero
-                                       // (k_dense_joint clears what it consumes); a fresh allocation, an export or a failed call does not
-    double *pose_lin = nullptr;        // l_pose_consist: [2][max_pairs][12] transforms at the linearisation (k_solve, kernels.h)
-    unsigned short *trace_bits = nullptr;   // tcsfm_debug_trace: caller-owned device buffers (null = off)
-    int *trace_decide = nullptr;
-    long long trace_bits_cap = 0, trace_decide_cap = 0;
-    bool tickets_dirty = false;        // a failed call may have left group tickets non-zero
-    bool profiling = false;
-    unsigned long long *stamp_buf = nullptr;   // in-kernel workgroup stamps of the linearisation launches of a profile session
-    size_t stamp_cap = 0, stamp_used = 0;      // capacity / use in (start, end) pairs
-    std::vector<std::pair<size_t, size_t>> stamp_launch;   // (first pair, workgroups) of every stamped launch
-    std::vector<hipEvent_t> ev_pool;
-    std::vector<int> ev_class;
-    size_t ev_used = 0;
-};
-
-namespace {
-
-// Every entry point runs on the handle's device and leaves the caller's current device as it found it (a process driving several
-// GPUs from one thread keeps allocating on the device it selected).
-struct DeviceGuard {
-    int prev = -1, dev;
-    explicit DeviceGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-
-#define HIPCHK(h, call)                                                                              \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                            \
-            (h)->tickets_dirty = true;                                                               \
-            return TCSFM_E_HIP;                                                                      \
-        }                                                                                            \
-    } while (0)
-
-}  // namespace
-
-template <class T>
-int DevBuf<T>::reserve(tcsfm_ctx *h, size_t n, const char *file, int line) {
-    if (cap >= n) return TCSFM_OK;
-    if (p) HIPCHK(h, hipFree(p));
-    p = nullptr; cap = 0;
-    HIPCHK(h, tcguard::alloc((void **)&p, n * sizeof(T), file, line));
-    cap = n;
-    return TCSFM_OK;
-}
-
-namespace {
-
-int fail(tcsfm_ctx *h, int code, const char *msg) {
-    h->err = msg;
-    return code;
-}
-
-// a call's arrays against the overlap contract of include/tcsfm.h: TCSFM_E_ARG with "<entry>: <out> overlaps <other>", or TCSFM_OK
-int check_overlap(tcsfm_ctx *h, const char *entry, const ArgRanges &a) {
-    std::string msg;
-    return a.refused(entry, msg) ? fail(h, TCSFM_E_ARG, msg.c_str()) : TCSFM_OK;
-}
-
-// The device-side pinhole guards (init_pair, k_ground) raise a host-mapped status word; it is reported -- as the documented
-// TCSFM_E_INTRINSICS -- by the next call on the handle or by tcsfm_synchronize, without a device synchronisation of its own.
-static bool k_known(const tcsfm_ctx *h, const float *K, int n) {
-    for (const auto &k : h->K_ok) if (k.p == K && K && n <= k.n) return true;
-    return false;
-}
-static void k_add(tcsfm_ctx *h, const float *K, int n) {
-    for (auto &k : h->K_ok) if (k.p == K) { if (n > k.n) k.n = n; return; }
-    h->K_ok[h->K_ok_next] = {K, n};
-    h->K_ok_next = (h->K_ok_next + 1) % 4;
-}
-static void k_forget(tcsfm_ctx *h) { for (auto &k : h->K_ok) k = {nullptr, 0}; }
-
-int pending_error(tcsfm_ctx *h) {
-    if (h->err_host && *reinterpret_cast<volatile int *>(h->err_host)) {
-        *reinterpret_cast<volatile int *>(h->err_host) = 0;
-        k_forget(h);
-        return fail(h, TCSFM_E_INTRINSICS, "an earlier asynchronous call was given non-pinhole intrinsics (detected on the device): its results are NaN");
-    }
-    return TCSFM_OK;
-}
-
-int check_common(tcsfm_ctx *h, const tcsfm_opts *o, int N) {
-    if (!h) return TCSFM_E_ARG;
-    if (!o) return fail(h, TCSFM_E_ARG, "opts is NULL");
-    if (N < 1 || N > h->max_pairs) return fail(h, TCSFM_E_ARG, "N out of range for this handle (1..max_pairs)");
-    if (o->refine != TCSFM_REFINE_POSE && o->refine != TCSFM_REFINE_POSE_SCALE) return fail(h, TCSFM_E_ARG, "opts.refine unsupported");
-    if (o->solver != TCSFM_SOLVER_GN && o->solver != TCSFM_SOLVER_LM) return fail(h, TCSFM_E_ARG, "opts.solver unsupported");
-    if (o->param != TCSFM_PARAM_SE3 && o->param != TCSFM_PARAM_EULER) return fail(h, TCSFM_E_ARG, "opts.param unsupported");
-    if (o->n_iters < 0 || o->n_iters > 1000) return fail(h, TCSFM_E_ARG, "opts.n_iters out of range");
-    if (o->depth_is_disp && !(o->min_depth > 0 && o->max_depth > o->min_depth)) return fail(h, TCSFM_E_ARG, "min_depth/max_depth invalid");
-    if (o->window_rule != TCSFM_WINDOW_PAIR && o->window_rule != TCSFM_WINDOW_REFERENCE) return fail(h, TCSFM_E_ARG, "opts.window_rule unsupported");
-    if (!(o->w_pose_consist >= 0.f) || (o->w_pose_consist > 0.f && (o->window_rule != TCSFM_WINDOW_REFERENCE || o->solver != TCSFM_SOLVER_GN ||
-                                                                   o->refine != TCSFM_REFINE_POSE || o->param != TCSFM_PARAM_SE3)))
-        return fail(h, TCSFM_E_ARG, "opts.w_pose_consist needs window_rule = TCSFM_WINDOW_REFERENCE, the Gauss-Newton solver, TCSFM_REFINE_POSE and the SE(3) chart");
-    return TCSFM_OK;
-}
-
-// The overlap contract (include/tcsfm.h) for the refine family, pose and dense modes, applied by every public form on its own behalf
-// before anything else happens (a graph replay and a queued call never reach the bodies' own staging with the caller's pointers).  The
-// arrays' extents are the call plan's (call_plan.h).
-// Honoured: pose_out at pose_in, and the dense depth_out anywhere over depth_t / depth_s -- *depth_on_input then says so (device pointers).  Arguments the
-// later validation refuses (NULL handle or options, sizes out of range) are left to it.
-int refine_overlap(tcsfm_ctx *h, const char *entry, const tcsfm_opts *o, int N, int win_B, int win_S, const CallArgs &c, bool dense,
-                   bool *depth_on_input = nullptr) {
-    if (depth_on_input) *depth_on_input = false;
-    if (!h || !o || N < 1 || N > h->max_pairs || o->n_iters < 0 || o->n_iters > 1000) return TCSFM_OK;
-    const PosePlan pl = pose_plan(N, win_B, win_S, 0, 0, 0, o->solver, o->n_iters, o->refine, o->argmin);
-    const size_t hw = (size_t)h->H * h->W, f = sizeof(float);
-    const bool scale = !dense && pl.np == 7;
-    ArgRanges a;
-    a.io_free = o->host_ptrs != 0;
-    a.in("tgt", c.tgt, pl.tgt(hw) * f); a.in(win_B ? "srcs" : "src", c.src, pl.src(hw) * f); a.in("depth_t", c.depth_t, pl.depth_t(hw) * f);
-    a.in("depth_s", c.depth_s, pl.depth_s(hw) * f); a.in("K", c.K, pl.K() * f); a.in("pose_in", c.pose_in, pl.pose() * f);
-    if (scale) a.in("log_scale_in", c.log_scale_in, pl.log_scale() * f);
-    a.out("pose_out", c.pose_out, pl.pose() * f);
-    if (scale) a.out("log_scale_out", c.log_scale_out, pl.log_scale() * f);
-    if (dense) a.out("depth_out", c.depth_out, pl.maps(hw) * f);
-    a.out("stats_out", c.stats_out, pl.stats() * f);
-    a.bless("pose_out", "pose_in");
-    if (dense) { a.bless_any("depth_out", "depth_t"); a.bless_any("depth_out", "depth_s"); }
-    std::string msg;
-    if (a.refused(entry, msg)) return fail(h, TCSFM_E_ARG, msg.c_str());
-    // (staged host arrays land in the library's own, disjoint device buffers: nothing to avoid there)
-    if (depth_on_input) *depth_on_input = dense && !a.io_free && (a.overlap("depth_out", "depth_t") || a.overlap("depth_out", "depth_s"));
-    return TCSFM_OK;
-}
-
-// The array arguments of one call.  With opts.host_ptrs in() stages a host array on the device and out() hands out a device buffer
-// that finish() copies back to its host pointer; with device pointers both pass the pointer through.  The device buffers are the
-// handle's staging slots (grown on demand), taken in order of registration -- a null argument takes its slot too, so an argument's
-// slot does not depend on which optional arguments a call passes.  Every array is registered under its argument's name with its
-// extent: ready() applies the overlap contract of include/tcsfm.h (arg_overlap.h) -- a forbidden overlap refuses the call before
-// anything is enqueued -- and only then sends the staged inputs up.  The first error sticks in rc: later steps do nothing.  Holds the
-// handle's device for the call and starts with the pending device-side error check.
-struct Staging {
-    tcsfm_ctx *h;
-    const tcsfm_opts *o;
-    DeviceGuard dev_guard;
-    int rc = TCSFM_OK;
-    size_t slot = 0;
-    struct Back { void *host; const void *dev; size_t bytes; };
-    std::vector<Back> back, up;
-    ArgRanges args;
-
-    Staging(tcsfm_ctx *h_, const tcsfm_opts *o_) : h(h_), o(o_), dev_guard(h_->device) {
-        rc = pending_error(h);
-        args.io_free = o->host_ptrs != 0;
-    }
-
-    // the next slot's device buffer, at least `bytes` long (null after an error)
-    void *scratch(size_t bytes) {
-        const size_t i = slot++;
-        if (rc) return nullptr;
-        if (h->stage.size() <= i) h->stage.resize(i + 1);
-        rc = h->stage[i].reserve(h, bytes, __FILE__, __LINE__);
-        return rc ? nullptr : h->stage[i].p;
-    }
-    template <typename T>
-    const T *in(const char *name, const T *p, size_t count) {
-        args.in(name, p, count * sizeof(T));
-        if (!o->host_ptrs || !p) { slot++; return p; }
-        void *d = scratch(count * sizeof(T));
-        if (d) up.push_back({const_cast<T *>(p), d, count * sizeof(T)});
-        return (const T *)d;
-    }
-    template <typename T>
-    T *out(const char *name, T *p, size_t count) {
-        args.out(name, p, count * sizeof(T));
-        if (!o->host_ptrs || !p) { slot++; return p; }
-        void *d = scratch(count * sizeof(T));
-        if (d) back.push_back({p, d, count * sizeof(T)});
-        return (T *)d;
-    }
-    // an output that is written on the host in every mode (takes no slot)
-    void host_out(const char *name, const void *p, size_t bytes) { args.out(name, p, bytes); }
-    void bless(const char *out_name, const char *in_name) { args.bless(out_name, in_name); }
-    // every array is registered: the overlap contract on behalf of `entry` (null: the caller has applied it), then the staged inputs go up
-    int ready(const char *entry) {
-        if (rc) return rc;
-        std::string msg;
-        if (entry && args.refused(entry, msg)) return rc = fail(h, TCSFM_E_ARG, msg.c_str());
-        for (const Back &u : up)
-            if ((rc = upload(const_cast<void *>(u.dev), u.host, u.bytes))) return rc;
-        up.clear();
-        return TCSFM_OK;
-    }
-    int upload(void *dev, const void *host, size_t bytes) {
-        HIPCHK(h, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream));
-        return TCSFM_OK;
-    }
-    // the outputs' copies back, in registration order, then a synchronisation when `sync` and the call staged host arrays
-    int finish(bool sync = true) {
-        if (rc) return rc;
-        for (const Back &b : back) HIPCHK(h, hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, h->stream));
-        if (o->host_ptrs && sync) HIPCHK(h, hipStreamSynchronize(h->stream));
-        return TCSFM_OK;
-    }
-};
-
-// intrinsics must be pinhole; checked on the host when they are host pointers, otherwise after a small D2H copy
-int check_intrinsics(tcsfm_ctx *h, const tcsfm_opts *o, const float *K_host_or_dev, int n) {
-    // Device intrinsics are validated with one blocking D2H copy the FIRST time a (pointer, count) is seen; repeated calls
-    // on the same buffer (a sequence, the bench loop) stay fully asynchronous.  The device side guards independently:
-    // init_pair() poisons the pose with NaN when K is not pinhole, so a buffer mutated behind our back still fails loudly.
-    if (!o->host_ptrs && k_known(h, K_host_or_dev, n)) return TCSFM_OK;
-    std::vector<float> k((size_t)n * 9);
-    if (o->host_ptrs) memcpy(k.data(), K_host_or_dev, k.size() * sizeof(float));
-    else {
-        HIPCHK(h, hipMemcpyAsync(k.data(), K_host_or_dev, k.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    for (int i = 0; i < n; i++) {
-        const float *K = &k[(size_t)i * 9];
-        if (K[1] != 0.f || K[3] != 0.f || K[6] != 0.f || K[7] != 0.f || K[8] != 1.f || !(K[0] != 0.f) || !(K[4] != 0.f))
-            return fail(h, TCSFM_E_INTRINSICS, "intrinsics must be pinhole [fx 0 cx; 0 fy cy; 0 0 1]");
-    }
-    if (!o->host_ptrs) k_add(h, K_host_or_dev, n);
-    return TCSFM_OK;
-}
-
-// RAII bracket: records a start event now and a stop event at scope exit when profiling is on
-struct ProfScope {
-    tcsfm_ctx *h;
-    bool on;
-    ProfScope(tcsfm_ctx *h_, int cls) : h(h_), on(h_->profiling) {
-        if (!on) return;
-        if (h->ev_used + 2 > h->ev_pool.size()) {
-            size_t old = h->ev_pool.size();
-            h->ev_pool.resize(old + 64);
-            for (size_t i = old; i < h->ev_pool.size(); i++)
-                if (hipEventCreate(&h->ev_pool[i]) != hipSuccess) { h->ev_pool.resize(i); break; }   // no event, no bracket
-            if (h->ev_used + 2 > h->ev_pool.size()) { on = false; return; }
-        }
-        h->ev_class.push_back(cls);
-        (void)hipEventRecord(h->ev_pool[h->ev_used], h->stream);
-    }
-    ~ProfScope() {
-        if (!on) return;
-        (void)hipEventRecord(h->ev_pool[h->ev_used + 1], h->stream);
-        h->ev_used += 2;
-    }
-};
-
-// while profiling, hand the next in-kernel stamp slots (one (start, end) pair per workgroup) to a linearisation launch
-void take_stamp(tcsfm_ctx *h, LinParams &P, size_t workgroups) {
-    P.stamp = nullptr;
-    if (h->profiling && h->stamp_buf && h->stamp_used + workgroups <= h->stamp_cap) {
-        P.stamp = h->stamp_buf + 2 * h->stamp_used;
-        h->stamp_launch.emplace_back(h->stamp_used, workgroups);
-        h->stamp_used += workgroups;
-    }
-}
-
-}  // namespace
+#include "context.h"       // the handle (tcsfm_ctx) over the owners of device_owned.h, HIPCHK / RESERVE, fail, Staging, ProfScope
 
 #include "pose_host.h"      // the pose modes: launch helpers, PoseDriver, pose_refine / pose_evaluate
 
@@ -630,73 +146,47 @@ int tcsfm_create(tcsfm_handle *out, int device, int H, int W, int max_pairs) {
     int cur = -1;
     hipError_t e = hipGetDevice(&cur);
     if (e == hipSuccess && cur != device) e = hipErrorInvalidDevice;
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&h->err_host, sizeof(int), hipHostMallocMapped);
-    if (e == hipSuccess) { *h->err_host = 0; e = hipHostGetDevicePointer((void **)&h->err_dev, h->err_host, 0); }
+    if (e == hipSuccess) e = h->own_stream.create();
+    if (e == hipSuccess) e = h->err_word.create();
     h->stream = h->own_stream;
-    if (e == hipSuccess) e = hipMalloc((void **)&h->tgtpack, n * hw * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->srcpack, n * (size_t)(H + 2) * (W + 2) * sizeof(float4));   // zero-bordered
-    if (e == hipSuccess) e = hipMalloc((void **)&h->depth_work, n * hw * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->partials, n * h->ngrp_pad * kMaxAcc * sizeof(float));
+    if (e == hipSuccess) e = DEV_RESERVE(h->tgtpack, n * hw);
+    if (e == hipSuccess) e = DEV_RESERVE(h->srcpack, n * (size_t)(H + 2) * (W + 2));   // zero-bordered
+    if (e == hipSuccess) e = DEV_RESERVE(h->depth_work, n * hw);
+    if (e == hipSuccess) e = DEV_RESERVE(h->partials, n * h->ngrp_pad * kMaxAcc);
     if (e == hipSuccess) e = hipMemset(h->partials, 0, n * h->ngrp_pad * kMaxAcc * sizeof(float));  // pad records stay 0
-    if (e == hipSuccess) e = hipMalloc((void **)&h->blockrec, n * h->nblk_alloc * kMaxAcc * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->tickets, n * h->ngrp_alloc * sizeof(int));
+    if (e == hipSuccess) e = DEV_RESERVE(h->blockrec, n * h->nblk_alloc * kMaxAcc);
+    if (e == hipSuccess) e = DEV_RESERVE(h->tickets, n * h->ngrp_alloc);
     if (e == hipSuccess) e = hipMemset(h->tickets, 0, n * h->ngrp_alloc * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->state, n * sizeof(PairState));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->pconst, n * sizeof(PairConst));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->lin_out, n * kLinOut * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->pose_dev, n * 6 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->ls_dev, n * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->K_dev, n * 9 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->pair_idx, 2 * n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->pose_lin, 2 * n * 12 * sizeof(double));
+    if (e == hipSuccess) e = DEV_RESERVE(h->state, n);
+    if (e == hipSuccess) e = DEV_RESERVE(h->pconst, n);
+    if (e == hipSuccess) e = DEV_RESERVE(h->lin_out, n * kLinOut);
+    if (e == hipSuccess) e = DEV_RESERVE(h->pose_dev, n * 6);
+    if (e == hipSuccess) e = DEV_RESERVE(h->ls_dev, n);
+    if (e == hipSuccess) e = DEV_RESERVE(h->K_dev, n * 9);
+    if (e == hipSuccess) e = DEV_RESERVE(h->pair_idx, 2 * n);
+    if (e == hipSuccess) e = DEV_RESERVE(h->pose_lin, 2 * n * 12);
     if (e != hipSuccess) {
         g_create_error = std::string("tcsfm_create: ") + hipGetErrorString(e);
         tcsfm_destroy(h);
         return e == hipErrorOutOfMemory ? TCSFM_E_NOMEM : TCSFM_E_HIP;
     }
-    if (getenv("TCSFM_DEBUG_STAMPS")) {
-        (void)hipMalloc((void **)&h->dbg_stamps, 8 * sizeof(long long));
-        (void)hipMemset(h->dbg_stamps, 0, 8 * sizeof(long long));
-    }
+    if (getenv("TCSFM_DEBUG_STAMPS") && DEV_RESERVE(h->dbg_stamps, 8) == hipSuccess) (void)hipMemset(h->dbg_stamps, 0, 8 * sizeof(long long));
     *out = h;
     return TCSFM_OK;
 }
 
+// The sequence is the contract: queued calls run, the lanes go, every stream that work may be on is drained, the graphs are dropped --
+// and only then do the handle's members release themselves (tcsfm_ctx: buffers and events before the streams).
 void tcsfm_destroy(tcsfm_handle h) {
     if (!h) return;
     (void)drain_queued(h);                // queued calls are not dropped: they run, and the synchronisations below wait for them
     for (tcsfm_ctx *c : h->lanes) tcsfm_destroy(c);
     h->lanes.clear();
     DeviceGuard dev_guard(h->device);
-    if (h->in_ev) (void)hipEventDestroy(h->in_ev);
-    if (h->done_ev) (void)hipEventDestroy(h->done_ev);
-    for (auto &e : h->marks) (void)hipEventDestroy(e);
-    if (h->seq_copy) { (void)hipStreamSynchronize(h->seq_copy); (void)hipStreamDestroy(h->seq_copy); }
-    if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
-    if (h->aux_fork) (void)hipEventDestroy(h->aux_fork);
-    if (h->aux_join) (void)hipEventDestroy(h->aux_join);
-    if (h->seq_pack) { (void)hipStreamSynchronize(h->seq_pack); (void)hipStreamDestroy(h->seq_pack); }
+    for (hipStream_t s : {(hipStream_t)h->seq_copy, (hipStream_t)h->aux_stream, (hipStream_t)h->seq_pack})
+        if (s) (void)hipStreamSynchronize(s);
     drop_graphs(h);                       // (a replay may still be running: it drains the streams one can be on before the executables go)
-    for (auto &e : h->seq_copied) (void)hipEventDestroy(e);
-    for (auto &e : h->seq_raw) (void)hipEventDestroy(e);
-    for (auto &e : h->seq_done) (void)hipEventDestroy(e);
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
-    void *ptrs[] = {h->stamp_buf, h->tgtpack, h->srcpack, h->depth_work, h->partials, h->blockrec, h->tickets, h->state, h->pconst, h->lin_out,
-                    h->pose_lin, h->pose_dev, h->ls_dev, h->K_dev, h->stats_dev, h->scale_keys, h->scale_hist, h->dbg_stamps, h->wgrad_rec, h->wgrad_fix, h->wgrad_gmax, h->pgrad_fwd, h->pgrad_cot,
-                    h->pair_idx, h->flip_ramp};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    h->dense.release();
-    for (DevBuf<float> *b : {&h->seq_img, &h->seq_depth, &h->seq_pose_in, &h->seq_pose_out, &h->seq_ls_out, &h->seq_K, &h->seq_fdepth, &h->seq_dense, &h->seq_dense_tmp, &h->seq_scale_dev})
-        b->release();
-    h->seq_fpack.release(); h->seq_u8.release(); h->seq_scale_keys.release(); h->seq_disp_dev.release(); h->eval_gt_dev.release(); h->eval_out_dev.release();
-    for (auto &t : h->resize_tabs)
-        if (t.dev) (void)hipFree(t.dev);
-    for (auto &s : h->stage) s.release();
-    for (auto &e : h->ev_pool) (void)hipEventDestroy(e);
-    if (h->err_host) (void)hipHostFree(h->err_host);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
 }
 
@@ -862,9 +352,9 @@ static int warp_backward_dev(tcsfm_ctx *h, const tcsfm_opts *o, int N, const flo
     const size_t hw = (size_t)h->H * h->W;
     const unsigned nblk = (unsigned)((hw + 255) / 256);
     if (!o_dt && !o_ds && !o_pose) return TCSFM_OK;
-    if (o_pose && !h->wgrad_rec) HIPCHK(h, hipMalloc((void **)&h->wgrad_rec, (size_t)h->max_pairs * nblk * 12 * sizeof(double)));
-    if (o_ds && d_gpd && !h->wgrad_fix) HIPCHK(h, hipMalloc((void **)&h->wgrad_fix, (size_t)h->max_pairs * hw * sizeof(long long)));
-    if (o_ds && d_gpd && !h->wgrad_gmax) HIPCHK(h, hipMalloc((void **)&h->wgrad_gmax, (size_t)h->max_pairs * sizeof(unsigned)));
+    if (o_pose) RESERVE(h, h->wgrad_rec, (size_t)h->max_pairs * nblk * 12);
+    if (o_ds && d_gpd) RESERVE(h, h->wgrad_fix, (size_t)h->max_pairs * hw);
+    if (o_ds && d_gpd) RESERVE(h, h->wgrad_gmax, (size_t)h->max_pairs);
     const dim3 grid(nblk, N);
     if (o_ds && !d_gpd) HIPCHK(h, hipMemsetAsync(o_ds, 0, N * hw * sizeof(float), h->stream));      // nothing flows into the source depth
     if (!o_dt && !o_pose && !(o_ds && d_gpd)) return TCSFM_OK;                                      // ... and nothing else is wanted: no kernel at all
@@ -975,8 +465,8 @@ int tcsfm_photometric_backward(tcsfm_handle h, const tcsfm_opts *o, int N, const
     bool inited = false;
     if (d_gdiff || d_gweight) {
         const size_t plane = (size_t)h->max_pairs * hw;
-        if (!h->pgrad_fwd) HIPCHK(h, hipMalloc((void **)&h->pgrad_fwd, 5 * plane * sizeof(float)));
-        if (!h->pgrad_cot) HIPCHK(h, hipMalloc((void **)&h->pgrad_cot, 5 * plane * sizeof(float)));
+        RESERVE(h, h->pgrad_fwd, 5 * plane);
+        RESERVE(h, h->pgrad_cot, 5 * plane);
         float *f_rec = h->pgrad_fwd, *f_pd = h->pgrad_fwd + 3 * plane, *f_cd = h->pgrad_fwd + 4 * plane;
         float *c_rec = h->pgrad_cot, *c_pd = h->pgrad_cot + 3 * plane, *c_cd = h->pgrad_cot + 4 * plane;
         if ((rc = run_init(h, o, N, d_pose_in, nullptr, d_K, 0))) return rc;
@@ -1130,16 +620,14 @@ int tcsfm_scale_recovery(tcsfm_handle h, const tcsfm_opts *o, int N, const float
     if (st.rc) return st.rc;
     if ((rc = check_intrinsics(h, o, K, N))) return rc;
     const size_t hw = (size_t)h->H * h->W;
-    if (!h->scale_keys) {
-        HIPCHK(h, hipMalloc((void **)&h->scale_keys, (size_t)h->max_pairs * hw * sizeof(unsigned)));
-        HIPCHK(h, hipMalloc((void **)&h->scale_hist, 260 * sizeof(unsigned)));
-    }
+    RESERVE(h, h->scale_keys, (size_t)h->max_pairs * hw);
+    RESERVE(h, h->scale_hist, 260);
     const float *d_depth = st.in("depth", depth, N * hw), *d_K = st.in("K", K, (size_t)N * 9);
     float *d_scale = st.out("scale_out", scale_out, (size_t)1), *d_med = st.out("median_out", median_out, (size_t)1), *d_h = st.out("height_out", height_out, N * hw), *d_m = st.out("mask_out", mask_out, N * hw);
     if (st.ready("tcsfm_scale_recovery")) return st.rc;
     HIPCHK(h, hipMemsetAsync(h->scale_hist, 0, 260 * sizeof(unsigned), h->stream));
     GroundParams G;
-    G.depth = d_depth; G.K = d_K; G.height = d_h; G.mask = d_m; G.keys = h->scale_keys; G.H = h->H; G.W = h->W; G.err = h->err_dev;
+    G.depth = d_depth; G.K = d_K; G.height = d_h; G.mask = d_m; G.keys = h->scale_keys; G.H = h->H; G.W = h->W; G.err = h->err_word.dev;
     hipLaunchKernelGGL(k_ground, dim3((unsigned)((hw + 255) / 256), N), dim3(256), 0, h->stream, G);
     // the reference pads the batch to config['minibatch'] with copies of image 0 (dnet_layers.py:307-311): weight image 0
     const int w0 = 1 + (pad_to_batch > N ? pad_to_batch - N : 0);
@@ -1161,7 +649,7 @@ static void launch_frame_scales(tcsfm_ctx *h, hipStream_t stream, int n, const f
                                 float real_cam_height, float *scale, float *median, int *count) {
     const size_t hw = (size_t)h->H * h->W;
     GroundParams G;
-    G.depth = depth; G.K = K; G.height = nullptr; G.mask = nullptr; G.keys = keys; G.H = h->H; G.W = h->W; G.err = h->err_dev; G.k_stride = k_stride;
+    G.depth = depth; G.K = K; G.height = nullptr; G.mask = nullptr; G.keys = keys; G.H = h->H; G.W = h->W; G.err = h->err_word.dev; G.k_stride = k_stride;
     hipLaunchKernelGGL(k_ground, dim3((unsigned)((hw + 255) / 256), n), dim3(256), 0, stream, G);
     const char *lds_env = getenv("TCSFM_MEDIAN_LDS_KEYS");
     const int lds_keys = lds_env ? atoi(lds_env) : kMedianLdsKeys;
@@ -1186,10 +674,8 @@ int tcsfm_scale_recovery_frames(tcsfm_handle h, const tcsfm_opts *o, int N, cons
     DeviceGuard dev_guard(h->device);
     if ((rc = pending_error(h))) return rc;
     if ((rc = check_intrinsics(h, o, (const float *)K, N))) return rc;
-    if (!h->scale_keys) {
-        HIPCHK(h, hipMalloc((void **)&h->scale_keys, (size_t)h->max_pairs * hw * sizeof(unsigned)));
-        HIPCHK(h, hipMalloc((void **)&h->scale_hist, 260 * sizeof(unsigned)));
-    }
+    RESERVE(h, h->scale_keys, (size_t)h->max_pairs * hw);
+    RESERVE(h, h->scale_hist, 260);
     launch_frame_scales(h, h->stream, N, (const float *)depth, (const float *)K, 9, h->scale_keys, real_cam_height, (float *)scale_out,
                         (float *)median_out, count_out);
     HIPCHK(h, hipGetLastError());
@@ -1430,21 +916,18 @@ int tcsfm_debug_check_guards(int *n_allocations, int *n_damaged) {
 int tcsfm_debug_guard_selftest(int *detected) {
     if (detected) *detected = -1;
     if (!tcguard::on()) return TCSFM_OK;
-    char *p = nullptr;
-    if (hipMalloc(&p, 1000) != hipSuccess) return TCSFM_E_HIP;
+    DevBuf<char> p, q;
+    if (DEV_RESERVE(p, 1000) != hipSuccess) return TCSFM_E_HIP;
     if (hipMemset(p + 1000, 0, 4) != hipSuccess) return TCSFM_E_HIP;      // four bytes past the end
     int found = 0;
     {
         std::lock_guard<std::mutex> lk(tcguard::mtx());
         for (auto &r : tcguard::recs())
-            if (r.base + tcguard::kBand == p) { long off = 0; found = tcguard::damaged(r, &off) == 4 && off == 1000; r.reported = true; }
+            if (r.base + tcguard::kBand == p.p) { long off = 0; found = tcguard::damaged(r, &off) == 4 && off == 1000; r.reported = true; }
     }
     // the check an entry runs over its OWN allocations before it frees them (tcsfm_debug_solve) sees the same damage, and only there
-    char *q = nullptr;
-    if (hipMalloc(&q, 1000) != hipSuccess) { (void)hipFree(p); return TCSFM_E_HIP; }
-    found = found && tcguard::damaged_among({(void *)p, (void *)q}) == 1 && tcguard::damaged_among({(void *)q}) == 0;
-    (void)hipFree(q);
-    (void)hipFree(p);
+    if (DEV_RESERVE(q, 1000) != hipSuccess) return TCSFM_E_HIP;
+    found = found && tcguard::damaged_among({(void *)p.p, (void *)q.p}) == 1 && tcguard::damaged_among({(void *)q.p}) == 0;
     if (detected) *detected = found;
     return TCSFM_OK;
 }
@@ -1455,14 +938,13 @@ static const double *flip_ramp_device(tcsfm_handle h) {
     if (h->flip_ramp) return h->flip_ramp;
     std::vector<double> ramp((size_t)h->W);
     flip_ramp(h->W, ramp.data());
-    double *dev = nullptr;
-    if (hipError_t e = hipMalloc((void **)&dev, ramp.size() * sizeof(double))) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return nullptr; }
+    DevBuf<double> dev;
+    if (hipError_t e = DEV_RESERVE(dev, ramp.size())) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return nullptr; }
     if (hipError_t e = hipMemcpy(dev, ramp.data(), ramp.size() * sizeof(double), hipMemcpyHostToDevice)) {      // (synchronous: ramp is a temporary)
         h->err = std::string("hipMemcpy: ") + hipGetErrorString(e);
-        (void)hipFree(dev);
         return nullptr;
     }
-    return h->flip_ramp = dev;
+    return h->flip_ramp = std::move(dev);
 }
 
 // k_disp_post over n planes: the vector form where the row pairs are aligned (W even, 8-byte l / rf, 16-byte out), else the scalar one
@@ -1483,17 +965,17 @@ static hipError_t launch_disp_post(hipStream_t s, int n, int H, int W, const flo
 static const ResizeTable *resize_table(tcsfm_handle h, int src_h, int src_w) {
     for (const auto &t : h->resize_tabs)
         if (t.sh == src_h && t.sw == src_w) return &t;
-    ResizeTable T;
+    tcsfm_ctx::OwnedResizeTable T;
     T.sh = src_h; T.sw = src_w; T.H = h->H; T.W = h->W;
     std::vector<int> blob;
     if (!resize_build_table(T, blob)) { h->err = "resize: the source size is beyond the kernel's tile (resize_u8_kernel.h)"; return nullptr; }
-    if (hipError_t e = hipMalloc((void **)&T.dev, blob.size() * sizeof(int))) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return nullptr; }
-    if (hipError_t e = hipMemcpy(T.dev, blob.data(), blob.size() * sizeof(int), hipMemcpyHostToDevice)) {      // (synchronous: blob is a temporary)
+    if (hipError_t e = DEV_RESERVE(T.blob, blob.size())) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return nullptr; }
+    if (hipError_t e = hipMemcpy(T.blob, blob.data(), blob.size() * sizeof(int), hipMemcpyHostToDevice)) {      // (synchronous: blob is a temporary)
         h->err = std::string("hipMemcpy: ") + hipGetErrorString(e);
-        (void)hipFree(T.dev);
         return nullptr;
     }
-    h->resize_tabs.push_back(T);
+    T.dev = T.blob;
+    h->resize_tabs.push_back(std::move(T));
     return &h->resize_tabs.back();
 }
 
@@ -1604,9 +1086,7 @@ int tcsfm_lane_event(tcsfm_handle h, int lane, void **event_out) {
     DeviceGuard dev_guard(h->device);
     constexpr size_t kMarks = 64;
     if (c->marks.size() < kMarks) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->marks.push_back(e);
+        HIPCHK(h, c->marks.grow(c->marks.size() + 1));
         c->mark_next = c->marks.size() - 1;
     }
     hipEvent_t e = c->marks[c->mark_next];
@@ -1767,10 +1247,8 @@ int tcsfm_profile_begin(tcsfm_handle h) {
     if (!h) return TCSFM_E_ARG;
     DeviceGuard dev_guard(h->device);
     if (int rc_ = pending_error(h)) return rc_;
-    if (!h->stamp_buf) {
-        h->stamp_cap = (size_t)4 << 20;     // 4 M workgroup stamps = 64 MB: ~8000 launches of the BASELINE config
-        HIPCHK(h, hipMalloc((void **)&h->stamp_buf, h->stamp_cap * 2 * sizeof(unsigned long long)));
-    }
+    h->stamp_cap = (size_t)4 << 20;         // 4 M workgroup stamps = 64 MB: ~8000 launches of the BASELINE config
+    RESERVE(h, h->stamp_buf, h->stamp_cap * 2);
     h->stamp_used = 0;
     h->stamp_launch.clear();
     for (tcsfm_ctx *c : h->lanes)                       // the lanes are bracketed too: their figures are added in profile_end
