@@ -176,3 +176,113 @@ int debug_solve_joint_run(tcsfm_ctx *h, const tcsfm_opts *o, tcsfm_debug_solve_j
 }
 
 }  // namespace
+
+int tcsfm_debug_solve_layout(int *sizeof_pair_state, int *sizeof_pair_const) {
+    if (sizeof_pair_state) *sizeof_pair_state = (int)sizeof(PairState);
+    if (sizeof_pair_const) *sizeof_pair_const = (int)sizeof(PairConst);
+    return TCSFM_OK;
+}
+
+int tcsfm_debug_solve_joint_layout(int *sizeof_pair_state, int *sizeof_pair_const, int *sizeof_joint_state) {
+    if (sizeof_joint_state) *sizeof_joint_state = (int)sizeof(JointState);
+    return tcsfm_debug_solve_layout(sizeof_pair_state, sizeof_pair_const);
+}
+int tcsfm_debug_solve_joint(tcsfm_handle h, const tcsfm_opts *o, tcsfm_debug_solve_joint_args *a) { return debug_solve_joint_run(h, o, a); }
+
+int tcsfm_debug_solve(tcsfm_handle h, const tcsfm_opts *o, tcsfm_debug_solve_args *a) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    if (!h) return TCSFM_E_ARG;
+#define DS_REFUSE(cond, msg) if (cond) return fail(h, TCSFM_E_ARG, "tcsfm_debug_solve: " msg)
+    DS_REFUSE(!o || !a, "NULL argument");
+    DS_REFUSE(!a->records || !a->state || !a->pconst, "records, state and pconst are required");
+    DS_REFUSE(a->variant < 0 || a->variant > 3, "variant must be 0 .. 3");
+    DS_REFUSE(a->mode < 0 || a->mode > 2, "mode must be 0, 1 or 2");
+    DS_REFUSE(a->N < 1 || a->N > 4096 || a->ngrp < 1 || a->ngrp > 65536, "N and ngrp must be at least 1");
+    DS_REFUSE(a->n_alloc < a->N || a->n_alloc > 8192, "n_alloc must be at least N");
+    DS_REFUSE(o->n_iters < 0 || o->n_iters > 1024 || a->it < 0 || a->it > o->n_iters, "need 0 <= it <= n_iters");
+    DS_REFUSE(o->solver != TCSFM_SOLVER_GN && o->solver != TCSFM_SOLVER_LM, "unknown solver");
+    DS_REFUSE(o->param != TCSFM_PARAM_SE3 && o->param != TCSFM_PARAM_EULER, "unknown param");
+    DS_REFUSE(o->refine != TCSFM_REFINE_POSE && o->refine != TCSFM_REFINE_POSE_SCALE, "unknown refine");
+    const int np = np_of(o), N = a->N, nacc = nacc_of(np);
+    const bool pc_asked = a->w_pc > 0.0 || a->w_pc != a->w_pc;
+    DS_REFUSE(a->variant >= 1 && o->param != TCSFM_PARAM_SE3, "variants 1 to 3 have the SE(3) chart only");
+    DS_REFUSE((a->variant == 1 || a->variant == 2) && pc_asked, "variants 1 and 2 have no pose-consistency term");
+    DS_REFUSE(a->variant >= 2 && np == 7, "k_solve_front solves 6-DoF pairs only");
+    DS_REFUSE(pc_asked && np == 7, "the pose-consistency term is 6-DoF only");
+    DS_REFUSE(a->mode == 2 && !a->lin_out, "mode 2 needs lin_out");
+    DS_REFUSE(a->grp_fwd < 0 || a->n_pairs < 0 || a->grp_fwd > a->n_pairs, "need 0 <= grp_fwd <= n_pairs");
+    DS_REFUSE(a->pc_np < 0 || a->pc_self0 < 0 || a->pc_part0 < 0 || a->pose_lin_pairs < 0, "negative pose_lin geometry");
+    DS_REFUSE(a->rule && a->n_pairs != N, "the window rule needs n_pairs == N");
+    if (a->rule && a->norms) {
+        DS_REFUSE(a->norm_B < 0 || a->norm_n < 1 || (a->norm_B > 0 && a->norm_Bt < 1), "bad norms geometry");
+        for (int n = 0; n < N; n++)
+            DS_REFUSE((a->norm_B > 0 ? (n % a->norm_Bt) / a->norm_B : 0) >= a->norm_n, "norms is shorter than a pair's group index needs");
+    }
+    if (a->pose_lin) {
+        const int per = a->pc_np > 0 ? a->pc_np : a->n_pairs;
+        DS_REFUSE(a->pc_np == 0 && a->n_pairs != N, "the unsliced pose-consistency form needs n_pairs == N");
+        DS_REFUSE(per < 1 || per != a->pose_lin_pairs, "pose_lin_pairs must be the pairs per pose_lin buffer (pc_np, or n_pairs)");
+        for (int n = 0; n < N; n++) {
+            const long long self = a->pc_np > 0 ? (long long)a->pc_self0 + n : n;
+            DS_REFUSE(self >= per, "a pair's own slot is outside pose_lin");
+            if (a->rule && pc_asked) {
+                const long long partner = a->pc_np > 0 ? (long long)a->pc_part0 + n : (n < a->grp_fwd ? (long long)n + a->grp_fwd : (long long)n - a->grp_fwd);
+                DS_REFUSE(partner < 0 || partner >= per, "a partner index is outside pose_lin");
+            }
+        }
+    }
+    DS_REFUSE(a->c_ncall < 0 || a->c_ncall > TC_MAX_COAL, "c_ncall out of range");
+    if (a->c_ncall > 0) {
+        DS_REFUSE(a->c_B < 1 || a->c_S < 1 || a->c_n0 < 0 || a->c_B > 4096 || a->c_S > 4096 || a->c_n0 > (1 << 20), "bad coalesce geometry");
+        for (int n = 0; n < N; n++) {
+            const CoalIdx ci = coal_index(a->c_ncall, a->c_B, a->c_S, n + a->c_n0);
+            DS_REFUSE(ci.call < 0 || ci.call >= a->c_ncall || !a->c_pose_out[ci.call] || ci.li < 0 || ci.li >= a->c_len[ci.call],
+                      "a coalesced pair's output slot is outside the given per-call arrays");
+        }
+    }
+#undef DS_REFUSE
+    DeviceGuard dev_guard(h->device);
+    if (int rc_ = pending_error(h)) return rc_;
+    SolveParams S = solve_params(h, o, np, 0);
+    DebugBufs B;
+    const size_t na = (size_t)a->n_alloc;
+    void *p = nullptr;
+#define DS_UP(dst, type, host, bytes, out) HIPCHK(h, B.up((host), (bytes), (out), &p)); dst = (type)p
+    DS_UP(S.partials, const float *, a->records, na * a->ngrp * nacc * sizeof(float), false);
+    DS_UP(S.st, PairState *, a->state, na * sizeof(PairState), true);
+    DS_UP(S.pc, PairConst *, a->pconst, na * sizeof(PairConst), true);
+    DS_UP(S.stats, float *, a->stats, na * (o->n_iters + 1) * TCSFM_NSTAT * sizeof(float), true);
+    DS_UP(S.lin_out, double *, a->lin_out, na * (np * np + np + 4) * sizeof(double), true);
+    DS_UP(S.delta_out, double *, a->delta_out, na * 8 * sizeof(double), true);
+    DS_UP(S.accept_out, int *, a->accept_out, na * sizeof(int), true);
+    DS_UP(S.trace_decide, int *, a->trace_decide, na * sizeof(int), true);
+    DS_UP(S.pose_out, float *, a->pose_out, na * 6 * sizeof(float), true);
+    DS_UP(S.log_scale_out, float *, a->log_scale_out, na * sizeof(float), true);
+    DS_UP(S.pose_lin, double *, a->pose_lin, (size_t)2 * a->pose_lin_pairs * 12 * sizeof(double), true);
+    DS_UP(S.norms, const int *, a->rule ? a->norms : nullptr, (size_t)a->norm_n * 2 * sizeof(int), false);
+    for (int i = 0; i < a->c_ncall; i++) {
+        DS_UP(S.c_pose_out[i], float *, a->c_pose_out[i], (size_t)a->c_len[i] * 6 * sizeof(float), true);
+        DS_UP(S.c_ls_out[i], float *, a->c_ls_out[i], (size_t)a->c_len[i] * sizeof(float), true);
+    }
+#undef DS_UP
+    S.ngrp = a->ngrp; S.it = a->it; S.mode = a->mode; S.dbg = nullptr;
+    S.rule = a->rule ? 1 : 0; S.grp_fwd = a->grp_fwd; S.n_pairs = a->n_pairs; S.scale_fwd = a->scale_fwd; S.scale_inv = a->scale_inv;
+    S.norm_Bt = a->norm_Bt; S.norm_B = a->norm_B;
+    S.w_pc = a->w_pc; S.pc_eps = a->pc_eps; S.pc_np = a->pc_np; S.pc_self0 = a->pc_self0; S.pc_part0 = a->pc_part0;
+    S.c_ncall = a->c_ncall; S.c_B = a->c_B; S.c_S = a->c_S; S.c_n0 = a->c_n0;
+    if (a->variant <= 1) launch_solve_as(h, S, N, np, a->variant == 1);
+    else {
+        JointSolveParams Pj;
+        memset(&Pj, 0, sizeof(Pj));       // B = 0: every workgroup takes the pair role
+        if (a->variant == 3) hipLaunchKernelGGL((k_solve_front<1, true>), dim3(N), dim3(JSOLVE_NT), 0, h->stream, Pj, S);
+        else hipLaunchKernelGGL((k_solve_front<1>), dim3(N), dim3(JSOLVE_NT), 0, h->stream, Pj, S);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (const auto &b : B.back) HIPCHK(h, hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
+    // the entry's allocations are freed when it returns, so tcsfm_debug_check_guards never sees them: their bands are checked here
+    const int hit = tcguard::damaged_among(B.dev);
+    if (hit < 0) return fail(h, TCSFM_E_HIP, "tcsfm_debug_solve: could not read the guard bands back");
+    if (hit > 0) return fail(h, TCSFM_E_HIP, "tcsfm_debug_solve: the launch wrote outside the entry's device arrays (guard bands damaged, details on stderr)");
+    return TCSFM_OK;
+}

@@ -782,3 +782,45 @@ int dense_pair_run(const DenseCall &c) { return DensePair(c).run(); }
 #undef DENSE_RESERVE
 
 }  // namespace
+
+static int drain_queued(tcsfm_ctx *h);      // (call_host.h)
+
+static int linearize_dense_window_impl(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
+                                       const float *depth_t, const float *depth_s, const float *K, const float *pose, const float *depth0,
+                                       double *scal_out, double *g_pose_out, float *g_rho_out, float *g_rho_src_out, const char *entry) {
+    if (int rc_q = drain_queued(h)) return rc_q;
+    if (!h) return TCSFM_E_ARG;
+    if (B < 1 || S < 1 || S > JMAXS || (long long)2 * B * S > h->max_pairs) return fail(h, TCSFM_E_ARG, "tcsfm_linearize_dense_window: need 1 <= S <= 4 and 2*B*S <= max_pairs");
+    const int N = 2 * B * S;
+    int rc = check_common(h, o, N);
+    if (rc) return rc;
+    if (!tgt || !srcs || !depth_t || !depth_s || !K || !pose || !scal_out || !g_pose_out || !g_rho_out) return fail(h, TCSFM_E_ARG, "tcsfm_linearize_dense_window: NULL argument");
+    if (!(o->min_depth > 0 && o->max_depth > o->min_depth) || !(o->prior_init >= 0.f)) return fail(h, TCSFM_E_ARG, "min_depth / max_depth / prior_init invalid");
+    Staging st(h, o);
+    if (st.rc) return st.rc;
+    if ((rc = check_intrinsics(h, o, K, B))) return rc;
+    const size_t hw = (size_t)h->H * h->W;
+    const float *d_tgt = st.in("tgt", tgt, (size_t)B * 3 * hw), *d_src = st.in("srcs", srcs, (size_t)S * B * 3 * hw), *d_dt = st.in("depth_t", depth_t, (size_t)B * hw);
+    const float *d_ds = st.in("depth_s", depth_s, (size_t)S * B * hw), *d_K = st.in("K", K, (size_t)B * 9), *d_pose = st.in("pose", pose, (size_t)N * 6);
+    const float *d_d0 = st.in("depth0", depth0, (size_t)B * hw);
+    float *d_g = st.out("g_rho_out", g_rho_out, (size_t)B * hw), *d_gs = st.out("g_rho_src_out", g_rho_src_out, (size_t)S * B * hw);
+    st.host_out("scal_out", scal_out, 8 * sizeof(double)); st.host_out("g_pose_out", g_pose_out, (size_t)N * 6 * sizeof(double));
+    if (st.ready(entry)) return st.rc;
+    tcsfm_opts oo = *o;
+    oo.n_iters = 1; oo.solver = TCSFM_SOLVER_GN;
+    DrefExport ex{scal_out, g_pose_out, d_g, d_d0, d_gs};
+    if ((rc = dense_ref_run(DenseCall{h, &oo, B, S, d_tgt, d_src, d_dt, d_ds, d_K, d_pose, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, &ex}))) return rc;
+    return st.finish();
+}
+
+int tcsfm_linearize_dense_window(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
+                                 const float *depth_t, const float *depth_s, const float *K, const float *pose, const float *depth0,
+                                 double *scal_out, double *g_pose_out, float *g_rho_out) {
+    return linearize_dense_window_impl(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose, depth0, scal_out, g_pose_out, g_rho_out, nullptr, "tcsfm_linearize_dense_window");
+}
+int tcsfm_linearize_dense_window_sources(tcsfm_handle h, const tcsfm_opts *o, int B, int S, const float *tgt, const float *srcs,
+                                         const float *depth_t, const float *depth_s, const float *K, const float *pose, const float *depth0,
+                                         double *scal_out, double *g_pose_out, float *g_rho_out, float *g_rho_src_out) {
+    if (!g_rho_src_out) return h ? fail(h, TCSFM_E_ARG, "tcsfm_linearize_dense_window_sources: NULL argument") : TCSFM_E_ARG;
+    return linearize_dense_window_impl(h, o, B, S, tgt, srcs, depth_t, depth_s, K, pose, depth0, scal_out, g_pose_out, g_rho_out, g_rho_src_out, "tcsfm_linearize_dense_window_sources");
+}
